@@ -10,10 +10,15 @@ A step = bin the batch by spatial tile -> fused forward -> loss -> fused backwar
 times inside the timed region (inputs resident in HBM).  Submaps are independent, so
 N GPUs run N submaps with no data-path collective (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (see the contract in the task description).
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), and the
+configuration.  A plain run does only what that line needs: set-up, the settle and warm-up steps, the K timed steps.
+--full adds everything else the benchmark measures or checks: the same protocol without the settle phase, per-kernel
+durations and the roofline, the secondary workloads (tools/bench_extras.py; --no-extras leaves them out), the
+multi-rank extras and the CPU baseline with its SDF comparison (--no-cpu-baseline leaves it out).
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, see dump_outputs.
 """
 import argparse
 import json
@@ -330,8 +335,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: leave out the secondary workloads")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -360,6 +369,7 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, timeout=tmo)
         else:
             dist.init_process_group(backend, rank=rank, world_size=world, timeout=tmo)
+    if dist is not None and args.full:
         # sanity value of the collective layer: every rank contributes rank + 1 -> world (world + 1) / 2
         from miso_amd import dist as mdist
         chk = torch.full((1,), float(rank + 1), device=dev)
@@ -375,18 +385,21 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
-    # for the record, the protocol WITHOUT the settle phase first (rank-local, no barrier): W warm-up steps and K timed
-    # steps on a device that has been idle -- the figure the clock ramp produces (settle_device), reported next to `value`
-    for _ in range(args.warmup):
-        step.run()
-    torch.cuda.synchronize()
-    gc.disable()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step.run()
-    torch.cuda.synchronize()
-    cold_elapsed = time.perf_counter() - t0
-    gc.enable()
+    cold_elapsed = None
+    if args.full:
+        # for the record, the protocol WITHOUT the settle phase first (rank-local, no barrier): W warm-up steps and K
+        # timed steps on a device that has been idle -- the figure the clock ramp produces (settle_device), reported
+        # next to `value`
+        for _ in range(args.warmup):
+            step.run()
+        torch.cuda.synchronize()
+        gc.disable()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step.run()
+        torch.cuda.synchronize()
+        cold_elapsed = time.perf_counter() - t0
+        gc.enable()
     settle_device(step)
     for _ in range(args.warmup):
         step.run()
@@ -407,9 +420,19 @@ def main():
         t = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+    # the outputs of the last timed step, before anything else runs on the step's buffers
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step, args.dump_outputs)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(base_record(args, step, world, elapsed)))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
-    # rank 0 finishes the headline record FIRST (per-kernel timings, roofline: single-rank work); the collective-bearing
-    # extras run after it, under a watchdog that prints the record if they hang or a rank fails
+    # --full: rank 0 finishes the headline record FIRST (per-kernel timings, roofline: single-rank work); the
+    # collective-bearing extras run after it, under a watchdog that prints the record if they hang or a rank fails
+    # 
     out = headline_record(args, step, dev, world, elapsed) if rank == 0 else None
     if rank == 0:
         out["without_settle_phase"] = {
@@ -452,10 +475,70 @@ def main():
         dist.destroy_process_group()
 
 
-def headline_record(args, step, dev, world, elapsed):
-    """The headline JSON record (rank 0): value, per-kernel durations measured live with HIP events, roofline."""
+def _exact_f32():
     from miso_amd import ops
+    return bool(ops._EXACT_F32) or os.environ.get("MISO_EXACT_F32", "0") not in ("", "0")
+
+
+def base_record(args, step, world, elapsed):
+    """The result line of a plain run (rank 0): the headline figure and the configuration it was measured on."""
+    from miso_amd import _lib
     ms_per_step = elapsed / args.steps * 1e3
+    value = world * N_POINTS * args.steps / elapsed
+    exact = _exact_f32()
+    L = len(LEVELS)
+    return {
+        "metric": "3D point-samples/sec (encode+decode fwd+bwd), 262144-pt batch",
+        "value": value, "unit": "point-samples/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "settle_steps": SETTLE_STEPS, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (exact fp32 decoder chains)" if exact else
+                 "f32 (decoder products as bf16x3 pieces on the 16-bit matrix cores, fp32 accumulate: error against float64 "
+                 "equal to the exact fp32 chains', tests/test_split_precision.py; MISO_F_EXACT_F32 selects those)",
+        "data": "synthetic",
+        "config": {"workload": "cfg-2: one submap per GPU, 3-level {32,64,128}^3 grid C=8 + MLP 24-64-64-1 "
+                               "(frozen, seeded random weights), 262144 uniform-in-bbox points per GPU per "
+                               "step, L1 loss, grads to all levels",
+                   "points_per_gpu": N_POINTS, "levels": list(LEVELS), "feature_dim": C,
+                   "decoder": [C * L, HIDDEN, HIDDEN, 1], "parallelism": f"submap-parallel x{world}",
+                   "launch": "one graph replay per step" if step._use_graph else
+                             "five stream launches per step (a graph replay leaves the device idle ~6 us between replays)"},
+        "binned": step.sorted is not None,
+        "library": _lib.load().miso_version().decode(),
+    }
+
+
+# a seeded sample of a gradient level larger than this many floats is written instead of the whole level
+DUMP_MAX_FLOATS = 1 << 22
+
+
+def dump_outputs(step, out_dir):
+    """What a caller of the timed step receives after its last iteration, as float32 .npy files in `out_dir`:
+    loss.npy (2,) = [sdf term, free-space term], and grad_level<l>.npy, the gradient of grid level l in its logical
+    (1, C, Z, Y, X) layout -- or, for a level of more than DUMP_MAX_FLOATS floats (the finest one, 67 MB), a fixed
+    sample of DUMP_MAX_FLOATS entries of it (flat indices drawn with seed 0, the same in every run), as
+    grad_level<l>_sample.npy.  About 25 MB in all."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"loss": step.loss}
+    for l, g in enumerate(step.grads):
+        if g is None:
+            continue
+        flat = g.contiguous().reshape(-1)
+        if flat.numel() > DUMP_MAX_FLOATS:
+            idx = torch.randint(flat.numel(), (DUMP_MAX_FLOATS,), generator=torch.Generator().manual_seed(0))
+            arrays[f"grad_level{l}_sample"] = flat[idx.to(flat.device)]
+        else:
+            arrays[f"grad_level{l}"] = g.contiguous()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().float().cpu().numpy())
+
+
+def headline_record(args, step, dev, world, elapsed):
+    """The --full record (rank 0): the result line of base_record, per-kernel durations measured live with HIP events,
+    roofline."""
+    from miso_amd import ops
     value = world * N_POINTS * args.steps / elapsed
 
     # ---- per-kernel durations (HIP events on the launch stream) and roofline --------------------
@@ -529,9 +612,7 @@ def headline_record(args, step, dev, world, elapsed):
     # HBM traffic and MFMA busy fraction are PMC figures (rocprofv3 --pmc, separate passes: tools/profile_bench.sh ->
     # tools/pmc_summary.py -> profiles/<round>_pmc_summary.json).  They are quoted only while that file was measured
     # on the kernels of THIS tree: it carries the source hash miso_version() embeds.
-    from miso_amd import _lib
     from miso_amd.csrc_hash import source_hash
-    lib_ver = _lib.load().miso_version().decode()
     traffic, mfma_pmc, pmc_note = None, None, "no PMC summary for these kernel sources (run tools/profile_bench.sh)"
     import glob
     for pmc in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_summary.json")), reverse=True):
@@ -553,7 +634,7 @@ def headline_record(args, step, dev, world, elapsed):
     F_ = L * C
     mlp_flop = 2.0 * (F_ * HIDDEN + HIDDEN * HIDDEN + HIDDEN) * N_POINTS
     t_bwd_mfma = t_bwd - t_pull
-    exact = bool(ops._EXACT_F32) or os.environ.get("MISO_EXACT_F32", "0") not in ("", "0")
+    exact = _exact_f32()
     if exact:
         # exact fp32 chains (v_mfma_f32_32x32x2_f32): the decoder's FLOPs over the fp32 matrix peak
         peak, flop_f, flop_b = 157.3, mlp_flop, mlp_flop
@@ -599,31 +680,15 @@ def headline_record(args, step, dev, world, elapsed):
                                 if dom[0] == "grad_pull_mc_kernel" else
                                 "grad_pull_block_kernel + its drain launch for queued slices of crowded tiles")
 
-    out = {
-        "metric": "3D point-samples/sec (encode+decode fwd+bwd), 262144-pt batch",
-        "value": value, "unit": "point-samples/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "settle_steps": SETTLE_STEPS, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32 (exact fp32 decoder chains)" if exact else
-                 "f32 (decoder products as bf16x3 pieces on the 16-bit matrix cores, fp32 accumulate: error against float64 "
-                 "equal to the exact fp32 chains', tests/test_split_precision.py; MISO_F_EXACT_F32 selects those)",
-        "data": "synthetic",
-        "config": {"workload": "cfg-2: one submap per GPU, 3-level {32,64,128}^3 grid C=8 + MLP 24-64-64-1 "
-                               "(frozen, seeded random weights), 262144 uniform-in-bbox points per GPU per "
-                               "step, L1 loss, grads to all levels",
-                   "points_per_gpu": N_POINTS, "levels": list(LEVELS), "feature_dim": C,
-                   "decoder": [C * L, HIDDEN, HIDDEN, 1], "parallelism": f"submap-parallel x{world}",
-                   "launch": "one graph replay per step" if step._use_graph else
-                             "five stream launches per step (a graph replay leaves the device idle ~6 us between replays)"},
+    out = base_record(args, step, world, elapsed)
+    out.update({
         "roofline": roofline,
         "step_fraction_of_hbm_roofline": value / world * (20 + 64 * L * C) / 8e12,
         "kernels_us": kernels_us,
-        "binned": sb is not None,
-        "library": lib_ver,
         "step_note": "a training step needs the loss and the gradients, not the per-point SDF in caller order "
                      "(keep_sdf=False): the 4 B/point SDF write of SURVEY 8(d)'s B_alg is not moved by this step "
                      "(1 MB of 408 MB); step_fraction_of_hbm_roofline uses the full B_alg = 20 + 64 L C",
-    }
+    })
     return out
 
 

@@ -2,10 +2,12 @@
 unmodified).  With ``miso_amd.compat`` installed -- ``grid_opt`` and ``cuda_gridsample`` resolve to this package -- and
 test-only stand-ins for the two GUI / evaluation packages the demos import at module top (open3d, evo: not in the
 image and outside the hot path), each demo's import block executes and every global name its functions use resolves.
-The demo sources are read from the reference checkout, which exists in the build container only: skipped elsewhere.
-tools/demo_synthetic.py then runs the two demos' call sequence end to end on synthetic frames (GPU test below)."""
+What the demos import and use is read from tests/golden/demo_surface.json (names only, written from the reference's
+demo sources by tools/make_demo_surface_golden.py).  tools/demo_synthetic.py then runs the two demos' call sequence end
+to end on synthetic frames (GPU test below)."""
 import ast
 import builtins
+import json
 import os
 import subprocess
 import sys
@@ -13,7 +15,6 @@ import types
 
 import pytest
 
-REF = os.environ.get("MISO_REFERENCE", "/root/reference")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -33,7 +34,18 @@ def _stub(name):
     return m
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "demo")), reason="reference checkout not present")
+def _import_nodes(spec):
+    """The recorded import statements of a demo as ast nodes, in the demo's order."""
+    nodes = []
+    for st in spec:
+        if "import" in st:
+            nodes.append(ast.Import(names=[ast.alias(name=n, asname=a) for n, a in st["import"]]))
+        else:
+            nodes.append(ast.ImportFrom(module=st["from"], names=[ast.alias(name=n, asname=a) for n, a in st["names"]],
+                                        level=st["level"]))
+    return [ast.fix_missing_locations(n) for n in nodes]
+
+
 @pytest.mark.parametrize("demo", ["build_submaps.py", "align_submaps.py"])
 def test_demo_import_block_and_globals_resolve(demo, monkeypatch):
     import miso_amd.compat  # noqa: F401
@@ -41,30 +53,20 @@ def test_demo_import_block_and_globals_resolve(demo, monkeypatch):
         monkeypatch.setitem(sys.modules, name, _stub(name))
     sys.modules["evo"].core = sys.modules["evo.core"]
     sys.modules["evo.core"].metrics = sys.modules["evo.core.metrics"]
-    src = open(os.path.join(REF, "demo", demo)).read()
-    tree = ast.parse(src)
-    imports = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
+    with open(os.path.join(ROOT, "tests", "golden", "demo_surface.json")) as f:
+        surface = json.load(f)[demo]
+    imports = _import_nodes(surface["imports"])
+    assert imports, demo
     ns = {"__name__": "demo_under_test"}
     exec(compile(ast.Module(body=imports, type_ignores=[]), demo, "exec"), ns)
     # module-level definitions of the script itself
-    defined = set(ns) | {n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.ClassDef))}
-    for node in tree.body:
-        if isinstance(node, ast.Assign):
-            defined |= {t.id for t in node.targets if isinstance(t, ast.Name)}
+    defined = set(ns) | set(surface["defined"])
+    # the names each of its functions loads without binding them itself
     missing = {}
-    for fn in (n for n in tree.body if isinstance(n, ast.FunctionDef)):
-        local = {a.arg for a in fn.args.args + fn.args.kwonlyargs}
-        for node in ast.walk(fn):
-            if isinstance(node, ast.Name) and isinstance(node.ctx, ast.Store):
-                local.add(node.id)
-            elif isinstance(node, (ast.For, ast.comprehension)):
-                local |= {t.id for t in ast.walk(node.target) if isinstance(t, ast.Name)}
-            elif isinstance(node, ast.withitem) and node.optional_vars is not None:
-                local |= {t.id for t in ast.walk(node.optional_vars) if isinstance(t, ast.Name)}
-        for node in ast.walk(fn):
-            if isinstance(node, ast.Name) and isinstance(node.ctx, ast.Load):
-                if node.id not in local and node.id not in defined and not hasattr(builtins, node.id):
-                    missing.setdefault(fn.name, set()).add(node.id)
+    for fn, names in surface["functions"].items():
+        for name in names:
+            if name not in defined and not hasattr(builtins, name):
+                missing.setdefault(fn, set()).add(name)
     assert not missing, f"{demo}: names the mirror does not provide: {missing}"
     # the attributes the demos reach for on the imported modules
     for mod, attrs in (("utils_scannet", ("scannet_scenes", "create_scannet_dataset")),

@@ -101,7 +101,8 @@ def test_rccl_single_rank_group_runs_the_collectives_and_the_sharded_loop(tmp_pa
 def test_bench_headline_survives_a_rank_that_fails_inside_an_extra():
     env = dict(os.environ, MISO_BENCH_BACKEND="gloo", MISO_BENCH_DEVICE="0", MISO_BENCH_FAIL="1:map_cfg3")
     t0 = time.time()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "3",
+                          "--full"],
                          capture_output=True, text=True, timeout=400, env=env)
     took = time.time() - t0
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

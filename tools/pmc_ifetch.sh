@@ -3,8 +3,8 @@
 out=gpurun_out/pmc_if
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_IFETCH InstrFetchLatency SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $out/a -o q -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $out/a.log 2>&1
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $out/b -o q -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $out/b.log 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_IFETCH InstrFetchLatency SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $out/a -o q -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $out/a.log 2>&1
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $out/b -o q -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $out/b.log 2>&1
 python3 - "$out" <<'PY'
 import csv, sys, glob, collections, re
 out = sys.argv[1]
