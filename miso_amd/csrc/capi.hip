@@ -387,6 +387,7 @@ int miso_sdf_bwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* pa
 // contributes nothing else (miso_encode_bwd2 on these rows is the whole double backward).
 int miso_sdf_bwd_rows(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
                       const float* grad_sdf, const uint32_t* relu_mask, float* grad_x, float* dfeat_rows, void* stream) {
+  if (!grid || !mlp) return MISO_E_BADARG;
   if (!dfeat_rows) return sdf_bwd_impl(grid, mlp, packed, x, n, grad_sdf, relu_mask, grad_x, nullptr, nullptr, stream);
   if (n < 0 || !packed || (n > 0 && (!grad_sdf || !relu_mask || !x))) return MISO_E_BADARG;
   if ((((uintptr_t)packed) & 15u) != 0 || (((uintptr_t)dfeat_rows) & 15u) != 0) return MISO_E_BADARG;

@@ -100,6 +100,8 @@ struct Axis {
   float mult;  // d ix / d x  (0 where border padding clipped the coordinate)
 };
 
+// (Without OCML_BASIC_ROUNDED_OPERATIONS HIP's __fadd_rn / __fsub_rn / __fmul_rn are plain operators, so the compiler may
+// contract them: (xn + 1) * size - 1 below is one v_fma_f32, a single rounding.  The same holds in axis_from_norm.)
 __device__ __forceinline__ Axis axis_coord(float x, float bmin, float bmax, int size, uint32_t flags) {
   float xn = x;
   float m = 1.0f;

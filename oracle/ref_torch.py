@@ -15,7 +15,12 @@ Parity status
   to any order (ATen has no double backward for ``grid_sampler_3d``); it is
   pinned against ``F.grid_sample`` (value + first derivatives), against
   ``torch.autograd.gradgradcheck`` in fp64, and against the known-answer inputs
-  of the reference's ``third_party/cuda_gridsample_grad2/test3d.py:17-35``.
+  of the reference's ``third_party/cuda_gridsample_grad2/test3d.py:17-35``.  With ``border`` padding it follows
+  ATen's set-grad convention: no coordinate gradient at or beyond either clip limit.
+* ``grid_sample_bwd2_aten`` is the second backward of the sampler from ATen calls alone (exact first backward plus
+  differences within a cell); ``trilinear_bwd2`` is the same by autograd through ``trilinear_gather``.  The two agree
+  to 1e-9 where the first applies, and the restatement is pinned to the reference's ``naive_gridsample.py`` off the
+  faces (``tests/golden/grad2_naive.npz``).
 * ``so3_exp_map`` / ``hat`` restate pytorch3d (un-vendored, unpinned
   ``git+https://github.com/facebookresearch/pytorch3d.git`` in the reference's
   ``environment.yaml:114``).  pytorch3d is absent from the image, so that
@@ -91,7 +96,10 @@ def trilinear_gather(feature: torch.Tensor, xn: torch.Tensor,
     for axis, size in ((0, w), (1, h), (2, d)):
         i = _unnormalize(xn[:, axis], size, align_corners)
         if padding_mode == "border":
-            i = torch.clamp(i, 0, size - 1)
+            # ATen clip_coordinates_set_grad (gridsample_cuda.cu:297-299): the clipped coordinate carries no
+            # gradient at either limit or beyond it (torch.clamp would pass it through at the limits themselves)
+            clip = (i <= 0) | (i >= size - 1)
+            i = torch.where(clip, i.detach().clamp(0, size - 1), i)
         coords.append(i)
     ix, iy, iz = coords
     x0 = torch.floor(ix).detach()
@@ -143,6 +151,152 @@ def encode_gather(features: Sequence[torch.Tensor], bound: torch.Tensor,
             v = torch.zeros_like(v)
         feats.append(v)
     return torch.cat(feats, dim=1)
+
+
+# --------------------------------------------------------------------------- #
+# Second backward of the sampler (gridsample_grad2.grad2_3d), two independent ways
+# --------------------------------------------------------------------------- #
+def trilinear_bwd2(feature, xn, gout, ggx=None, ggf=None, align_corners=False, padding_mode="zeros"):
+    """Double backward of ``trilinear_gather`` by autograd: with cotangents ``ggx`` (N,3) of grad_x and ``ggf``
+    (shape of feature) of grad_feature, returns (gg_out (N,C), g_x (N,3), g_feature) -- the three outputs of
+    gridsample_grad2.grad2_3d.  Valid everywhere (lattice planes and border clip limits included: the one-sided
+    floor / set-grad conventions of ATen are built into the restatement)."""
+    f = feature.detach().requires_grad_(True)
+    x = xn.detach().requires_grad_(True)
+    go = gout.detach().requires_grad_(True)
+    out = trilinear_gather(f, x, align_corners, padding_mode)
+    gf, gx = torch.autograd.grad(out, [f, x], go, create_graph=True)
+    s = 0
+    if ggx is not None:
+        s = s + (gx * ggx).sum()
+    if ggf is not None:
+        s = s + (gf * ggf).sum()
+    if not torch.is_tensor(s) or not s.requires_grad:
+        return torch.zeros_like(gout), torch.zeros_like(xn), torch.zeros_like(feature)
+    r = torch.autograd.grad(s, [go, x, f], allow_unused=True)
+    return tuple(torch.zeros_like(t) if g is None else g for g, t in zip(r, (gout, xn, feature)))
+
+
+def fd_safe(xn, sizes_xyz, align_corners, margin=1e-3):
+    """(N,) bool: every unnormalised coordinate lies at least ``margin`` index units from an integer (cell planes
+    and both clip limits are integers) and is finite -- where ``grid_sample_bwd2_aten``'s differences stay in a cell."""
+    ok = torch.ones(xn.shape[0], dtype=torch.bool, device=xn.device)
+    for axis, size in enumerate(sizes_xyz):
+        i = _unnormalize(xn[:, axis].double(), size, align_corners)
+        ok &= torch.isfinite(i) & ((i - torch.round(i)).abs() >= margin)
+    return ok
+
+
+def _fd5(fn, h):
+    """d/dt fn(t) at 0, five-point stencil: exact up to rounding for polynomials of degree <= 4 (the trilinear
+    interpolant and its gradient are of degree <= 3 along a line that stays in one cell)."""
+    return (8 * (fn(h) - fn(-h)) - (fn(2 * h) - fn(-2 * h))) / (12 * h)
+
+
+def grid_sample_bwd2_aten(feature, xn, gout, ggx=None, ggf=None, padding_mode="zeros", align_corners=False,
+                          step=2.0 ** -12):
+    """The second backward of the sampler from ATen alone: ``F.grid_sample`` and its first backward, fp64.
+
+    With E(f; x) the sample and phi(x) = <gout, E(feature; x)>:
+      gg_out    = D_ggx E(feature; x) + E(ggf; x)
+      g_x       = D_ggx grad_x phi(x) + grad_x <gout, E(ggf; x)>            (the Hessian of phi is symmetric)
+      g_feature = D_ggx grad_feature phi(x)
+    where D_ggx is the derivative along each point's ggx, taken by a five-point difference of exact ATen calls along
+    the unit direction (step ``step`` index units on the finest axis) and scaled by |ggx|.  The interpolant is
+    multilinear within a cell, so the difference is exact up to rounding wherever the stencil stays in one cell:
+    the returned mask ``fd_safe`` marks those points (1e-3 index units from every integer); elsewhere the values are
+    not an oracle.  Returns (gg_out, g_x, g_feature, safe), fp64."""
+    feature, xn, gout = feature.double(), xn.double(), gout.double()
+    _, c, d, h, w = feature.shape
+    n = xn.shape[0]
+    scale = max([(s - 1) / 2 if align_corners else s / 2 for s in (w, h, d)] + [1e-30])
+    hn = step / scale                                           # normalised step: <= ``step`` index units per axis
+    if ggx is not None:
+        ggx = ggx.double()
+        nrm = ggx.norm(dim=1, keepdim=True)
+        u = torch.where(nrm > 0, ggx / torch.where(nrm > 0, nrm, torch.ones_like(nrm)), torch.zeros_like(ggx))
+    gg_out = torch.zeros(n, c, dtype=torch.float64)
+    g_x = torch.zeros(n, 3, dtype=torch.float64)
+    g_f = torch.zeros_like(feature)
+
+    def E(f, x):
+        return grid_sample_stock(f, x, align_corners, padding_mode)
+
+    def vjp(f, x, go, wrt_f):
+        f_ = f.detach().requires_grad_(wrt_f)
+        x_ = x.detach().requires_grad_(not wrt_f)
+        out = E(f_, x_)
+        (g,) = torch.autograd.grad(out, [f_ if wrt_f else x_], go)
+        return g
+
+    if ggx is not None:
+        gg_out = gg_out + nrm * _fd5(lambda t: E(feature, xn + t * u), hn)
+        g_x = g_x + nrm * _fd5(lambda t: vjp(feature, xn + t * u, gout, False), hn)
+        g_f = g_f + _fd5(lambda t: vjp(feature, xn + t * u, gout * nrm, True), hn)
+    if ggf is not None:
+        gg_out = gg_out + E(ggf.double(), xn)
+        g_x = g_x + vjp(ggf.double(), xn, gout, False)
+    return gg_out, g_x, g_f, fd_safe(xn, (w, h, d), align_corners)
+
+
+def _encode_bwd2(one, features, bound, x, gout, ggx, ggf, ignore_level):
+    x = x.double()
+    bound = bound.double().to(x.device)
+    xn = normalize_coordinates(x, bound)
+    sc = (2 / (bound[:, 1] - bound[:, 0])).view(1, 3)          # d xn / d x
+    n = x.shape[0]
+    gg_out = torch.zeros(n, gout.shape[1], dtype=torch.float64)
+    g_x = torch.zeros(n, 3, dtype=torch.float64)
+    g_f, safe = [], torch.ones(n, dtype=torch.bool)
+    c0 = 0
+    for l, f in enumerate(features):
+        c = f.shape[1]
+        if ignore_level is not None and ignore_level[l]:
+            g_f.append(torch.zeros_like(f, dtype=torch.float64))
+        else:
+            r = one(f, xn, gout[:, c0:c0 + c], None if ggx is None else ggx.double() * sc,
+                    None if ggf is None else ggf[l])
+            gg_out[:, c0:c0 + c] = r[0]
+            g_x += r[1] * sc
+            g_f.append(r[2])
+            if len(r) > 3:
+                safe &= r[3]
+        c0 += c
+    return gg_out, g_x, g_f, safe
+
+
+def encode_bwd2_aten(features, bound, x, gout, ggx=None, ggf=None, ignore_level=None):
+    """``grid_sample_bwd2_aten`` in the encode form (metres, levels concatenated, zeros padding, align_corners=False):
+    (gg_out (N,F), g_x (N,3) per metre, [g_feature per level], safe (N,)) in fp64.  ``ggf``: per level or None."""
+    return _encode_bwd2(lambda f, xn, go, e, gg: grid_sample_bwd2_aten(f, xn, go, e, gg, "zeros", False),
+                        features, bound, x, gout, ggx, ggf, ignore_level)
+
+
+def encode_bwd2_gather(features, bound, x, gout, ggx=None, ggf=None, ignore_level=None):
+    """The same three outputs by autograd through ``trilinear_gather`` (any dtype of the inputs: fp64 for the oracle,
+    fp32 to measure what a float32 evaluation of the formula costs).  Returns (gg_out, g_x, [g_feature])."""
+    dt = features[0].dtype
+    x = x.to(dt)
+    bound = bound.to(dt).to(x.device)
+    xn = normalize_coordinates(x, bound)
+    sc = (2 / (bound[:, 1] - bound[:, 0])).view(1, 3)
+    n = x.shape[0]
+    gg_out = torch.zeros(n, gout.shape[1], dtype=dt)
+    g_x = torch.zeros(n, 3, dtype=dt)
+    g_f = []
+    c0 = 0
+    for l, f in enumerate(features):
+        c = f.shape[1]
+        if ignore_level is not None and ignore_level[l]:
+            g_f.append(torch.zeros_like(f))
+        else:
+            r = trilinear_bwd2(f, xn, gout[:, c0:c0 + c].to(dt), None if ggx is None else ggx.to(dt) * sc,
+                               None if ggf is None or ggf[l] is None else ggf[l].to(dt), False, "zeros")
+            gg_out[:, c0:c0 + c] = r[0]
+            g_x += r[1] * sc
+            g_f.append(r[2])
+        c0 += c
+    return gg_out, g_x, g_f
 
 
 # --------------------------------------------------------------------------- #

@@ -864,6 +864,10 @@ def test_capi_rejects_bad_arguments_before_launching():
                                  ops._ptr(rows), st) == BAD
     assert lib.miso_sdf_bwd_rows(C.byref(g), C.byref(m), ops._ptr(packed), ops._ptr(x), n, ops._ptr(gs), ops._ptr(mask), None,
                                  C.c_void_p(rows.data_ptr() + 4), st) == BAD                       # rows must be 16-B aligned
+    assert lib.miso_sdf_bwd_rows(None, C.byref(m), ops._ptr(packed), ops._ptr(x), n, ops._ptr(gs), ops._ptr(mask), None,
+                                 ops._ptr(rows), st) == BAD                                        # no grid
+    assert lib.miso_sdf_bwd_rows(C.byref(g), None, ops._ptr(packed), ops._ptr(x), n, ops._ptr(gs), ops._ptr(mask), None,
+                                 ops._ptr(rows), st) == BAD                                        # no decoder
     g4 = ops._fill_grid(fdd, meta)
     g4.flags = _lib.F_GRAD_OVERWRITE
     assert lib.miso_sdf_bwd_rows(C.byref(g4), C.byref(m), ops._ptr(packed), ops._ptr(x), n, ops._ptr(gs), ops._ptr(mask), None,

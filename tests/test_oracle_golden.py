@@ -243,3 +243,131 @@ def test_lidar_samples_match_reference():
     assert torch.equal(cat["sdfs_valid"], T(g["lidar_batch_valid"]))
     assert torch.equal(cat["signs"], T(g["lidar_batch_signs"]))
     torch.testing.assert_close(cat["weights"], T(g["lidar_batch_weights"]), rtol=0, atol=1e-6)
+
+
+# --------------------------------------------------------------------------- #
+# The second backward of the sampler: the restatement against an independent fp64 oracle built from ATen alone
+# (oracle.grid_sample_bwd2_aten) and against the reference's naive sampler (tests/golden/grad2_naive.npz)
+# --------------------------------------------------------------------------- #
+MODES = [(pad, ac) for pad in ("zeros", "border") for ac in (False, True)]
+
+
+def _max_rel(a, b):
+    return ((a - b).abs().max() / b.abs().max().clamp_min(1e-300)).item()
+
+
+@pytest.mark.parametrize("pad,ac", MODES)
+@pytest.mark.parametrize("cot", ["ggx", "ggf", "both"])
+def test_gather_double_backward_equals_aten_differences(pad, ac, cot):
+    """(a) gg_out, g_x and g_feature of the restatement equal the ATen-built oracle to 1e-9 on FD-safe points, in- and
+    out-of-bounds."""
+    g = torch.Generator().manual_seed(11)
+    f = torch.randn(1, 3, 5, 6, 7, generator=g, dtype=torch.float64)
+    x = torch.rand(600, 3, generator=g, dtype=torch.float64) * 2.8 - 1.4
+    go = torch.randn(600, 3, generator=g, dtype=torch.float64)
+    ggx = torch.randn(600, 3, generator=g, dtype=torch.float64) if cot != "ggf" else None
+    ggf = torch.randn(f.shape, generator=g, dtype=torch.float64) if cot != "ggx" else None
+    safe = R.fd_safe(x, (7, 6, 5), ac)
+    assert safe.sum() > 500
+    x, go = x[safe], go[safe]
+    ggx = None if ggx is None else ggx[safe]
+    a = R.grid_sample_bwd2_aten(f, x, go, ggx, ggf, pad, ac)
+    b = R.trilinear_bwd2(f, x, go, ggx, ggf, ac, pad)
+    assert a[3].all()
+    for u, v in zip(b, a[:3]):
+        if v.abs().max() > 0:
+            assert _max_rel(u, v) < 1e-9
+        else:
+            assert u.abs().max() == 0
+
+
+def test_restatement_reproduces_the_reference_naive_sampler():
+    """(b) tests/golden/grad2_naive.npz: the reference's naive_gridsample.py (border, align_corners=True) run as
+    test3d.py:cmp_with_naive does, fp64.  Off the faces every output agrees; at a face the coordinate gradients follow
+    ATen (set-grad zero at the clip limits), which naive does not at the lower face -- there the first coordinate
+    gradient is checked against ATen instead."""
+    g = _load("grad2_naive")
+    n_face = 0
+    for k in range(int(g["n_cases"])):
+        image, optical = T(g[f"{k}_image"]), T(g[f"{k}_optical"])
+        face = T(g[f"{k}_on_face"])
+        n_face += int(face.sum())
+        q = optical.reshape(-1, 3)
+
+        def run(qq):
+            im = image.clone().requires_grad_(True)
+            qq = qq.clone().requires_grad_(True)
+            out = R.trilinear_gather(im, qq, True, "border")
+            gi, gq = torch.autograd.grad((out ** 2).sum(), [im, qq], create_graph=True)
+            g2i, g2q = torch.autograd.grad(gi.sum() + gq.sum(), [im, qq])
+            return out.detach(), gi.detach(), gq.detach(), g2i, g2q
+
+        val, gi, gq, g2i, g2q = run(q)
+        tol = dict(rtol=1e-12, atol=1e-12)
+        torch.testing.assert_close(val, T(g[f"{k}_value"]).reshape(val.shape[1], -1).t(), **tol)
+        torch.testing.assert_close(gi, T(g[f"{k}_g_image"]), **tol)
+        off = ~face
+        torch.testing.assert_close(gq[off], T(g[f"{k}_g_optical"]).reshape(-1, 3)[off], **tol)
+        torch.testing.assert_close(g2q[off], T(g[f"{k}_g2_optical"]).reshape(-1, 3)[off], **tol)
+        if off.any():
+            torch.testing.assert_close(run(q[off])[3], T(g[f"{k}_g2_image_off"]), **tol)
+        if face.any():
+            qa = q[face].clone().requires_grad_(True)
+            b = R.grid_sample_stock(image, qa, True, "border")
+            (ga,) = torch.autograd.grad((b ** 2).sum(), [qa])
+            torch.testing.assert_close(gq[face], ga, **tol)
+    assert n_face >= 20, "the lattice case must put points on the faces"
+
+
+def _lattice_points(sizes_xyz, ac, n, g):
+    """Normalised points whose unnormalised coordinates are half-integers from -1 to size (cell planes, edges,
+    vertices, both faces, half a cell outside): dyadic for these sizes, hence exact in every step."""
+    cols = []
+    for s in sizes_xyz:
+        i = torch.randint(-2, 2 * s + 1, (n,), generator=g).double() / 2
+        cols.append(i * 2 / (s - 1) - 1 if ac else (2 * i + 1) / s - 1)
+    return torch.stack(cols, 1)
+
+
+@pytest.mark.parametrize("pad,ac", MODES)
+def test_gather_first_derivatives_match_aten_on_planes_faces_and_vertices(pad, ac):
+    """(c) value and first derivatives on the lattice itself, which random points never reach."""
+    g = torch.Generator().manual_seed(3)
+    sizes = (9, 5, 3) if ac else (8, 4, 2)
+    inp = torch.randn(1, 2, sizes[2], sizes[1], sizes[0], generator=g, dtype=torch.float64)
+    xn = _lattice_points(sizes, ac, 400, g)
+    assert (~R.fd_safe(xn, sizes, ac)).float().mean() > 0.7     # on a plane in at least one axis
+    go = torch.randn(400, 2, generator=g, dtype=torch.float64)
+    outs = []
+    for fn in (R.trilinear_gather, R.grid_sample_stock):
+        i_, x_ = inp.clone().requires_grad_(True), xn.clone().requires_grad_(True)
+        o = fn(i_, x_, ac, pad)
+        outs.append((o.detach(), *torch.autograd.grad((o * go).sum(), [i_, x_])))
+    for a, b in zip(*outs):
+        torch.testing.assert_close(a, b, rtol=1e-12, atol=1e-12)
+
+
+def test_encode_form_double_backward_two_ways():
+    """(d) the encode form (bounds in metres as cfg-3, several levels, an ignored level): restatement = ATen-built oracle
+    on FD-safe points, for ggx only, ggf on every level, ggf on one level."""
+    g = torch.Generator().manual_seed(7)
+    bound = torch.tensor([[-10.0, 10.0], [-5.0, 5.0], [-10.0, 10.0]], dtype=torch.float64)
+    feats = [torch.randn(1, 2, z, y, x, generator=g, dtype=torch.float64) for (x, y, z) in ((6, 4, 5), (11, 7, 9), (20, 10, 20))]
+    n = 500
+    x = (torch.rand(n, 3, generator=g, dtype=torch.float64) * 1.2 - 0.1) * (bound[:, 1] - bound[:, 0]) + bound[:, 0]
+    gout = torch.randn(n, 6, generator=g, dtype=torch.float64)
+    ggx = torch.randn(n, 3, generator=g, dtype=torch.float64)
+    ggf = [torch.randn(f.shape, generator=g, dtype=torch.float64) for f in feats]
+    ign = [False, True, False]
+    for e, gg in ((ggx, None), (ggx, ggf), (None, [ggf[0], None, None])):
+        a = R.encode_bwd2_aten(feats, bound, x, gout, e, gg, ign)
+        s = a[3]
+        assert s.sum() > 400
+        a = R.encode_bwd2_aten(feats, bound, x[s], gout[s], None if e is None else e[s], gg, ign)
+        b = R.encode_bwd2_gather(feats, bound, x[s], gout[s], None if e is None else e[s], gg, ign)
+        assert (a[0][:, 2:4] == 0).all() and (b[0][:, 2:4] == 0).all() and (a[2][1] == 0).all()
+        for u, v in zip([b[0], b[1]] + b[2], [a[0], a[1]] + a[2]):
+            if v.abs().max() > 0:
+                assert _max_rel(u, v) < 1e-9
+            else:
+                assert u.abs().max() == 0

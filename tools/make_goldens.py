@@ -919,6 +919,83 @@ def gen_second_order(GridNet, rloss, risdf, gc):
     print("[second_order]", {k: float(v) for k, v in out.items() if np.ndim(v) == 0})
 
 
+def gen_grad2_naive(gc):
+    """The reference's pure-torch sampler (third_party/cuda_gridsample_grad2/naive_gridsample.py, border padding,
+    align_corners=True), imported and run in fp64 as the ``nv_*`` half of test3d.py:176-208 (cmp_with_naive):
+    out = sum(grid_sample_3d(image, optical)^2); its gradients w.r.t. image and optical with create_graph=True; the
+    gradients of sum(g_image) + sum(g_optical).  Inputs: test3d.py:17-30, six seeded random volumes as
+    create_random_input makes them (test3d.py:154-174; batch 1, non-cubic sizes 2-9, C in {1, 3, 8}, in- and
+    out-of-bounds points), and one dyadic lattice (size - 1 a power of two: points on cell planes, edges, vertices and
+    both faces, exact in fp32 too).
+
+    At a lower face (unnormalised coordinate exactly 0) the naive code differentiates the clipped coordinate, where
+    ATen's grid_sampler_compute_source_index_set_grad -- what the reference's CUDA kernel runs -- gives zero; so each
+    point carries an ``on_face`` flag, and ``g2_image_off`` is the image second gradient over the points off every
+    face (the per-point outputs depend on their own point only)."""
+    sys.path.insert(0, os.path.join(REF, "third_party", "cuda_gridsample_grad2"))
+    import naive_gridsample as nv
+    from torch.autograd import grad
+
+    def run(image, optical):
+        image = image.clone().requires_grad_(True)
+        optical = optical.clone().requires_grad_(True)
+        out = nv.grid_sample_3d(image, optical)
+        val = out.detach().clone()
+        s = torch.sum(out ** 2)
+        g_image, g_optical = grad(s, [image, optical], create_graph=True)
+        g2_image, g2_optical = grad(torch.sum(g_image) + torch.sum(g_optical), [image, optical])
+        return val, g_image.detach(), g_optical.detach(), g2_image, g2_optical
+
+    def on_face(image, optical):
+        _, _, d, h, w = image.shape
+        q = optical.reshape(-1, 3)
+        f = torch.zeros(q.shape[0], dtype=torch.bool)
+        for a, size in enumerate((w, h, d)):
+            i = (q[:, a] + 1) / 2 * (size - 1)
+            f |= (i == 0) | (i == size - 1)
+        return f
+
+    cases = [
+        (np.arange(27).reshape(1, 1, 3, 3, 3), np.array([0.1, 0.1, 0.1]).reshape(1, 1, 1, 1, 3)),
+        (np.array([[1, 2], [3, 4], [5, 6], [7, 8]]).reshape(1, 1, 2, 2, 2), np.array([0.1, 1.1, 0.1]).reshape(1, 1, 1, 1, 3)),
+        (np.arange(27).reshape(1, 1, 3, 3, 3), np.array([-2.1, 0.1, 0.1]).reshape(1, 1, 1, 1, 3)),
+    ]
+    rs = np.random.RandomState(20260)
+    for k, c in enumerate((1, 3, 8, 1, 3, 8)):
+        d, h, w = (int(v) for v in rs.randint(2, 10, size=3))
+        oob = k % 2 == 1
+        lo, hi = (-2, 2) if oob else (-1, 1)
+        dg, hg, wg = 2, 3, 5
+        optical = rs.uniform(lo, hi, size=(1, dg, hg, wg, 3))
+        image = rs.normal(size=(1, c, d, h, w))
+        cases.append((image, optical))
+    # dyadic lattice: (size - 1) in {2, 4, 8}; index coordinates on the half-integers from -1 to size, every one of
+    # which (vertices, edge / plane midpoints, both faces, half a cell outside) is a dyadic fraction
+    d, h, w = 3, 5, 9
+    image = rs.normal(size=(1, 4, d, h, w))
+    idx = [rs.randint(-2, 2 * s + 1, size=120) / 2.0 for s in (w, h, d)]
+    idx[0][:8] = [0, w - 1, 0, w - 1, 3, 0, 2.5, w - 1]
+    idx[1][:8] = [0, h - 1, h - 1, 0, 2, 1.5, 0, 2]
+    idx[2][:8] = [0, d - 1, 0, 1, d - 1, 1, 0.5, 1]
+    optical = np.stack([2 * i / (s - 1) - 1 for i, s in zip(idx, (w, h, d))], axis=-1).reshape(1, 1, 1, 120, 3)
+    cases.append((image, optical))
+    out = {"n_cases": np.int64(len(cases))}
+    for k, (image, optical) in enumerate(cases):
+        image = torch.tensor(image, dtype=torch.float64)
+        optical = torch.tensor(optical, dtype=torch.float64)
+        val, gi, go, g2i, g2o = run(image, optical)
+        face = on_face(image, optical)
+        off = torch.nonzero(~face).squeeze(1)
+        q = optical.reshape(-1, 3)[off].reshape(1, 1, 1, -1, 3)
+        g2i_off = run(image, q)[3] if off.numel() else torch.zeros_like(image)
+        for key, v in (("image", image), ("optical", optical), ("value", val), ("g_image", gi), ("g_optical", go),
+                       ("g2_image", g2i), ("g2_optical", g2o), ("g2_image_off", g2i_off), ("on_face", face)):
+            out[f"{k}_{key}"] = v.numpy()
+    np.savez_compressed(gc.golden_path("grad2_naive"), **out)
+    print("[grad2_naive]", len(cases), "cases,", sum(int(out[f"{k}_on_face"].sum()) for k in range(len(cases))),
+          "points on a face")
+
+
 def main():
     import_reference()
     import golden_cases as gc
@@ -935,7 +1012,7 @@ def main():
     os.makedirs(gc.GOLDEN_DIR, exist_ok=True)
     torch.manual_seed(0)
     np.random.seed(0)
-    which = sys.argv[1:] or ["small", "cfg1", "cfg2", "atlas", "losses", "trainer", "tracker", "so3", "samples", "extra", "geometry", "formats", "encoder", "second_order", "atlas_branches"]
+    which = sys.argv[1:] or ["small", "cfg1", "cfg2", "atlas", "losses", "trainer", "tracker", "so3", "samples", "extra", "geometry", "formats", "encoder", "second_order", "atlas_branches", "grad2_naive"]
     for name in which:
         if name in gc.CASES:
             gen_encode_decode(name, GridNet, rloss, gc)
@@ -963,6 +1040,8 @@ def main():
             gen_second_order(GridNet, rloss, risdf, gc)
         elif name == "atlas_branches":
             gen_atlas_branches(GridAtlas, miso, gc)
+        elif name == "grad2_naive":
+            gen_grad2_naive(gc)
 
 
 if __name__ == "__main__":
