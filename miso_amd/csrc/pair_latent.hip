@@ -30,7 +30,7 @@ struct PairK {
   double* out;         // 24 doubles, zeroed by the launcher
   const float* boxes;  // per run of ALIGN_BOX_VERTS vertices {min xyz, max xyz}, or nullptr (AlignPairK::boxes)
 };
-constexpr float BOX_SLACK = 2e-3f;      // metres: the exact test rounds a mapped coordinate by ~1e-5 at 100 m
+constexpr float BOX_SLACK = 2e-3f;      // metres, plus terms in the size of the coordinates (pair_latent_body)
 
 // hardware fp64 add at L2 (global_atomic_add_f64, no return value)
 __device__ __forceinline__ void atomic_add_f64(double* p, double v) {
@@ -95,7 +95,7 @@ __device__ __forceinline__ void pair_latent_body(const GridK& g, const float* __
   //  * pass 1 itself: a vertex is a candidate when M p + q_0 lies inside the bound widened by the slack -- 12 multiply-adds
   //    on 12 values read back from LDS per chunk, where forming w, w - td and Rd^T . per vertex kept 24 pose values live
   //    as scalar registers the compiler had to spill and reload inside every one of the eight unrolled steps.
-  // The slack covers the rounding of either form (~1e-5 m at 100 m, growing with the size of the world coordinates): a
+  // The slack covers the rounding of either form (~1e-5 m at 100 m, growing with the size of the coordinates): a
   // vertex the composed map puts inside the bound shrunk by the slack is in bound exactly, one outside the widened bound
   // is out, and the few in between take the exact test.  NaN poses compare false: no candidates, as the exact test finds.
   __shared__ float s_aff[16];
@@ -106,8 +106,14 @@ __device__ __forceinline__ void pair_latent_body(const GridK& g, const float* __
     s_aff[a * 4 + 2] = Rd[a] * Rs[2] + Rd[3 + a] * Rs[5] + Rd[6 + a] * Rs[8];
     s_aff[a * 4 + 3] = Rd[a] * (ts[0] - td[0]) + Rd[3 + a] * (ts[1] - td[1]) + Rd[6 + a] * (ts[2] - td[2]);
   }
+  // The slack grows with the size of the coordinates both forms round: the translations (q_0) and the vertex itself.  A
+  // vertex whose decision the slack has to cover maps to within the slack of the bound, so |p| = |M p| <= |q| + |q_0| is
+  // bounded by the bound's distance from the origin plus the translations (a bound 1e4 m out: ~7e-3 m of rounding,
+  // where the fixed 2e-3 m let two of 11 000 vertices within 6e-3 m of a face be decided wrongly).
   if (threadIdx.x == 3)
-    s_aff[12] = BOX_SLACK + 4e-6f * (fabsf(ts[0]) + fabsf(ts[1]) + fabsf(ts[2]) + fabsf(td[0]) + fabsf(td[1]) + fabsf(td[2]));
+    s_aff[12] = BOX_SLACK + 4e-6f * (fabsf(ts[0]) + fabsf(ts[1]) + fabsf(ts[2]) + fabsf(td[0]) + fabsf(td[1]) + fabsf(td[2])) +
+                1e-5f * (fmaxf(fabsf(g.bmin[0]), fabsf(g.bmax[0])) + fmaxf(fabsf(g.bmin[1]), fabsf(g.bmax[1])) +
+                         fmaxf(fabsf(g.bmin[2]), fabsf(g.bmax[2])));
   __syncthreads();
   for (int64_t c0 = (int64_t)bx * chunk; c0 < k.n; c0 += (int64_t)nbx * chunk) {
     const int64_t w0 = c0 + (int64_t)wave_ * (PAIR_K * 64);
@@ -294,7 +300,9 @@ __device__ __forceinline__ void pair_latent_body(const GridK& g, const float* __
   if (threadIdx.x < NACC)
     red[4][threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
   __syncthreads();
-  if (threadIdx.x < 23) {
+  // (a workgroup without an in-bound vertex adds nothing: its sums are zeros, and a NaN pose -- no vertex in bound --
+  // would turn the products with the pose below into NaN)
+  if (threadIdx.x < 23 && red[4][1] != 0.0) {
     // out[0] term, [1] count, [2..4] G, [5 + 3a + b] sum d_a g_b = (Rs S)_ab + (ts - td)_a G_b, [14 + 3a + b] sum (Rd g)_a p_b
     // = sum_c Rd[a][c] S[b][c]
     const double* T = red[4];

@@ -32,6 +32,7 @@ gradcheck / error measurement).
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -568,3 +569,299 @@ def lidar_frame_samples(pts_world, R_wf, t_wf, g_near, u_free, u_behind, *, near
     return {"points_frame": frame, "points_world_gt": world, "sdfs": sdf,
             "sdfs_valid": (sdf.abs() < trunc_dist).float(), "signs": torch.cat(sgn).float(),
             "weights": torch.cat(wts).float()}
+
+
+# --------------------------------------------------------------------------- #
+# Latent alignment at the kernel's own fp32 coordinates (pair_latent.hip, align.hip)
+# --------------------------------------------------------------------------- #
+def index32(xn32, size, align_corners=False):
+    """The kernel's axis_from_norm on an fp32 normalised coordinate (common.hpp), fp32 step by step.  Without
+    OCML_BASIC_ROUNDED_OPERATIONS HIP's __fmul_rn / __fsub_rn are plain operators, and the compiler contracts
+    (xn + 1) * size - 1 into one fma: a single rounding, replayed here through the exact fp64 product."""
+    one = torch.tensor(1.0, dtype=torch.float32)
+    a = xn32 + one
+    if align_corners:
+        return (a * torch.tensor(0.5, dtype=torch.float32)) * torch.tensor(float(size - 1), dtype=torch.float32)
+    return (a.double() * size - 1).float() * torch.tensor(0.5, dtype=torch.float32)
+
+
+def norm32(x32, bound):
+    """axis_norm's fp32 normalisation of metres (common.hpp): 2 (x - bmin) / len - 1, rounded after each step.
+    bound: (3,2) rows [min, max]."""
+    b = torch.as_tensor(bound, dtype=torch.float32)
+    return (torch.tensor(2.0, dtype=torch.float32) * (x32 - b[:, 0])) / (b[:, 1] - b[:, 0]) - \
+        torch.tensor(1.0, dtype=torch.float32)
+
+
+def _fma32(a, b, c):
+    """fp32 fma: the product of two fp32 values is exact in fp64, the sum rounds there and again to fp32 -- a double
+    rounding that differs from one fma in about 1 case of 2^29."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def src_to_dst32(p, Rs, ts, Rd, td, bound=None):
+    """pair_latent.hip src_to_dst in fp32, operation by operation: w_r = fma(Rs[r,2], z, fma(Rs[r,1], y, Rs[r,0] x))
+    + ts_r, d = w - td, q_c = fma(Rd[2,c], d_2, fma(Rd[1,c], d_1, Rd[0,c] d_0)).  The source writes these with
+    __fmaf_rn / __fmul_rn / __fadd_rn / __fsub_rn; the gfx950 code of overlap_count_kernel (hipcc -O3 -S) is
+    v_mul_f32, two v_fmac_f32, v_add_f32 (ts), v_subrev_f32 (td) per row of Rs and v_mul / v_fma (v_pk_fma_f32 for
+    two columns) in this order for Rd^T: nothing is contracted or reassociated beyond what the source writes.
+    p (N,3), R (3,3), t (3,) fp32 -> d (N,3), q (N,3) fp32 and, with a (3,2) bound, the inclusive in-bound mask.
+    A count that differs from the kernel's by one: look at that vertex for the double rounding of _fma32 first."""
+    f = lambda t: torch.as_tensor(t, dtype=torch.float32).reshape(-1)
+    p = p.to(torch.float32)
+    Rs, ts, Rd, td = f(Rs).view(3, 3), f(ts), f(Rd).view(3, 3), f(td)
+    px, py, pz = p[:, 0], p[:, 1], p[:, 2]
+    d = torch.stack([(_fma32(Rs[r, 2], pz, _fma32(Rs[r, 1], py, Rs[r, 0] * px)) + ts[r]) - td[r] for r in range(3)], 1)
+    q = torch.stack([_fma32(Rd[2, c], d[:, 2], _fma32(Rd[1, c], d[:, 1], Rd[0, c] * d[:, 0])) for c in range(3)], 1)
+    if bound is None:
+        return d, q
+    b = torch.as_tensor(bound, dtype=torch.float32)
+    return d, q, ((q >= b[:, 0]) & (q <= b[:, 1])).all(1)
+
+
+def _trilinear_jet(feature, ix, dtype):
+    """Value (N,C) and index-space derivative (N,C,3) of the zero-padded trilinear interpolant in the cell of
+    floor(ix) (ATen's convention), plus sum_corners |v| (N,C): ix (N,3) fp64 index coordinates (x, y, z)."""
+    _, c, d, h, w = feature.shape
+    flat = feature.detach().reshape(c, d * h * w).to(dtype)
+    i0 = torch.floor(ix)
+    fr = (ix - i0).to(dtype)
+    i0 = i0.clamp(-2, max(w, h, d) + 1).long()
+    n = ix.shape[0]
+    val = torch.zeros(n, c, dtype=dtype)
+    der = torch.zeros(n, c, 3, dtype=dtype)
+    mag = torch.zeros(n, c, dtype=dtype)
+    for k in range(8):
+        o = (k & 1, (k >> 1) & 1, k >> 2)
+        xi, yi, zi = i0[:, 0] + o[0], i0[:, 1] + o[1], i0[:, 2] + o[2]
+        inb = (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h) & (zi >= 0) & (zi < d)
+        lin = ((zi.clamp(0, d - 1) * h + yi.clamp(0, h - 1)) * w + xi.clamp(0, w - 1))
+        v = flat[:, lin].t() * inb.to(dtype)[:, None]
+        wt = [fr[:, a] if o[a] else 1 - fr[:, a] for a in range(3)]
+        sg = [1.0 if o[a] else -1.0 for a in range(3)]
+        val += v * (wt[0] * wt[1] * wt[2])[:, None]
+        der[:, :, 0] += v * (sg[0] * wt[1] * wt[2])[:, None]
+        der[:, :, 1] += v * (sg[1] * wt[0] * wt[2])[:, None]
+        der[:, :, 2] += v * (sg[2] * wt[0] * wt[1])[:, None]
+        mag += v.abs()
+    return val, der, mag
+
+
+def pair_latent_sums64(p, fsrc, feats_dst, bound, pose, loss_type="L2", ignore_mask=0, dtype=torch.float64,
+                       exact=False, level_sign=None):
+    """The 24 sums of miso_pair_latent (torch_ops.pair_latent_fwd_bwd: [0] sum term, [1] in-bound count, [2:5] sum g,
+    [5+3a+b] sum d_a g_b, [14+3a+b] sum (Rd g)_a p_b) evaluated at the kernel's own fp32 mapped coordinates.
+
+    p (N,3) fp32 source vertices, fsrc (N, >= F) source features, feats_dst the destination levels (1,C,Z,Y,X),
+    bound (3,2), pose (24,) = R_s, t_s, R_d, t_d.  The in-bound set is src_to_dst32's; the normalised and index
+    coordinates are norm32 / index32 of that q, carried to fp64 exactly; from there on everything is ``dtype``
+    (fp64: the oracle; fp32: what a careful fp32 implementation at the same coordinates computes, summed in fp32 over
+    runs of 8 vertices like a kernel lane).  Returns (sums (24,) fp64, A (24,) fp64): A is the same sum built from
+    per-vertex absolute bounds -- |term|; a_i = sum_l mult_l sum_c |d term / d f_c| sum_corners |v| per axis (|d w / d ix|
+    <= 1 in a cell); sum_c (|Rs||p| + |ts - td|)_a a_b for the d sums (the kernel forms them as Rs S + (ts - td) G,
+    so d's terms count separately); sum_c |Rd_ac| a_c |p_b| for the last nine.  A[1] = 0: the count is exact.
+    exact=True: the map, the bound test and the coordinates in fp64 from fp64 inputs instead (the formulas alone,
+    for comparing with autograd through pairwise_latent_loss in fp64).
+    level_sign: optional (N, levels) of +-1 multiplying each level's share of g per source vertex -- the sums a kernel
+    that got a level's gradient sign wrong on those vertices would produce (for the sensitivity tests)."""
+    pose = torch.as_tensor(pose, dtype=torch.float64 if exact else torch.float32).reshape(24)
+    Rs, ts, Rd, td = pose[:9].view(3, 3), pose[9:12], pose[12:21].view(3, 3), pose[21:24]
+    if exact:
+        b64 = torch.as_tensor(bound, dtype=torch.float64)
+        q = (p.double() @ Rs.T + (ts - td)) @ Rd
+        m = ((q >= b64[:, 0]) & (q <= b64[:, 1])).all(1)
+    else:
+        b64 = torch.as_tensor(bound, dtype=torch.float32).double()
+        _, q, m = src_to_dst32(p, Rs, ts, Rd, td, bound)
+    idx = torch.nonzero(m).flatten()
+    pi, qi = p[idx].to(torch.float64 if exact else torch.float32), q[idx]
+    F_ = sum(int(f.shape[1]) for f in feats_dst)
+    fs = fsrc[idx, :F_].to(dtype)
+    xn = normalize_coordinates(qi, b64) if exact else norm32(qi, bound)
+    fto, jac, mags, mults = [], [], [], []
+    for l, f in enumerate(feats_dst):
+        _, c, d, h, w = f.shape
+        sizes = (w, h, d)
+        ix = torch.stack([_unnormalize(xn[:, a], sizes[a], False) if exact else index32(xn[:, a], sizes[a]).double()
+                          for a in range(3)], 1)
+        mult = torch.tensor([sizes[a] / (b64[a, 1] - b64[a, 0]).item() for a in range(3)], dtype=dtype)
+        v, dv, mg = _trilinear_jet(f, ix, dtype)
+        if (ignore_mask >> l) & 1:
+            v, dv, mg = torch.zeros_like(v), torch.zeros_like(dv), torch.zeros_like(mg)
+        fto.append(v)
+        if level_sign is not None:
+            dv = dv * level_sign[idx, l].to(dtype)[:, None, None]
+        jac.append(dv * mult)
+        mags.append(mg[:, :, None] * mult)
+    fto, jac, mags = torch.cat(fto, 1), torch.cat(jac, 1), torch.cat(mags, 1)     # (n,F), (n,F,3), (n,F,3)
+    r = fs - fto
+    if loss_type == "L2":
+        term = (r * r).sum(1)
+        dt = -2 * r
+    elif loss_type == "L1":
+        term = (r * r).sum(1).sqrt()
+        inv = torch.where(term > 0, 1 / term, torch.zeros_like(term))            # vector_norm's backward at 0: 0
+        dt = -r * inv[:, None]
+    else:
+        raise ValueError(loss_type)
+    g = (dt[:, :, None] * jac).sum(1)                                             # (n,3) d term / d q
+    a = (dt.abs()[:, :, None] * mags).sum(1)                                      # (n,3) bound on |g|
+    Rs64, ts64, Rd64, td64 = Rs.double(), ts.double(), Rd.double(), td.double()
+    p64 = pi.double()
+    dvec = p64 @ Rs64.T + (ts64 - td64)                                           # d = Rs p + ts - td
+    dabs = p64.abs() @ Rs64.abs().T + (ts64 - td64).abs()
+    cnt = float(idx.numel())
+
+    def total(x):
+        """sum over vertices: fp64 directly, or fp32 over runs of 8 and then fp64"""
+        x = x.reshape(x.shape[0], math.prod(x.shape[1:]))
+        if dtype == torch.float64:
+            return x.sum(0)
+        pad = (-x.shape[0]) % 8
+        x = torch.cat([x, x.new_zeros(pad, x.shape[1])]).view(-1, 8, x.shape[1])
+        return x.sum(1).double().sum(0)
+
+    g64, a64 = g, a
+    sums = torch.zeros(24, dtype=torch.float64)
+    A = torch.zeros(24, dtype=torch.float64)
+    sums[0], A[0] = total(term)[0], total(term.abs())[0]
+    sums[1] = cnt
+    sums[2:5], A[2:5] = total(g64), total(a64)
+    if dtype == torch.float64:
+        sums[5:14] = (dvec[:, :, None] * g64[:, None, :]).sum(0).flatten()
+        sums[14:23] = ((g64 @ Rd64.T)[:, :, None] * p64[:, None, :]).sum(0).flatten()
+    else:       # the kernel's own decomposition: S = sum p (x) g in fp32, then Rs S + (ts - td) G and Rd S^T in fp64
+        S = total(pi[:, :, None] * g[:, None, :]).view(3, 3)
+        G = sums[2:5]
+        sums[5:14] = (Rs64 @ S + (ts64 - td64)[:, None] * G[None, :]).flatten()
+        sums[14:23] = (Rd64 @ S.T).flatten()
+    a64 = a64.double()
+    A[5:14] = (dabs[:, :, None] * a64[:, None, :]).sum(0).flatten()
+    A[14:23] = ((a64 @ Rd64.abs().T)[:, :, None] * p64.abs()[:, None, :]).sum(0).flatten()
+    return sums, A
+
+
+def pair_sums_excess(got, sums, A, rel=1e-5):
+    """(24,) how far each kernel sum lies beyond its bar: count exactly, the others |got - fp64| <= rel A + 1e-12.
+    Positive entries are failures; NaN in ``got`` is a failure too."""
+    got = torch.as_tensor(got, dtype=torch.float64).detach().cpu().reshape(24)
+    ex = (got - sums).abs() - (rel * A + 1e-12)
+    ex[1] = (got[1] - sums[1]).abs() if got[1] != sums[1] else -1.0
+    ex[23] = got[23].abs()
+    return torch.where(torch.isnan(ex), torch.full_like(ex, float("inf")), ex)
+
+
+def pair_pose_grads64(sums, Rd, loss_type, n_ch, weight=1.0):
+    """fp64 chain rule of ops._PairLatent on fp64 sums: loss, d/dR_s, d/dt_s, d/dR_d, d/dt_d."""
+    denom = max(float(sums[1]), 1.0) * (n_ch if loss_type == "L2" else 1)
+    s = weight / denom
+    h = torch.as_tensor(Rd, dtype=torch.float64).reshape(3, 3) @ sums[2:5]
+    return (sums[0] * s, sums[14:23].view(3, 3) * s, h.view(3, 1) * s, sums[5:14].view(3, 3) * s, -h.view(3, 1) * s)
+
+
+def so3_exp_jacobian64(w):
+    """d Exp(w)_ij / d w_k (3,3,3) in fp64 by autograd through so3_exp_map (its clamp of |w|^2 at 1e-4 included)."""
+    w = torch.as_tensor(w, dtype=torch.float64).reshape(3)
+    return torch.autograd.functional.jacobian(lambda v: so3_exp_map(v.view(1, 3))[0], w)
+
+
+def so3_exp_backward64(w, G):
+    """d sum(G * Exp(w)) / d w in fp64 (align.hpp so3_exp_backward)."""
+    return torch.einsum("ijk,ij->k", so3_exp_jacobian64(w), torch.as_tensor(G, dtype=torch.float64).view(3, 3))
+
+
+def align_epilogue64(out, cnt, pairs, S, pose, R0, params, *, loss_type="L2", align_weight=3000.0,
+                     overlap_thresh=1e-2):
+    """Epilogue A of align.hip in fp64 from given pair sums: per pair the normalisation, the overlap gate (decided
+    on the fp32 fraction, as the kernel does), nan_to_num; per submap the sum of its pairs' cotangents, the pull-back
+    through R = R0 Exp(dr) and so3_exp_map's backward.  out (P,24) fp64, cnt (P,) counts, pairs: dicts with src, dst,
+    n_ch and gate_n (0: no gate); pose (S,12) the poses the sums were taken at; R0 (S,3,3); params (S,6).  Returns
+    (pair losses (P,), flat (7S+1,) = 6S gradients, the loss sum, S "had a gradient" flags, and the same pull-back with
+    every pair's sums and every matrix entry in absolute value (6S,): the yardstick of flat)."""
+    out = torch.as_tensor(out, dtype=torch.float64).reshape(-1, 24)
+    pose = torch.as_tensor(pose, dtype=torch.float64).reshape(S, 12)
+    R0 = torch.as_tensor(R0, dtype=torch.float64).reshape(S, 3, 3)
+    params = torch.as_tensor(params, dtype=torch.float32).reshape(S, 6)
+    gR = torch.zeros(S, 3, 3, dtype=torch.float64)
+    gt = torch.zeros(S, 3, dtype=torch.float64)
+    aR = torch.zeros(S, 3, 3, dtype=torch.float64)
+    at = torch.zeros(S, 3, dtype=torch.float64)
+    had = torch.zeros(S, dtype=torch.bool)
+    losses = torch.zeros(len(pairs), dtype=torch.float64)
+    for i, pr in enumerate(pairs):
+        o = out[i]
+        denom = max(float(o[1]), 1.0) * (pr["n_ch"] if loss_type == "L2" else 1)
+        val = float(o[0]) / denom
+        finite = math.isfinite(float(torch.tensor(val, dtype=torch.float32)))
+        gate = True
+        if pr.get("gate_n", 0):
+            frac = torch.tensor(float(cnt[i]), dtype=torch.float32) / torch.tensor(float(pr["gate_n"]),
+                                                                                  dtype=torch.float32)
+            gate = bool(frac > overlap_thresh)
+        losses[i] = (float(torch.nan_to_num(torch.tensor(val, dtype=torch.float32))) * align_weight) if gate else 0.0
+        s, d = int(pr["src"]), int(pr["dst"])
+        had[s] |= gate
+        had[d] |= gate
+        if not (finite and gate):
+            continue
+        sc = align_weight / denom
+        Rd = pose[d, :9].view(3, 3)
+        h, ha = Rd @ o[2:5], Rd.abs() @ o[2:5].abs()
+        gR[s] += o[14:23].view(3, 3) * sc
+        gt[s] += h * sc
+        gR[d] += o[5:14].view(3, 3) * sc
+        gt[d] -= h * sc
+        aR[s] += o[14:23].view(3, 3).abs() * sc
+        aR[d] += o[5:14].view(3, 3).abs() * sc
+        at[s] += ha * sc
+        at[d] += ha * sc
+    flat = torch.zeros(7 * S + 1, dtype=torch.float64)
+    absf = torch.zeros(6 * S, dtype=torch.float64)
+    for s in range(S):
+        G = R0[s].T @ gR[s]
+        Ga = R0[s].T.abs() @ aR[s]
+        w = params[s, :3].double()
+        J = so3_exp_jacobian64(w)
+        flat[6 * s:6 * s + 3] = torch.einsum("ijk,ij->k", J, G)
+        absf[6 * s:6 * s + 3] = torch.einsum("ijk,ij->k", J.abs(), Ga)      # the same map in absolute values
+        flat[6 * s + 3:6 * s + 6] = gt[s]
+        absf[6 * s + 3:6 * s + 6] = at[s]
+        flat[6 * S + 1 + s] = float(had[s])
+    flat[6 * S] = losses.sum()
+    return losses, flat, absf
+
+
+def align_epilogue_b64(flat, params, adam_m, adam_v, adam_t, *, lr=1e-2, betas=(0.9, 0.999), eps=1e-8,
+                       reg_weight=0.0, reg_thresh_rad=1.0, reg_thresh_m=1.0):
+    """Epilogue B of align.hip in fp64: the trust-region regulariser (grid_atlas_pose_trust_region_loss) on every
+    submap, the NaN guard, and Adam on submaps 1..S-1 with a step count per submap; a submap without a gradient
+    (none of its pairs passed the gate, no regulariser) keeps value, moments and count.  Returns (total loss,
+    params, m, v, steps) -- the state after the step."""
+    flat = torch.as_tensor(flat, dtype=torch.float64)
+    prm = torch.as_tensor(params, dtype=torch.float64).clone().reshape(-1, 6)
+    m = torch.as_tensor(adam_m, dtype=torch.float64).clone().reshape(-1, 6)
+    v = torch.as_tensor(adam_v, dtype=torch.float64).clone().reshape(-1, 6)
+    t = torch.as_tensor(adam_t).clone().to(torch.int64).reshape(-1)
+    S = prm.shape[0]
+    nr, nt = prm[:, :3].norm(dim=1), prm[:, 3:].norm(dim=1)
+    total = float(flat[6 * S])
+    if reg_weight > 0:
+        total += float(reg_weight * (torch.relu(nr - reg_thresh_rad) + torch.relu(nt - reg_thresh_m)).sum())
+    if math.isnan(total):
+        return total, prm, m, v, t
+    b1, b2 = betas
+    for s in range(1, S):
+        if not (reg_weight > 0 or flat[6 * S + 1 + s] > 0):
+            continue
+        g = flat[6 * s:6 * s + 6].clone()
+        if reg_weight > 0:
+            if nr[s] > reg_thresh_rad:
+                g[:3] += reg_weight * prm[s, :3] / nr[s]
+            if nt[s] > reg_thresh_m:
+                g[3:] += reg_weight * prm[s, 3:] / nt[s]
+        t[s] += 1
+        m[s] = b1 * m[s] + (1 - b1) * g
+        v[s] = b2 * v[s] + (1 - b2) * g * g
+        bc1, bc2 = 1 - b1 ** int(t[s]), 1 - b2 ** int(t[s])
+        prm[s] -= lr / bc1 * m[s] / (v[s].sqrt() / math.sqrt(bc2) + eps)
+    return total, prm, m, v, t

@@ -710,6 +710,9 @@ def test_overlap_count_vs_oracle(n):
     got = ops.overlap_count(R_s.to(DEV), t_s.to(DEV), R_d.to(DEV), t_d.to(DEV), pts.to(DEV), bound)
     # a point within a few ulps of a face may fall on either side (different summation order)
     assert abs(int(got.item()) - ref) <= max(2, n // 50000)
+    # ... and none does against the kernel's own fp32 arithmetic, replayed operation by operation
+    _, _, m32 = R.src_to_dst32(pts, R_s, t_s, R_d, t_d, bound)
+    assert int(got.item()) == int(m32.sum())
 
 
 @pytest.mark.parametrize("name,n", [("small", 20000), ("cfg2", 40000)])

@@ -31,21 +31,9 @@ F64 = torch.float64
 # --------------------------------------------------------------------------- #
 # Oracle at the kernel's coordinates
 # --------------------------------------------------------------------------- #
-def _index32(xn32, size, ac):
-    """The kernel's axis_coord on an fp32 normalised coordinate (common.hpp), fp32 step by step.  Without
-    OCML_BASIC_ROUNDED_OPERATIONS HIP's __fmul_rn / __fsub_rn are plain operators, and the compiler contracts
-    (xn + 1) * size - 1 into one fma: a single rounding, replayed here through the exact fp64 product."""
-    one = torch.tensor(1.0, dtype=F32)
-    a = xn32 + one
-    if ac:
-        return (a * torch.tensor(0.5, dtype=F32)) * torch.tensor(float(size - 1), dtype=F32)
-    return (a.double() * size - 1).float() * torch.tensor(0.5, dtype=F32)
-
-
-def _norm32(x32, bound):
-    """axis_norm's fp32 normalisation of metres (common.hpp): 2 (x - bmin) / len - 1, rounded after each step."""
-    b = torch.tensor(bound, dtype=F32)
-    return (torch.tensor(2.0, dtype=F32) * (x32 - b[:, 0])) / (b[:, 1] - b[:, 0]) - torch.tensor(1.0, dtype=F32)
+# (the kernel's fp32 normalisation and index coordinate, shared with tests/test_pose_jacobian_oracle.py)
+_index32 = R.index32
+_norm32 = R.norm32
 
 
 def _xn64_at_kernel_index(xn32, sizes_xyz, ac):
