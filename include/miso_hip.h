@@ -50,6 +50,11 @@
  *                     feeds the path): get_batch_data / sample_along_rays
  *                     (grid_opt/utils/utils_sample.py:142-302), bounds_ray (sdf_rgbd.py:525-534), the
  *                     per-keyframe world -> keyframe loop (:436-445) and the truncation labels (:447-455).
+ *
+ * This file is also the ONLY statement of the ABI for Python: miso_amd/_lib.py reads its structs, integer constants and
+ * prototypes at import and refuses what it cannot read.  Keep the declarations in the style used below: block comments,
+ * `#define MISO_NAME <integer>[u]`, `typedef struct { ... } miso_name_t;` of fixed-width scalars, `int`, pointers, arrays
+ * sized by a literal or a MISO_* constant and earlier structs by value; prototypes with every parameter named.
  */
 #ifndef MISO_HIP_H
 #define MISO_HIP_H

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

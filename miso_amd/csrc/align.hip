@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 #include "align.hpp"
+#include "launch.hpp"
 
 namespace miso {
 
@@ -306,9 +307,6 @@ __global__ __launch_bounds__(64) void align_epilogue_b_kernel(AlignK k) {
   __syncthreads();
   if (!ctrl[CTRL_STOPPED]) align_prologue_body(k, ctrl[CTRL_ITER], false);
 }
-
-hipError_t launch_pair_batch(const AlignPairK*, int, int64_t, int64_t, bool, const float*, int, double*, float*,
-                             const int32_t*, int64_t, const int32_t*, hipStream_t);
 
 hipError_t launch_align_a(const AlignK& k, int64_t max_n, int64_t max_gate_n, int64_t max_gate_rows, bool vec4,
                           bool poses_ready, hipStream_t s) {

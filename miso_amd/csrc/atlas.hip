@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "decoder.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

@@ -5,82 +5,8 @@
 
 #include "common.hpp"
 #include "align.hpp"
+#include "launch.hpp"
 #include "version.inc"
-
-namespace miso {
-hipError_t launch_encode_fwd(const GridK&, bool, const float*, int64_t, float*, int64_t, const int*, hipStream_t);
-hipError_t launch_encode_bwd(const GridK&, bool, const float*, int64_t, const float*, int64_t, float*, const int*,
-                             hipStream_t);
-hipError_t launch_encode_bwd2(const GridK&, bool, const float*, int64_t, const float*, int64_t, const float*, float*,
-                              int64_t, float*, const int*, hipStream_t);
-bool fused_shape_supported(int C, int L, int H, int NH);
-int64_t sdf_train_lds_bytes(int C, int L, int H, int NH, bool scat);
-hipError_t launch_sdf_fwd(int, int, int, int, const GridK&, const float*, const float*, int64_t, float*,
-                          uint32_t*, const int*, const LossInK&, hipStream_t);
-hipError_t launch_sdf_bwd(int, int, int, int, const GridK&, const float*, const float*, int64_t,
-                          const float*, const uint32_t*, float*, bool, const int*, float*, uint32_t, bool,
-                          hipStream_t);
-hipError_t launch_sdf_train(int, int, int, int, const GridK&, const float*, const float*, int64_t, float*, const int*,
-                            const LossInK&, float*, uint32_t, bool, hipStream_t);
-int64_t sort_workspace_bytes(int64_t n, int T);
-hipError_t launch_sort(const GridK&, const float*, int64_t, int, void*, float*, float*, int*, int*,
-                       hipStream_t);
-hipError_t launch_pair_latent(const GridK&, bool, const float*, const float*, const float*, int64_t, int64_t, int,
-                              double*, hipStream_t);
-hipError_t launch_zero_fill(float*, int64_t, hipStream_t);
-hipError_t launch_adam_touched(float*, float*, float*, float*, unsigned char*, unsigned char*, int64_t, double, double,
-                               double, double, int, int, const float*, hipStream_t, const float*, const int32_t*, int);
-hipError_t launch_adam_bump(int32_t*, const float*, hipStream_t);
-hipError_t launch_adam_active_multi(const miso_adam_tensor_t*, int, double, double, double, double, int, const float*, int,
-                                    const int32_t*, const float*, hipStream_t);
-hipError_t launch_loss_total_bump(const float*, int, float*, int32_t*, float*, int, hipStream_t);
-hipError_t launch_lm_track_head(const LmTrackK&, hipStream_t);
-hipError_t launch_track_loss(const TrackAdamK&, hipStream_t);
-hipError_t launch_track_tail(const TrackAdamK&, hipStream_t);
-hipError_t launch_lm_track_tail(const LmTrackK&, const float*, const float*, int, float, hipStream_t);
-void adam_scalars_table(double, double, double, double, int, int, float*);
-hipError_t launch_mapping_batch(const float*, const float*, int32_t, const int64_t*, int64_t, const int64_t*,
-                                const float*, const float*, const void*, const float*, const float*, int64_t, float*,
-                                float*, const int64_t*, int, int, hipStream_t);
-hipError_t launch_mapping_loss_rows(int, float, float, float, const float*, const float*, int64_t, float*, float*,
-                                    hipStream_t);
-uint32_t plan_grad_pull(const GridK&, int);
-hipError_t launch_grad_pull(const GridK&, int, int, const int*, const float*, const float*, int64_t, const int*,
-                            uint32_t, int, const float*, int32_t*, int64_t, hipStream_t, uint32_t push_mask, int64_t n);
-uint32_t plan_push(const GridK&, int, int64_t, uint32_t);
-bool mc_pull_ok(const GridK& g, int C, const int T[3], uint32_t level_mask, int64_t n, int64_t ld);
-int64_t pull_queue_ints(int64_t);
-hipError_t launch_rigid_by_index(const float*, const float*, const int64_t*, const float*, int64_t, int32_t, int, float*,
-                                 hipStream_t);
-int64_t mc_words(int32_t, int32_t, int32_t);
-int64_t mc_workspace_bytes(int32_t, int32_t, int32_t);
-hipError_t launch_mc_classify(const float*, int32_t, int32_t, int32_t, float, void*, int32_t*, hipStream_t);
-hipError_t launch_mc_emit(int32_t, int32_t, int32_t, void*, const int64_t*, int32_t, int64_t, int64_t*, hipStream_t);
-hipError_t launch_mc_vertices(const float*, int32_t, int32_t, int32_t, float, void*, const int64_t*, int32_t, int64_t,
-                              float*, hipStream_t);
-void mc_copy_table(int8_t*);
-hipError_t launch_overlap_count(const float*, const float*, int64_t, const float*, const float*, float*, hipStream_t);
-hipError_t launch_src_boxes(const float*, int64_t, float*, hipStream_t);
-hipError_t launch_lm_normal_eq(const float*, const float*, const float*, const float*, const float*, int64_t, int,
-                               float, float*, hipStream_t);
-size_t sample_rays_workspace_bytes(int64_t, int32_t);
-hipError_t launch_sample_rays(const miso_ray_frames_t&, const miso_ray_sampling_t&, const float*, int64_t,
-                              const int64_t*, const int64_t*, const int64_t*, const float*, const float*, void*,
-                              float*, int64_t*, float*, float*, float*, int32_t*, hipStream_t);
-hipError_t launch_grid_pool_avg(const float*, const float*, int64_t, int32_t, int64_t, const float*, float, int32_t, int32_t,
-                                int32_t, float*, int32_t*, hipStream_t);
-hipError_t launch_atlas_sdf(int C, int L, int H, int NH, const AtlasK& a, const float* packed, bool exact, hipStream_t s);
-hipError_t launch_mlp_pack(const MlpK&, int, int, int, float*, hipStream_t);
-int64_t mlp_packed_floats(int F, int H, int NH);
-hipError_t launch_adam(float*, float*, float*, float*, int64_t, double, double, double, double, int, int,
-                       hipStream_t);
-hipError_t launch_adam_active(float*, float*, float*, float*, unsigned char*, int64_t, double, double, double, double, int,
-                              int, const float*, hipStream_t, const float*, const int32_t*, int);
-hipError_t launch_mapping_loss(int, float, float, float, const float*, const float*, const float*,
-                               const float*, const float*, int64_t, float*, float*, float*, hipStream_t);
-hipError_t launch_align_a(const AlignK&, int64_t, int64_t, int64_t, bool, bool, hipStream_t);
-hipError_t launch_align_b(const AlignK&, hipStream_t);
-}  // namespace miso
 
 using namespace miso;
 

@@ -81,9 +81,6 @@ inline bool tiles_xyz(int32_t code, int T[3]) {
 }
 inline bool tiles_cubic16(int32_t code) { return code >= 1 && code <= 16; }
 
-// clears n_words 32-bit words with a kernel (loss.hip; see there why not hipMemsetAsync)
-hipError_t launch_zero_words(void* p, int n_words, hipStream_t s);
-
 struct MlpK {
   const float* w[MISO_MAX_LINEAR];
   const float* b[MISO_MAX_LINEAR];

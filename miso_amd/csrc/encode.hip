@@ -10,6 +10,7 @@
 // Math: SURVEY.md Appendix B; it restates ATen grid_sampler_3d (bilinear) and
 // the double backward of third_party/cuda_gridsample_grad2/gridsample_cuda.cu:443-531.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

@@ -24,6 +24,7 @@
 
 #include "common.hpp"
 #include "grad_pull.hpp"
+#include "launch.hpp"
 
 namespace miso {
 
@@ -1060,11 +1061,6 @@ uint32_t plan_push(const GridK& g, int tiles, int64_t n, uint32_t pull) {
   return push;
 }
 
-bool mc_pull_ok(const GridK& g, int C, const int T[3], uint32_t level_mask, int64_t n, int64_t ld);
-hipError_t launch_grad_pull_mc(const GridK& g, int C, const int T[3], const int* tile_off, const float* xn,
-                               const float* dfeat, int64_t ld, const int* perm, uint32_t level_mask, int overwrite,
-                               int64_t n, hipStream_t s);
-
 static hipError_t launch_push(const GridK& g, int C, int T, const int* tile_off, const float* xn, const float* dfeat,
                               int64_t ld, const int* perm, int level, int64_t n, hipStream_t s) {
   // samples per wavefront: 512 (fewest region flushes per sample) once that still makes >= 2048 wavefronts -- two per
@@ -1087,7 +1083,6 @@ static hipError_t launch_push(const GridK& g, int C, int T, const int* tile_off,
   return hipGetLastError();
 }
 
-hipError_t launch_zero_fill(float*, int64_t, hipStream_t);
 hipError_t launch_grad_pull(const GridK& g, int C, int tiles, const int* tile_off, const float* xn,
                             const float* dfeat, int64_t ld, const int* perm, uint32_t level_mask,
                             int overwrite, const float* ggx, int32_t* queue, int64_t queue_ints, hipStream_t s,

@@ -33,6 +33,7 @@
 #include <string.h>
 
 #include "grad_pull.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

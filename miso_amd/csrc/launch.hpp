@@ -1,0 +1,137 @@
+// Host functions that cross a translation unit, grouped by the .hip that defines them; capi.hip (and, where noted,
+// another .hip) calls them.  Every defining file includes this header, so a definition sits under the eye of its
+// declaration; one that drifts from it is a second overload, and the library no longer loads (unresolved symbol).
+#pragma once
+#include "common.hpp"
+
+namespace miso {
+
+struct AlignK;  // align.hpp
+
+// ---- encode.hip
+hipError_t launch_encode_fwd(const GridK& g, bool vec4, const float* x, int64_t n, float* out, int64_t ld,
+                             const int* perm, hipStream_t s);
+hipError_t launch_encode_bwd(const GridK& g, bool vec4, const float* x, int64_t n, const float* gf, int64_t ld,
+                             float* gx, const int* perm, hipStream_t s);
+hipError_t launch_encode_bwd2(const GridK& g, bool vec4, const float* x, int64_t n, const float* gf, int64_t ld,
+                              const float* ggx, float* ggo, int64_t ldgg, float* gx, const int* perm, hipStream_t s);
+
+// ---- sdf_fused.hip
+bool fused_shape_supported(int C, int L, int H, int NH);
+int64_t sdf_train_lds_bytes(int C, int L, int H, int NH, bool scat);
+int64_t mlp_packed_floats(int F, int H, int NH);
+hipError_t launch_mlp_pack(const MlpK& m, int F, int H, int NH, float* out, hipStream_t s);
+hipError_t launch_sdf_fwd(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,
+                          float* sdf, uint32_t* mask, const int* perm, const LossInK& lin, hipStream_t s);
+hipError_t launch_sdf_bwd(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,
+                          const float* gsdf, const uint32_t* mask, float* gx, bool want_grid, const int* perm,
+                          float* dfeat_out, uint32_t defer_mask, bool gsdf_sorted, hipStream_t s);
+hipError_t launch_sdf_train(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,
+                            float* sdf, const int* perm, const LossInK& lin, float* dfeat_out, uint32_t defer_mask,
+                            bool scat, hipStream_t s);
+
+// ---- atlas.hip
+hipError_t launch_atlas_sdf(int C, int L, int H, int NH, const AtlasK& a, const float* packed, bool exact, hipStream_t s);
+
+// ---- sort.hip
+int64_t sort_workspace_bytes(int64_t n, int tiles);
+hipError_t launch_sort(const GridK& g, const float* x, int64_t n, int tiles, void* ws, float* xs, float* xn, int* perm,
+                       int* tile_off, hipStream_t s);
+
+// ---- grad_pull.hip
+uint32_t plan_grad_pull(const GridK& g, int tiles);
+uint32_t plan_push(const GridK& g, int tiles, int64_t n, uint32_t pull);
+int64_t pull_queue_ints(int64_t n);
+hipError_t launch_grad_pull(const GridK& g, int C, int tiles, const int* tile_off, const float* xn, const float* dfeat,
+                            int64_t ld, const int* perm, uint32_t level_mask, int overwrite, const float* ggx,
+                            int32_t* queue, int64_t queue_ints, hipStream_t s, uint32_t push_mask, int64_t n);
+
+// ---- grad_pull_mc.hip (launch_grad_pull_mc: called by launch_grad_pull)
+bool mc_pull_ok(const GridK& g, int C, const int T[3], uint32_t level_mask, int64_t n, int64_t ld);
+hipError_t launch_grad_pull_mc(const GridK& g, int C, const int T[3], const int* tile_off, const float* xn,
+                               const float* dfeat, int64_t ld, const int* perm, uint32_t level_mask, int overwrite,
+                               int64_t n, hipStream_t s);
+
+// ---- pair_latent.hip (launch_pair_batch: called by launch_align_a)
+hipError_t launch_src_boxes(const float* p, int64_t n, float* boxes, hipStream_t s);
+hipError_t launch_overlap_count(const float* pose, const float* p, int64_t n, const float* bmin, const float* bmax,
+                                float* out, hipStream_t s);
+hipError_t launch_pair_latent(const GridK& g, bool vec4, const float* pose, const float* p, const float* fsrc, int64_t ld,
+                              int64_t n, int loss_type, double* out, hipStream_t s);
+hipError_t launch_pair_batch(const AlignPairK* plan_dev, int n_pairs, int64_t max_n, int64_t max_gate_n, bool vec4,
+                             const float* pose_all, int loss_type, double* out_all, float* cnt_all,
+                             const int32_t* stopped, int64_t max_gate_rows, const int32_t* order, hipStream_t s);
+
+// ---- align.hip
+hipError_t launch_align_a(const AlignK& k, int64_t max_n, int64_t max_gate_n, int64_t max_gate_rows, bool vec4,
+                          bool poses_ready, hipStream_t s);
+hipError_t launch_align_b(const AlignK& k, hipStream_t s);
+
+// ---- lm.hip
+hipError_t launch_lm_normal_eq(const float* x, const float* R, const float* grad, const float* sdf, const float* gt,
+                               int64_t n, int loss_type, float gm_scale, float* out, hipStream_t s);
+hipError_t launch_track_loss(const TrackAdamK& k, hipStream_t st);
+hipError_t launch_track_tail(const TrackAdamK& k, hipStream_t st);
+hipError_t launch_lm_track_head(const LmTrackK& k, hipStream_t s);
+hipError_t launch_lm_track_tail(const LmTrackK& k, const float* grad, const float* sdf, int loss_type, float gm_scale,
+                                hipStream_t s);
+
+// ---- sample.hip
+size_t sample_rays_workspace_bytes(int64_t n_rays, int32_t n_frames);
+hipError_t launch_sample_rays(const miso_ray_frames_t& f, const miso_ray_sampling_t& c, const float* lin, int64_t n_rays,
+                              const int64_t* pix_b, const int64_t* pix_h, const int64_t* pix_w, const float* u,
+                              const float* g, void* workspace, float* coords, int64_t* ids, float* aux, float* pc_world,
+                              float* z_vals, int32_t* counts, hipStream_t s);
+
+// ---- adam.hip (table / step_dev: the captured-graph form, miso_adam_step_dev; nullptr = the scalars from the host)
+void adam_scalars_table(double lr, double b1, double b2, double eps, int first_step, int count, float* out);
+hipError_t launch_adam_bump(int32_t* step, const float* guard, hipStream_t s);
+hipError_t launch_loss_total_bump(const float* slots, int n, float* total, int32_t* step, float* host_ring, int ring_len,
+                                  hipStream_t s);
+hipError_t launch_adam(float* p, float* g, float* m, float* v, int64_t n, double lr, double b1, double b2, double eps,
+                       int step, int zero_grad, hipStream_t s);
+hipError_t launch_adam_active(float* p, float* g, float* m, float* v, unsigned char* active, int64_t n, double lr,
+                              double b1, double b2, double eps, int step, int zero_grad, const float* guard,
+                              hipStream_t s, const float* table, const int32_t* step_dev, int table_len);
+hipError_t launch_adam_touched(float* p, float* g, float* m, float* v, unsigned char* active, unsigned char* touched,
+                               int64_t n, double lr, double b1, double b2, double eps, int step, int zero_grad,
+                               const float* guard, hipStream_t s, const float* table, const int32_t* step_dev,
+                               int table_len);
+hipError_t launch_adam_active_multi(const miso_adam_tensor_t* t, int count, double lr, double b1, double b2, double eps,
+                                    int step, const float* table, int table_len, const int32_t* step_dev,
+                                    const float* guard, hipStream_t s);
+
+// ---- loss.hip (launch_zero_words clears n_words 32-bit words with a kernel; see there why not hipMemsetAsync)
+hipError_t launch_zero_fill(float* p, int64_t n, hipStream_t s);
+hipError_t launch_zero_words(void* p, int n_words, hipStream_t s);
+hipError_t launch_mapping_loss(int loss_type, float w_sdf, float w_fs, float trunc, const float* pred, const float* targ,
+                               const float* valid, const float* sign, const float* weight, int64_t n, float* gpred,
+                               float* gpred_fs, float* loss_out, hipStream_t s);
+hipError_t launch_mapping_loss_rows(int loss_type, float w_sdf, float w_fs, float trunc, const float* pred,
+                                    const float* rows, int64_t n, float* gpred, float* loss_out, hipStream_t s);
+
+// ---- mcubes.hip
+int64_t mc_words(int32_t nx, int32_t ny, int32_t nz);
+int64_t mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+void mc_copy_table(int8_t* out);
+hipError_t launch_mc_classify(const float* u, int32_t nx, int32_t ny, int32_t nz, float iso, void* workspace,
+                              int32_t* counts, hipStream_t s);
+hipError_t launch_mc_emit(int32_t nx, int32_t ny, int32_t nz, void* workspace, const int64_t* offsets, int32_t n_listed,
+                          int64_t capacity, int64_t* faces, hipStream_t s);
+hipError_t launch_mc_vertices(const float* u, int32_t nx, int32_t ny, int32_t nz, float iso, void* workspace,
+                              const int64_t* offsets, int32_t n_listed, int64_t capacity, float* verts, hipStream_t s);
+
+// ---- rigid.hip
+hipError_t launch_mapping_batch(const float* R, const float* t, int32_t K, const int64_t* table, int64_t table_len,
+                                const int64_t* frame_ids, const float* x, const float* target, const void* valid,
+                                const float* sign, const float* weight, int64_t n, float* y, float* rows,
+                                const int64_t* strides, int valid_is_bool, int sanitize, hipStream_t s);
+hipError_t launch_rigid_by_index(const float* R, const float* t, const int64_t* idx, const float* x, int64_t n, int32_t K,
+                                 int transpose, float* y, hipStream_t s);
+
+// ---- pool.hip
+hipError_t launch_grid_pool_avg(const float* coords, const float* feat, int64_t n, int32_t d, int64_t ld,
+                                const float* bmin, float cell, int32_t nx, int32_t ny, int32_t nz, float* acc,
+                                int32_t* cnt, hipStream_t s);
+
+}  // namespace miso

@@ -10,6 +10,7 @@
 // stay with the caller (they are 36 floats).
 #include "common.hpp"
 #include "align.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

@@ -6,6 +6,7 @@
 // as combined by MisoLossMappingBase.compute (loss.py:776-806).  Replaces ~20
 // elementwise launches + 2 reductions + their autograd backward by one kernel.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

@@ -25,6 +25,7 @@
 // Triangles come out in cell order (x-major), a cell's triangles in table order: the list a serial sweep makes.
 // Scratch: 5 bits per sample (+ the counts / offsets).  Written: 24 B per triangle, 12 B per vertex.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 namespace {

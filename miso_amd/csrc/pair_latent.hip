@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

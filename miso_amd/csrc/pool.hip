@@ -5,6 +5,7 @@
 // one integer atomic per point), normalise.  Cell index op for op as the reference: ((p - bound_min) / cell_size) truncated
 // like .long(), clamped to [0, size - 1]; linear index (ix ny + iy) nz + iz.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 namespace {

@@ -5,6 +5,7 @@
 // temporary through HBM three times; here it is one pass: 8 B of index + 12 B in + 12 B out per row, the K
 // poses (K <= a few hundred) come from L1/L2.
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 namespace {

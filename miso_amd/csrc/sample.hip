@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

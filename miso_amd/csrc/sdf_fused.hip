@@ -25,6 +25,7 @@
 #include <stdlib.h>
 
 #include "decoder.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.hpp"
+#include "launch.hpp"
 
 namespace miso {
 

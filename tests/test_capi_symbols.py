@@ -10,10 +10,13 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
+def _header_code():
     src = open(os.path.join(ROOT, "include", "miso_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(miso_[a-z0-9_]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+
+
+def _declared():
+    return sorted(set(re.findall(r"\b(miso_[a-z0-9_]+)\s*\(", _header_code())))
 
 
 def test_library_exports_every_declared_symbol():
@@ -108,9 +111,6 @@ def test_round2_entry_points_validate_arguments_without_gpu():
     assert lib.miso_lm_track_step(ctypes.byref(g), None, None, ctypes.byref(a), None) == E      # no pose pointers
     t = _lib.TrackAdam()
     assert lib.miso_track_adam_step(ctypes.byref(g), None, None, ctypes.byref(t), None) == E
-    # struct sizes the header implies (LP64)
-    assert ctypes.sizeof(_lib.LmTrack) == 4 * 8 + 3 * 8 + 8 + 8 + 8 + 8 + 4 * 8 + 4 + 4 + 4 + 4 + 9 * 8
-    assert ctypes.sizeof(_lib.TrackAdam) == ctypes.sizeof(_lib.LmTrack) + 4 + 4 + 4 + 4 + 8 + 8 + 8 + 8 + 8 + 8
 
 
 def test_gradient_plans_are_host_logic():
@@ -150,30 +150,121 @@ def test_gradient_plans_are_host_logic():
     assert lib.miso_grad_pull_levels(ctypes.byref(border), T) == 0
 
 
+def _gcc(tmp_path, name, text, *flags):
+    """Compiles `text` against include/miso_hip.h; returns the finished gcc run and the output path."""
+    import subprocess
+    src, out = tmp_path / name, tmp_path / (name + ".out")
+    src.write_text(text)
+    run = subprocess.run(["gcc", "-Werror", "-I", os.path.join(ROOT, "include"), *flags, str(src), "-o", str(out)],
+                         capture_output=True, text=True)
+    return run, out
+
+
 def test_struct_sizes_and_offsets_equal_the_headers_as_a_c_compiler_sees_it(tmp_path):
-    """include/miso_hip.h compiled by gcc: sizeof of every struct the ctypes binding mirrors and the offsets of the
-    fields added last (a binding that drifts from the header corrupts arguments silently)."""
-    import ctypes
-    import os
+    """include/miso_hip.h compiled by gcc: sizeof of EVERY struct of the binding, and offsetof and sizeof of every field
+    (a binding that drifts from the header corrupts arguments silently).  The list comes from the binding, which refuses
+    a header it reads only in part (test_reader_refuses_what_it_cannot_parse); the struct count is re-checked here."""
     import subprocess
     from miso_amd import _lib
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = tmp_path / "layout.c"
-    names = [("miso_level_t", _lib.Level), ("miso_grid_t", _lib.Grid), ("miso_mlp_t", _lib.Mlp),
-             ("miso_sorted_t", _lib.Sorted), ("miso_align_pair_t", _lib.AlignPair), ("miso_align_t", _lib.Align),
-             ("miso_lm_track_t", _lib.LmTrack), ("miso_track_adam_t", _lib.TrackAdam),
-             ("miso_adam_tensor_t", _lib.AdamTensor)]
-    offs = [("miso_align_t", "poses_ready", _lib.Align), ("miso_align_t", "state", _lib.Align),
-            ("miso_sorted_t", "pull_queue_ints", _lib.Sorted), ("miso_level_t", "grad_touched", _lib.Level)]
-    body = "".join(f'  printf("%zu\\n", sizeof({n}));\n' for n, _ in names)
-    body += "".join(f'  printf("%zu\\n", offsetof({n}, {f}));\n' for n, f, _ in offs)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "miso_hip.h"\nint main(void) {\n' + body + "  return 0;\n}\n")
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
+    assert len(_lib.STRUCTS) == len(re.findall(r"\btypedef\s+struct\b", _header_code())) >= 11
+    assert _lib.STRUCTS["miso_level_t"] is _lib.Level and _lib.STRUCTS["miso_ray_sampling_t"] is _lib.RaySampling
+    probes = []
+    for n, c in _lib.STRUCTS.items():
+        probes.append((f"sizeof({n})", ctypes.sizeof(c)))
+        for f, _ in c._fields_:
+            probes.append((f"offsetof({n}, {f})", getattr(c, f).offset))
+            probes.append((f"sizeof((({n}*)0)->{f})", getattr(c, f).size))
+    body = "".join(f'  printf("%zu\\n", {expr});\n' for expr, _ in probes)
+    run, exe = _gcc(tmp_path, "layout.c", '#include <stdio.h>\n#include <stddef.h>\n#include "miso_hip.h"\n'
+                    "int main(void) {\n" + body + "  return 0;\n}\n")
+    assert run.returncode == 0, run.stderr
     got = [int(v) for v in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    want = [ctypes.sizeof(c) for _, c in names] + [getattr(c, f).offset for _, f, c in offs]
-    assert got == want, list(zip([n for n, _ in names] + [f"{n}.{f}" for n, f, _ in offs], got, want))
-    assert _lib is not None
+    assert len(got) == len(probes)
+    wrong = [(expr, g, want) for (expr, want), g in zip(probes, got) if g != want]
+    assert not wrong, wrong
+
+
+# Parameter and return types of every declared function as the compiler sees them, reduced to what a ctypes call can get
+# wrong: a scalar stays itself (kind, width, signedness), a pointer to a miso_*_t struct keeps the struct, const char*
+# stays a string, every other pointer is void*.  The expected type is spelled from the binding's restype / argtypes.
+_SIG_PRELUDE = """#include <type_traits>
+#include "miso_hip.h"
+template <class T> struct arg { using type = T; };
+template <class T> struct arg<T*> {
+  using U = std::remove_cv_t<T>;
+  using type = std::conditional_t<std::is_class_v<U> || std::is_same_v<U, char>, U, void>*;
+};
+template <class F> struct abi;
+template <class R, class... A> struct abi<R(A...)> { using type = typename arg<R>::type(typename arg<A>::type...); };
+"""
+_C_SCALARS = {"i": "int", "I": "unsigned int", "l": "long", "L": "unsigned long", "b": "signed char", "B": "unsigned char",
+              "f": "float", "d": "double", "P": "void*", "z": "char*"}
+
+
+def _signature_checks(structs, signatures):
+    names = {c: n for n, c in structs.items()}
+
+    def spell(t):
+        return names[t._type_] + "*" if hasattr(t, "contents") else _C_SCALARS[t._type_]
+
+    return _SIG_PRELUDE + "".join(
+        f'static_assert(std::is_same_v<abi<decltype({n})>::type, {spell(res)}({", ".join(map(spell, args))})>, "{n}");\n'
+        for n, (res, args) in signatures.items())
+
+
+def test_function_signatures_equal_the_headers_as_a_compiler_sees_them(tmp_path):
+    """Nothing else checks a function's argument list: a ctypes call with a missing argument, or an int32 where the header
+    says int64_t, passes garbage in a register and the kernel runs on it.  gcc (as C++, for the parameter packs) compares
+    every prototype of the header with the type spelled from the binding; three wrong bindings must each be refused."""
+    from miso_amd import _lib
+    C = ctypes
+
+    def accepted(name, signatures):
+        run, _ = _gcc(tmp_path, name, _signature_checks(_lib.STRUCTS, signatures), "-x", "c++", "-std=c++17", "-c")
+        return run.returncode == 0, run.stderr
+
+    sigs = _lib.SIGNATURES
+    assert set(sigs) == set(_declared()) and len(sigs) >= 69
+    ok, err = accepted("sig.cpp", sigs)
+    assert ok, err
+
+    def mutated(name, change):
+        res, args = sigs[name]
+        args = list(args)
+        change(args)
+        return {**sigs, name: (res, args)}
+
+    def to_int32(args):
+        assert args[4] is C.c_int64
+        args[4] = C.c_int32
+
+    def swap_float_double(args):                      # (lr, beta1 .. eps) are doubles; make the first one a float
+        assert args[5] is C.c_double
+        args[5] = C.c_float
+
+    wrong = {"dropped.cpp": mutated("miso_atlas_sdf_fwd", lambda a: a.pop()),
+             "narrow.cpp": mutated("miso_encode_fwd", to_int32),                              # ld_out
+             "float.cpp": mutated("miso_adam_dense", swap_float_double),
+             "struct.cpp": mutated("miso_sdf_supported", lambda a: a.__setitem__(1, C.POINTER(_lib.Grid))),
+             "return.cpp": {**sigs, "miso_sort_workspace_bytes": (C.c_int32, sigs["miso_sort_workspace_bytes"][1])}}
+    for name, bad in wrong.items():
+        ok, err = accepted(name, bad)
+        assert not ok and "static assertion failed" in err, (name, err)
+
+
+def test_reader_refuses_what_it_cannot_parse():
+    """A declaration the reader skipped would leave a symbol or a struct unbound without a word: it raises instead."""
+    from miso_amd import _lib
+    header = open(os.path.join(ROOT, "include", "miso_hip.h")).read()
+    consts, structs, sigs = _lib.read_header(header)
+    assert consts["MISO_MAX_LEVELS"] == _lib.MAX_LEVELS == 8 and set(sigs) == set(_lib.SIGNATURES)
+    at = header.rindex("#ifdef __cplusplus")
+    for extra in ("typedef union { int a; } u_t;", "long miso_x(long);", "int miso_x(int32_t);", "int miso_x(int a[3]);",
+                  "typedef struct { long a; } miso_x_t;", "typedef struct { float* a, b; } miso_x_t;",
+                  "typedef struct { int a[MISO_NO_SUCH]; } miso_x_t;", "typedef struct { int a; } other_t;",
+                  "#define MISO_X (1 << 3)", "#pragma pack(1)"):
+        with pytest.raises(_lib.HeaderError):
+            _lib.read_header(header[:at] + extra + "\n" + header[at:])
 
 
 def test_tile_codes_pack_and_choose():
