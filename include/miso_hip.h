@@ -165,8 +165,9 @@ int miso_mlp_pack(const miso_mlp_t* mlp, float* packed, void* stream);
 int miso_sdf_supported(const miso_grid_t* grid, const miso_mlp_t* mlp);
 /* Dynamic LDS (bytes) of the one-launch training kernel (miso_sdf_train / miso_sdf_train_sorted) for this (levels, C,
  * hidden width, hidden layers) shape -- scattering != 0: the form that scatters some level from the kernel (cell records
- * beside the d-feat tiles); 0: every level deferred to the pull.  0 = shape not covered.  A caller routes a shape whose
- * figure exceeds the device's LDS per workgroup (160 KB on gfx950) to the two-launch path instead of failing in the launch. */
+ * beside the d-feat tiles); 0: every level deferred to the pull.  Returns 0 when the shape is not covered or the figure
+ * exceeds the device's LDS per workgroup (160 KB on gfx950): a caller routes such a shape to the two-launch path instead
+ * of failing in the launch. */
 int64_t miso_sdf_train_lds_bytes(const miso_grid_t* grid, const miso_mlp_t* mlp, int32_t scattering);
 
 /* uint32 words of ReLU sign bits per point: (n_linear-1) * hidden_dim/32 */

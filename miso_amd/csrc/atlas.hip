@@ -14,10 +14,7 @@
 // coordinates from the point index and three short axis tables: no (N,3) tensor is ever formed.
 // A chunk with no point inside any submap (the empty corners of a scene's bounding box) decodes the all-zero feature row:
 // that value is computed once per wavefront and stored.
-#include <stdlib.h>
-
-#include "decoder.hpp"
-#include "launch.hpp"
+#include "sdf_fused.hpp"
 
 namespace miso {
 
@@ -145,12 +142,8 @@ __global__ __launch_bounds__(256, 2) void atlas_sdf_kernel(AtlasK a, const float
   }
 }
 
-#define MISO_ATLAS_SHAPES(X) \
-  X(4, 1, 32, 1) X(4, 1, 64, 1) X(4, 2, 32, 1) X(4, 2, 64, 1) X(4, 3, 64, 1) X(4, 4, 64, 1) \
-  X(8, 1, 64, 1) X(8, 2, 64, 1) X(8, 3, 64, 1) X(8, 4, 64, 1) X(8, 3, 32, 1)
-
 template <int C, int L, int H, int NH>
-static hipError_t launch_atlas_t(const AtlasK& a, const float* packed, bool split, hipStream_t s) {
+static hipError_t launch_atlas_t(FusedShape<C, L, H, NH>, const AtlasK& a, const float* packed, bool split, hipStream_t s) {
   PackLayout pl(C * L, H, NH);
   size_t lds = (size_t)(split ? pl.s_fwd_end - pl.s_w0 + (pl.n_bias() + 3) / 4 * 4 : (pl.fwd_end + 3) / 4 * 4) * sizeof(float);
   if (!a.sdf) lds = 16;
@@ -166,13 +159,9 @@ static hipError_t launch_atlas_t(const AtlasK& a, const float* packed, bool spli
 
 hipError_t launch_atlas_sdf(int C, int L, int H, int NH, const AtlasK& a, const float* packed, bool exact, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
-  static const bool env_exact = [] { const char* e = getenv("MISO_EXACT_F32"); return e && atoi(e) != 0; }();
-  const bool split = !exact && !env_exact;
-#define X(c, l, h, nh) \
-  if (C == c && L == l && H == h && NH == nh) return launch_atlas_t<c, l, h, nh>(a, packed, split, s);
-  MISO_ATLAS_SHAPES(X)
-#undef X
-  return hipErrorInvalidValue;
+  const bool split = use_split(exact);
+  return with_fused_shape(C, L, H, NH, hipErrorInvalidValue,
+                          [&](auto shape) { return launch_atlas_t(shape, a, packed, split, s); });
 }
 
 }  // namespace miso

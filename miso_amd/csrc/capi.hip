@@ -16,6 +16,12 @@ namespace {
 // which pointer of a level a call needs
 enum Need { NEED_DATA = 1, NEED_GRAD_OPT = 2 };
 
+// elements from a level's first to its last, + 1 (miso_level_t or LevelK)
+template <class Level>
+int64_t level_span(const Level& s) {
+  return (int64_t)(s.C - 1) * s.sC + (int64_t)(s.X - 1) * s.sX + (int64_t)(s.Y - 1) * s.sY + (int64_t)(s.Z - 1) * s.sZ + 1;
+}
+
 int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) {
   if (!in || in->n_levels < 1 || in->n_levels > MISO_MAX_LEVELS) return MISO_E_BADARG;
   if (in->flags & ~(MISO_F_ALIGN_CORNERS | MISO_F_PAD_BORDER | MISO_F_COORDS_NORMALIZED | MISO_F_GRAD_OVERWRITE |
@@ -36,9 +42,7 @@ int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) 
     if (s.C < 1 || s.X < 1 || s.Y < 1 || s.Z < 1) return MISO_E_BADARG;
     if (need_data && !s.data) return MISO_E_BADARG;
     if (s.sC < 0 || s.sX < 0 || s.sY < 0 || s.sZ < 0) return MISO_E_BADARG;
-    int64_t span = (int64_t)(s.C - 1) * s.sC + (int64_t)(s.X - 1) * s.sX + (int64_t)(s.Y - 1) * s.sY +
-                   (int64_t)(s.Z - 1) * s.sZ + 1;
-    if (span >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+    if (level_span(s) >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
     LevelK& d = out->lv[l];
     d.data = s.data; d.grad = s.grad; d.gg = nullptr;
     d.touched = s.grad ? s.grad_touched : nullptr;
@@ -66,6 +70,33 @@ int fused_shape(const GridK& g, bool vec4, const miso_mlp_t* m, int* C, int* L, 
   if (!fused_shape_supported(c, g.n_levels, m->hidden_dim, nh)) return MISO_E_UNSUPPORTED;
   *C = c; *L = g.n_levels; *H = m->hidden_dim; *NH = nh;
   return MISO_OK;
+}
+
+// zero-fill the gradient of the levels in `levels`: those a launch adds to with atomics start from zero
+// (a kernel, not hipMemsetAsync: memset nodes of a captured graph that is replayed back to back with other
+// launches in between now and then fill with garbage on ROCm 7.2 -- see loss.hip:zero_words_kernel)
+hipError_t zero_level_grads(const GridK& g, uint32_t levels, hipStream_t st) {
+  for (int l = 0; l < g.n_levels; ++l) {
+    const LevelK& lv = g.lv[l];
+    if (!lv.grad || !((levels >> l) & 1u)) continue;
+    hipError_t e = launch_zero_fill(lv.grad, level_span(lv), st);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// the loss side of a fused launch: the mapping loss's parameters, its input rows, where d loss / d sdf (binned order) and
+// the loss slots go; the mean is over n rows, or over *n_live of a padded batch
+LossInK loss_in(int loss_type, float w_sdf, float w_fs, float trunc, const float* loss_inputs, float* gsdf_sorted,
+                float* loss_slots, int64_t n, const int32_t* n_live) {
+  LossInK lin;
+  memset(&lin, 0, sizeof(lin));
+  lin.p.loss_type = loss_type; lin.p.w_sdf = w_sdf; lin.p.w_fs = w_fs; lin.p.trunc = trunc;
+  lin.aux = reinterpret_cast<const float4*>(loss_inputs);
+  lin.gsdf_sorted = gsdf_sorted; lin.loss_out = loss_slots;
+  lin.inv_n = 1.0f / (float)n;
+  lin.n_live = n_live;
+  return lin;
 }
 
 }  // namespace
@@ -272,17 +303,9 @@ static int sdf_bwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
   if (pull && !pull_serviceable(sorted, n, g.F)) return MISO_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (overwrite && !(grid->flags & MISO_F_GRAD_ZEROED)) {
-    // levels that are scattered or pushed with atomics start from zero; pulled levels need no fill
-    for (int l = 0; l < g.n_levels; ++l) {
-      const LevelK& lv = g.lv[l];
-      if (!lv.grad || (((pull & ~push) >> l) & 1u)) continue;
-      size_t span = (size_t)(lv.C - 1) * lv.sC + (size_t)(lv.X - 1) * lv.sX + (size_t)(lv.Y - 1) * lv.sY +
-                    (size_t)(lv.Z - 1) * lv.sZ + 1;
-      // (a kernel, not hipMemsetAsync: memset nodes of a captured graph that is replayed back to back with other
-      // launches in between now and then fill with garbage on ROCm 7.2 -- see loss.hip:zero_words_kernel)
-      hipError_t e = launch_zero_fill(lv.grad, (int64_t)span, st);
-      if (e != hipSuccess) return (int)e;
-    }
+    // levels that are scattered or pushed with atomics; pulled levels need no fill
+    hipError_t e = zero_level_grads(g, ~(pull & ~push), st);
+    if (e != hipSuccess) return (int)e;
   }
   if (n == 0 && !pull) return MISO_OK;
   if (n > 0) {
@@ -391,13 +414,7 @@ int miso_sdf_fwd_sorted_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, con
     return MISO_E_BADARG;
   if (((uintptr_t)loss_inputs & 15u) != 0) return MISO_E_BADARG;
   if (n == 0) return (int)launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, (hipStream_t)stream);
-  LossInK lin;
-  memset(&lin, 0, sizeof(lin));
-  lin.p.loss_type = loss_type; lin.p.w_sdf = weight_sdf; lin.p.w_fs = weight_fs; lin.p.trunc = trunc_dist;
-  lin.aux = reinterpret_cast<const float4*>(loss_inputs);
-  lin.gsdf_sorted = grad_sdf_sorted; lin.loss_out = loss_slots;
-  lin.inv_n = n > 0 ? 1.0f / (float)n : 0.0f;
-  lin.n_live = n_live;
+  const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, grad_sdf_sorted, loss_slots, n, n_live);
   return sdf_fwd_impl(grid, mlp, packed, nullptr, n, sdf, relu_mask, sorted, stream, &lin);
 }
 
@@ -408,12 +425,7 @@ int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const floa
     return MISO_E_BADARG;
   if (((uintptr_t)loss_inputs & 15u) != 0) return MISO_E_BADARG;
   if (n == 0) return (int)launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, (hipStream_t)stream);
-  LossInK lin;
-  memset(&lin, 0, sizeof(lin));
-  lin.p.loss_type = loss_type; lin.p.w_sdf = weight_sdf; lin.p.w_fs = weight_fs; lin.p.trunc = trunc_dist;
-  lin.aux = reinterpret_cast<const float4*>(loss_inputs);
-  lin.gsdf_sorted = grad_sdf; lin.loss_out = loss_slots;
-  lin.inv_n = 1.0f / (float)n;
+  const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, grad_sdf, loss_slots, n, nullptr);
   return sdf_fwd_impl(grid, mlp, packed, x, n, sdf, relu_mask, nullptr, stream, &lin);
 }
 
@@ -541,26 +553,14 @@ static int sdf_train_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const 
   hipStream_t st = (hipStream_t)stream;
   const bool overwrite = sorted && (grid->flags & MISO_F_GRAD_OVERWRITE) != 0;
   if (overwrite && !(grid->flags & MISO_F_GRAD_ZEROED)) {
-    for (int l = 0; l < g.n_levels; ++l) {      // pushed and scattered levels are added to with atomics: they start from zero
-      const LevelK& lv = g.lv[l];
-      if (!lv.grad || !(((push | scat) >> l) & 1u)) continue;
-      size_t span = (size_t)(lv.C - 1) * lv.sC + (size_t)(lv.X - 1) * lv.sX + (size_t)(lv.Y - 1) * lv.sY +
-                    (size_t)(lv.Z - 1) * lv.sZ + 1;
-      hipError_t e = launch_zero_fill(lv.grad, (int64_t)span, st);
-      if (e != hipSuccess) return (int)e;
-    }
+    hipError_t e = zero_level_grads(g, push | scat, st);
+    if (e != hipSuccess) return (int)e;
   }
   if (n == 0) {
     hipError_t e = launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, st);
     if (e != hipSuccess) return (int)e;
   } else {
-    LossInK lin;
-    memset(&lin, 0, sizeof(lin));
-    lin.p.loss_type = loss_type; lin.p.w_sdf = weight_sdf; lin.p.w_fs = weight_fs; lin.p.trunc = trunc_dist;
-    lin.aux = reinterpret_cast<const float4*>(loss_inputs);
-    lin.loss_out = loss_slots;
-    lin.inv_n = 1.0f / (float)n;
-    lin.n_live = n_live;
+    const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, nullptr, loss_slots, n, n_live);
     GridK gp = g;
     if (sorted) x = sorted_points(&gp, sorted);
     if (sorted && !sorted->perm) gp.flags |= MISO_F_INDEX_IN_XN;

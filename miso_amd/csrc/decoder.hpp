@@ -1,5 +1,5 @@
 // Frozen-decoder MLP (MLPNet: grid_opt/models/modules.py:11-32) on the matrix cores: the packed-weight layout shared by
-// mlp_pack_kernel and every kernel that decodes (sdf_fused.hip, atlas.hip), the register-level helpers of the ReLU / gate
+// mlp_pack_kernel and every kernel that decodes (sdf_fused.hip, sdf_train.hip, atlas.hip), the register-level helpers of the ReLU / gate
 // passes, and the split-precision (bf16x3, mlp_split.hpp) forward and backward chains.
 #pragma once
 #include "common.hpp"

@@ -18,7 +18,6 @@ hipError_t launch_encode_bwd2(const GridK& g, bool vec4, const float* x, int64_t
 
 // ---- sdf_fused.hip
 bool fused_shape_supported(int C, int L, int H, int NH);
-int64_t sdf_train_lds_bytes(int C, int L, int H, int NH, bool scat);
 int64_t mlp_packed_floats(int F, int H, int NH);
 hipError_t launch_mlp_pack(const MlpK& m, int F, int H, int NH, float* out, hipStream_t s);
 hipError_t launch_sdf_fwd(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,
@@ -26,6 +25,9 @@ hipError_t launch_sdf_fwd(int C, int L, int H, int NH, const GridK& g, const flo
 hipError_t launch_sdf_bwd(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,
                           const float* gsdf, const uint32_t* mask, float* gx, bool want_grid, const int* perm,
                           float* dfeat_out, uint32_t defer_mask, bool gsdf_sorted, hipStream_t s);
+
+// ---- sdf_train.hip (sdf_train_lds_bytes: 0 = shape not covered, or its widest launch does not fit a workgroup's LDS)
+int64_t sdf_train_lds_bytes(int C, int L, int H, int NH, bool scat);
 hipError_t launch_sdf_train(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,
                             float* sdf, const int* perm, const LossInK& lin, float* dfeat_out, uint32_t defer_mask,
                             bool scat, hipStream_t s);

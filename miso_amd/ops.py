@@ -638,50 +638,23 @@ def sdf_fwd_loss_raw(features, meta, pack: DecoderPack, sorted_batch: SortedBatc
 
 
 def sdf_train_supported(features, meta, grads, pack: Optional["DecoderPack"] = None) -> bool:
-    """True when sdf_train_raw / sdf_train_unsorted_raw cover this gradient request: a level with a gradient exists
-    (the fused decoder shape itself is sdf_fused_supported's business).  Levels the pull / push cannot form from the
-    d-feat rows are scattered with float atomics from the same launch (sdf_train_scattered_levels).
+    """True when sdf_train_raw / sdf_train_unsorted_raw cover this gradient request: a level with a gradient exists and
+    the training kernel takes the grids (channels-last levels of one width) with this decoder.  Levels the pull / push
+    cannot form from the d-feat rows are scattered with float atomics from the same launch (sdf_train_scattered_levels).
     pack: the decoder (its hidden width and depth size the kernel's LDS; without it 64 x 1, the reference's decoder)."""
     if not any(gr is not None and not (meta.ignore_mask >> l) & 1 for l, gr in enumerate(grads)):
         return False
-    # (ADVICE r3 / r4) the scattering variant keeps cell records beside the weights: make sure the widest form of the launch
-    # fits a workgroup's LDS, so that a shape that does not is routed to the two-launch path instead of failing there --
-    # asked of the library itself (miso_sdf_train_lds_bytes: computed from the kernel's own PackLayout) when the decoder
-    # is at hand
-    if pack is not None and features[0].is_cuda:
-        m, _ = pack.get()
+    # (ADVICE r3 / r4) the scattering variant keeps cell records beside the weights: a shape whose widest launch does not
+    # fit a workgroup's LDS is routed to the two-launch path instead of failing there.  The library plans that launch
+    # (miso_sdf_train_lds_bytes: host code, CPU tensors will do; 0 = not covered by the kernel, or too wide for it).
+    if pack is not None:
+        m, _ = pack._struct()          # (its dimensions are all the query reads)
         if m is None:
             return False
-        need = int(_lib.load().miso_sdf_train_lds_bytes(C.byref(_fill_grid(features, meta, grads, data=False)), C.byref(m), 1))
-        return 0 < need <= LDS_PER_WORKGROUP
-    H = pack.weights[0].shape[0] if pack is not None else 64
-    NH = len(pack.weights) - 2 if pack is not None else 1
-    return sdf_train_lds_bytes(features[0].shape[1], len(features), H, scat=True, hidden_layers=NH) <= LDS_PER_WORKGROUP
-
-
-LDS_PER_WORKGROUP = 160 * 1024      # gfx950
-
-
-def sdf_train_lds_bytes(C: int, L: int, H: int, scat: bool, hidden_layers: int = 1) -> int:
-    """Dynamic LDS of sdf_train_kernel<C, L, H, NH, SCAT> (sdf_fused.hip: PackLayout + four wavefronts' d-feat tiles
-    [64][FP] and, scattering, their cell records [64][L][8] -- two blocks of them where 160 KB allow)."""
-    F, RT, KS0, KS1, NH = C * L, H // 32, (C * L + 1) // 2, H // 2, hidden_layers
-    exact = KS0 * 64 * RT + 2 * NH * KS1 * 64 * RT + H + NH * H + H + 4 + KS1 * 64
-    # the bf16x3 form (decoder.hpp): its matrices as [k-block][row tile][3 pieces][64 lanes][4 dwords] + biases and output
-    # weights -- the larger of the two packs for every covered shape, and the one the default launch stages
-    smd = lambda kb, rt: kb * rt * 3 * 64 * 4                                           # noqa: E731
-    KB0, KBH = (F + 15) // 16, H // 16
-    split = (smd(KB0, RT) + NH * smd(KBH, RT) + smd(KBH, RT if NH >= 1 else 1) + max(NH - 1, 0) * smd(KBH, RT)
-             + (smd(KBH, 1) if NH >= 1 else 0) + (H + NH * H + H + 4 + 3) // 4 * 4)
-    pack = max((exact + 3) // 4 * 4, split)
-    FP = (F + 3) // 4 * 4 + 4
-    words = pack + 4 * (64 * FP + (64 * L * 8 if scat else 0))
-    if scat and F <= 12 and 4 * (words + 4 * 64 * L * 8) <= LDS_PER_WORKGROUP:
-        words += 4 * 64 * L * 8          # a second block of cell records where it fits (the rotated loop, launch_train_t)
-        eight = pack + 8 * (64 * FP + 2 * 64 * L * 8)          # ... and the eight-wavefront form of it
-        if 4 * eight <= LDS_PER_WORKGROUP:
-            words = max(words, eight)
-    return 4 * words
+    else:
+        m = _lib.Mlp()
+        m.n_linear, m.in_dim, m.hidden_dim, m.out_dim = 3, _feature_dim(features), 64, 1
+    return int(_lib.load().miso_sdf_train_lds_bytes(C.byref(_fill_grid(features, meta, grads, data=False)), C.byref(m), 1)) > 0
 
 
 def sdf_train_scattered_levels(features, meta, grads, tiles=None) -> int:
