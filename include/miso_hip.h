@@ -729,6 +729,26 @@ int miso_atlas_sdf_fwd(const void* plan, int32_t n_submaps, const miso_grid_t* s
                        const float* axis_y, const float* axis_z, int32_t nx, int32_t ny, int32_t nz, float* sdf,
                        float* feats, int64_t ld_feats, uint32_t flags, void* stream);
 
+/* --- sphere tracing: utils_sdf.sphere_tracing in one launch -----------------------------------------------------------
+ * Replaces the loop of grid_opt/utils/utils_sdf.py:197-236 (per round: norm, one model call, three masks, a host sync on
+ * torch.sum(mask_stop) == n, a blended update of all N points) when the model is a GridAtlas or a GridNet: one wavefront
+ * per 64 rays, the field evaluated by the body of miso_atlas_sdf_fwd (same bits at the same point), a ray's state in
+ * registers.  Per ray: p = o + min_dist d; up to max_iters times: dist = |p - o|, s = f(p), converged = s < epsilon,
+ * far = dist > max_dist; the ray stops where either holds, else p = p + s d (product and sum rounded separately, as
+ * the two tensor ops).
+ *   `plan`, `n_submaps`, `shape`, `poses`, `mlp`, `packed`: as for miso_atlas_sdf_fwd.  `origins`, `dirs`: device
+ *   (n_rays, 3); dirs of unit length (the caller normalises: utils.normalize_last_dim).  Outputs (device): `points`
+ *   (n_rays, 3) and `hit` (n_rays bytes, 1 = converged in the ray's last iteration) as the reference returns them; each
+ *   NULL or `sdf` (n_rays) f at the returned point, `steps` (n_rays) the iterations in which the ray moved, `grad`
+ *   (n_rays, 3) central differences (f(p + h e_a) - f(p - h e_a)) / (2 h) with h = fd_step > 0 at the returned point
+ *   (diff.gradient3d, method 'finitediff').  flags: MISO_F_EXACT_F32, MISO_F_ATLAS_NO_BOUND.  n_rays == 0 launches
+ *   nothing. */
+int miso_atlas_sphere_trace(const void* plan, int32_t n_submaps, const miso_grid_t* shape, const float* poses,
+                            const miso_mlp_t* mlp, const float* packed, const float* origins, const float* dirs,
+                            int64_t n_rays, float min_dist, float max_dist, int32_t max_iters, float epsilon,
+                            float fd_step, float* points, uint8_t* hit, float* sdf, int32_t* steps, float* grad,
+                            uint32_t flags, void* stream);
+
 /* --- marching cubes on the dense SDF volume ------------------------------------
  * Replaces mcubes.marching_cubes(u, threshold) as called by extract_geometry
  * (grid_opt/utils/utils_sdf.py:89-101; PyMCubes is a third-party dependency of the reference) with the

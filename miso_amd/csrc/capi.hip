@@ -1060,6 +1060,36 @@ int miso_atlas_sdf_fwd(const void* plan, int32_t n_submaps, const miso_grid_t* s
   return (int)launch_atlas_sdf(C, L, H, NH, a, packed, (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
 }
 
+// ---- sphere tracing through the fused atlas query (trace.hip) ------------------------------------------------------------
+int miso_atlas_sphere_trace(const void* plan, int32_t n_submaps, const miso_grid_t* shape, const float* poses,
+                            const miso_mlp_t* mlp, const float* packed, const float* origins, const float* dirs,
+                            int64_t n_rays, float min_dist, float max_dist, int32_t max_iters, float epsilon,
+                            float fd_step, float* points, uint8_t* hit, float* sdf, int32_t* steps, float* grad,
+                            uint32_t flags, void* stream) {
+  if (!plan || !poses || !shape || !mlp || !packed || !origins || !dirs || !points || !hit) return MISO_E_BADARG;
+  if (n_submaps < 1 || n_rays < 0 || max_iters < 1 || (grad && !(fd_step > 0.0f))) return MISO_E_BADARG;
+  if (flags & ~(MISO_F_EXACT_F32 | MISO_F_ATLAS_NO_BOUND)) return MISO_E_BADARG;
+  if (((uintptr_t)packed) & 15u) return MISO_E_BADARG;
+  GridK g; bool v4;
+  int rc = convert_grid(shape, &g, false, &v4);
+  if (rc) return rc;
+  int C = g.lv[0].C, L = g.n_levels, H = 64, NH = 1;
+  rc = fused_shape(g, true, mlp, &C, &L, &H, &NH);
+  if (rc) return rc;
+  if (n_rays == 0) return MISO_OK;
+  AtlasK a;
+  memset(&a, 0, sizeof(a));
+  a.submaps = reinterpret_cast<const GridK*>(plan);
+  a.poses = poses; a.n_submaps = n_submaps; a.n = n_rays;
+  a.no_bound = (flags & MISO_F_ATLAS_NO_BOUND) ? 1 : 0;
+  TraceK t;
+  memset(&t, 0, sizeof(t));
+  t.origins = origins; t.dirs = dirs; t.n = n_rays;
+  t.min_dist = min_dist; t.max_dist = max_dist; t.epsilon = epsilon; t.fd_step = fd_step; t.max_iters = max_iters;
+  t.points = points; t.hit = hit; t.sdf = sdf; t.steps = steps; t.grad = grad;
+  return (int)launch_atlas_trace(C, L, H, NH, a, t, packed, (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
+}
+
 int64_t miso_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
   if (mc_check_dims(nx, ny, nz)) return -1;
   return mc_workspace_bytes(nx, ny, nz);

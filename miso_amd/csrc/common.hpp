@@ -60,6 +60,22 @@ struct AtlasK {
   int32_t no_bound;          // MISO_F_ATLAS_NO_BOUND: no coords_in_bound test (one submap queried as GridNet.forward does)
 };
 
+// One sphere-tracing launch (trace.hip; miso_atlas_sphere_trace): the rays, the reference's loop constants, the outputs.
+// The field is the AtlasK that goes with it (x, sdf, feats unused; n = n_rays).
+struct TraceK {
+  const float* origins;      // (N,3)
+  const float* dirs;         // (N,3), unit length (the caller normalises)
+  int64_t n;
+  float min_dist, max_dist, epsilon;
+  float fd_step;             // central-difference step of grad
+  int32_t max_iters;
+  float* points;             // (N,3)
+  uint8_t* hit;              // (N): s < epsilon in the ray's last iteration
+  float* sdf;                // (N) field value at points, or nullptr
+  int32_t* steps;            // (N) iterations in which the ray moved, or nullptr
+  float* grad;               // (N,3) central differences at points, or nullptr
+};
+
 __device__ __forceinline__ void load_point(const GridK& g, const float* __restrict__ x, int64_t p, float& px,
                                            float& py, float& pz) {
   if (g.xstride == 4) {

@@ -33,8 +33,18 @@ __device__ __forceinline__ float gate(float x, uint32_t m, int t, int j) {
   return __uint_as_float(__float_as_uint(x) & (uint32_t)e);
 }
 
+// acc += a b.  Left as a product and a sum (PIN_FMA = false), whether the two become one v_fma is up to the vectoriser
+// and the contraction heuristics, which decide by the surrounding code: in sdf_fwd_kernel every one of them does.  A
+// kernel that has to give sdf_fwd_kernel's bits from inside other code (atlas_eval.hpp: inlined into two kernels, at
+// several places) asks for the fused form outright (PIN_FMA = true) in the gather and in the output dot product.
+template <bool PIN_FMA>
+__device__ __forceinline__ void mul_acc(float& acc, float a, float b) {
+  if constexpr (PIN_FMA) acc = __builtin_fmaf(a, b, acc);
+  else acc += a * b;
+}
+
 // lane-per-point trilinear gather of one level (channels-last rows of C floats, 16-B loads): f[0..C) = sum_k w_k v_k
-template <int C>
+template <int C, bool PIN_FMA = false>
 __device__ __forceinline__ void gather_level(const LevelK& lv, const Cell& c, float* f) {
   // lane-per-point gather of one level: 8 corners x C channels, channels-last.
 #pragma unroll
@@ -54,7 +64,8 @@ __device__ __forceinline__ void gather_level(const LevelK& lv, const Cell& c, fl
 #pragma unroll
     for (int q = 0; q < C; q += 4) {
       float4 v = *reinterpret_cast<const float4*>(lv.data + off + q);
-      f[q + 0] += v.x * w; f[q + 1] += v.y * w; f[q + 2] += v.z * w; f[q + 3] += v.w * w;
+      mul_acc<PIN_FMA>(f[q + 0], v.x, w); mul_acc<PIN_FMA>(f[q + 1], v.y, w);
+      mul_acc<PIN_FMA>(f[q + 2], v.z, w); mul_acc<PIN_FMA>(f[q + 3], v.w, w);
     }
   }
 }
@@ -182,7 +193,7 @@ __device__ __forceinline__ uint32_t mask_pair_from_bits(uint32_t m, int t, int j
 // of the exact kernels: word l*RT + r, tile t's element j at bit 31 - (16 t + j)); BITS_LAST = false leaves the last
 // layer's words unwritten and MASKB = true returns the last ReLU's mask as the B operand of the first backward product.
 //   sw: LDS, the pack's [s_w0, s_fwd_end) block;  bias: LDS, the pack's [o_b0, fwd_end) block (b0, bh, wo, bo)
-template <int F, int H, int NH, bool HALF, bool BITS_LAST, bool MASKB, int FN>
+template <int F, int H, int NH, bool HALF, bool BITS_LAST, bool MASKB, bool PIN_FMA = false, int FN = 0>
 __device__ __forceinline__ void decoder_fwd_split(const uint32_t* __restrict__ sw, const float* __restrict__ bias, int lane,
                                                   const float (&f)[FN], uint32_t (&mw)[(NH + 1) * (H / 32)],
                                                   u32x4 (&maskB)[H / 16][HALF ? 1 : 2], float& p0, float& p1,
@@ -238,8 +249,8 @@ __device__ __forceinline__ void decoder_fwd_split(const uint32_t* __restrict__ s
         const float y0 = relu1(acc[0][j]), y1 = HALF ? 0.0f : relu1(acc[NT - 1][j]);
         if (BITS_LAST) { push_gt0(m, y0); if (!HALF) push_gt0(m1, y1); }
         const float wv = wo[32 * r + row_of(j, hi)];
-        p0 += wv * y0;
-        if (!HALF) p1 += wv * y1;
+        mul_acc<PIN_FMA>(p0, wv, y0);
+        if (!HALF) mul_acc<PIN_FMA>(p1, wv, y1);
         if (MASKB && (j & 1)) {
           maskB[2 * r + (j >> 3)][0][(j & 7) >> 1] = mask_pair_bf16(relu1(acc[0][j - 1]), y0);
           if (!HALF) maskB[2 * r + (j >> 3)][NT - 1][(j & 7) >> 1] = mask_pair_bf16(relu1(acc[NT - 1][j - 1]), y1);
@@ -298,8 +309,8 @@ __device__ __forceinline__ void decoder_fwd_split(const uint32_t* __restrict__ s
         const float y0 = relu1(acc[0][j]), y1 = HALF ? 0.0f : relu1(acc[NT - 1][j]);
         if (BITS_LAST) { push_gt0(m, y0); if (!HALF) push_gt0(m1, y1); }
         const float wv = wo[32 * r + row_of(j, hi)];
-        p0 += wv * y0;
-        if (!HALF) p1 += wv * y1;
+        mul_acc<PIN_FMA>(p0, wv, y0);
+        if (!HALF) mul_acc<PIN_FMA>(p1, wv, y1);
         if (MASKB && (j & 1)) {
           maskB[2 * r + (j >> 3)][0][(j & 7) >> 1] = mask_pair_bf16(relu1(acc[0][j - 1]), y0);
           if (!HALF) maskB[2 * r + (j >> 3)][NT - 1][(j & 7) >> 1] = mask_pair_bf16(relu1(acc[NT - 1][j - 1]), y1);
@@ -386,7 +397,7 @@ __device__ __forceinline__ void decoder_bwd_split(const uint32_t* __restrict__ s
 // The exact fp32 chains of the forward (v_mfma_f32_32x32x2_f32; the accumulators of a layer ARE the next layer's B operand:
 // sdf_fused.hip's header), as sdf_fwd_kernel and atlas_sdf_kernel run them behind MISO_F_EXACT_F32.  w0p / whp / b0 / bh / wo:
 // the fp32 pack's forward part in LDS.  Same outputs as decoder_fwd_split (p0 / p1: this lane's partial output sums).
-template <int F, int H, int NH, int FN>
+template <int F, int H, int NH, bool PIN_FMA = false, int FN = 0>
 __device__ __forceinline__ void decoder_fwd_exact(const float* __restrict__ w0p, const float* __restrict__ whp,
                                                   const float* __restrict__ b0, const float* __restrict__ bh,
                                                   const float* __restrict__ wo, int lane, const float (&f)[FN],
@@ -473,8 +484,8 @@ __device__ __forceinline__ void decoder_fwd_exact(const float* __restrict__ w0p,
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         float wv = wo[32 * r + row_of(j, hi)];
-        p0 += wv * buf[0][r][0][j];
-        p1 += wv * buf[0][r][1][j];
+        mul_acc<PIN_FMA>(p0, wv, buf[0][r][0][j]);
+        mul_acc<PIN_FMA>(p1, wv, buf[0][r][1][j]);
       }
   } else {
     constexpr int h = NH > 0 ? NH - 1 : 0, ci = h & 1;
@@ -499,8 +510,8 @@ __device__ __forceinline__ void decoder_fwd_exact(const float* __restrict__ w0p,
         push_gt0(m, y0);
         push_gt0(m1, y1);
         float wv = wo[32 * r + row_of(j, hi)];
-        p0 += wv * y0;
-        p1 += wv * y1;
+        mul_acc<PIN_FMA>(p0, wv, y0);
+        mul_acc<PIN_FMA>(p1, wv, y1);
       }
       mw[(h + 1) * RT + r] = (m << 16) | m1;
     }

@@ -35,6 +35,10 @@ hipError_t launch_sdf_train(int C, int L, int H, int NH, const GridK& g, const f
 // ---- atlas.hip
 hipError_t launch_atlas_sdf(int C, int L, int H, int NH, const AtlasK& a, const float* packed, bool exact, hipStream_t s);
 
+// ---- trace.hip
+hipError_t launch_atlas_trace(int C, int L, int H, int NH, const AtlasK& a, const TraceK& t, const float* packed, bool exact,
+                              hipStream_t s);
+
 // ---- sort.hip
 int64_t sort_workspace_bytes(int64_t n, int tiles);
 hipError_t launch_sort(const GridK& g, const float* x, int64_t n, int tiles, void* ws, float* xs, float* xn, int* perm,

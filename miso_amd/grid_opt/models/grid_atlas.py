@@ -267,15 +267,14 @@ class GridAtlas(BaseNet):
             s.zero_features()
 
     # ---- queries (hot path) ----------------------------------------------------------------------
-    def _fused_query(self, x_world=None, axes=None, want_sdf=True, want_feats=False):
-        """query_feature / forward as ONE launch (ops.AtlasQuery -> miso_atlas_sdf_fwd) when nothing has to be
-        differentiated: the per-submap loop below encodes every point in every submap and moves (N,F) temporaries
-        through HBM per submap; the kernel tests the bound first, encodes where a point is inside, keeps sum, count and
-        mean in registers and decodes them on the spot.  None when the query is not eligible (autograd on, host
-        tensors, a decoder or grid shape the fused kernels do not cover): the caller then runs the loop."""
+    def _fused_inputs(self, probe, want_sdf=True):
+        """What a one-launch query of the active submaps needs -- (query, features, metas, pose table, decoder pack) --
+        or None when the query is not eligible: autograd on, host tensors, a decoder or grid shape the fused kernels do
+        not cover.  probe: the tensor whose device decides (the points, or None: the first submap's features)."""
         if torch.is_grad_enabled() or not self.active_submaps:
             return None
-        probe = x_world if x_world is not None else self.get_submap(self.active_submaps[0]).features[0].feature
+        if probe is None:
+            probe = self.get_submap(self.active_submaps[0]).features[0].feature
         if not probe.is_cuda:
             return None
         subs = [self.get_submap(s) for s in self.active_submaps]
@@ -317,9 +316,41 @@ class GridAtlas(BaseNet):
             poses = torch.stack(rows).to(device=probe.device, dtype=torch.float32).contiguous()
             self.__dict__['_atlas_poses'] = (pkey, poses)
         q = self.__dict__.setdefault('_atlas_query', ops.AtlasQuery())
+        return q, feats, metas, poses, pack
+
+    def _fused_query(self, x_world=None, axes=None, want_sdf=True, want_feats=False):
+        """query_feature / forward as ONE launch (ops.AtlasQuery -> miso_atlas_sdf_fwd) when nothing has to be
+        differentiated: the per-submap loop below encodes every point in every submap and moves (N,F) temporaries
+        through HBM per submap; the kernel tests the bound first, encodes where a point is inside, keeps sum, count and
+        mean in registers and decodes them on the spot.  None when the query is not eligible (_fused_inputs): the
+        caller then runs the loop."""
+        got = self._fused_inputs(x_world, want_sdf)
+        if got is None:
+            return None
+        q, feats, metas, poses, pack = got
         try:
             return q(feats, metas, poses, pack, x=x_world, axes=axes, want_sdf=want_sdf, want_feats=want_feats)
         except RuntimeError as e:              # a shape outside the kernel table: the loop serves it
+            if "not covered" in str(e):
+                return None
+            raise
+
+    def sphere_trace(self, origins: Tensor, directions: Tensor, min_dist=1e-3, max_dist=5e1, max_iters=100,
+                     epsilon=1e-5, **extras):
+        """utils_sdf.sphere_tracing(self, ...) in ONE launch (ops.AtlasQuery.trace -> miso_atlas_sphere_trace): the same
+        points and mask as the loop over forward(), bit for bit.  extras: want_sdf, want_steps, grad_step (see
+        AtlasQuery.trace).  -> (points (N,3), mask (N,1) bool, extras dict), or None when the fused query is not eligible
+        (_fused_inputs): utils_sdf.sphere_tracing then runs its loop."""
+        if not (origins.is_cuda and directions.is_cuda):
+            return None
+        got = self._fused_inputs(origins)
+        if got is None:
+            return None
+        q, feats, metas, poses, pack = got
+        try:
+            return q.trace(feats, metas, poses, pack, origins, utils.normalize_last_dim(directions), min_dist=min_dist,
+                           max_dist=max_dist, max_iters=max_iters, epsilon=epsilon, **extras)
+        except RuntimeError as e:
             if "not covered" in str(e):
                 return None
             raise

@@ -283,6 +283,27 @@ class GridNet(BaseNet):
             pred = pred + torch.randn(pred.shape, device=x.device) * noise_std
         return pred
 
+    def sphere_trace(self, origins: torch.Tensor, directions: torch.Tensor, min_dist=1e-3, max_dist=5e1, max_iters=100,
+                     epsilon=1e-5, **extras):
+        """utils_sdf.sphere_tracing(self, ...) in ONE launch: this grid as a one-submap atlas with an identity pose row
+        and no bound test, which is forward() bit for bit (ops.AtlasQuery.trace; extras: want_sdf, want_steps,
+        grad_step).  -> (points (N,3), mask (N,1) bool, extras dict); None when autograd is on, the tensors are on the
+        host or the fused decoder does not cover this model: utils_sdf.sphere_tracing then runs its loop."""
+        if torch.is_grad_enabled() or not (origins.is_cuda and directions.is_cuda):
+            return None
+        pack = self._fused_decoder()
+        if pack is None:
+            return None
+        q = self.__dict__.setdefault('_trace_query', ops.AtlasQuery())
+        ident = self.__dict__.get('_trace_ident')
+        if ident is None or ident.device != origins.device:
+            ident = torch.tensor([[1., 0., 0., 0., 1., 0., 0., 0., 1., 0., 0., 0.]], device=origins.device)
+            self.__dict__['_trace_ident'] = ident
+        feats = [g.feature.detach() for g in self.features]
+        meta = self.features[0].grid_meta(self.ignore_level_)
+        return q.trace([feats], [meta], ident, pack, origins, utils.normalize_last_dim(directions), min_dist=min_dist,
+                       max_dist=max_dist, max_iters=max_iters, epsilon=epsilon, no_bound=True, **extras)
+
     def sdf_and_gradient(self, x: torch.Tensor):
         """(sdf (N,1), d sdf / d x (N,3)), both detached: what the tracker's Gauss-Newton step needs
         (reference tracker.py:176-181 runs a forward and an autograd backward for it).  With the fused

@@ -6,7 +6,11 @@ points per call, forward-only fused encode+decode) and copied to the host once.
 Mesh extraction (reference :89-140) runs on the volume where it lies: ``extract_geometry`` hands the
 device-resident volume to the HIP marching cubes (``ops.marching_cubes``; the reference copies it to the
 host for PyMCubes) and ``save_mesh`` writes the PLY itself -- mcubes, trimesh and open3d are not needed;
-the returned ``TriangleMesh`` carries the arrays an open3d mesh would (vertices, triangles, vertex_normals)."""
+the returned ``TriangleMesh`` carries the arrays an open3d mesh would (vertices, triangles, vertex_normals).
+
+Sphere tracing (reference :197-236) is the reference's loop over any callable, and ONE launch when the callable is a
+GridAtlas / GridNet queried without autograd on the device (``model.sphere_trace``); ``render_depth`` turns it into
+the depth and normal image of a camera pose -- the cheap view of a map now that the Open3D viewers are stubs."""
 import logging
 import os
 
@@ -165,3 +169,76 @@ def save_mesh(model, bounds: torch.Tensor, save_path=None, resolution=256, devic
     if save_path is not None:
         mesh.export_ply(save_path)
     return mesh.compute_vertex_normals()
+
+
+def sphere_tracing(query_func, origins, directions, min_dist=1e-3, max_dist=5e1, max_iters=100, epsilon=1e-5):
+    """March N rays through the SDF ``query_func`` (reference :197-236).  origins, directions: (N,3).
+    -> points (N,3), the ray-surface intersections (arbitrary for rays that do not hit), and mask (N,1) bool, true for
+    the rays that hit.  A model (or its bound forward) that has ``sphere_trace`` serves the call in one launch when
+    autograd is off and the tensors are on the device; anything else runs the loop below."""
+    n = origins.shape[0]
+    assert origins.ndim == 2 and directions.ndim == 2, f"Wrong shape: origins {origins.shape}, directions {directions.shape}"
+    assert directions.shape[0] == n
+    if max_iters < 1:
+        raise ValueError(f"max_iters must be at least 1, got {max_iters}")   # (upstream: an unbound name at the return)
+    model = getattr(query_func, '__self__', query_func)
+    if hasattr(model, 'sphere_trace') and not torch.is_grad_enabled() and origins.is_cuda and directions.is_cuda:
+        got = model.sphere_trace(origins, directions, min_dist=min_dist, max_dist=max_dist, max_iters=max_iters,
+                                 epsilon=epsilon)
+        if got is not None:
+            return got[0], got[1].reshape(-1, 1)
+    directions = utils.normalize_last_dim(directions)
+    points = origins + min_dist * directions
+    for i in range(max_iters):
+        dists = torch.norm(points - origins, dim=1, keepdim=True)
+        sdfs = query_func(points)
+        mask_converge = sdfs < epsilon
+        mask_far = dists > max_dist
+        mask_stop = torch.logical_or(mask_converge, mask_far)
+        if torch.sum(mask_stop) == n:       # all rays finished
+            break
+        points = mask_stop * points + ~mask_stop * (points + sdfs * directions)
+    return points, mask_converge.reshape(-1, 1)
+
+
+def render_depth(model, R_world_cam, t_world_cam, cam, H=None, W=None, max_dist=5e1, normals=False, **trace_kw):
+    """Depth image of the field ``model`` seen by the pinhole ``cam`` (utils_data.CameraParameters) at the pose
+    (R_world_cam (3,3), t_world_cam (3,) or (3,1)): one sphere-traced ray per pixel (utils_sample.ray_dirs_C, row-major).
+    -> (depth (H,W), mask (H,W) bool[, normals (H,W,3)]): z-depth in metres -- the ray parameter over the length of the
+    unnormalised direction ((c-cx)/fx, (r-cy)/fy, 1) -- and 0 where the ray did not hit, the "0 = no return" of a
+    PosedSdfRgbd frame; with normals=True unit normals in the world frame from central differences of the field at the
+    hit points (``grad_step`` in trace_kw, default 1e-2: diff.gradient3d's), zero where not hit.  H, W default to the
+    camera's; trace_kw: min_dist, max_iters, epsilon.  The device is the model's."""
+    import miso_amd.grid_opt.utils.utils_sample as utils_sample
+    from miso_amd.grid_opt import diff
+    H = int(cam.H if H is None else H)
+    W = int(cam.W if W is None else W)
+    grad_step = trace_kw.pop('grad_step', 1e-2)
+    p0 = next(model.parameters(), None) if hasattr(model, 'parameters') else None
+    device = R_world_cam.device if p0 is None else p0.device
+    R = R_world_cam.detach().to(device=device, dtype=torch.float32).reshape(3, 3)
+    t = t_world_cam.detach().to(device=device, dtype=torch.float32).reshape(1, 3)
+    dirs_c = utils_sample.ray_dirs_C(1, H, W, cam.fx, cam.fy, cam.cx, cam.cy, device, 'z').reshape(-1, 3)
+    dirs_w = dirs_c @ R.T
+    origins = t.expand(H * W, 3).contiguous()
+    grad = None
+    with torch.no_grad():
+        fused = None
+        if hasattr(model, 'sphere_trace') and origins.is_cuda:
+            fused = model.sphere_trace(origins, dirs_w, max_dist=max_dist,
+                                       grad_step=grad_step if normals else None, **trace_kw)
+        if fused is not None:
+            points, mask, extras = fused
+            grad = extras.get('grad')
+        else:
+            points, mask = sphere_tracing(lambda p: model(p), origins, dirs_w, max_dist=max_dist, **trace_kw)
+            if normals:
+                grad = diff.gradient3d(points, model, 'finitediff', grad_step)
+        mask = mask.reshape(-1, 1)
+        depth = torch.norm(points - origins, dim=1, keepdim=True) / torch.norm(dirs_c, dim=1, keepdim=True)
+        depth = torch.where(mask, depth, torch.zeros_like(depth)).reshape(H, W)
+        if not normals:
+            return depth, mask.reshape(H, W)
+        nrm = utils.normalize_last_dim(grad)
+        nrm = torch.where(mask, nrm, torch.zeros_like(nrm)).reshape(H, W, 3)
+    return depth, mask.reshape(H, W), nrm

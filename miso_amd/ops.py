@@ -952,6 +952,44 @@ class AtlasQuery:
             flags, _stream(poses)), "miso_atlas_sdf_fwd")
         return sdf, feats
 
+    def trace(self, features, metas, poses, pack: "DecoderPack", origins, dirs, *, min_dist, max_dist, max_iters,
+              epsilon, no_bound=False, want_sdf=False, want_steps=False, grad_step=None):
+        """utils_sdf.sphere_tracing (reference grid_opt/utils/utils_sdf.py:197-236) over this atlas in ONE launch
+        (miso_atlas_sphere_trace, csrc/trace.hip).  origins, dirs: (N,3) device floats, dirs already of unit length.
+        -> (points (N,3), mask (N,1) bool, extras): extras['sdf'] (N,1) the field at the returned points (want_sdf),
+        extras['steps'] (N,) int32 the iterations in which a ray moved (want_steps), extras['grad'] (N,3) central
+        differences with step grad_step at the returned points (grad_step is not None)."""
+        if int(max_iters) < 1:
+            raise ValueError(f"max_iters must be at least 1, got {max_iters}")
+        _require_hip(origins, dirs, poses)
+        self._prepare(features, metas)
+        S = len(features)
+        assert poses.shape == (S, 12) and poses.is_contiguous() and poses.dtype == torch.float32
+        assert origins.ndim == 2 and origins.shape[1] == 3 and dirs.shape == origins.shape
+        origins, dirs = origins.detach().contiguous(), dirs.detach().contiguous()
+        n, dev = origins.shape[0], poses.device
+        m, packed = pack.get()
+        if m is None:
+            raise RuntimeError("decoder shape is not covered by the fused kernels")
+        points = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        mask = torch.empty((n, 1), device=dev, dtype=torch.bool)
+        extras = {}
+        if want_sdf:
+            extras['sdf'] = torch.empty((n, 1), device=dev, dtype=torch.float32)
+        if want_steps:
+            extras['steps'] = torch.empty((n,), device=dev, dtype=torch.int32)
+        if grad_step is not None:
+            extras['grad'] = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        if n == 0:          # (an empty tensor has no address to hand over; nothing to launch)
+            return points, mask, extras
+        flags = (_lib.F_EXACT_F32 if _EXACT_F32 else 0) | (_lib.F_ATLAS_NO_BOUND if no_bound else 0)
+        _lib.check(_lib.load().miso_atlas_sphere_trace(
+            _ptr(self._plan), S, C.byref(self._shape), _ptr(poses), C.byref(m), _ptr(packed), _ptr(origins), _ptr(dirs),
+            n, float(min_dist), float(max_dist), int(max_iters), float(epsilon),
+            0.0 if grad_step is None else float(grad_step), _ptr(points), _ptr(mask), _ptr(extras.get('sdf')),
+            _ptr(extras.get('steps')), _ptr(extras.get('grad')), flags, _stream(poses)), "miso_atlas_sphere_trace")
+        return points, mask, extras
+
 
 # --------------------------------------------------------------------------- #
 # dense Adam

@@ -19,7 +19,11 @@ room instead of ``utils_scannet.create_scannet_dataset`` (:48-50), the decoder k
           first alignment only has to run.  On the shared field there IS a pose to come back to: the trajectory error
           must fall by 5x (asserted).
 
-    python tools/demo_synthetic.py --save_dir /tmp/miso_demo [--quick]
+  look: --render DIR writes the depth and the normal image of the aligned atlas seen from the first and the last
+          keyframe (utils_sdf.render_depth: one sphere-tracing launch per image) as .npy, and as .png where matplotlib
+          is installed -- in place of the Open3D windows.
+
+    python tools/demo_synthetic.py --save_dir /tmp/miso_demo [--quick] [--render /tmp/miso_demo/views]
 """
 import argparse
 import json
@@ -182,11 +186,34 @@ def perturb_and_align(model_path, cfg, dataset, noise_rot, noise_tra, shared_fie
     return grid_atlas, align_info, metrics_bef, metrics_aft
 
 
+def render_views(grid_atlas, dataset, cam, out_dir):
+    """Depth and normals of the atlas from the first and the last keyframe's true pose: {depth,normals}_kf<k>.npy (.png)."""
+    utils.cond_mkdir(out_dir)
+    try:
+        import matplotlib
+        matplotlib.use("Agg")
+        import matplotlib.pyplot as plt
+    except ImportError:
+        plt = None
+    for k in (0, dataset.num_kfs - 1):
+        R, t = dataset.true_kf_pose_in_world(k)
+        depth, mask, normals = utils_sdf.render_depth(grid_atlas, R, t, cam, max_dist=12.0, normals=True, epsilon=1e-3)
+        depth, normals = depth.cpu().numpy(), normals.cpu().numpy()
+        np.save(join(out_dir, f'depth_kf{k}.npy'), depth)
+        np.save(join(out_dir, f'normals_kf{k}.npy'), normals)
+        if plt is not None:
+            plt.imsave(join(out_dir, f'depth_kf{k}.png'), depth, cmap='viridis')
+            plt.imsave(join(out_dir, f'normals_kf{k}.png'), 0.5 * normals + 0.5 * (np.abs(normals).sum(-1, keepdims=True) > 0))
+        print(f"keyframe {k}: {int(mask.sum())} of {mask.numel()} pixels hit, images in {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--save_dir', type=str, default='./results/demo/synthetic')
     ap.add_argument('--device', type=str, default='cuda:0')
     ap.add_argument('--quick', action='store_true', help='small images, few iterations (the GPU test)')
+    ap.add_argument('--render', type=str, default=None, metavar='DIR',
+                    help='write depth and normal images of the aligned atlas from the first and last keyframe to DIR')
     args = ap.parse_args()
     if args.quick:
         H, W, n_kf, args.submap_size, n_rays = 60, 80, 12, 4, 120
@@ -234,6 +261,8 @@ def main():
     it = align_info['hier_latent_level1_L2']['iteration_results']
     assert sorted(it) == list(range(args.align_iters + 1)) and it[0].shape == (grid_atlas.num_submaps, 4, 4)
     print(f"alignment: {len(it)} pose snapshots per level, gpu_time {align_info['gpu_time_sec']:.3f} s")
+    if args.render:
+        render_views(grid_atlas, dataset, cam, args.render)
 
 
 if __name__ == "__main__":

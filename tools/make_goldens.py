@@ -996,6 +996,60 @@ def gen_grad2_naive(gc):
           "points on a face")
 
 
+def trace_reference(GridNet, rsdf, stc, cam=None):
+    """The reference's sphere_tracing on the reference's GridNet holding the scene of tests/sphere_trace_cases.py, in
+    fp32 and on net.double(), both runs (max_iters 100 and 12); every query_func call's values and distances logged for
+    the fp64 run.  -> the arrays of tests/golden/sphere_trace.npz."""
+    tr = stc.TRACE
+    o32, d32 = (T(a) for a in (stc.golden_rays() if cam is None else stc.rays(cam)))
+    out = {}
+    for dtype, tag in ((torch.float32, "32"), (torch.float64, "64")):
+        net = stc.bake(GridNet(stc.model_cfg(), device="cpu"))
+        if dtype == torch.float64:
+            net = net.double()
+            net.bound = net.bound.double()
+            for g in net.features:
+                g.bound = g.bound.double()
+        o, d = o32.to(dtype), d32.to(dtype)
+        for iters in stc.RUNS:
+            log = []
+
+            def query(p):
+                s = net(p)
+                log.append((s.detach().clone(), torch.norm(p - o, dim=1, keepdim=True)))
+                return s
+
+            with torch.no_grad():
+                pts, mask = rsdf.sphere_tracing(query, o, d, min_dist=tr["min_dist"], max_dist=tr["max_dist"],
+                                                max_iters=iters, epsilon=tr["epsilon"])
+            out[f"points{tag}_{iters}"] = pts.numpy()
+            out[f"mask{tag}_{iters}"] = mask.numpy()
+            if tag == "64":
+                sd = torch.stack([a for a, _ in log])          # (iterations, N, 1)
+                di = torch.stack([b for _, b in log])
+                near = ((sd - tr["epsilon"]).abs() < 2e-5) | ((di - tr["max_dist"]).abs() < 2e-5)
+                out[f"near_{iters}"] = near.any(dim=0).numpy()
+    for iters in stc.RUNS:
+        out[f"marginal_{iters}"] = (out[f"mask32_{iters}"] != out[f"mask64_{iters}"]) | out.pop(f"near_{iters}")
+        out[f"dev32_{iters}"] = np.float64(np.abs(out[f"points32_{iters}"].astype(np.float64) - out[f"points64_{iters}"]).max())
+    return out
+
+
+def gen_sphere_trace(GridNet, gc):
+    import grid_opt.utils.utils_sdf as rsdf
+    import sphere_trace_cases as stc
+    out = trace_reference(GridNet, rsdf, stc)
+    for iters in stc.RUNS:
+        m = out[f"marginal_{iters}"]
+        # a condition on the scene, not a measurement: rays whose stop decision hangs on the last digits of the field
+        # are left out of the mask comparison, and there may only be few of them
+        assert m.mean() <= 0.02, f"max_iters={iters}: {m.mean():.3%} of the rays are marginal; move the camera"
+        print(f"[sphere_trace] max_iters={iters}: hit {int(out[f'mask32_{iters}'].sum())} of {m.size}, marginal "
+              f"{int(m.sum())}, fp32/fp64 masks differ on {int((out[f'mask32_{iters}'] != out[f'mask64_{iters}']).sum())}, "
+              f"dev32 {float(out[f'dev32_{iters}']):.2e}")
+    np.savez_compressed(gc.golden_path("sphere_trace"), **out)
+
+
 def main():
     import_reference()
     import golden_cases as gc
@@ -1012,7 +1066,7 @@ def main():
     os.makedirs(gc.GOLDEN_DIR, exist_ok=True)
     torch.manual_seed(0)
     np.random.seed(0)
-    which = sys.argv[1:] or ["small", "cfg1", "cfg2", "atlas", "losses", "trainer", "tracker", "so3", "samples", "extra", "geometry", "formats", "encoder", "second_order", "atlas_branches", "grad2_naive"]
+    which = sys.argv[1:] or ["small", "cfg1", "cfg2", "atlas", "losses", "trainer", "tracker", "so3", "samples", "extra", "geometry", "formats", "encoder", "second_order", "atlas_branches", "grad2_naive", "sphere_trace"]
     for name in which:
         if name in gc.CASES:
             gen_encode_decode(name, GridNet, rloss, gc)
@@ -1042,6 +1096,8 @@ def main():
             gen_atlas_branches(GridAtlas, miso, gc)
         elif name == "grad2_naive":
             gen_grad2_naive(gc)
+        elif name == "sphere_trace":
+            gen_sphere_trace(GridNet, gc)
 
 
 if __name__ == "__main__":
