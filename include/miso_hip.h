@@ -297,7 +297,8 @@ int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const floa
 uint32_t miso_grad_pull_levels(const miso_grid_t* grid, int32_t tiles_per_axis);
 /* 1 when the pull of those levels over n points with d-feat rows of pitch ld_d runs as grad_pull_mc_kernel (the sums on the
  * fp32 matrix cores, grad_pull_mc.hip), 0 when the vector kernels of grad_pull.hip take it (second-order weights are always
- * theirs): what a profile of the call will show -- bench.py names its dominant kernel by this, not by assumption. */
+ * theirs) or nothing is left to pull: what a profile of the call will show -- bench.py names its dominant kernel by this,
+ * not by assumption.  This and the three level queries read the plan the entry points follow (csrc/grad_plan.hip). */
 int miso_grad_pull_on_matrix_cores(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n, int64_t ld_d);
 int miso_grad_pull(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, const float* dfeat,
                    int64_t ld_d, int32_t rows_in_caller_order, void* stream);

@@ -5,22 +5,13 @@
 
 #include "common.hpp"
 #include "align.hpp"
+#include "grad_plan.hpp"
 #include "launch.hpp"
 #include "version.inc"
 
 using namespace miso;
 
-
 namespace {
-
-// which pointer of a level a call needs
-enum Need { NEED_DATA = 1, NEED_GRAD_OPT = 2 };
-
-// elements from a level's first to its last, + 1 (miso_level_t or LevelK)
-template <class Level>
-int64_t level_span(const Level& s) {
-  return (int64_t)(s.C - 1) * s.sC + (int64_t)(s.X - 1) * s.sX + (int64_t)(s.Y - 1) * s.sY + (int64_t)(s.Z - 1) * s.sZ + 1;
-}
 
 int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) {
   if (!in || in->n_levels < 1 || in->n_levels > MISO_MAX_LEVELS) return MISO_E_BADARG;
@@ -72,17 +63,17 @@ int fused_shape(const GridK& g, bool vec4, const miso_mlp_t* m, int* C, int* L, 
   return MISO_OK;
 }
 
-// zero-fill the gradient of the levels in `levels`: those a launch adds to with atomics start from zero
-// (a kernel, not hipMemsetAsync: memset nodes of a captured graph that is replayed back to back with other
-// launches in between now and then fill with garbage on ROCm 7.2 -- see loss.hip:zero_words_kernel)
-hipError_t zero_level_grads(const GridK& g, uint32_t levels, hipStream_t st) {
-  for (int l = 0; l < g.n_levels; ++l) {
-    const LevelK& lv = g.lv[l];
-    if (!lv.grad || !((levels >> l) & 1u)) continue;
-    hipError_t e = launch_zero_fill(lv.grad, level_span(lv), st);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+// what a call asks of plan_grad (sorted == nullptr: an unbinned batch, nothing is pulled), the pointers its launch reads
+GradAsk grad_ask(GradCaller who, bool v4, const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, int64_t ld,
+                 const void* workspace, bool ggx) {
+  GradAsk a = {who, v4, grid->flags, n, ld, ggx, workspace && ((uintptr_t)workspace & 15u) == 0, false, false, 0, 0};
+  if (!sorted) return a;
+  a.sorted = true; a.xn = sorted->xn_sorted != nullptr; a.tiles = sorted->tiles_per_axis;
+  a.queue_ints = sorted->pull_queue ? sorted->pull_queue_ints : 0;
+  return a;
+}
+PullBatch pull_batch(const miso_sorted_t* s, const float* dfeat, const int* perm, const float* ggx) {
+  return PullBatch{s->tile_offsets, s->xn_sorted, dfeat, perm, ggx, s->pull_queue};
 }
 
 // the loss side of a fused launch: the mapping loss's parameters, its input rows, where d loss / d sdf (binned order) and
@@ -266,15 +257,6 @@ static int sdf_fwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
   return (int)launch_sdf_fwd(C, L, H, NH, g, packed, x, n, sdf, relu_mask, perm, lin, (hipStream_t)stream);
 }
 
-// A per-axis (or finer than 16) binning is served by the matrix-core pull alone, and that kernel addresses the d-feat
-// rows with 32-bit byte offsets: a batch whose rows pass 2 GB cannot be pulled under such a binning.  Said here, BEFORE
-// the step's first kernel is launched (the launch used to fail after the backward had already deferred the
-// levels to the pull).
-static bool pull_serviceable(const miso_sorted_t* sorted, int64_t n, int64_t ld) {
-  if (!sorted || tiles_cubic16(sorted->tiles_per_axis)) return true;
-  return n * ld * 4 < ((int64_t)1 << 31);
-}
-
 static int sdf_bwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
                         const float* x, int64_t n, const float* grad_sdf, const uint32_t* relu_mask,
                         float* grad_x, const miso_sorted_t* sorted, float* workspace, void* stream) {
@@ -289,35 +271,23 @@ static int sdf_bwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
   int C, L, H, NH;
   rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
   if (rc) return rc;
-  bool want_grid = false;
-  for (int l = 0; l < g.n_levels; ++l) want_grid = want_grid || (g.lv[l].grad != nullptr);
+  // owned levels leave their d-feat rows in the workspace (a pushed level's go the same way); the rest is scattered
+  const GradPlan plan = plan_grad(g, grad_ask(GRAD_BWD, v4, grid, sorted, n, g.F, workspace, false), pull_knobs());
+  const bool want_grid = plan.want != 0;
   if (!want_grid && !grad_x) return MISO_OK;
-  const bool overwrite = (grid->flags & MISO_F_GRAD_OVERWRITE) != 0;
-  const int* perm = sorted ? sorted->perm : nullptr;
-  uint32_t pull = 0;
-  if (sorted && sorted->xn_sorted && workspace && want_grid && ((uintptr_t)workspace & 15u) == 0)
-    pull = plan_grad_pull(g, sorted->tiles_per_axis);
-  // coarse levels under a crowd: the matrix-core push (grad_pull.hip; its d-feat rows go through the workspace like a
-  // pulled level's, so it stays in `pull`)
-  const uint32_t push = (pull && sorted) ? plan_push(g, sorted->tiles_per_axis, n, pull) : 0u;
-  if (pull && !pull_serviceable(sorted, n, g.F)) return MISO_E_UNSUPPORTED;
+  if (plan.refuse) return MISO_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  if (overwrite && !(grid->flags & MISO_F_GRAD_ZEROED)) {
-    // levels that are scattered or pushed with atomics; pulled levels need no fill
-    hipError_t e = zero_level_grads(g, ~(pull & ~push), st);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (n == 0 && !pull) return MISO_OK;
+  hipError_t e = zero_level_grads(g, plan.fill, st);
+  if (e != hipSuccess) return (int)e;
+  if (n == 0 && !plan.owned) return MISO_OK;
   if (n > 0) {
-    rc = (int)launch_sdf_bwd(C, L, H, NH, gp, packed, x, n, grad_sdf, relu_mask, grad_x, want_grid, perm,
-                             pull ? workspace : nullptr, pull,
+    rc = (int)launch_sdf_bwd(C, L, H, NH, gp, packed, x, n, grad_sdf, relu_mask, grad_x, want_grid,
+                             sorted ? sorted->perm : nullptr, plan.owned ? workspace : nullptr, plan.owned,
                              sorted && (grid->flags & MISO_F_GRAD_SDF_SORTED), st);
     if (rc) return rc;
   }
-  if (!pull) return MISO_OK;
-  return (int)launch_grad_pull(g, C, sorted->tiles_per_axis, sorted->tile_offsets, sorted->xn_sorted, workspace,
-                               g.F, nullptr, pull, overwrite ? 1 : 0, nullptr, sorted->pull_queue,
-                               sorted->pull_queue_ints, st, push, n);
+  if (!plan.owned) return MISO_OK;
+  return (int)launch_grad_pull(g, plan, pull_batch(sorted, workspace, nullptr, nullptr), st);
 }
 
 int miso_sdf_fwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
@@ -429,49 +399,29 @@ int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const floa
   return sdf_fwd_impl(grid, mlp, packed, x, n, sdf, relu_mask, nullptr, stream, &lin);
 }
 
-// levels (with a gradient requested) the owner-computes pull covers for this grid
-static int pull_plan(const miso_grid_t* grid, int32_t tiles_per_axis, GridK* g, int* C, uint32_t* mask) {
-  bool v4;
-  int rc = convert_grid(grid, g, false, &v4);
-  if (rc) return rc;
-  *mask = 0;
-  *C = g->lv[0].C;
-  { int t3_[3]; if (!tiles_xyz(tiles_per_axis, t3_)) return MISO_E_BADARG; }
-  if (!v4 || (*C != 4 && *C != 8)) return MISO_OK;
-  for (int l = 0; l < g->n_levels; ++l)
-    if (g->lv[l].C != *C) return MISO_OK;
-  *mask = plan_grad_pull(*g, tiles_per_axis);
-  return MISO_OK;
+// The plan a binned backward or training step of n samples follows with every buffer in place: what the four queries
+// report.  All zero (nothing owned, PULL_NONE) for a grid or a tiles code the entry points refuse.
+static GradPlan query_plan(const miso_grid_t* grid, int32_t tiles, int64_t n, int64_t ld) {
+  GridK g; bool v4;
+  if (convert_grid(grid, &g, false, &v4)) return GradPlan{};
+  GradAsk a = grad_ask(GRAD_BWD, v4, grid, nullptr, n, ld, nullptr, false);
+  a.tiles = tiles; a.sorted = a.xn = a.workspace = true;
+  const GradPlan p = plan_grad(g, a, pull_knobs());
+  return p.valid ? p : GradPlan{};
 }
 
 uint32_t miso_sdf_bwd_scattered_levels(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n) {
-  GridK g; int C; uint32_t mask;
-  if (pull_plan(grid, tiles_per_axis, &g, &C, &mask)) return 0;
-  const uint32_t owned = mask & ~plan_push(g, tiles_per_axis, n, mask);
-  uint32_t out = 0;
-  for (int l = 0; l < g.n_levels; ++l)
-    if (g.lv[l].grad && !((owned >> l) & 1u)) out |= 1u << l;
-  return out;
+  const GradPlan p = query_plan(grid, tiles_per_axis, n, 0);
+  return p.scatter | p.push;      // every level that atomics add to
 }
-
 uint32_t miso_sdf_bwd_push_levels(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n) {
-  GridK g; int C; uint32_t mask;
-  if (pull_plan(grid, tiles_per_axis, &g, &C, &mask)) return 0;
-  return plan_push(g, tiles_per_axis, n, mask);
+  return query_plan(grid, tiles_per_axis, n, 0).push;
 }
-
 int miso_grad_pull_on_matrix_cores(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n, int64_t ld_d) {
-  GridK g; int C; uint32_t mask;
-  if (pull_plan(grid, tiles_per_axis, &g, &C, &mask) || !mask) return 0;
-  int T3[3];
-  if (!tiles_xyz(tiles_per_axis, T3)) return 0;
-  return mc_pull_ok(g, C, T3, mask & ~plan_push(g, tiles_per_axis, n, mask), n, ld_d) ? 1 : 0;
+  return query_plan(grid, tiles_per_axis, n, ld_d).form == PULL_MC ? 1 : 0;
 }
-
 uint32_t miso_grad_pull_levels(const miso_grid_t* grid, int32_t tiles_per_axis) {
-  GridK g; int C; uint32_t mask;
-  if (pull_plan(grid, tiles_per_axis, &g, &C, &mask)) return 0;
-  return mask;
+  return query_plan(grid, tiles_per_axis, 0, 0).owned;
 }
 
 static int grad_pull_impl(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, const float* dfeat,
@@ -480,19 +430,16 @@ static int grad_pull_impl(const miso_grid_t* grid, const miso_sorted_t* sorted, 
   if (rc) return rc;
   if (n < 0 || (n > 0 && (!sorted->xn_sorted || !dfeat)) || ((uintptr_t)dfeat & 15u) != 0 || (ld_d & 3) != 0)
     return MISO_E_BADARG;
-  GridK g; int C; uint32_t pull;
-  rc = pull_plan(grid, sorted->tiles_per_axis, &g, &C, &pull);
+  GridK g; bool v4;
+  rc = convert_grid(grid, &g, false, &v4);
   if (rc) return rc;
   if (ld_d < g.F) return MISO_E_BADARG;
-  if (pull && !gg_x && !pull_serviceable(sorted, n, ld_d)) return MISO_E_UNSUPPORTED;
-  for (int l = 0; l < g.n_levels; ++l)
-    if (g.lv[l].grad && !((pull >> l) & 1u)) return MISO_E_UNSUPPORTED;   // every requested level must be pullable
+  const GradPlan plan = plan_grad(g, grad_ask(GRAD_PULL, v4, grid, sorted, n, ld_d, dfeat, gg_x != nullptr), pull_knobs());
+  if (plan.refuse) return MISO_E_UNSUPPORTED;
   if (gg_x && !(g.flags & MISO_F_COORDS_NORMALIZED))
     for (int a = 0; a < 3; ++a) g.gscale[a] = 2.0f / (g.bmax[a] - g.bmin[a]);   // d xn / d x (axis_coord's m)
-  return (int)launch_grad_pull(g, C, sorted->tiles_per_axis, sorted->tile_offsets, sorted->xn_sorted, dfeat, ld_d,
-                               rows_in_caller_order ? sorted->perm : nullptr, pull,
-                               (grid->flags & MISO_F_GRAD_OVERWRITE) ? 1 : 0, gg_x, sorted->pull_queue,
-                               sorted->pull_queue_ints, (hipStream_t)stream, 0u, n);
+  return (int)launch_grad_pull(g, plan, pull_batch(sorted, dfeat, rows_in_caller_order ? sorted->perm : nullptr, gg_x),
+                               (hipStream_t)stream);
 }
 
 int miso_grad_pull(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, const float* dfeat,
@@ -540,24 +487,14 @@ static int sdf_train_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const 
   int C, L, H, NH;
   rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
   if (rc) return rc;
-  uint32_t want = 0;
-  for (int l = 0; l < g.n_levels; ++l)
-    if (g.lv[l].grad && !((g.ignore_mask >> l) & 1u)) want |= 1u << l;
-  if (!want) return MISO_E_UNSUPPORTED;
-  // levels formed from the d-feat rows (pull or push); the rest is scattered from the kernel
-  // (an ignored level with a gradient buffer stays in `pull`: the pull writes its zeros, as miso_sdf_bwd_sorted does)
-  const uint32_t pull = (sorted && workspace) ? plan_grad_pull(g, sorted->tiles_per_axis) : 0u;
-  const uint32_t push = pull ? plan_push(g, sorted->tiles_per_axis, n, pull) : 0u;
-  if (pull && !pull_serviceable(sorted, n, g.F)) return MISO_E_UNSUPPORTED;
-  const uint32_t scat = want & ~pull;
+  // owned levels are formed from the d-feat rows (pull or push); the rest is scattered from the kernel
+  const GradPlan plan = plan_grad(g, grad_ask(GRAD_TRAIN, v4, grid, sorted, n, g.F, workspace, false), pull_knobs());
+  if (!plan.want || plan.refuse) return MISO_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  const bool overwrite = sorted && (grid->flags & MISO_F_GRAD_OVERWRITE) != 0;
-  if (overwrite && !(grid->flags & MISO_F_GRAD_ZEROED)) {
-    hipError_t e = zero_level_grads(g, push | scat, st);
-    if (e != hipSuccess) return (int)e;
-  }
+  hipError_t e = zero_level_grads(g, plan.fill, st);
+  if (e != hipSuccess) return (int)e;
   if (n == 0) {
-    hipError_t e = launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, st);
+    e = launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, st);
     if (e != hipSuccess) return (int)e;
   } else {
     const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, nullptr, loss_slots, n, n_live);
@@ -565,13 +502,11 @@ static int sdf_train_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const 
     if (sorted) x = sorted_points(&gp, sorted);
     if (sorted && !sorted->perm) gp.flags |= MISO_F_INDEX_IN_XN;
     rc = (int)launch_sdf_train(C, L, H, NH, gp, packed, x, n, sdf, sorted ? sorted->perm : nullptr, lin,
-                               pull ? workspace : nullptr, pull, scat != 0, st);
+                               plan.owned ? workspace : nullptr, plan.owned, plan.scatter != 0, st);
     if (rc) return rc;
   }
-  if (!pull) return MISO_OK;
-  return (int)launch_grad_pull(g, C, sorted->tiles_per_axis, sorted->tile_offsets, sorted->xn_sorted, workspace, g.F,
-                               nullptr, pull, overwrite ? 1 : 0, nullptr, sorted->pull_queue, sorted->pull_queue_ints,
-                               st, push, n);
+  if (!plan.owned) return MISO_OK;
+  return (int)launch_grad_pull(g, plan, pull_batch(sorted, workspace, nullptr, nullptr), st);
 }
 
 int miso_sdf_train_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,

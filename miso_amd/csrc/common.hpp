@@ -21,6 +21,12 @@ struct LevelK {
   int32_t foff;            // first output column of this level
 };
 
+// elements from a level's first to its last, + 1 (miso_level_t or LevelK)
+template <class Level>
+inline int64_t level_span(const Level& s) {
+  return (int64_t)(s.C - 1) * s.sC + (int64_t)(s.X - 1) * s.sX + (int64_t)(s.Y - 1) * s.sY + (int64_t)(s.Z - 1) * s.sZ + 1;
+}
+
 // internal GridK::flags bit (not part of the ABI): the batch is binned, there is no perm[] and the original index of
 // sorted point p is the integer in xn[p].w (miso_sort_points with perm == NULL; sdf_train_kernel)
 constexpr uint32_t MISO_F_INDEX_IN_XN = 1u << 20;
@@ -310,8 +316,6 @@ struct TrackAdamK {
   int ring_len;
 };
 
-
-
 // Pointwise mapping loss (grid_opt/loss.py:594-635, :668-700) shared by loss.hip and the fused
 // backward.  g / gf: d(w_sdf * sdf term) / ds and d(w_fs * free-space term) / ds BEFORE the 1/N of
 // the mean; s_sdf / s_fs accumulate the unweighted term sums.
@@ -341,7 +345,6 @@ __device__ __forceinline__ void map_loss_one(const MapLossK& p, float s, float t
     else if (lo > up) gf = -p.w_fs;
   }
 }
-
 
 // The mapping loss folded into the fused forward (sdf_fwd_kernel): with loss_type != 0 the kernel
 // forms d loss / d sdf for every point right after its SDF and writes it in the binned order.

@@ -23,7 +23,7 @@
 #include <string.h>
 
 #include "common.hpp"
-#include "grad_pull.hpp"
+#include "grad_plan.hpp"
 #include "launch.hpp"
 
 namespace miso {
@@ -430,10 +430,6 @@ __device__ __forceinline__ void pull_level(const GridK& g, const PullK& pk, cons
   wave_sync_lds();   // the caller reuses the list and the staging area
 }
 
-// One wavefront per spatial tile.  The 3x3x3 tile neighbourhood is swept ONCE for all pulled
-// levels (a candidate's coordinates are loaded once and tested against every level's box).
-// DRAIN = false: one wavefront per tile (slice 0 of a cut tile, queueing the rest); true: the second launch that
-// works off the queued slices -- a separate instantiation so that profiles tell the two apart.
 // One tile, swept by ONE wavefront: the 3x3x3 tile neighbourhood is read row by row, every candidate tested against
 // the catchment box of every pulled level, the hits compacted into per-level LDS lists, the lists binned / pulled /
 // stored by pull_level.  The general path: any grid size, heavy tiles cut into slices (sl of ns; DRAIN: a queued
@@ -671,8 +667,6 @@ __global__ __launch_bounds__(256) void grad_pull_kernel(GridK g, PullK pk) {
 // batch), runs the per-tile routine for its eight tiles -- heavy-tile slicing included -- in the same launch.
 constexpr int BLK_WAVES = 8;
 constexpr int BLK_CAND = 1152;        // survivor table (uniform cfg-2 batch: ~1000 per block, sigma ~31)
-constexpr int BLK_POOL = 704;         // 16-bit list slots per tile, split over the levels by the launcher in
-                                      // proportion to their catchment volumes (uniform cfg-2: 91 / 125 / 218 used)
 constexpr int BLK_UN = 8;             // 64-candidate steps in flight per wavefront
 
 template <int C, int NLV, int MODE>
@@ -839,25 +833,7 @@ __global__ __launch_bounds__(512, 4) void grad_pull_block_kernel(GridK g, PullK 
 // atomics (the regions of neighbouring tiles overlap).  The level's gradient is zero-filled by the caller.
 // Measured at the ScanNet shape (540 000 samples): the dense wave walk this replaces cost ~85 us of the backward pass
 // and a workgroup-per-tile owner-computes kernel with register accumulators 187 us (27 x candidate sweep).
-constexpr int PUSH_R = 5;          // region vertices per axis
 constexpr int PUSH_WAVES = 4;
-
-struct PushRegion { int r0[3]; };
-
-// first region vertex of tile coordinate t along an axis of `size` vertices: the smallest base corner of a sample of
-// the tile, pos >= t size / T - 1/2 (the -1: a tile boundary that is an integer position keeps the vertex below it, a
-// sample may sit an ulp on the other side of it than its tile says)
-__host__ __device__ inline int push_r0(int t, int size, int T) {
-  const int a = 2 * t * size - T - 1, b = 2 * T;
-  int q = a / b;
-  return (a % b != 0 && a < 0) ? q - 1 : q;
-}
-// last region vertex: the largest base corner (pos < (t + 1) size / T - 1/2, the bound included) plus one
-__host__ __device__ inline int push_r1(int t, int size, int T) {
-  const int a = 2 * (t + 1) * size - T, b = 2 * T;
-  int q = a / b;
-  return ((a % b != 0 && a < 0) ? q - 1 : q) + 1;
-}
 
 template <int C>
 __global__ __launch_bounds__(64 * PUSH_WAVES) void grad_push_mfma_kernel(GridK g, PullK pk, int64_t n, int run) {
@@ -1005,207 +981,100 @@ __global__ __launch_bounds__(64 * PUSH_WAVES) void grad_push_mfma_kernel(GridK g
   }
 }
 
-// Levels the pull kernels can own: default sampling convention, a gradient requested, and a brick of at most
-// PULL_BMAX^3 vertices per tile (swept together, at most PULL_MAXL of them).  Levels with larger bricks (ScanNet's
-// 200 x 100 x 200 over 16 tiles: 13 x 7 x 13) are scattered with float atomics from the backward kernel: owner-computes
-// was built for them four ways over two rounds (tools/experiments/README.md) and every version cost at least what the
-// 4.3 M atomic requests cost.
-uint32_t plan_grad_pull(const GridK& g, int tiles) {
-  if (g.flags & (MISO_F_ALIGN_CORNERS | MISO_F_PAD_BORDER)) return 0;
-  int T3[3];
-  if (!tiles_xyz(tiles, T3)) return 0;
-  // a per-axis or finer-than-16 binning is served by the matrix-core pull only (grad_pull_mc.hip): its levels must be
-  // at least as fine as the binning and share the channel count it is compiled for
-  const bool mc_only = !tiles_cubic16(tiles);
-  uint32_t mask = 0;
-  int cnt = 0;
+// zero-fill the gradient of the levels in `levels`: those a launch adds to with atomics start from zero
+// (a kernel, not hipMemsetAsync: memset nodes of a captured graph that is replayed back to back with other
+// launches in between now and then fill with garbage on ROCm 7.2 -- see loss.hip:zero_words_kernel)
+hipError_t zero_level_grads(const GridK& g, uint32_t levels, hipStream_t st) {
   for (int l = 0; l < g.n_levels; ++l) {
     const LevelK& lv = g.lv[l];
-    if (!lv.grad) continue;
-    const int size[3] = {lv.X, lv.Y, lv.Z};
-    bool ok = true;
-    for (int a = 0; a < 3; ++a) {
-      if ((size[a] + T3[a] - 1) / T3[a] > PULL_BMAX) ok = false;
-      if ((int64_t)size[a] * T3[a] >= (1 << 28)) ok = false;
-      if (mc_only && 3 * size[a] < 2 * T3[a]) ok = false;
-    }
-    if (mc_only && ((lv.C != 4 && lv.C != 8) || lv.sC != 1 || lv.C != g.lv[0].C)) ok = false;
-    if (!ok) continue;
-    if (cnt++ >= PULL_MAXL) continue;
-    mask |= 1u << l;
+    if (!lv.grad || !((levels >> l) & 1u)) continue;
+    hipError_t e = launch_zero_fill(lv.grad, level_span(lv), st);
+    if (e != hipSuccess) return e;
   }
-  return mask;
+  return hipSuccess;
 }
 
-// levels (subset of `pull`) for the matrix-core push: a crowd of at least MISO_DENSE_MIN (100) samples per tile on
-// average, 4 or 8 channels, and every tile's region within PUSH_R vertices per axis
-uint32_t plan_push(const GridK& g, int tiles, int64_t n, uint32_t pull) {
-  if (!tiles_cubic16(tiles)) return 0;      // (a finer binning: the matrix-core pull takes crowded levels as they come)
-  const int T = tiles;
-  static const int dense_min = [] { const char* e = getenv("MISO_DENSE_MIN"); return e ? atoi(e) : 100; }();
-  // MISO_F_CROWDED: the caller knows the batch piles up on a few tiles (ray samples: a 54 000-sample batch of the
-  // synthetic RGB-D demo put 112 us of pull + drain launches on the 40 x 20 x 40 level, the push 46 us), where the
-  // average density says nothing; a uniform batch below the threshold is better off pulled (cfg-2: 107 -> 180 us)
-  const bool crowded = (g.flags & MISO_F_CROWDED) != 0 && n >= 4096;
-  if (dense_min <= 0 || (!crowded && n < (int64_t)dense_min * T * T * T) || n >= (1ll << 31)) return 0;
-  uint32_t push = 0;
-  for (int l = 0; l < g.n_levels && l < 16; ++l) {
-    const LevelK& lv = g.lv[l];
-    if (!((pull >> l) & 1u) || (lv.C != 4 && lv.C != 8)) continue;
-    const int size[3] = {lv.X, lv.Y, lv.Z};
-    bool ok = true;
-    for (int a = 0; a < 3 && ok; ++a)
-      for (int t = 0; t < T && ok; ++t) ok = push_r1(t, size[a], T) - push_r0(t, size[a], T) + 1 <= PUSH_R;
-    if (ok) push |= 1u << l;
-  }
-  return push;
+static PullK pull_args(const GradPlan& p, const PullBatch& b) {
+  PullK pk;
+  memset(&pk, 0, sizeof(pk));
+  pk.T = p.T[0]; pk.tile_off = b.tile_off; pk.xn = reinterpret_cast<const float4*>(b.xn); pk.dfeat = b.dfeat;
+  pk.ld = p.ld; pk.perm = b.perm; pk.debug = p.debug;
+  return pk;
 }
 
-static hipError_t launch_push(const GridK& g, int C, int T, const int* tile_off, const float* xn, const float* dfeat,
-                              int64_t ld, const int* perm, int level, int64_t n, hipStream_t s) {
+static hipError_t launch_push(const GridK& g, const GradPlan& p, const PullBatch& b, int level, hipStream_t s) {
   // samples per wavefront: 512 (fewest region flushes per sample) once that still makes >= 2048 wavefronts -- two per
   // SIMD, one staging while the other multiplies (540 000 samples: 512 / 384 / 256 / 128 per wavefront give a trainer
   // step of 360 / 356 / 353 / 366 us); a small batch is cut finer so that the chip is not left to a few dozen
   // wavefronts (54 000 samples: 105 of them, 46 us; 844 of 64 samples, 26 us)
+  const int64_t n = p.n;
   const int run = (int)min((int64_t)512, max((int64_t)64, ((n / 2048 + 63) / 64) * 64));
-  PullK pk;
-  memset(&pk, 0, sizeof(pk));
-  pk.T = T; pk.tile_off = tile_off; pk.xn = reinterpret_cast<const float4*>(xn); pk.dfeat = dfeat;
-  pk.ld = ld; pk.perm = perm;
+  PullK pk = pull_args(p, b);
   pk.lev[0] = level; pk.nl = 1;
-  static const int dbg = [] { const char* e = getenv("MISO_DEBUG_PULL"); return e ? atoi(e) : 0; }();   // dev ablation
-  pk.debug = dbg;
   const int64_t waves = (n + run - 1) / run;
   const unsigned blocks = (unsigned)((waves + PUSH_WAVES - 1) / PUSH_WAVES);
   if (!blocks) return hipSuccess;
-  if (C == 8) grad_push_mfma_kernel<8><<<blocks, 64 * PUSH_WAVES, 0, s>>>(g, pk, n, run);
+  if (g.lv[0].C == 8) grad_push_mfma_kernel<8><<<blocks, 64 * PUSH_WAVES, 0, s>>>(g, pk, n, run);
   else grad_push_mfma_kernel<4><<<blocks, 64 * PUSH_WAVES, 0, s>>>(g, pk, n, run);
   return hipGetLastError();
 }
 
-hipError_t launch_grad_pull(const GridK& g, int C, int tiles, const int* tile_off, const float* xn,
-                            const float* dfeat, int64_t ld, const int* perm, uint32_t level_mask,
-                            int overwrite, const float* ggx, int32_t* queue, int64_t queue_ints, hipStream_t s,
-                            uint32_t push_mask, int64_t n) {
-  int T3[3];
-  if (!tiles_xyz(tiles, T3)) return hipErrorInvalidValue;
-  const int T = T3[0];       // (the vector kernels below: cubic binning only)
-  // push_mask: levels of plan_push the caller has zero-filled (overwrite) -- added to with atomics
-  push_mask &= level_mask;
-  if (push_mask && !ggx) {
-    for (int l = 0; l < g.n_levels; ++l)
-      if ((push_mask >> l) & 1u) {
-        hipError_t e = launch_push(g, C, T, tile_off, xn, dfeat, ld, perm, l, n, s);
-        if (e != hipSuccess) return e;
-      }
-    level_mask &= ~push_mask;
-  }
-  if (!level_mask) return hipSuccess;
-  {
-    // first-order gradients on grids at least as fine as the binning: the matrix-core pull (grad_pull_mc.hip)
-    if (!ggx && mc_pull_ok(g, C, T3, level_mask, n, ld))
-      return launch_grad_pull_mc(g, C, T3, tile_off, xn, dfeat, ld, perm, level_mask, overwrite, n, s);
-    if (!tiles_cubic16(tiles)) {
-      // plan_grad_pull admits a per-axis binning for the matrix-core kernel only.  What it cannot serve: an empty batch
-      // (the gradient of nothing is zero -- written here when the caller asked for overwrite, as the vector
-      // kernels of a cubic binning do) and d-feat rows past its 32-bit offsets (pull_serviceable: refused by the entry
-      // points before anything is launched)
-      if (n > 0) return hipErrorInvalidValue;
-      for (int l = 0; overwrite && l < g.n_levels; ++l)
-        if ((level_mask >> l) & 1u) {
-          const LevelK& lv = g.lv[l];
-          const size_t span = (size_t)(lv.C - 1) * lv.sC + (size_t)(lv.X - 1) * lv.sX + (size_t)(lv.Y - 1) * lv.sY +
-                              (size_t)(lv.Z - 1) * lv.sZ + 1;
-          hipError_t e = launch_zero_fill(lv.grad, (int64_t)span, s);
-          if (e != hipSuccess) return e;
-        }
-      return hipSuccess;
-    }
-  }
-  PullK pk;
-  memset(&pk, 0, sizeof(pk));
-  pk.T = T; pk.tile_off = tile_off; pk.xn = reinterpret_cast<const float4*>(xn); pk.dfeat = dfeat;
-  pk.ld = ld; pk.perm = perm; pk.ggx = ggx;
-  for (int l = 0; l < g.n_levels; ++l)
-    if ((level_mask >> l) & 1u) {
-      const int size[3] = {g.lv[l].X, g.lv[l].Y, g.lv[l].Z};
-      for (int a = 0; a < 3; ++a) {
-        pk.bdiv[pk.nl][a] = (size[a] % T == 0) ? size[a] / T : 0;
-        pk.inv_size[pk.nl][a] = 1.0f / (float)size[a];
-      }
-      pk.lev[pk.nl++] = l;
-    }
-  pk.overwrite = overwrite;
-  if (queue && queue_ints > PULL_QHDR && T <= 16 && !getenv("MISO_PULL_NO_SPLIT")) {
-    pk.queue = queue;
-    pk.qcap = (int)((queue_ints - PULL_QHDR) < (1 << 30) ? (queue_ints - PULL_QHDR) : (1 << 30));
-  }
-  pk.work0 = PULL_WORK0;
-  if (const char* d = getenv("MISO_DEBUG_PULL")) pk.debug = atoi(d);
-  const int cap = pull_cap(C, ggx ? 1 : 0);
-  const int per_wave = pk.nl * PULL_LIST + PULL_ARRW + cap * pull_rec(ggx ? 1 : 0) + cap * C;
-  size_t lds = (size_t)per_wave * 4 * sizeof(float);
-  const int ntiles = T * T * T;
-  unsigned blocks = (unsigned)((ntiles + 3) / 4);
-  if (blocks > 2048u) blocks = 2048u;
-  void (*k)(GridK, PullK) = nullptr;
-  void (*kd)(GridK, PullK) = nullptr;
-  void (*kb)(GridK, PullK) = nullptr;
+// PULL_WAVE / PULL_BLOCK, then the drain
+static hipError_t launch_pull_vector(const GridK& g, const GradPlan& p, const PullBatch& b, hipStream_t s) {
+  const int C = g.lv[0].C, T = p.T[0], mode = b.ggx ? 1 : 0;
+  PullK pk = pull_args(p, b);
+  pk.ggx = b.ggx; pk.nl = p.nl; pk.overwrite = p.overwrite; pk.work0 = PULL_WORK0;
+  memcpy(pk.lev, p.lev, sizeof(pk.lev)); memcpy(pk.bdiv, p.bdiv, sizeof(pk.bdiv));
+  memcpy(pk.inv_size, p.inv_size, sizeof(pk.inv_size));
+  memcpy(pk.blk_off, p.blk_off, sizeof(pk.blk_off)); memcpy(pk.blk_cap, p.blk_cap, sizeof(pk.blk_cap));
+  if (p.drain) { pk.queue = b.queue; pk.qcap = p.qcap; }
+  const int cap = pull_cap(C, mode), stage = PULL_ARRW + cap * pull_rec(mode) + cap * C;
+  const size_t lds = (size_t)(pk.nl * PULL_LIST + stage) * 4 * sizeof(float);
+  void (*k)(GridK, PullK) = nullptr, (*kd)(GridK, PullK) = nullptr, (*kb)(GridK, PullK) = nullptr;
 #define PICK(c, n)                                                                            \
   if (C == c && pk.nl == n) {                                                                 \
-    k = ggx ? grad_pull_kernel<c, n, 1, false> : grad_pull_kernel<c, n, 0, false>;            \
-    kd = ggx ? grad_pull_kernel<c, n, 1, true> : grad_pull_kernel<c, n, 0, true>;             \
+    k = mode ? grad_pull_kernel<c, n, 1, false> : grad_pull_kernel<c, n, 0, false>;           \
+    kd = mode ? grad_pull_kernel<c, n, 1, true> : grad_pull_kernel<c, n, 0, true>;            \
   }
   PICK(8, 1) PICK(8, 2) PICK(8, 3) PICK(8, 4) PICK(4, 1) PICK(4, 2) PICK(4, 3) PICK(4, 4)
 #undef PICK
 #define PICKB(c, n) \
-  if (C == c && pk.nl == n) kb = ggx ? grad_pull_block_kernel<c, n, 1> : grad_pull_block_kernel<c, n, 0>;
+  if (C == c && pk.nl == n) kb = mode ? grad_pull_block_kernel<c, n, 1> : grad_pull_block_kernel<c, n, 0>;
   PICKB(8, 1) PICKB(8, 2) PICKB(8, 3) PICKB(4, 1) PICKB(4, 2) PICKB(4, 3)
 #undef PICKB
-  if (!k) return hipErrorInvalidValue;
-  // block kernel (one workgroup per 2x2x2 tiles): bricks must be (size / T)^3 for every pulled level
-  bool block_ok = (T % 2 == 0) && kb != nullptr;
-  for (int d = 0; d < pk.nl; ++d)
-    for (int a = 0; a < 3; ++a) block_ok = block_ok && pk.bdiv[d][a] > 0;
-  if (block_ok) {
-    const int rec = pull_rec(ggx ? 1 : 0);
-    // a tile's list pool, split in proportion to the catchment volume ((B+1)/B)^3 of each level's brick
-    double w[PULL_MAXL], wsum = 0.0;
-    for (int d = 0; d < pk.nl; ++d) {
-      w[d] = 1.0;
-      for (int a = 0; a < 3; ++a) w[d] *= (double)(pk.bdiv[d][a] + 1) / (double)pk.bdiv[d][a];
-      wsum += w[d];
-    }
-    int off = 0;
-    for (int d = 0; d < pk.nl; ++d) {
-      pk.blk_off[d] = off;
-      pk.blk_cap[d] = (d + 1 == pk.nl) ? BLK_POOL - off : ((int)(BLK_POOL * w[d] / wsum) & ~1);
-      off += pk.blk_cap[d];
-    }
-    const size_t words = (size_t)BLK_CAND * 4 + (size_t)BLK_WAVES * BLK_POOL / 2 + 32 +
-                         (size_t)BLK_WAVES * (PULL_ARRW + cap * rec + cap * C);
-    const size_t blds = words * sizeof(float);
-    hipError_t e = allow_dynamic_lds((const void*)kb, blds);
-    if (e != hipSuccess) return e;
-    const int nb = T / 2;
-    kb<<<(unsigned)(nb * nb * nb), 512, blds, s>>>(g, pk);
-  } else {
-    {
-      hipError_t e = allow_dynamic_lds((const void*)k, lds);
-      if (e != hipSuccess) return e;
-    }
-    k<<<blocks, 256, lds, s>>>(g, pk);
+  if (!k || (p.form == PULL_BLOCK && !kb)) return hipErrorInvalidValue;
+  hipError_t e;
+  if (p.form == PULL_BLOCK) {      // one workgroup of eight wavefronts per 2 x 2 x 2 tiles
+    const size_t blds = ((size_t)BLK_CAND * 4 + (size_t)BLK_WAVES * BLK_POOL / 2 + 32 + (size_t)BLK_WAVES * stage) * sizeof(float);
+    if ((e = allow_dynamic_lds((const void*)kb, blds)) != hipSuccess) return e;
+    kb<<<(unsigned)(T * T * T / 8), 64 * BLK_WAVES, blds, s>>>(g, pk);
+  } else {                         // four tiles (wavefronts) per workgroup
+    if ((e = allow_dynamic_lds((const void*)k, lds)) != hipSuccess) return e;
+    k<<<min((unsigned)((T * T * T + 3) / 4), 2048u), 256, lds, s>>>(g, pk);
   }
-  if (pk.queue) {
+  if (p.drain) {
     pk.drain = 1;
-    const unsigned dblocks = 1024;
-    {
-      hipError_t e = allow_dynamic_lds((const void*)kd, lds);
-      if (e != hipSuccess) return e;
-    }
-    kd<<<dblocks, 256, lds, s>>>(g, pk);
+    if ((e = allow_dynamic_lds((const void*)kd, lds)) != hipSuccess) return e;
+    kd<<<1024, 256, lds, s>>>(g, pk);
   }
   return hipGetLastError();
+}
+
+// Carries out a plan (grad_plan.hpp): the pushed levels, then the one pull form it names.  Nothing is decided here.
+hipError_t launch_grad_pull(const GridK& g, const GradPlan& p, const PullBatch& b, hipStream_t s) {
+  if (!p.valid) return hipErrorInvalidValue;
+  for (int l = 0; l < g.n_levels; ++l)      // (the caller has zero-filled these under OVERWRITE: added to with atomics)
+    if ((p.push >> l) & 1u) {
+      hipError_t e = launch_push(g, p, b, l, s);
+      if (e != hipSuccess) return e;
+    }
+  switch (p.form) {
+    case PULL_NONE: return hipSuccess;
+    case PULL_MC: return launch_grad_pull_mc(g, p, b, s);
+    case PULL_FILL: return p.overwrite ? zero_level_grads(g, p.owned & ~p.push, s) : hipSuccess;
+    case PULL_WAVE: case PULL_BLOCK: return launch_pull_vector(g, p, b, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 // ints a slice queue for a batch of n points needs: every point is swept by at most 64 tiles, a slice is cut

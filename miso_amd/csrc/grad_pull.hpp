@@ -17,6 +17,8 @@ constexpr int pull_rec(int mode) { return mode ? 6 : 4; }
 constexpr int pull_cap(int C, int mode) { return mode ? ((PULL_CAP * (4 + C)) / (6 + C)) & ~1 : PULL_CAP; }
 constexpr int PULL_RB = 4;        // rounds of 64 vertices pulled per pass over the staged records
 constexpr int PULL_MAXL = 4;      // levels swept together (the fused kernels cover <= 4 levels)
+constexpr int BLK_POOL = 704;     // block kernel: 16-bit list slots per tile, split over the levels by the plan in
+                                  // proportion to their catchment volumes (uniform cfg-2: 91 / 125 / 218 used)
 // Heavy tiles.  One wavefront drains one tile serially (~50 ns per swept candidate), so a batch that piles its
 // points into a few tiles -- depth samples crowd around the cameras and hug surfaces; a uniform batch has ~1700
 // swept candidates per tile -- would be bound by its heaviest tile: 1.5 ms instead of 0.1 ms at the ScanNet
@@ -50,6 +52,23 @@ struct PullK {
   int work0;             // swept candidates per slice
   int blk_off[PULL_MAXL], blk_cap[PULL_MAXL];   // block kernel: partition of a tile's list pool over the levels
 };
+
+// The matrix-core push (grad_push_mfma_kernel) and the plan that picks its levels share a tile's REGION:
+constexpr int PUSH_R = 5;          // region vertices per axis
+// first region vertex of tile coordinate t along an axis of `size` vertices: the smallest base corner of a sample of
+// the tile, pos >= t size / T - 1/2 (the -1: a tile boundary that is an integer position keeps the vertex below it, a
+// sample may sit an ulp on the other side of it than its tile says)
+__host__ __device__ inline int push_r0(int t, int size, int T) {
+  const int a = 2 * t * size - T - 1, b = 2 * T;
+  int q = a / b;
+  return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+// last region vertex: the largest base corner (pos < (t + 1) size / T - 1/2, the bound included) plus one
+__host__ __device__ inline int push_r1(int t, int size, int T) {
+  const int a = 2 * (t + 1) * size - T, b = 2 * T;
+  int q = a / b;
+  return ((a % b != 0 && a < 0) ? q - 1 : q) + 1;
+}
 
 __device__ __forceinline__ int floor_div(int a, int b) {   // b > 0
   int q = a / b;

@@ -32,7 +32,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "grad_pull.hpp"
+#include "grad_plan.hpp"
 #include "launch.hpp"
 
 namespace miso {
@@ -43,9 +43,8 @@ constexpr int MC_CAND = 1152;          // table entries (a uniform cfg-2 batch: 
 constexpr int MC_POOL = 4608;          // (sample, sub-brick) pairs incl. padding (uniform cfg-2: 3830 +- 130, max 4200; more: halved ranges)
 constexpr int MC_ITEMS = 512;          // sub-brick code space: level (2 bits) | sz (3) | sy (2) | sx (2)
 constexpr int MC_UN = 8;               // 64-sample steps in flight per wavefront in the sweep
-constexpr int MC_NULL = 0xFFFF;        // pool padding
 constexpr int MC_LVL = 20;             // words per level record in LDS
-constexpr int MC_MAXL = 4;
+constexpr int MC_MAXL = PULL_MAXL;   // (a plan owns no more)
 
 // one pulled level, as the kernel reads it (everything by value: no dependent kernel-argument loads)
 struct McLv {
@@ -803,57 +802,28 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
     atomicAdd(&pk.prof[((blockIdx.x + blockIdx.y * 5 + blockIdx.z * 11) & 63) * 16 + threadIdx.x], (unsigned long long)misc[M_PROF + threadIdx.x]);
 }
 
-// true when the matrix-core kernel can take the pull of these levels (else grad_pull.hip's kernels)
-bool mc_pull_ok(const GridK& g, int C, const int T[3], uint32_t level_mask, int64_t n, int64_t ld) {
-  const char* env = getenv("MISO_PULL_MC");          // dev / tests: MISO_PULL_MC=0 keeps the vector kernels of grad_pull.hip
-  const bool off = env && atoi(env) == 0;
-  if (off || (C != 4 && C != 8)) return false;
-  if (n <= 0 || ld <= 0 || n * ld * 4 >= (1ll << 31)) return false;        // d-feat rows are addressed by 32-bit offsets
-  int nl = 0;
-  for (int l = 0; l < g.n_levels; ++l)
-    if ((level_mask >> l) & 1u) {
-      const LevelK& lv = g.lv[l];
-      const int size[3] = {lv.X, lv.Y, lv.Z};
-      if (lv.C != C || lv.sC != 1) return false;
-      for (int a = 0; a < 3; ++a) {
-        if (3 * size[a] < 2 * T[a]) return false;                // cells much wider than tiles: the sweep (<= 7 tile rows per axis,
-                                                                 // 64 in all: the lane table of row bounds) would not cover them
-        if ((size[a] + T[a] - 1) / T[a] > PULL_BMAX) return false;
-        if ((int64_t)size[a] * T[a] >= (1 << 28)) return false;
-      }
-      if (++nl > MC_MAXL) return false;
-    }
-  return nl > 0;
-}
-
-hipError_t launch_grad_pull_mc(const GridK& g, int C, const int T[3], const int* tile_off, const float* xn,
-                               const float* dfeat, int64_t ld, const int* perm, uint32_t level_mask, int overwrite,
-                               int64_t n, hipStream_t s) {
+// PULL_MC of a plan (grad_plan.hpp: first-order rows below 2 GB, every pulled level at least 2/3 as fine as the binning)
+hipError_t launch_grad_pull_mc(const GridK& g, const GradPlan& p, const PullBatch& b, hipStream_t s) {
+  const int C = g.lv[0].C;
   McK pk;
   memset(&pk, 0, sizeof(pk));
-  for (int a = 0; a < 3; ++a) { pk.T[a] = T[a]; pk.nb[a] = (T[a] + 1) / 2; }
-  pk.tile_off = tile_off; pk.xn = reinterpret_cast<const float4*>(xn); pk.dfeat = dfeat; pk.perm = perm; pk.ld = ld;
-  for (int l = 0; l < g.n_levels; ++l)
-    if ((level_mask >> l) & 1u) {
-      const LevelK& lv = g.lv[l];
-      McLv& o = pk.lv[pk.nl++];
-      const int size[3] = {lv.X, lv.Y, lv.Z};
-      o.grad = lv.grad; o.touched = lv.touched;
-      o.X = lv.X; o.Y = lv.Y; o.Z = lv.Z; o.foff = lv.foff;
-      o.sX = lv.sX; o.sY = lv.sY; o.sZ = lv.sZ;
-      o.live = ((g.ignore_mask >> l) & 1u) ? 0 : 1;
-      for (int a = 0; a < 3; ++a) {
-        o.bdiv[a] = (size[a] % T[a] == 0) ? size[a] / T[a] : 0;
-        o.inv_size[a] = 1.0f / (float)size[a];
-      }
-    }
-  pk.overwrite = overwrite;
-  pk.drow_bytes = (unsigned int)(n * ld * 4);
+  for (int a = 0; a < 3; ++a) { pk.T[a] = p.T[a]; pk.nb[a] = (p.T[a] + 1) / 2; }
+  pk.tile_off = b.tile_off; pk.xn = reinterpret_cast<const float4*>(b.xn); pk.dfeat = b.dfeat; pk.perm = b.perm; pk.ld = p.ld;
+  for (pk.nl = 0; pk.nl < p.nl; ++pk.nl) {
+    const LevelK& lv = g.lv[p.lev[pk.nl]];
+    McLv& o = pk.lv[pk.nl];
+    o.grad = lv.grad; o.touched = lv.touched;
+    o.X = lv.X; o.Y = lv.Y; o.Z = lv.Z; o.foff = lv.foff;
+    o.sX = lv.sX; o.sY = lv.sY; o.sZ = lv.sZ;
+    o.live = ((g.ignore_mask >> p.lev[pk.nl]) & 1u) ? 0 : 1;
+    for (int a = 0; a < 3; ++a) { o.bdiv[a] = p.bdiv[pk.nl][a]; o.inv_size[a] = p.inv_size[pk.nl][a]; }
+  }
+  pk.overwrite = p.overwrite;
+  pk.drow_bytes = (unsigned int)(p.n * p.ld * 4);
   const bool small = getenv("MISO_MC_SMALL") != nullptr;      // tests: epochs and halved ranges on ordinary batches
   pk.cand_cap = small ? 192 : MC_CAND;
   pk.pool_cap = small ? 640 : MC_POOL;
-  static const int dbg = [] { const char* e = getenv("MISO_DEBUG_PULL"); return e ? atoi(e) : 0; }();   // dev ablation
-  pk.debug = dbg;
+  pk.debug = p.debug;
   // dev: MISO_MC_PROF=1 prints the clocks wavefront 0 of every workgroup spent per phase, averaged, every 64 launches
   static unsigned long long* prof = [] {
     unsigned long long* p = nullptr;

@@ -6,7 +6,9 @@
 
 namespace miso {
 
-struct AlignK;  // align.hpp
+struct AlignK;    // align.hpp
+struct GradPlan;  // grad_plan.hpp (with plan_grad, the host-side plan of a binned call's grid gradient)
+struct PullBatch;
 
 // ---- encode.hip
 hipError_t launch_encode_fwd(const GridK& g, bool vec4, const float* x, int64_t n, float* out, int64_t ld,
@@ -44,19 +46,13 @@ int64_t sort_workspace_bytes(int64_t n, int tiles);
 hipError_t launch_sort(const GridK& g, const float* x, int64_t n, int tiles, void* ws, float* xs, float* xn, int* perm,
                        int* tile_off, hipStream_t s);
 
-// ---- grad_pull.hip
-uint32_t plan_grad_pull(const GridK& g, int tiles);
-uint32_t plan_push(const GridK& g, int tiles, int64_t n, uint32_t pull);
+// ---- grad_pull.hip (zero_level_grads: the gradient buffers of `levels`, cleared by kernels)
 int64_t pull_queue_ints(int64_t n);
-hipError_t launch_grad_pull(const GridK& g, int C, int tiles, const int* tile_off, const float* xn, const float* dfeat,
-                            int64_t ld, const int* perm, uint32_t level_mask, int overwrite, const float* ggx,
-                            int32_t* queue, int64_t queue_ints, hipStream_t s, uint32_t push_mask, int64_t n);
+hipError_t zero_level_grads(const GridK& g, uint32_t levels, hipStream_t s);
+hipError_t launch_grad_pull(const GridK& g, const GradPlan& plan, const PullBatch& batch, hipStream_t s);
 
-// ---- grad_pull_mc.hip (launch_grad_pull_mc: called by launch_grad_pull)
-bool mc_pull_ok(const GridK& g, int C, const int T[3], uint32_t level_mask, int64_t n, int64_t ld);
-hipError_t launch_grad_pull_mc(const GridK& g, int C, const int T[3], const int* tile_off, const float* xn,
-                               const float* dfeat, int64_t ld, const int* perm, uint32_t level_mask, int overwrite,
-                               int64_t n, hipStream_t s);
+// ---- grad_pull_mc.hip (called by launch_grad_pull for a plan of form PULL_MC)
+hipError_t launch_grad_pull_mc(const GridK& g, const GradPlan& plan, const PullBatch& batch, hipStream_t s);
 
 // ---- pair_latent.hip (launch_pair_batch: called by launch_align_a)
 hipError_t launch_src_boxes(const float* p, int64_t n, float* boxes, hipStream_t s);

@@ -113,7 +113,7 @@ def test_round2_entry_points_validate_arguments_without_gpu():
     assert lib.miso_track_adam_step(ctypes.byref(g), None, None, ctypes.byref(t), None) == E
 
 
-def test_gradient_plans_are_host_logic():
+def test_gradient_plans_are_host_logic(monkeypatch):
     """Which levels the binned backward pulls, pushes or scatters is decided on the host from the grid shape, the batch
     size and the flags (miso_grad_pull_levels / miso_sdf_bwd_push_levels): no device call, so it is checked here."""
     from miso_amd import _lib
@@ -148,6 +148,49 @@ def test_gradient_plans_are_host_logic():
     assert lib.miso_grad_pull_levels(ctypes.byref(ncd), T) == 0b01                   # 38 vertices per tile and axis
     border = grid([(32, 32, 32)], 8, flags=2)                                         # padding_mode='border'
     assert lib.miso_grad_pull_levels(ctypes.byref(border), T) == 0
+
+    # One plan (csrc/grad_plan.hip) answers all four queries.  The values below were read from the library before the
+    # plan existed and are pinned as literals.
+    from miso_amd import ops
+    pulled, pushed = lib.miso_grad_pull_levels, lib.miso_sdf_bwd_push_levels
+    scattered, on_mc = lib.miso_sdf_bwd_scattered_levels, lib.miso_grad_pull_on_matrix_cores
+    pyramid = grid([(16,) * 3, (32,) * 3, (48,) * 3, (64,) * 3, (128,) * 3], 4)
+    assert pulled(ctypes.byref(pyramid), T) == 0b01111                                # PULL_MAXL levels are swept together
+    assert scattered(ctypes.byref(pyramid), T, 1000) == 0b10000                       # ... the fifth is scattered
+    tiny = grid([(8, 8, 8)], 8)
+    assert pulled(ctypes.byref(tiny), T) == 0b1                                        # by the vector kernels:
+    assert on_mc(ctypes.byref(tiny), T, 1000, 8) == 0                                  # cells twice as wide as tiles
+    assert pulled(ctypes.byref(tiny), ops.pack_tiles((16, 16, 17))) == 0               # ... which serve no per-axis binning
+    assert on_mc(ctypes.byref(cfg2), T, 262144, 24) == 1
+    assert on_mc(ctypes.byref(cfg2), T, 1 << 26, 24) == 0                              # 6 GB of d-feat rows: 32-bit offsets
+    assert on_mc(ctypes.byref(cfg2), T, (1 << 31) // 96 - 1, 24) == 1 and on_mc(ctypes.byref(cfg2), T, (1 << 31) // 96 + 1, 24) == 0
+    assert on_mc(ctypes.byref(cfg2), T, 0, 24) == 0                                    # an empty batch
+    with monkeypatch.context() as m:
+        m.setenv("MISO_PULL_MC", "0")                                                 # read at every call
+        assert on_mc(ctypes.byref(cfg2), T, 262144, 24) == 0
+        assert pulled(ctypes.byref(cfg2), T) == 0b111
+    assert on_mc(ctypes.byref(cfg2), T, 262144, 24) == 1
+    ignored = grid([(32, 32, 32), (64, 64, 64), (128, 128, 128)], 8)
+    ignored.ignore_mask = 0b010
+    assert pulled(ctypes.byref(ignored), T) == 0b111                                  # the pull writes its zeros
+    assert scattered(ctypes.byref(ignored), T, 262144) == 0
+    for C in (12, 6):                                                                 # no kernel is compiled for them
+        odd = grid([(32, 32, 32), (64, 64, 64)], C)
+        assert pulled(ctypes.byref(odd), T) == 0 and pushed(ctypes.byref(odd), T, 540000) == 0
+        assert scattered(ctypes.byref(odd), T, 540000) == 0b11 and on_mc(ctypes.byref(odd), T, 1000, 2 * C) == 0
+    # the crowd threshold: 100 samples a tile on average; a pushed level is added to with atomics, like a scattered one
+    for g, n, push, scat in ((scannet, 100 * 4096 - 1, 0, 0b10), (scannet, 100 * 4096, 0b01, 0b11),
+                             (crowded, 4096, 0b01, 0b11), (crowded, 4095, 0, 0b10)):
+        assert pushed(ctypes.byref(g), T, n) == push and scattered(ctypes.byref(g), T, n) == scat, n
+    assert on_mc(ctypes.byref(scannet), T, 100 * 4096 - 1, 8) == 1 and on_mc(ctypes.byref(scannet), T, 100 * 4096, 8) == 0
+    # a per-axis binning: bricks of 8 x 7 x 8 on the fine level, everything on the matrix cores, nothing pushed
+    xyz = ops.pack_tiles((25, 16, 25))
+    assert xyz == 25 | (16 << 8) | (25 << 16)
+    assert pulled(ctypes.byref(scannet), xyz) == 0b11 and pushed(ctypes.byref(scannet), xyz, 540000) == 0
+    assert scattered(ctypes.byref(scannet), xyz, 540000) == 0 and on_mc(ctypes.byref(scannet), xyz, 540000, 8) == 1
+    assert on_mc(ctypes.byref(scannet), xyz, 1 << 26, 8) == 0 and on_mc(ctypes.byref(scannet), xyz, 0, 8) == 0
+    assert pulled(ctypes.byref(cfg2), ops.pack_tiles((32, 32, 32))) == 0b111
+    assert pulled(ctypes.byref(cfg2), 17) == 0 and scattered(ctypes.byref(cfg2), 17, 1000) == 0      # not a tiles code
 
 
 def _gcc(tmp_path, name, text, *flags):
