@@ -134,6 +134,13 @@ typedef struct {
   const float* bias[MISO_MAX_LINEAR]; /* NULL = no bias */
 } miso_mlp_t;
 
+/* Where miso_sdf_wgrad writes the decoder's gradients: one buffer per nn.Linear, the layout of miso_mlp_t's weight /
+ * bias ((out,in) row-major).  weight[l] is required for l < n_linear; bias[l] NULL = not wanted (a layer without bias). */
+typedef struct {
+  float* weight[MISO_MAX_LINEAR];
+  float* bias[MISO_MAX_LINEAR];
+} miso_mlp_grad_t;
+
 const char* miso_version(void);
 const char* miso_error_string(int code);
 
@@ -156,7 +163,9 @@ int miso_encode_bwd2(const miso_grid_t* grid, const miso_grid_t* gg_grid, const 
                      int64_t n, const float* grad_feats, int64_t ld_g, const float* gg_x,
                      float* gg_out, int64_t ld_gg, float* g_x, void* stream);
 
-/* --- fused encode + decoder (frozen decoder, out_dim == 1) ---------------- */
+/* --- fused encode + decoder (out_dim == 1) --------------------------------
+ * miso_sdf_fwd / miso_sdf_bwd* treat the decoder's weights as constants; a trainable decoder adds miso_sdf_wgrad (below,
+ * after the binned entry points) for its weight and bias gradients and re-packs (miso_mlp_pack) after every update. */
 /* Size in floats of the packed-weight buffer for this decoder, or 0 if the fused
  * kernels do not cover the shape (then use miso_encode_* + a library GEMM). */
 int64_t miso_mlp_packed_floats(const miso_mlp_t* mlp);
@@ -338,6 +347,22 @@ int64_t miso_sdf_bwd_workspace_floats(const miso_grid_t* grid, int64_t n);
 int miso_sdf_bwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
                         const miso_sorted_t* sorted, int64_t n, const float* grad_sdf,
                         const uint32_t* relu_mask, float* grad_x, float* workspace, void* stream);
+
+/* --- decoder weight gradients (trainable decoder) ---------------------------
+ * For every nn.Linear l of the decoder: grads->weight[l][out][in] = sum_p delta_l[p][out] a_{l-1}[p][in] and
+ * grads->bias[l][out] = sum_p delta_l[p][out], where a_{-1} is the encoded feature row, a_l the ReLU outputs (recomputed
+ * in exact fp32) and delta_l the cotangent of grad_sdf at layer l's output, gated by relu_mask -- the sign bits the
+ * forward wrote, in either decoder arithmetic.  The outputs are WRITTEN, not accumulated, and are deterministic (no
+ * atomics: per-workgroup partial sums in `workspace`, added in a fixed order; n == 0 writes zeros).
+ *   sorted == NULL: x, relu_mask and grad_sdf in the caller's order (miso_sdf_fwd / miso_sdf_bwd).
+ *   sorted != NULL: x is ignored, relu_mask is in the binned order (miso_sdf_fwd_sorted), grad_sdf in the caller's
+ *                   order, or in the binned order with flags = MISO_F_GRAD_SDF_SORTED (the only flag accepted).
+ * workspace: miso_sdf_wgrad_workspace_floats(grid, mlp, n) floats, 16-byte aligned (0 floats: shape not covered, or
+ * n == 0; at most a few MB). */
+int64_t miso_sdf_wgrad_workspace_floats(const miso_grid_t* grid, const miso_mlp_t* mlp, int64_t n);
+int miso_sdf_wgrad(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
+                   const float* grad_sdf, const uint32_t* relu_mask, const miso_sorted_t* sorted, uint32_t flags,
+                   const miso_mlp_grad_t* grads, float* workspace, int64_t workspace_floats, void* stream);
 
 /* --- latent alignment residual of a submap pair (pose-Jacobian path) --------
  * pairwise_loss_latent (grid_opt/align/miso.py:116-211) for the L2 / L1 variants.

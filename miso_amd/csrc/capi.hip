@@ -468,6 +468,47 @@ int miso_sdf_bwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
                       stream);
 }
 
+int64_t miso_sdf_wgrad_workspace_floats(const miso_grid_t* grid, const miso_mlp_t* mlp, int64_t n) {
+  GridK g; bool v4;
+  if (n < 0 || convert_grid(grid, &g, false, &v4)) return 0;
+  int C, L, H, NH;
+  if (fused_shape(g, v4, mlp, &C, &L, &H, &NH) != MISO_OK) return 0;
+  return sdf_wgrad_workspace_floats(C, L, H, NH, n);
+}
+
+// The decoder's weight and bias gradients (decoder_wgrad.hip): the sign bits and the point order are those of the forward
+// that wrote relu_mask (miso_sdf_fwd: caller order, sorted == NULL; miso_sdf_fwd_sorted: binned order).
+int miso_sdf_wgrad(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
+                   const float* grad_sdf, const uint32_t* relu_mask, const miso_sorted_t* sorted, uint32_t flags,
+                   const miso_mlp_grad_t* grads, float* workspace, int64_t workspace_floats, void* stream) {
+  if (!grid || !mlp || !packed || !grads || n < 0 || (n > 0 && (!grad_sdf || !relu_mask))) return MISO_E_BADARG;
+  if (((uintptr_t)packed & 15u) != 0 || (flags & ~MISO_F_GRAD_SDF_SORTED)) return MISO_E_BADARG;
+  if ((flags & MISO_F_GRAD_SDF_SORTED) && !sorted) return MISO_E_BADARG;
+  if (sorted) {
+    int rc = check_sorted(sorted, n);
+    if (rc) return rc;
+  }
+  GridK g; bool v4;
+  int rc = convert_grid(grid, &g, n > 0, &v4);
+  if (rc) return rc;
+  int C, L, H, NH;
+  rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
+  if (rc) return rc;
+  WgradOutK out;
+  memset(&out, 0, sizeof(out));
+  for (int l = 0; l < mlp->n_linear; ++l) {
+    if (!grads->weight[l]) return MISO_E_BADARG;
+    out.w[l] = grads->weight[l];
+    out.b[l] = grads->bias[l];
+  }
+  const int64_t need = sdf_wgrad_workspace_floats(C, L, H, NH, n);
+  if (need > 0 && (!workspace || workspace_floats < need || ((uintptr_t)workspace & 15u) != 0)) return MISO_E_BADARG;
+  if (sorted) x = sorted_points(&g, sorted);
+  if (n > 0 && !x) return MISO_E_BADARG;
+  return (int)launch_sdf_wgrad(C, L, H, NH, g, packed, x, n, grad_sdf, relu_mask, sorted ? sorted->perm : nullptr,
+                               (flags & MISO_F_GRAD_SDF_SORTED) != 0, out, workspace, (hipStream_t)stream);
+}
+
 // One training iteration of a frozen-decoder submap: forward + mapping loss + decoder backward in ONE launch
 // (sdf_train_kernel).  sorted != nullptr: a binned batch -- the levels the pull / push can form get their gradient from
 // the d-feat rows left in `workspace`, the others (bricks beyond the pull's reach) are scattered with float atomics from

@@ -107,6 +107,11 @@ struct MlpK {
   const float* w[MISO_MAX_LINEAR];
   const float* b[MISO_MAX_LINEAR];
 };
+// where the decoder's weight gradients go (decoder_wgrad.hip): nn.Linear layout, nullptr = not wanted / no bias
+struct WgradOutK {
+  float* w[MISO_MAX_LINEAR];
+  float* b[MISO_MAX_LINEAR];
+};
 
 // Per-axis sample position.  Mirrors the reference op by op (no FMA
 // contraction) so coordinates are bit-identical to the PyTorch path:

@@ -28,6 +28,12 @@ hipError_t launch_sdf_bwd(int C, int L, int H, int NH, const GridK& g, const flo
                           const float* gsdf, const uint32_t* mask, float* gx, bool want_grid, const int* perm,
                           float* dfeat_out, uint32_t defer_mask, bool gsdf_sorted, hipStream_t s);
 
+// ---- decoder_wgrad.hip (sdf_wgrad_workspace_floats: 0 = shape not covered, or an empty batch)
+int64_t sdf_wgrad_workspace_floats(int C, int L, int H, int NH, int64_t n);
+hipError_t launch_sdf_wgrad(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,
+                            const float* gsdf, const uint32_t* mask, const int* perm, bool gsdf_sorted,
+                            const WgradOutK& out, float* workspace, hipStream_t s);
+
 // ---- sdf_train.hip (sdf_train_lds_bytes: 0 = shape not covered, or its widest launch does not fit a workgroup's LDS)
 int64_t sdf_train_lds_bytes(int C, int L, int H, int NH, bool scat);
 hipError_t launch_sdf_train(int C, int L, int H, int NH, const GridK& g, const float* packed, const float* x, int64_t n,

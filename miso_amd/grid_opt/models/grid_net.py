@@ -17,6 +17,11 @@ from .modules import MLPNet
 
 logger = logging.getLogger(__name__)
 
+# A decoder with trainable weights keeps the fused forward and backward: GridNet.forward hands ops.sdf_fused the pack and
+# the weight gradients come from the HIP weight-gradient kernel (csrc/decoder_wgrad.hip).  MISO_NO_FUSED_WGRAD=1 (read
+# once, here) restores the op-by-op route for such a decoder: query_feature + utils.grid_decode, torch's own autograd.
+_FUSED_WGRAD = os.environ.get("MISO_NO_FUSED_WGRAD", "0") in ("", "0")
+
 
 class GridNet(BaseNet):
     def __init__(self, cfg: dict, device='cuda:0', dtype=torch.float32, initial_features=dict()):
@@ -259,11 +264,12 @@ class GridNet(BaseNet):
         self._check_coords(x)
         return utils.grid_interp_regular(self.feature_stability, x, None)
 
-    def _fused_decoder(self):
-        """DecoderPack if encode+decode can run as one kernel for this model, else None."""
+    def _fused_decoder(self, trainable=False):
+        """DecoderPack if encode+decode can run as one kernel for this model, else None.  trainable=True (forward() only):
+        a decoder with trainable weights qualifies too -- ops.sdf_fused then forms their gradients in HIP."""
         if self.decoder is None or not self.pos_invariant or not isinstance(self.decoder, MLPNet):
             return None
-        pack = self.decoder.decoder_pack()
+        pack = self.decoder.decoder_pack(trainable=trainable)
         if pack is None:
             return None
         feats = [g.feature for g in self.features]
@@ -272,7 +278,7 @@ class GridNet(BaseNet):
 
     def forward(self, x: torch.Tensor, noise_std=0):
         self._check_coords(x)
-        pack = self._fused_decoder() if x.is_cuda else None
+        pack = self._fused_decoder(trainable=_FUSED_WGRAD) if x.is_cuda else None
         if pack is not None:
             meta = self.features[0].grid_meta(self.ignore_level_)
             pred = ops.sdf_fused(x, [g.feature for g in self.features], meta, pack)

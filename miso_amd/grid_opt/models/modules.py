@@ -53,16 +53,18 @@ class MLPNet(nn.Module):
             state.pop(k, None)                             # cached layer / parameter lists: rebuilt on demand
         return state
 
-    def decoder_pack(self):
+    def decoder_pack(self, trainable=False):
         """Packed weights for the fused encode+decode kernels, or None if the decoder
-        cannot take that path (trainable weights, non-ReLU activation)."""
+        cannot take that path (trainable weights, non-ReLU activation).  trainable=True: the pack of a decoder with
+        trainable weights as well (the same cached object) -- for ops.sdf_fused alone, which then forms the weight
+        gradients too; every other user of the pack treats the weights as constants and must not ask for it."""
         relu_only = self.__dict__.get('_relu_only')
         if relu_only is None:
             # a module unpickled from a file the reference wrote (torch.save(grid_atlas), demo/build_submaps.py:141) carries
             # the reference's attributes only: read the activation off the layer list
             relu_only = self.__dict__['_relu_only'] = all(
                 isinstance(m, (nn.Linear, nn.ReLU)) for m in self.network)
-        if not relu_only or not self.is_frozen():
+        if not relu_only or not (trainable or self.is_frozen()):
             return None
         pack = self.__dict__.get('_pack')
         lin = self.linears()

@@ -360,11 +360,12 @@ def grid_sample_3d(input: torch.Tensor, grid: torch.Tensor, padding_mode: str = 
 
 
 # --------------------------------------------------------------------------- #
-# fused encode + frozen decoder
+# fused encode + decoder
 # --------------------------------------------------------------------------- #
 class DecoderPack:
-    """Weights of a frozen MLPNet pre-permuted into MFMA operand order
-    (miso_mlp_pack).  Re-packed automatically when a weight tensor changes."""
+    """Weights of an MLPNet pre-permuted into MFMA operand order (miso_mlp_pack).  Re-packed automatically when a weight
+    tensor changes (an in-place optimizer step bumps its version).  The kernels read the weights as constants; where a
+    tensor requires grad, sdf_fused adds the weight-gradient launch (sdf_wgrad_raw)."""
 
     def __init__(self, weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]]):
         self.weights = list(weights)
@@ -412,6 +413,20 @@ class DecoderPack:
         _lib.check(_lib.load().miso_mlp_pack(C.byref(m), _ptr(packed), _stream(packed)), "miso_mlp_pack")
         self._mlp, self._packed, self._keep = m, packed, keep
         return m, packed
+
+    def trainable(self) -> bool:
+        """Does any weight or bias take a gradient?  sdf_fused then also forms the decoder's gradients (sdf_wgrad_raw)."""
+        return any(t is not None and t.requires_grad for t in self.weights + self.biases)
+
+    def wgrad_workspace(self, floats: int, stream) -> torch.Tensor:
+        """Partial sums of sdf_wgrad_raw (one block per workgroup): kept with the pack, not allocated per call -- one buffer
+        per stream (``stream``: the raw handle), so that backward passes of models that share this decoder may run on
+        different streams."""
+        cache = self.__dict__.setdefault("_wgrad_ws", {})
+        ws = cache.get(stream)
+        if ws is None or ws.numel() < floats or ws.device != self.weights[0].device:
+            ws = cache[stream] = torch.empty(max(floats, 4), device=self.weights[0].device, dtype=torch.float32)
+        return ws
 
 
 def sdf_fused_supported(features, meta: GridMeta, pack: DecoderPack) -> bool:
@@ -577,6 +592,41 @@ def sdf_bwd_raw(x, features, meta, pack: DecoderPack, gsdf, mask, need_x, need_f
         _lib.check(_lib.load().miso_sdf_bwd(C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _ptr(gsdf),
                                             _ptr(mask), _ptr(gx), _stream(x)), "miso_sdf_bwd")
     return gx, grads
+
+
+def sdf_wgrad_raw(x, features, meta, pack: DecoderPack, gsdf, mask, sorted_batch: Optional[SortedBatch] = None,
+                  gsdf_sorted: bool = False):
+    """Weight and bias gradients of the decoder for d loss / d sdf = ``gsdf`` (miso_sdf_wgrad): -> (grad_weights,
+    grad_biases), one tensor per nn.Linear in its own layout, None for an absent bias.  ``mask``: the sign bits of the
+    forward (sdf_fwd_raw) over the same points -- with ``sorted_batch`` in the binned order, ``gsdf`` then in the
+    caller's order or (gsdf_sorted) the binned one.  Deterministic; the results are written, not accumulated."""
+    _require_hip(x, gsdf, *features)
+    m, packed = pack.get()
+    if m is None:
+        raise RuntimeError("decoder shape is not covered by the fused kernels")
+    x = x.contiguous()
+    gsdf = gsdf.contiguous()
+    n = x.shape[0]
+    assert not gsdf_sorted or sorted_batch is not None
+    kw = dict(device=x.device, dtype=torch.float32)
+    gw = [torch.empty(tuple(w.shape), **kw) for w in pack.weights]
+    gb = [None if b is None else torch.empty(tuple(b.shape), **kw) for b in pack.biases]
+    out = _lib.MlpGrad()
+    for i, (w, b) in enumerate(zip(gw, gb)):
+        out.weight[i] = w.data_ptr()
+        out.bias[i] = None if b is None else b.data_ptr()
+    g = _fill_grid(features, meta)
+    lib = _lib.load()
+    floats = int(lib.miso_sdf_wgrad_workspace_floats(C.byref(g), C.byref(m), n))
+    if floats == 0 and n > 0:
+        raise RuntimeError("decoder / grid shape is not covered by the fused kernels")
+    stream = _stream(x)
+    ws = pack.wgrad_workspace(floats, stream.value)
+    _lib.check(lib.miso_sdf_wgrad(C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _ptr(gsdf), _ptr(mask),
+                                  None if sorted_batch is None else C.byref(sorted_batch.struct),
+                                  _lib.F_GRAD_SDF_SORTED if gsdf_sorted else 0, C.byref(out), _ptr(ws), ws.numel(),
+                                  stream), "miso_sdf_wgrad")
+    return gw, gb
 
 
 def sdf_bwd_rows_raw(x, features, meta, pack: DecoderPack, gsdf, mask, need_x, need_f, grads=None):
@@ -863,8 +913,64 @@ class _SdfFused(torch.autograd.Function):
         return (gx, None, None, *grads)
 
 
+class _SdfFusedTrainable(torch.autograd.Function):
+    """_SdfFused with the decoder's weights and biases as differentiable inputs: the same forward launch, the same
+    backward launch for x and the grids, plus one launch of the weight-gradient kernel (sdf_wgrad_raw).  The tensors of
+    ``pack`` are passed again as inputs (``n_feat`` features, then the weights, then the biases that exist), so that
+    autograd routes their gradients; the launches read them through the pack."""
+
+    @staticmethod
+    def forward(ctx, x, meta, pack, n_feat, *tensors):
+        features = tensors[:n_feat]
+        sb = None
+        if (any(ctx.needs_input_grad[4:4 + n_feat]) and SortedBatch.AUTO_MIN_POINTS is not None
+                and x.shape[0] >= SortedBatch.AUTO_MIN_POINTS):
+            sb = SortedBatch(x.shape[0], x.device).sort(x, meta)      # as _SdfFused: both passes use the binned order
+        sdf, mask = sdf_fwd_raw(x, features, meta, pack, want_mask=any(ctx.needs_input_grad), sorted_batch=sb)
+        ctx.save_for_backward(x, mask, *tensors)      # (the weights too: an in-place step before backward() is an error)
+        ctx.meta, ctx.pack, ctx.sb, ctx.n_feat = meta, pack, sb, n_feat
+        return sdf
+
+    @staticmethod
+    def backward(ctx, gsdf):
+        x, mask, *tensors = ctx.saved_tensors
+        n_feat, pack = ctx.n_feat, ctx.pack
+        features, params = tensors[:n_feat], tensors[n_feat:]
+        need_x = ctx.needs_input_grad[0]
+        need_f = tuple(ctx.needs_input_grad[4:4 + n_feat])
+        need_p = tuple(ctx.needs_input_grad[4 + n_feat:])
+        n_w = len(pack.weights)
+        if torch.is_grad_enabled():
+            # create_graph=True: the graph rebuilt from encode + torch.nn.functional.linear (the MISO_BWD2_TORCH branch of
+            # _SdfFused.backward, with the weights and biases among the wanted) -- the double backward of the weight path
+            # is not built in HIP
+            if _ONLY_X:
+                need_f, need_p = (False,) * n_feat, (False,) * len(params)
+            ws, rest = list(params[:n_w]), list(params[n_w:])
+            bs = [None if b is None else rest.pop(0) for b in pack.biases]
+            with torch.enable_grad():
+                out = _mlp_torch(encode(x, features, ctx.meta), ws, bs)
+                wanted = [t for t, nd in zip((x, *features, *params), (need_x, *need_f, *need_p)) if nd]
+                got = list(torch.autograd.grad(out, wanted, gsdf, create_graph=True, allow_unused=True))
+            res = [got.pop(0) if nd else None for nd in (need_x, *need_f, *need_p)]
+            return (res[0], None, None, None, *res[1:])
+        gx, grads = None, [None] * n_feat
+        if need_x or any(need_f):
+            gx, grads = sdf_bwd_raw(x, features, ctx.meta, pack, gsdf, mask, need_x, need_f, sorted_batch=ctx.sb,
+                                    overwrite=True)
+        gp = [None] * len(params)
+        if any(need_p):
+            gw, gb = sdf_wgrad_raw(x, features, ctx.meta, pack, gsdf, mask, sorted_batch=ctx.sb)
+            gp = [t if nd else None for t, nd in zip(gw + [b for b in gb if b is not None], need_p)]
+        return (gx, None, None, None, *grads, *gp)
+
+
 def sdf_fused(x, features, meta: GridMeta, pack: DecoderPack) -> torch.Tensor:
-    """(N,3) -> (N,1) SDF with a frozen decoder: one kernel forward, one backward."""
+    """(N,3) -> (N,1) SDF: one kernel forward, one backward.  A pack whose tensors take no gradient (a frozen decoder) runs
+    _SdfFused; one with a trainable weight or bias runs _SdfFusedTrainable, whose backward adds the weight-gradient kernel."""
+    if pack.trainable():
+        return _SdfFusedTrainable.apply(x, meta, pack, len(features), *features, *pack.weights,
+                                        *[b for b in pack.biases if b is not None])
     return _SdfFused.apply(x, meta, pack, *features)
 
 

@@ -189,7 +189,7 @@ def _(x, features, weights, biases, bound, ignore_mask, flags, want_mask):
 def decode_bwd(gsdf: torch.Tensor, x: torch.Tensor, features: Sequence[torch.Tensor], weights: Sequence[torch.Tensor],
                biases: Sequence[torch.Tensor], mask: torch.Tensor, bound: Sequence[float], ignore_mask: int, flags: int,
                need_x: bool, need_f: Sequence[bool]) -> List[torch.Tensor]:
-    """-> [grad x (N,3) or empty, grad of every level or empty] (the decoder is frozen: no weight gradients)"""
+    """-> [grad x (N,3) or empty, grad of every level or empty] (the decoder's weights are constants of this operator: their gradients are ops.sdf_wgrad_raw's)"""
     gx, grads = ops.sdf_bwd_raw(x, list(features), _meta(bound, ignore_mask, flags), _pack(weights, biases), gsdf, mask,
                                 need_x, list(need_f))
     return [_or_empty(gx, x)] + [_or_empty(g, x) for g in grads]
