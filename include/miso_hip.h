@@ -755,6 +755,34 @@ int miso_atlas_sdf_fwd(const void* plan, int32_t n_submaps, const miso_grid_t* s
                        const float* axis_y, const float* axis_z, int32_t nx, int32_t ny, int32_t nz, float* sdf,
                        float* feats, int64_t ld_feats, uint32_t flags, void* stream);
 
+/* --- backward of the fused atlas query: the gradients of GridAtlas.forward in one launch ----------------------------------
+ * Replaces what autograd does behind the per-submap loop of grid_opt/models/grid_atlas.py:374-399 (per submap the
+ * backward of mask * grid_interp_regular over every point, an (N,F) cotangent through memory, the division by the count)
+ * with one wavefront per 64 world points: the forward again (the bits of miso_atlas_sdf_fwd, ReLU signs kept), the decoder
+ * backward, and per submap a point is inside d feats = d mean / count -- the count is a constant and the bound mask is not
+ * differentiated, as autograd treats inside * interp.  The decoder takes no gradient.
+ *   miso_atlas_bwd_workspace_bytes  device scratch for the pose gradient of a call over n points (every block's (S,12)
+ *       partial sum; 0 for n == 0); non-decreasing in n.  4-byte aligned; not needed when gposes == NULL.
+ *   miso_atlas_sdf_bwd  `plan`, `n_submaps`, `shape`, `poses`, `mlp`, `packed`, flags: as for miso_atlas_sdf_fwd, the plan
+ *       built by miso_atlas_plan_build from grids whose levels carry their `grad` pointer (the layout of `data`), or NULL
+ *       for a level that takes no gradient (a locked submap).  `x` (N,3) world points (no lattice form), `gsdf` (N)
+ *       d loss / d sdf.  Grid gradients are ADDED with fp32 atomics: the caller clears them.  Outputs, each NULL or:
+ *       `gx` (N,3) d loss / d x, written for every point (zeros where it is inside no submap); `gposes` (n_submaps, 12)
+ *       the gradient of the pose table as passed in `poses`, row = {d R_submap_world (9, row-major), d t_submap_world
+ *       (3)}, written (the blocks' partial sums are added in fp64; n_submaps <= MISO_ATLAS_BWD_MAX_SUBMAPS, else
+ *       MISO_E_UNSUPPORTED).
+ *       n == 0 launches nothing and writes nothing.
+ *   miso_atlas_bwd_supported  1 when miso_atlas_sdf_bwd serves this grid / decoder shape over n_submaps submaps (with a
+ *       pose gradient when want_poses) in both arithmetic forms -- the shape is in the kernel table and the launch fits
+ *       a workgroup's LDS -- else 0: what a caller asks BEFORE it routes a forward through the fused pair, since a refusal
+ *       inside the backward has nothing to fall back to. */
+#define MISO_ATLAS_BWD_MAX_SUBMAPS 256
+int miso_atlas_bwd_supported(const miso_grid_t* shape, const miso_mlp_t* mlp, int32_t n_submaps, int want_poses);
+int64_t miso_atlas_bwd_workspace_bytes(int64_t n, int32_t n_submaps);
+int miso_atlas_sdf_bwd(const void* plan, int32_t n_submaps, const miso_grid_t* shape, const float* poses,
+                       const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n, const float* gsdf,
+                       float* gx, float* gposes, void* workspace, uint32_t flags, void* stream);
+
 /* --- sphere tracing: utils_sdf.sphere_tracing in one launch -----------------------------------------------------------
  * Replaces the loop of grid_opt/utils/utils_sdf.py:197-236 (per round: norm, one model call, three masks, a host sync on
  * torch.sum(mask_stop) == n, a blended update of all N points) when the model is a GridAtlas or a GridNet: one wavefront

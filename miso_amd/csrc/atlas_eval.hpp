@@ -126,6 +126,69 @@ __device__ __forceinline__ float atlas_eval(const AtlasK& a, const AtlasDecoder<
   return any_inside ? dec.decode(mean) : dec.sdf_empty;      // (wave-uniform choice)
 }
 
+// The lane's world point in submap s's frame (xl) and whether it counts as inside that submap (`ps`: the submap's row
+// of the pose table, `g`: its grid; both wave-uniform).  The operations of atlas_eval's loop, in its order: the
+// backward (atlas_bwd.hip) has to find the same lanes inside the same submaps.
+__device__ __forceinline__ bool atlas_to_submap(const AtlasK& a, const float* ps, const GridK& g, bool valid, float wx,
+                                                float wy, float wz, float (&xl)[3]) {
+  // transfrom_points_from (utils_geometry.py:227-240) = transform_points_to with (R^T, -R^T t), both formed by the
+  // caller with the reference's own tensor ops; the row-times-matrix product in torch's order: ((x r0) + y r1) + z r2, + t
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    float v = __fmul_rn(wx, ps[3 * j]);
+    v = __fmaf_rn(wy, ps[3 * j + 1], v);
+    v = __fmaf_rn(wz, ps[3 * j + 2], v);
+    xl[j] = __fadd_rn(v, ps[9 + j]);
+  }
+  // coords_in_bound (utils_geometry.py:11-27): min <= x <= max on every axis
+  return valid && (a.no_bound || (xl[0] >= g.bmin[0] && xl[0] <= g.bmax[0] && xl[1] >= g.bmin[1] &&
+                                  xl[1] <= g.bmax[1] && xl[2] >= g.bmin[2] && xl[2] <= g.bmax[2]));
+}
+
+// The first half of atlas_eval for a caller that runs the decoder itself (atlas_sdf_bwd_kernel keeps the ReLU signs):
+// the masked mean over the submaps at one world point per lane, operation for operation the loop of atlas_eval above.
+// (A second copy on purpose: atlas_eval's own body stays as it is, so that the forward and trace kernels keep their code.)  mean[] receives the mean feature row (zeros past F), den the number of
+// submaps the lane is inside (1 where it is inside none: the divisor of the mean); returns whether any lane of the
+// wavefront is inside any submap (wave-uniform).
+template <int C, int L, int NF>
+__device__ __forceinline__ bool atlas_mean(const AtlasK& a, bool valid, float wx, float wy, float wz, float (&mean)[NF],
+                                           float& den) {
+  constexpr int F = C * L;
+  float sum[NF];
+#pragma unroll
+  for (int i = 0; i < NF; ++i) sum[i] = 0.0f;
+  float cnt = 0.0f;
+  bool any_inside = false;
+  for (int s = 0; s < a.n_submaps; ++s) {
+    const GridK& g = a.submaps[s];
+    float xl[3];
+    const bool inside = atlas_to_submap(a, a.poses + s * 12, g, valid, wx, wy, wz, xl);
+    if (!__any(inside)) continue;
+    any_inside = true;
+    if (inside) {
+      cnt += 1.0f;
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        if ((g.ignore_mask >> l) & 1u) continue;      // (zeros: utils.py:160-163; the atlas queries never set it)
+        const LevelK lv = g.lv[l];
+        Axis ax = axis_coord(xl[0], g.bmin[0], g.bmax[0], lv.X, g.flags);
+        Axis ay = axis_coord(xl[1], g.bmin[1], g.bmax[1], lv.Y, g.flags);
+        Axis az = axis_coord(xl[2], g.bmin[2], g.bmax[2], lv.Z, g.flags);
+        Cell c = make_cell(ax, ay, az, lv);
+        float fl[C];
+        gather_level<C, true>(lv, c, fl);
+#pragma unroll
+        for (int q = 0; q < C; ++q) sum[l * C + q] += fl[q];      // sum_feats += mask * feats, submap by submap
+      }
+    }
+  }
+  // sum_weights[sum_weights == 0] = 1; mean = sum / weights
+  den = cnt == 0.0f ? 1.0f : cnt;
+#pragma unroll
+  for (int i = 0; i < NF; ++i) mean[i] = (i < F) ? __fdiv_rn(sum[i], den) : 0.0f;
+  return any_inside;
+}
+
 // Launch shape of the kernels that run atlas_eval: dynamic LDS for the decoder image (split or fp32 pack; `staged` =
 // false for a feature-only query, which stages nothing) and a persistent grid of four wavefronts per block, one per 64
 // points at a time.

@@ -1036,6 +1036,44 @@ int miso_atlas_sdf_fwd(const void* plan, int32_t n_submaps, const miso_grid_t* s
   return (int)launch_atlas_sdf(C, L, H, NH, a, packed, (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
 }
 
+// ---- backward of the fused atlas query (atlas_bwd.hip) ------------------------------------------------------------------
+int64_t miso_atlas_bwd_workspace_bytes(int64_t n, int32_t n_submaps) {
+  return atlas_bwd_workspace_bytes(n, n_submaps);
+}
+
+int miso_atlas_bwd_supported(const miso_grid_t* shape, const miso_mlp_t* mlp, int32_t n_submaps, int want_poses) {
+  GridK g; bool v4;
+  if (!shape || !mlp || convert_grid(shape, &g, false, &v4)) return 0;
+  if (g.flags & MISO_F_COORDS_NORMALIZED) return 0;
+  int C, L, H, NH;
+  if (fused_shape(g, true, mlp, &C, &L, &H, &NH)) return 0;
+  return atlas_bwd_covered(C, L, H, NH, n_submaps, want_poses != 0) ? 1 : 0;
+}
+
+int miso_atlas_sdf_bwd(const void* plan, int32_t n_submaps, const miso_grid_t* shape, const float* poses,
+                       const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n, const float* gsdf,
+                       float* gx, float* gposes, void* workspace, uint32_t flags, void* stream) {
+  if (!plan || !poses || !shape || !mlp || !packed || n_submaps < 1 || n < 0) return MISO_E_BADARG;
+  if (flags & ~(MISO_F_EXACT_F32 | MISO_F_ATLAS_NO_BOUND)) return MISO_E_BADARG;
+  if (((uintptr_t)packed) & 15u) return MISO_E_BADARG;
+  GridK g; bool v4;
+  int rc = convert_grid(shape, &g, false, &v4);
+  if (rc) return rc;
+  int C = g.lv[0].C, L = g.n_levels, H = 64, NH = 1;
+  rc = fused_shape(g, true, mlp, &C, &L, &H, &NH);
+  if (rc) return rc;
+  if (!atlas_bwd_covered(C, L, H, NH, n_submaps, gposes != nullptr)) return MISO_E_UNSUPPORTED;
+  if (n == 0) return MISO_OK;
+  if (!x || !gsdf || (gposes && (!workspace || (((uintptr_t)workspace) & 3u)))) return MISO_E_BADARG;
+  AtlasK a;
+  memset(&a, 0, sizeof(a));
+  a.submaps = reinterpret_cast<const GridK*>(plan);
+  a.poses = poses; a.n_submaps = n_submaps; a.n = n; a.x = x;
+  a.no_bound = (flags & MISO_F_ATLAS_NO_BOUND) ? 1 : 0;
+  return (int)launch_atlas_sdf_bwd(C, L, H, NH, a, packed, gsdf, gx, gposes, reinterpret_cast<float*>(workspace),
+                                   (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
+}
+
 // ---- sphere tracing through the fused atlas query (trace.hip) ------------------------------------------------------------
 int miso_atlas_sphere_trace(const void* plan, int32_t n_submaps, const miso_grid_t* shape, const float* poses,
                             const miso_mlp_t* mlp, const float* packed, const float* origins, const float* dirs,

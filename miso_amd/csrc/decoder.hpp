@@ -518,4 +518,64 @@ __device__ __forceinline__ void decoder_fwd_exact(const float* __restrict__ w0p,
   }
 }
 
+// The exact fp32 chains of the backward, as sdf_bwd_kernel runs them: d sdf of the two point tiles (ds[t]) -> d feats in
+// accumulator layout, gated by the sign words mw of decoder_fwd_exact.  whT / w0T / wo: the fp32 pack's transposed weights
+// and output weights in LDS.  Same outputs as decoder_bwd_split.
+template <int F, int H, int NH>
+__device__ __forceinline__ void decoder_bwd_exact(const float* __restrict__ whT, const float* __restrict__ w0T,
+                                                  const float* __restrict__ wo, int lane,
+                                                  const uint32_t (&mw)[(NH + 1) * (H / 32)], const float (&ds)[2],
+                                                  f32x16 (&df)[2]) {
+  constexpr int RT = H / 32, KS1 = H / 2;
+  const int hi = lane >> 5;
+  f32x16 dbuf[2][RT][2];      // two accumulator sets ping-pong
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const float wv = wo[32 * r + row_of(j, hi)];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) dbuf[0][r][t][j] = gate(wv * ds[t], mw[NH * RT + r], t, j);
+    }
+#pragma unroll
+  for (int hh = 0; hh < NH; ++hh) {
+    const int h = NH - 1 - hh;
+    const int ci = hh & 1, ni = ci ^ 1;
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) { dbuf[ni][r][0][j] = 0.0f; dbuf[ni][r][1][j] = 0.0f; }
+#pragma unroll
+    for (int rp = 0; rp < RT; ++rp)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int ks = rp * 16 + j;
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+          const float a = whT[((h * KS1 + ks) * 64 + lane) * RT + r];
+          dbuf[ni][r][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, dbuf[ci][rp][0][j], dbuf[ni][r][0], 0, 0, 0);
+          dbuf[ni][r][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, dbuf[ci][rp][1][j], dbuf[ni][r][1], 0, 0, 0);
+        }
+      }
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) dbuf[ni][r][t][j] = gate(dbuf[ni][r][t][j], mw[h * RT + r], t, j);
+  }
+  f32x16 (&d)[RT][2] = dbuf[NH & 1];
+  // d feats = W0^T d   (one 32-row tile; rows >= F are zero)
+#pragma unroll
+  for (int j = 0; j < 16; ++j) { df[0][j] = 0.0f; df[1][j] = 0.0f; }
+#pragma unroll
+  for (int rp = 0; rp < RT; ++rp)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const float a = w0T[(rp * 16 + j) * 64 + lane];
+      df[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, d[rp][0][j], df[0], 0, 0, 0);
+      df[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, d[rp][1][j], df[1], 0, 0, 0);
+    }
+}
+
 }  // namespace miso

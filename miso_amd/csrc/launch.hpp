@@ -43,6 +43,12 @@ hipError_t launch_sdf_train(int C, int L, int H, int NH, const GridK& g, const f
 // ---- atlas.hip
 hipError_t launch_atlas_sdf(int C, int L, int H, int NH, const AtlasK& a, const float* packed, bool exact, hipStream_t s);
 
+// ---- atlas_bwd.hip (atlas_bwd_covered: shape in the kernel table and its launch fits a workgroup's LDS, both arithmetics)
+int64_t atlas_bwd_workspace_bytes(int64_t n, int n_submaps);
+bool atlas_bwd_covered(int C, int L, int H, int NH, int n_submaps, bool poses);
+hipError_t launch_atlas_sdf_bwd(int C, int L, int H, int NH, const AtlasK& a, const float* packed, const float* gsdf,
+                                float* gx, float* gposes, float* workspace, bool exact, hipStream_t s);
+
 // ---- trace.hip
 hipError_t launch_atlas_trace(int C, int L, int H, int NH, const AtlasK& a, const TraceK& t, const float* packed, bool exact,
                               hipStream_t s);

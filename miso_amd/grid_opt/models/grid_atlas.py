@@ -20,6 +20,11 @@ logger = logging.getLogger(__name__)
 
 
 class GridAtlas(BaseNet):
+    # forward() under autograd as ONE launch forward and ONE backward (ops.AtlasQuery.differentiable) where the atlas is
+    # eligible for the fused query, instead of the per-submap loop with op-by-op autograd behind it.  Off by default; no
+    # double backward through it (an eikonal term with an autograd grad_method needs the loop).  Fuser.fuse switches it on.
+    fused_backward = False
+
     def __init__(self, cfg: dict, device='cuda:0', dtype=torch.float32):
         super().__init__(cfg, device, dtype)
         self.cfg = cfg
@@ -267,11 +272,11 @@ class GridAtlas(BaseNet):
             s.zero_features()
 
     # ---- queries (hot path) ----------------------------------------------------------------------
-    def _fused_inputs(self, probe, want_sdf=True):
-        """What a one-launch query of the active submaps needs -- (query, features, metas, pose table, decoder pack) --
-        or None when the query is not eligible: autograd on, host tensors, a decoder or grid shape the fused kernels do
-        not cover.  probe: the tensor whose device decides (the points, or None: the first submap's features)."""
-        if torch.is_grad_enabled() or not self.active_submaps:
+    def _fused_eligible(self, probe, want_sdf=True):
+        """(features, metas, decoder pack) of the active submaps when the fused atlas kernels cover them, else None: host
+        tensors, a decoder or grid shape outside the kernel table.  probe: the tensor whose device decides (the points,
+        or None: the first submap's features)."""
+        if not self.active_submaps:
             return None
         if probe is None:
             probe = self.get_submap(self.active_submaps[0]).features[0].feature
@@ -297,6 +302,30 @@ class GridAtlas(BaseNet):
             self.__dict__['_atlas_eligible'] = (ekey, ok)
         if not self.__dict__['_atlas_eligible'][1]:
             return None
+        return feats, metas, pack
+
+    def _pose_table(self, device):
+        """(S,12) rows {R_submap_world row-major, t_submap_world} of the active submaps, as the atlas kernels read them;
+        built with torch ops from updated_submap_pose, so under autograd it carries the graph to the corrections."""
+        rows = []
+        for s in self.active_submaps:
+            R, t = self.updated_submap_pose(s)
+            # transfrom_points_from (utils_geometry.py:227-240): R_src_dst = R^T, t_src_dst = -R^T t
+            Rinv = R.T
+            rows.append(torch.cat((Rinv.reshape(-1), (-(Rinv @ t)).reshape(-1))))
+        return torch.stack(rows).to(device=device, dtype=torch.float32).contiguous()
+
+    def _fused_inputs(self, probe, want_sdf=True):
+        """What a one-launch query of the active submaps needs -- (query, features, metas, pose table, decoder pack) --
+        or None when the query is not eligible: autograd on, or not _fused_eligible."""
+        if torch.is_grad_enabled():
+            return None
+        got = self._fused_eligible(probe, want_sdf)
+        if got is None:
+            return None
+        feats, metas, pack = got
+        if probe is None:
+            probe = feats[0][0]
         # the pose table, rebuilt when a correction (or an initial pose) changed: S exponential maps and ~10 small
         # launches per submap otherwise, per query
         act = tuple(self.active_submaps)
@@ -307,13 +336,7 @@ class GridAtlas(BaseNet):
         if hit is not None and hit[0] == pkey and hit[1].device == probe.device:
             poses = hit[1]
         else:
-            rows = []
-            for s in act:
-                R, t = self.updated_submap_pose(s)
-                # transfrom_points_from (utils_geometry.py:227-240): R_src_dst = R^T, t_src_dst = -R^T t
-                Rinv = R.T
-                rows.append(torch.cat((Rinv.reshape(-1), (-(Rinv @ t)).reshape(-1))))
-            poses = torch.stack(rows).to(device=probe.device, dtype=torch.float32).contiguous()
+            poses = self._pose_table(probe.device)
             self.__dict__['_atlas_poses'] = (pkey, poses)
         q = self.__dict__.setdefault('_atlas_query', ops.AtlasQuery())
         return q, feats, metas, poses, pack
@@ -330,6 +353,34 @@ class GridAtlas(BaseNet):
         q, feats, metas, poses, pack = got
         try:
             return q(feats, metas, poses, pack, x=x_world, axes=axes, want_sdf=want_sdf, want_feats=want_feats)
+        except RuntimeError as e:              # a shape outside the kernel table: the loop serves it
+            if "not covered" in str(e):
+                return None
+            raise
+
+    def _fused_differentiable(self, x_world: Tensor):
+        """forward() under autograd through ops.AtlasQuery.differentiable (one launch forward, one backward: gradients
+        to the points, to the submap pose corrections through the pose table, to the features of unlocked submaps) when
+        fused_backward is set and the atlas is _fused_eligible with a frozen decoder; else None: the loop serves it.
+        The pose table is built anew in every call: its graph is freed by the backward, so it cannot be cached the
+        way _fused_inputs caches the inference table."""
+        if not (self.fused_backward and torch.is_grad_enabled() and x_world.is_cuda and x_world.dtype == torch.float32):
+            return None
+        if x_world.ndim != 2 or len(self.active_submaps) > ops.ATLAS_BWD_MAX_SUBMAPS:
+            return None
+        got = self._fused_eligible(x_world)
+        if got is None or got[2].trainable():
+            return None
+        feats, metas, pack = got
+        # the backward has nothing to fall back to: ask now whether it will be served (once per set of feature tensors)
+        bkey = (self.__dict__['_atlas_eligible'][0], len(feats))
+        if self.__dict__.get('_atlas_bwd_ok', (None, False))[0] != bkey:
+            self.__dict__['_atlas_bwd_ok'] = (bkey, ops.AtlasQuery.backward_supported(feats, metas, pack))
+        if not self.__dict__['_atlas_bwd_ok'][1]:
+            return None
+        q = self.__dict__.setdefault('_atlas_query', ops.AtlasQuery())
+        try:
+            return q.differentiable(feats, metas, self._pose_table(x_world.device), pack, x_world)
         except RuntimeError as e:              # a shape outside the kernel table: the loop serves it
             if "not covered" in str(e):
                 return None
@@ -388,6 +439,8 @@ class GridAtlas(BaseNet):
         if got is not None:
             pred = got[0]
         else:
+            pred = self._fused_differentiable(x_world)
+        if pred is None:
             feats = self.query_feature(x_world)
             pred = utils.grid_decode(feats, None, self.submaps[0].decoder, True)
         if noise_std > 0:

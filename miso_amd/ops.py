@@ -996,7 +996,8 @@ def grid_pool_avg(coords, features, bound_min, cell_size: float, dims):
 class AtlasQuery:
     """The per-submap loop of GridAtlas.query_feature / forward (grid_opt/models/grid_atlas.py:374-399) as ONE launch
     (miso_atlas_sdf_fwd, csrc/atlas.hip): frame change, bound test, multi-level encode of the points that are inside,
-    mean over the submaps that contain a point, submap 0's decoder -- inference only (no autograd).
+    mean over the submaps that contain a point, submap 0's decoder.  __call__ and trace are inference (no autograd);
+    differentiable() is the same forward with the one-launch backward behind it (miso_atlas_sdf_bwd, csrc/atlas_bwd.hip).
 
     features: per submap the list of level tensors (1,C,Z,Y,X), channels-last; metas: per submap its GridMeta (bound).
     The device-resident plan is rebuilt when a feature tensor's storage or a bound changes."""
@@ -1058,6 +1059,65 @@ class AtlasQuery:
             flags, _stream(poses)), "miso_atlas_sdf_fwd")
         return sdf, feats
 
+    def differentiable(self, features, metas, poses, pack: "DecoderPack", x):
+        """__call__(..., x=x) -> sdf (N,1) under autograd: the forward is the same launch, the backward ONE launch
+        (miso_atlas_sdf_bwd) that hands gradients to x (N,3), to the pose table ``poses`` (S,12) and to every feature
+        tensor that requires grad (dense, zero-filled then scattered into).  Only tensors that require grad get one.  The
+        decoder is a constant: a pack with a trainable tensor is refused.  A second backward through the result raises."""
+        if pack.trainable():
+            raise RuntimeError("AtlasQuery.differentiable: the decoder takes no gradient through the atlas; "
+                               "freeze it or use the per-submap loop")
+        assert poses.shape == (len(features), 12) and poses.dtype == torch.float32
+        assert x.ndim == 2 and x.shape[1] == 3 and x.dtype == torch.float32
+        _require_hip(x, poses)
+        flat = [f for fs in features for f in fs]
+        return _AtlasSdf.apply(self, tuple(metas), pack, tuple(len(fs) for fs in features), x, poses, *flat)
+
+    @staticmethod
+    def backward_supported(features, metas, pack: "DecoderPack") -> bool:
+        """Will differentiable() find its backward (miso_atlas_bwd_supported: the shape in the kernel table, the launch
+        within a workgroup's LDS, pose gradient included)?  Asked before a forward is routed through it."""
+        m, _ = pack.get()
+        if m is None:
+            return False
+        return bool(_lib.load().miso_atlas_bwd_supported(C.byref(_fill_grid(features[0], metas[0])), C.byref(m),
+                                                          len(features), 1))
+
+    def _backward(self, features, metas, poses, pack, x, gsdf, need_x, need_poses, need_feats, exact, grads=None):
+        """-> (gx or None, gposes or None, per submap the list of level gradients / None).  grads: buffers to ADD the
+        level gradients into (the layout of the features; None per level: no gradient), instead of new zero-filled ones."""
+        S, n, dev = len(features), x.shape[0], poses.device
+        if grads is None:
+            grads = [[torch.zeros_like(f) if nd else None for f, nd in zip(fs, nds)]
+                     for fs, nds in zip(features, need_feats)]
+        gx = torch.empty((n, 3), device=dev, dtype=torch.float32) if need_x else None
+        gposes = torch.empty((S, 12), device=dev, dtype=torch.float32) if need_poses else None
+        if n == 0:
+            if gposes is not None:
+                gposes.zero_()
+            return gx, gposes, grads
+        # the plan again, with the gradients' addresses in it (they are new tensors in every backward)
+        grids = (_lib.Grid * S)()
+        for s, (fs, gs, m) in enumerate(zip(features, grads, metas)):
+            g = _fill_grid(fs, m, grads=gs)
+            C.memmove(C.addressof(grids[s]), C.addressof(g), C.sizeof(_lib.Grid))
+        lib = _lib.load()
+        host = (C.c_char * int(lib.miso_atlas_plan_bytes(S)))()
+        _lib.check(lib.miso_atlas_plan_build(grids, S, C.cast(host, C.c_void_p)), "miso_atlas_plan_build")
+        # (pinned, on the stream: the upload does not wait for the device, and the host does not wait for the upload)
+        plan = torch.frombuffer(host, dtype=torch.uint8).clone().pin_memory().to(dev, non_blocking=True)
+        m, packed = pack.get()
+        if m is None:
+            raise RuntimeError("decoder shape is not covered by the fused kernels")
+        ws = None
+        if need_poses:
+            ws = torch.empty(int(lib.miso_atlas_bwd_workspace_bytes(n, S)) // 4, device=dev, dtype=torch.float32)
+        flags = _lib.F_EXACT_F32 if exact else 0
+        _lib.check(lib.miso_atlas_sdf_bwd(
+            _ptr(plan), S, C.byref(_fill_grid(features[0], metas[0])), _ptr(poses), C.byref(m), _ptr(packed), _ptr(x), n,
+            _ptr(gsdf), _ptr(gx), _ptr(gposes), _ptr(ws), flags, _stream(poses)), "miso_atlas_sdf_bwd")
+        return gx, gposes, grads
+
     def trace(self, features, metas, poses, pack: "DecoderPack", origins, dirs, *, min_dist, max_dist, max_iters,
               epsilon, no_bound=False, want_sdf=False, want_steps=False, grad_step=None):
         """utils_sdf.sphere_tracing (reference grid_opt/utils/utils_sdf.py:197-236) over this atlas in ONE launch
@@ -1095,6 +1155,44 @@ class AtlasQuery:
             0.0 if grad_step is None else float(grad_step), _ptr(points), _ptr(mask), _ptr(extras.get('sdf')),
             _ptr(extras.get('steps')), _ptr(extras.get('grad')), flags, _stream(poses)), "miso_atlas_sphere_trace")
         return points, mask, extras
+
+
+ATLAS_BWD_MAX_SUBMAPS = _lib.ATLAS_BWD_MAX_SUBMAPS      # submaps whose pose gradient one miso_atlas_sdf_bwd call forms
+
+
+class _AtlasSdf(torch.autograd.Function):
+    """AtlasQuery.differentiable: forward miso_atlas_sdf_fwd, backward miso_atlas_sdf_bwd (which runs the forward again: only
+    the inputs are saved).  The decoder arithmetic of the forward call is the backward's too."""
+
+    @staticmethod
+    def forward(ctx, query, metas, pack, levels, x, poses, *flat):
+        feats, i = [], 0
+        for n_l in levels:
+            feats.append([f.detach() for f in flat[i:i + n_l]])
+            i += n_l
+        xd, pd = x.detach().contiguous(), poses.detach().contiguous()
+        if xd.shape[0] == 0:
+            sdf = torch.empty((0, 1), device=pd.device, dtype=torch.float32)
+        else:
+            sdf, _ = query(feats, list(metas), pd, pack, x=xd)
+        ctx.query, ctx.metas, ctx.pack, ctx.levels, ctx.exact = query, metas, pack, levels, _EXACT_F32
+        ctx.save_for_backward(xd, pd, *flat)
+        return sdf
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gsdf):
+        xd, pd, *flat = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        feats, need_f, i = [], [], 0
+        for n_l in ctx.levels:
+            feats.append([f.detach() for f in flat[i:i + n_l]])
+            need_f.append(list(need[6 + i:6 + i + n_l]))
+            i += n_l
+        gx, gposes, grads = ctx.query._backward(feats, list(ctx.metas), pd, ctx.pack, xd,
+                                                gsdf.reshape(-1).to(torch.float32).contiguous(), need[4], need[5],
+                                                need_f, ctx.exact)
+        return (None, None, None, None, gx, gposes, *[g for gs in grads for g in gs])
 
 
 # --------------------------------------------------------------------------- #
