@@ -50,6 +50,11 @@
  *                     feeds the path): get_batch_data / sample_along_rays
  *                     (grid_opt/utils/utils_sample.py:142-302), bounds_ray (sdf_rgbd.py:525-534), the
  *                     per-keyframe world -> keyframe loop (:436-445) and the truncation labels (:447-455).
+ *   miso_voxel_down_sample / miso_voxel_select_rows
+ *                     utils_geometry.voxel_down_sample_torch, grid_opt/utils/utils_geometry.py:292-335, as
+ *                     PosedSdfRgbd.getitem_sdf runs it on the host in every iteration (grid_opt/datasets/
+ *                     sdf_rgbd.py:460-470: .cpu(), unique + scatter_reduce, six indexed gathers) and the LiDAR
+ *                     dataset per loaded frame (grid_opt/datasets/sdf_3d_lidar.py:108-122).
  *
  * This file is also the ONLY statement of the ABI for Python: miso_amd/_lib.py reads its structs, integer constants and
  * prototypes at import and refuses what it cannot read.  Keep the declarations in the style used below: block comments,
@@ -732,6 +737,31 @@ int miso_mapping_loss_rows(int loss_type, float weight_sdf, float weight_fs, flo
 int miso_grid_pool_avg(const float* coords, const float* features, int64_t n, int32_t d, int64_t ld_features,
                        const float* bound_min, float cell_size, int32_t nx, int32_t ny, int32_t nz, float* pooled,
                        int32_t* counts, void* stream);
+
+/* --- voxel down-sampling: one point per occupied voxel ---------------------------------------------------------------
+ * utils_geometry.voxel_down_sample_torch (grid_opt/utils/utils_geometry.py:292-335) with the arithmetic of the reference's
+ * CPU run (where the reference always runs it: grid_opt/datasets/sdf_rgbd.py:460-470), every operation rounded once to fp32:
+ * cell = floor(p / v), dist to the cell centre quantised into 1000 steps relative to the largest dist, ijk = cell -
+ * floor(min p / v), side = float(max ijk), and the reference's fp32 voxel key (ix + iy side) + (iz side) side -- including
+ * that a cell with ix == side shares a key with (0, iy + 1, iz) and that keys above 2^24 merge neighbouring voxels.  Per
+ * distinct key the point with the smallest (quantised dist, index) wins; winners are listed in ascending key order, as
+ * torch.unique orders them.  Same index array as the reference, bit for bit; identical from run to run.
+ *   points (capacity, 3) fp32 with row stride ld >= 3 (elements); n_live (one int32 on the DEVICE, or NULL = capacity):
+ *   rows at or beyond it are never read.  workspace: miso_voxel_down_workspace_bytes(capacity) bytes, 8-byte aligned
+ *   (0 = capacity out of range).  out_idx (capacity) int64: the winners' row indices in [0, out_count), -1 behind them;
+ *   out_count: one int32 on the device.  No host synchronisation, no allocation: the call replays inside a captured graph.
+ *   capacity >= 2^22 -> MISO_E_TOOLARGE (the index field of the 64-bit sort key); capacity == 0 writes out_count = 0.
+ *   Inputs the reference cannot handle either are outside the contract: NaN coordinates, all points on cell centres.
+ * miso_voxel_select_rows applies a selection to a sample table (the buffers of miso_sample_rays): dst row i = src row
+ * out_idx[i] for i < out_count, the neutral row (coordinates 0, id 0, aux = 0: valid = sign = weight = 0) for
+ * out_count <= i < capacity, and live_rows (one int32, device) = out_count.  src and dst must not overlap; both aux
+ * tables 16-B aligned. */
+int64_t miso_voxel_down_workspace_bytes(int64_t capacity);
+int miso_voxel_down_sample(const float* points, int64_t ld, int64_t capacity, const int32_t* n_live, float voxel_size,
+                           void* workspace, int64_t* out_idx, int32_t* out_count, void* stream);
+int miso_voxel_select_rows(const float* src_coords, const int64_t* src_ids, const float* src_aux, const int64_t* out_idx,
+                           const int32_t* out_count, int64_t capacity, float* dst_coords, int64_t* dst_ids, float* dst_aux,
+                           int32_t* live_rows, void* stream);
 
 /* --- fused atlas query: GridAtlas.query_feature / GridAtlas.forward in one launch (round 6) ---------------------------
  * Replaces the per-submap loop of grid_opt/models/grid_atlas.py:374-399 (for each active submap: transfrom_points_from,

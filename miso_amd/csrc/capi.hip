@@ -979,6 +979,36 @@ int miso_grid_pool_avg(const float* coords, const float* features, int64_t n, in
                                    (hipStream_t)stream);
 }
 
+// ---- voxel down-sampling (voxel.hip) -------------------------------------------------------------------------------------
+int64_t miso_voxel_down_workspace_bytes(int64_t capacity) {
+  if (capacity < 0 || capacity >= (int64_t(1) << 22)) return 0;
+  return voxel_down_workspace_bytes(capacity);
+}
+
+int miso_voxel_down_sample(const float* points, int64_t ld, int64_t capacity, const int32_t* n_live, float voxel_size,
+                           void* workspace, int64_t* out_idx, int32_t* out_count, void* stream) {
+  if (capacity < 0 || ld < 3 || !out_count || !(voxel_size > 0.0f) || !(voxel_size < __builtin_huge_valf()))
+    return MISO_E_BADARG;
+  if (capacity >= (int64_t(1) << 22)) return MISO_E_TOOLARGE;      // the index field of the sort key
+  if (capacity == 0) return (int)launch_zero_words(out_count, 1, (hipStream_t)stream);
+  if (!points || !workspace || !out_idx || ((uintptr_t)workspace & 7u)) return MISO_E_BADARG;
+  return (int)launch_voxel_down_sample(points, ld, capacity, n_live, voxel_size, workspace, out_idx, out_count,
+                                       (hipStream_t)stream);
+}
+
+int miso_voxel_select_rows(const float* src_coords, const int64_t* src_ids, const float* src_aux, const int64_t* out_idx,
+                           const int32_t* out_count, int64_t capacity, float* dst_coords, int64_t* dst_ids, float* dst_aux,
+                           int32_t* live_rows, void* stream) {
+  if (capacity < 0 || !out_count || !live_rows) return MISO_E_BADARG;
+  if (capacity >= (int64_t(1) << 22)) return MISO_E_TOOLARGE;
+  if (capacity > 0 && (!src_coords || !src_ids || !src_aux || !out_idx || !dst_coords || !dst_ids || !dst_aux))
+    return MISO_E_BADARG;
+  if ((((uintptr_t)src_aux) | ((uintptr_t)dst_aux)) & 15u) return MISO_E_BADARG;
+  if (capacity > 0 && (src_coords == dst_coords || src_ids == dst_ids || src_aux == dst_aux)) return MISO_E_BADARG;
+  return (int)launch_voxel_select_rows(src_coords, src_ids, src_aux, out_idx, out_count, capacity, dst_coords, dst_ids,
+                                       dst_aux, live_rows, (hipStream_t)stream);
+}
+
 // ---- fused atlas query (atlas.hip) ------------------------------------------------------------------------------------
 int64_t miso_atlas_plan_bytes(int32_t n_submaps) {
   return n_submaps < 1 ? 0 : (int64_t)n_submaps * (int64_t)sizeof(GridK);

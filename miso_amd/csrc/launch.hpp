@@ -148,4 +148,12 @@ hipError_t launch_grid_pool_avg(const float* coords, const float* feat, int64_t 
                                 const float* bmin, float cell, int32_t nx, int32_t ny, int32_t nz, float* acc,
                                 int32_t* cnt, hipStream_t s);
 
+// ---- voxel.hip
+int64_t voxel_down_workspace_bytes(int64_t capacity);
+hipError_t launch_voxel_down_sample(const float* points, int64_t ld, int64_t capacity, const int32_t* n_live, float voxel_size,
+                                    void* workspace, int64_t* out_idx, int32_t* out_count, hipStream_t s);
+hipError_t launch_voxel_select_rows(const float* src_coords, const int64_t* src_ids, const float* src_aux,
+                                    const int64_t* out_idx, const int32_t* out_count, int64_t capacity, float* dst_coords,
+                                    int64_t* dst_ids, float* dst_aux, int32_t* live_rows, hipStream_t s);
+
 }  // namespace miso

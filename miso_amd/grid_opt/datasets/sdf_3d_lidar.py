@@ -6,8 +6,9 @@ iteration, draws a subset per frame with ``np.random.choice`` and concatenates f
 ``[x y z | sdf valid sign weight]`` plus frame offsets, built with batched device ops, and a batch is one random
 key sort plus one row gather -- no per-frame loop, nothing on the host.
 
-Point-cloud files (.pcd / .ply through open3d, :100-102) and their voxel down-sampling are storage concerns
-outside this path: frames enter through ``from_frames`` as sensor-frame point arrays.
+Point-cloud files (.pcd / .ply through open3d, :100-102) are a storage concern outside this path: frames enter through
+``from_frames`` as sensor-frame point arrays.  The reference's per-frame (adaptive) voxel down-sampling (:108-133) is
+``from_frames(voxel_size=..., adaptive_range=...)``: the selection runs as the HIP operator when ``device`` is a GPU.
 """
 import logging
 
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 from miso_amd.grid_opt.datasets.submap_dataset import SubmapDataset
-from miso_amd.grid_opt.utils.utils_geometry import pose_matrix
+from miso_amd.grid_opt.utils.utils_geometry import pose_matrix, voxel_down_sample_torch
 
 logger = logging.getLogger(__name__)
 
@@ -36,9 +37,12 @@ class PosedSdf3DLidar(SubmapDataset):
     def from_frames(cls, points_local, poses_gt, poses_init=None, frame_batchsize=2 ** 10, frame_samples=2 ** 10,
                     near_surface_n=4, near_surface_std=0.1, free_space_n=2, behind_surface_n=1, trunc_dist=0.50,
                     distance_std=0., min_dist_ratio=0.30, min_z=-3.0, max_z=60.0, min_range=1.5, max_range=60.0,
-                    crop=True, device='cuda:0', generator=None, draws=None):
+                    crop=True, device='cuda:0', generator=None, draws=None, voxel_size=None, adaptive_range=False):
         """points_local: list of (n_f,3) sensor-frame clouds; poses_*: (F,4,4) world poses.  ``draws`` (tests):
-        per frame a dict {perm, g_near, u_free, u_behind} replacing the random draws of sample_frames."""
+        per frame a dict {perm, g_near, u_free, u_behind} replacing the random draws of sample_frames.
+        ``voxel_size``: every frame is voxel-down-sampled as the reference loads it (:108-133) -- with
+        ``adaptive_range`` the crop range shrinks to twice the frame's smaller x / y half-extent and the voxel size
+        with it -- and then cropped with that range; None (default): frames are taken as they come."""
         self = cls.__new__(cls)
         SubmapDataset.__init__(self)
         self.frame_batchsize, self.frame_samples = frame_batchsize, frame_samples
@@ -47,7 +51,7 @@ class PosedSdf3DLidar(SubmapDataset):
         self.trunc_dist, self.distance_std, self.min_dist_ratio = trunc_dist, distance_std, min_dist_ratio
         self.max_range_hehind_surface = 4 * near_surface_std
         self.min_z, self.max_z, self.min_range, self.max_range = min_z, max_z, min_range, max_range
-        self.device = device
+        self.device, self.voxel_size, self.adaptive_range = device, voxel_size, adaptive_range
         if distance_std > 1e-12:
             raise ValueError("Noise on surface points not implemented yet.")
         poses_gt = torch.as_tensor(np.asarray(poses_gt), dtype=torch.float32)
@@ -60,14 +64,32 @@ class PosedSdf3DLidar(SubmapDataset):
         self.frames_lidar = []
         for f, pts in enumerate(points_local):
             pts = torch.as_tensor(np.asarray(pts), dtype=torch.float32)
+            frame_max_range = max_range
+            if voxel_size is not None and pts.shape[0] > 0:
+                pts, frame_max_range = self._voxel_down_frame(pts)
             if crop:
-                pts, _ = crop_points(pts, None, min_z, max_z, min_range, max_range)
+                pts, _ = crop_points(pts, None, min_z, max_z, min_range, frame_max_range)
             glob = pts.double() @ self.R_world_frame_gt[f].double().T + self.t_world_frame_gt[f].double().T
             self.frames_lidar.append({"points_local": pts, "points_global": glob})
         self._selected_kfs = None
         self._plan = {}
         self.sample_frames(generator=generator, draws=draws)
         return self
+
+    def _voxel_down_frame(self, pts):
+        """Reference :108-122 for one sensor-frame cloud: -> (down-sampled points, this frame's crop range).  The
+        selection runs where the dataset lives (on a GPU: miso_voxel_down_sample); the scalars are the reference's
+        fp32 expressions."""
+        dev_pts = pts.to(self.device)
+        crop_max_range = self.max_range
+        if self.adaptive_range:
+            hi, lo = dev_pts.max(dim=0)[0].cpu(), dev_pts.min(dim=0)[0].cpu()
+            min_x_range = min(torch.abs(hi[0]), torch.abs(lo[0]))
+            min_y_range = min(torch.abs(hi[1]), torch.abs(lo[1]))
+            crop_max_range = min(self.max_range, 2.0 * max(min_x_range, min_y_range))
+        adapt_voxel = float((crop_max_range / self.max_range) * self.voxel_size)
+        keep = voxel_down_sample_torch(dev_pts, adapt_voxel)
+        return dev_pts[keep].cpu(), float(crop_max_range)
 
     @property
     def num_kfs(self):

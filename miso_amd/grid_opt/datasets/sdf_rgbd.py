@@ -106,9 +106,10 @@ class PosedSdfRgbd(SubmapDataset):
 
     def _configure(self, cam_params, min_depth, max_depth, voxel_size, n_rays, dist_behind_surf, n_strat_samples,
                    n_surf_samples, trunc_dist, device):
-        if voxel_size is not None:
-            raise NotImplementedError("per-iteration voxel down-sampling (reference :462-470, a host round trip "
-                                      "the reference itself marks FIXME) is not part of the device path")
+        if voxel_size is not None and torch.device(device).type != 'cuda':
+            raise NotImplementedError("per-iteration voxel down-sampling (reference :462-470) runs as a HIP operator "
+                                      "(ops.voxel_down_sample): the dataset has to live on a GPU, nothing falls back "
+                                      "to CPU compute")
         self._cam_params = cam_params
         self.min_depth, self.max_depth, self.voxel_size = min_depth, max_depth, voxel_size
         self.n_rays, self.dist_behind_surf = n_rays, dist_behind_surf
@@ -117,6 +118,7 @@ class PosedSdfRgbd(SubmapDataset):
         self.device, self.use_clip = device, False
         self._selected_kfs = None
         self._frame_cache = {}
+        self._voxel_bufs = None     # (selection idx, count) of the current capacity
         self.dirs_C = None    # built on demand: the sampler derives directions from the intrinsics itself
 
     def _install_frames(self, depth, R_gt, t_gt, R_est=None, t_est=None, normals=None):
@@ -213,12 +215,25 @@ class PosedSdfRgbd(SubmapDataset):
         return {"pc": b.pc_world[:rays * b.S].reshape(rays, b.S, 3), "z_vals": b.z_vals[:rays * b.S].reshape(rays, b.S),
                 "depth_batch": self._selected_frames()[0]}
 
+    def _voxel_down(self, b: ops.RayBatch) -> ops.RayBatch:
+        """One sample per occupied voxel of ``coords_frame`` (keyframe-frame coordinates, live rows only), the
+        reference's selection (:460-470) without its host round trip: miso_voxel_down_sample + one row gather, the live
+        count stays on the device."""
+        bufs = self._voxel_bufs
+        if bufs is None or bufs[0].numel() != b.capacity:
+            dev = b.aux.device
+            bufs = self._voxel_bufs = (torch.empty(b.capacity, device=dev, dtype=torch.int64),
+                                       torch.empty(1, device=dev, dtype=torch.int32))
+        ops.voxel_down_sample(b.coords_frame, self.voxel_size, n_live=b.live_rows, out=bufs)
+        return b.select(*bufs)      # a fresh batch, like the sampler's: an earlier item stays what it was
+
     def getitem_sdf(self, index, draws=None):
         """Exact-size rows like the reference (one read-back of the row count), or with ``padded=True`` the whole
         fixed-capacity batch plus ``input_dict['live_rows']`` (int32 on the device): dropped rays leave neutral
         rows at the tail, nothing is read back and the batch shape never changes, so the trainer replays one
-        captured step."""
-        b = self.sample_batch(draws=draws)
+        captured step.  With a ``voxel_size`` the rows are voxel-down-sampled first (``_voxel_down``), in both forms."""
+        b = self._voxel_down(self.sample_batch(draws=draws)) if self.voxel_size is not None \
+            else self.sample_batch(draws=draws)
         if self.padded:
             aux = b.aux
             input_dict = {'coords_frame': b.coords_frame, 'sample_frame_ids': b.sample_frame_ids[:, None],

@@ -159,7 +159,19 @@ def aabb_torch(points: torch.Tensor, buffer: float = 0.0):
 def voxel_down_sample_torch(points: torch.Tensor, voxel_size: float):
     """Indices of one point per occupied voxel: the one closest to the voxel centre after quantising the distance
     into 1000 steps, ties to the lowest index (reference :292-335, incl. its float voxel key).  Returned in the
-    order of the sorted voxel keys."""
+    order of the sorted voxel keys.  A cloud on the HIP device goes through miso_voxel_down_sample, which returns
+    what this function returns on the CPU (where the reference always runs it) -- not what the torch ops below give
+    on a GPU, where ``tensor / scalar`` is a multiply by the reciprocal; one read-back of the count."""
+    if points.is_cuda:
+        from miso_amd import ops
+        idx, count = ops.voxel_down_sample(points.detach().to(torch.float32), voxel_size)
+        return idx[:int(count.item())]
+    return voxel_down_sample_torch_ops(points, voxel_size)
+
+
+def voxel_down_sample_torch_ops(points: torch.Tensor, voxel_size: float):
+    """voxel_down_sample_torch as tensor ops on whatever device ``points`` is on (the CPU path of the function above;
+    tools/bench_voxel_down.py also times it on the GPU)."""
     steps = 1000
     cell = torch.floor(points / voxel_size)
     dist = ((points - (cell + 0.5) * voxel_size) ** 2).sum(dim=1) ** 0.5

@@ -65,7 +65,8 @@ def create_scannet_dataset(scannet_root: str, scene_id: str, trunc_dist: float =
                            n_rays: int = 200, n_surf_samples: int = 8, n_strat_samples: int = 19,
                            voxel_size: float = None, device='cuda:0', padded=False) -> PosedSdfRgbd:
     """Reference :85-113, same defaults.  ``device`` / ``padded`` are additions (the frames live on the device;
-    padded batches let the trainer replay one captured step, see PosedSdfRgbd)."""
+    padded batches let the trainer replay one captured step, see PosedSdfRgbd).  ``voxel_size`` (the ScanNet demo maps with
+    0.01 and tracks with 0.05) down-samples every batch on the device (ops.voxel_down_sample); it needs a GPU ``device``."""
     scene_name = f"scene{scene_id}"
     scene_file = join(scannet_root, scene_name, f"{scene_name}.txt")
     info = get_scannet_metadata(scene_file)

@@ -990,6 +990,43 @@ def grid_pool_avg(coords, features, bound_min, cell_size: float, dims):
     return out
 
 
+VOXEL_MAX_ROWS = (1 << 22) - 1      # the index field of miso_voxel_down_sample's sort key
+_voxel_ws = {}                      # (device index, capacity) -> workspace
+
+
+def voxel_down_sample(points, voxel_size: float, n_live: Optional[torch.Tensor] = None, out=None):
+    """utils_geometry.voxel_down_sample_torch on the device (miso_voxel_down_sample), the index array of the reference's
+    CPU run bit for bit.  points (capacity, 3) fp32; ``n_live`` (1,) int32 on the device: rows at or beyond it are not
+    read.  -> (idx, count): ``idx`` (capacity,) int64 whose first ``count`` entries are the selection in voxel-key order
+    (-1 behind them), ``count`` (1,) int32 on the device.  ``out`` = (idx, count) reuses buffers.  Nothing is read back
+    and, once the workspace of this capacity exists, nothing is allocated: the call replays inside a captured graph."""
+    _require_hip(points)
+    assert points.ndim == 2 and points.shape[1] == 3, "voxel_down_sample takes an (N, 3) cloud"
+    points = points.detach()
+    cap = int(points.shape[0])
+    if cap <= 1 or points.stride(1) != 1 or points.stride(0) < 3:       # a row-strided view is read in place
+        points = points.contiguous()
+    dev = points.device
+    if n_live is not None and not (n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() >= 1):
+        raise RuntimeError("n_live must be an int32 tensor on the HIP device")
+    if out is None:
+        out = (torch.empty(cap, device=dev, dtype=torch.int64), torch.empty(1, device=dev, dtype=torch.int32))
+    idx, count = out
+    assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() >= cap
+    assert count.is_cuda and count.dtype == torch.int32 and count.numel() >= 1
+    lib = _lib.load()
+    ws = None
+    if 0 < cap <= VOXEL_MAX_ROWS:
+        key = (dev.index if dev.index is not None else torch.cuda.current_device(), cap)
+        ws = _voxel_ws.get(key)
+        if ws is None:
+            ws = _voxel_ws[key] = torch.empty(int(lib.miso_voxel_down_workspace_bytes(cap)), device=dev, dtype=torch.uint8)
+    _lib.check(lib.miso_voxel_down_sample(_ptr(points), points.stride(0) if cap > 1 else 3, cap, _ptr(n_live),
+                                          float(voxel_size), _ptr(ws), _ptr(idx), _ptr(count), _stream(points)),
+               "miso_voxel_down_sample")
+    return idx, count
+
+
 # --------------------------------------------------------------------------- #
 # fused atlas query (GridAtlas.query_feature / forward in one launch)
 # --------------------------------------------------------------------------- #
@@ -1936,6 +1973,21 @@ class RayBatch:
 
     def rows(self) -> int:
         return int(self.counts[2].item())
+
+    def select(self, idx: torch.Tensor, count: torch.Tensor, out: Optional["RayBatch"] = None) -> "RayBatch":
+        """The rows ``idx[:count]`` of this batch, in that order, as a batch of the same capacity: neutral rows
+        (coordinates 0, id 0, aux 0) behind them and ``live_rows = count`` (miso_voxel_select_rows).  ``idx`` (capacity,)
+        int64 and ``count`` (1,) int32 on the device, as voxel_down_sample returns them; nothing is read back."""
+        if out is None:
+            out = RayBatch(self.n_rays, self.S, self.aux.device)
+        assert out is not self and out.capacity == self.capacity
+        assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() >= self.capacity
+        assert count.is_cuda and count.dtype == torch.int32 and count.numel() >= 1
+        _lib.check(_lib.load().miso_voxel_select_rows(
+            _ptr(self.coords_frame), _ptr(self.sample_frame_ids), _ptr(self.aux), _ptr(idx), _ptr(count), self.capacity,
+            _ptr(out.coords_frame), _ptr(out.sample_frame_ids), _ptr(out.aux), _ptr(out.live_rows), _stream(self.aux)),
+            "miso_voxel_select_rows")
+        return out
 
 
 class RaySampler:

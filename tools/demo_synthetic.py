@@ -214,6 +214,8 @@ def main():
     ap.add_argument('--quick', action='store_true', help='small images, few iterations (the GPU test)')
     ap.add_argument('--render', type=str, default=None, metavar='DIR',
                     help='write depth and normal images of the aligned atlas from the first and last keyframe to DIR')
+    ap.add_argument('--voxel_size', type=float, default=None,
+                    help='voxel down-sample every batch of the dataset (the ScanNet demo maps with 0.01); default: off')
     args = ap.parse_args()
     if args.quick:
         H, W, n_kf, args.submap_size, n_rays = 60, 80, 12, 4, 120
@@ -229,7 +231,8 @@ def main():
     cam = CameraParameters(fx=0.9 * W, fy=0.9 * W, cx=(W - 1) / 2, cy=(H - 1) / 2, H=H, W=W)
     depth, R_gt, t_gt = synthetic_sequence(n_kf, cam)
     dataset = PosedSdfRgbd.from_frames(depth, R_gt, t_gt, cam, n_rays=n_rays, n_surf_samples=8, n_strat_samples=19,
-                                       trunc_dist=0.15, min_depth=0.07, max_depth=12.0, device=args.device)
+                                       trunc_dist=0.15, min_depth=0.07, max_depth=12.0, device=args.device,
+                                       voxel_size=args.voxel_size)
     # ---------------------------------------------------------------- build_submaps.main_scannet
     model_path = join(args.save_dir, 'grid_atlas.pth')
     cfg, grid_atlas = initialize(args, dataset)
