@@ -138,7 +138,19 @@ def load():
     return lib
 
 
+class MisoError(RuntimeError):
+    """A call of the library came back with ``code`` (a MISO_E_* value or a hipError_t); ``what``: the entry's name."""
+
+    def __init__(self, message, code, what):
+        super().__init__(message)
+        self.code, self.what = code, what
+
+
+class NotCovered(MisoError):
+    """MISO_E_UNSUPPORTED, before any launch: what a caller with another path for the shape catches, and nothing else."""
+
+
 def check(rc: int, what: str):
     if rc != 0:
         msg = load().miso_error_string(rc).decode()
-        raise RuntimeError(f"{what} failed: {msg} (code {rc})")
+        raise (NotCovered if rc == E_UNSUPPORTED else MisoError)(f"{what} failed: {msg} (code {rc})", rc, what)

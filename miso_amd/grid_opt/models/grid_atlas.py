@@ -295,14 +295,22 @@ class GridAtlas(BaseNet):
                 return None
         feats = [[g.feature for g in sm.features] for sm in subs]
         metas = [sm.features[0].grid_meta() for sm in subs]
-        ekey = (id(pack), tuple(f.data_ptr() for fs in feats for f in fs))
-        if self.__dict__.get('_atlas_eligible', (None, False))[0] != ekey:
-            ok = all(ops.sdf_fused_supported(f, m, pack) if pack is not None else (f[0].shape[1] % 4 == 0)
-                     for f, m in zip(feats, metas)) and len({(len(f), f[0].shape[1]) for f in feats}) == 1
-            self.__dict__['_atlas_eligible'] = (ekey, ok)
-        if not self.__dict__['_atlas_eligible'][1]:
-            return None
-        return feats, metas, pack
+        # decided once per set of feature tensors, per (decoder, kind of query); _fused_refused writes into the same record
+        ptrs = tuple(f.data_ptr() for fs in feats for f in fs)
+        memo = self.__dict__.get('_atlas_eligible')
+        if memo is None or memo[0] != ptrs:
+            memo = self.__dict__['_atlas_eligible'] = (ptrs, {})
+        ok = memo[1].get((id(pack), want_sdf))
+        if ok is None:
+            ok = memo[1][(id(pack), want_sdf)] = all(
+                ops.sdf_fused_supported(f, m, pack) if pack is not None else (f[0].shape[1] % 4 == 0)
+                for f, m in zip(feats, metas)) and len({(len(f), f[0].shape[1]) for f in feats}) == 1
+        return (feats, metas, pack) if ok else None
+
+    def _fused_refused(self, pack, want_sdf=True):
+        """A launch answered ops.NotCovered -- a shape _fused_eligible's test lets through and the kernel table does not
+        hold: remembered, so that the next query of these feature tensors goes to the loop without building a plan."""
+        self.__dict__['_atlas_eligible'][1][(id(pack), want_sdf)] = False
 
     def _pose_table(self, device):
         """(S,12) rows {R_submap_world row-major, t_submap_world} of the active submaps, as the atlas kernels read them;
@@ -353,10 +361,8 @@ class GridAtlas(BaseNet):
         q, feats, metas, poses, pack = got
         try:
             return q(feats, metas, poses, pack, x=x_world, axes=axes, want_sdf=want_sdf, want_feats=want_feats)
-        except RuntimeError as e:              # a shape outside the kernel table: the loop serves it
-            if "not covered" in str(e):
-                return None
-            raise
+        except ops.NotCovered:                 # a shape outside the kernel table: the loop serves it, from now on
+            return self._fused_refused(pack, want_sdf)
 
     def _fused_differentiable(self, x_world: Tensor):
         """forward() under autograd through ops.AtlasQuery.differentiable (one launch forward, one backward: gradients
@@ -373,7 +379,7 @@ class GridAtlas(BaseNet):
             return None
         feats, metas, pack = got
         # the backward has nothing to fall back to: ask now whether it will be served (once per set of feature tensors)
-        bkey = (self.__dict__['_atlas_eligible'][0], len(feats))
+        bkey = (self.__dict__['_atlas_eligible'][0], id(pack), len(feats))
         if self.__dict__.get('_atlas_bwd_ok', (None, False))[0] != bkey:
             self.__dict__['_atlas_bwd_ok'] = (bkey, ops.AtlasQuery.backward_supported(feats, metas, pack))
         if not self.__dict__['_atlas_bwd_ok'][1]:
@@ -381,10 +387,8 @@ class GridAtlas(BaseNet):
         q = self.__dict__.setdefault('_atlas_query', ops.AtlasQuery())
         try:
             return q.differentiable(feats, metas, self._pose_table(x_world.device), pack, x_world)
-        except RuntimeError as e:              # a shape outside the kernel table: the loop serves it
-            if "not covered" in str(e):
-                return None
-            raise
+        except ops.NotCovered:                 # a shape outside the kernel table: the loop serves it, from now on
+            return self._fused_refused(pack)
 
     def sphere_trace(self, origins: Tensor, directions: Tensor, min_dist=1e-3, max_dist=5e1, max_iters=100,
                      epsilon=1e-5, **extras):
@@ -401,10 +405,8 @@ class GridAtlas(BaseNet):
         try:
             return q.trace(feats, metas, poses, pack, origins, utils.normalize_last_dim(directions), min_dist=min_dist,
                            max_dist=max_dist, max_iters=max_iters, epsilon=epsilon, **extras)
-        except RuntimeError as e:
-            if "not covered" in str(e):
-                return None
-            raise
+        except ops.NotCovered:
+            return self._fused_refused(pack)
 
     def sdf_on_lattice(self, xs: Tensor, ys: Tensor, zs: Tensor):
         """forward() on the meshgrid(xs, ys, zs, indexing='ij') lattice as an (nx, ny, nz) volume, the points generated

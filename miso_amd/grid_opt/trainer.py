@@ -91,7 +91,10 @@ class _FastMappingPlan:
 
                                sort=prev_step.sorted is not None, share_grads=prev_step.grads,
                                adam_device=dev, adam_state=adam_state)
-        except (ValueError, RuntimeError, AssertionError) as exc:
+        # what the two constructors raise on purpose: ops.NotCovered -- MappingStep, a (grid, decoder) shape outside the
+        # fused kernels -- and ValueError -- AdamDeviceStep, betas whose step-scalar table would not end; _fill_grid, more
+        # levels than the library takes.  Their asserts guard arguments this function forms itself: none is caught.
+        except (ops.NotCovered, ValueError) as exc:
             logger.info(f"fast captured step not built ({type(exc).__name__}: {exc})")
             return None
         self = cls()

@@ -13,14 +13,18 @@ device and the library must be built, otherwise the call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 from dataclasses import dataclass
-from typing import List, Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
 from . import _lib
+from ._lib import MisoError, NotCovered      # noqa: F401  (what a call of the library raises; NotCovered: fall back)
+
+_LOSS_TYPES = {"L1": 1, "L2": 2}
 
 
 @dataclass(frozen=True)
@@ -60,19 +64,14 @@ def set_exact_fp32(on: bool) -> bool:
     return prev
 
 
-class exact_fp32:
+@contextlib.contextmanager
+def exact_fp32(on: bool = True):
     """with ops.exact_fp32(): ... -- the exact fp32 decoder chains inside the block."""
-
-    def __init__(self, on: bool = True):
-        self.on = on
-
-    def __enter__(self):
-        self.prev = set_exact_fp32(self.on)
-        return self
-
-    def __exit__(self, *exc):
-        set_exact_fp32(self.prev)
-        return False
+    prev = set_exact_fp32(on)
+    try:
+        yield
+    finally:
+        set_exact_fp32(prev)
 
 
 def _require_hip(*tensors):
@@ -96,6 +95,15 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _grid_header(meta: GridMeta) -> _lib.Grid:
+    """A Grid with the bound and the flags of ``meta`` and no level yet (the process-wide _EXACT_F32 is _fill_grid's)."""
+    g = _lib.Grid()
+    g.flags = meta.flags
+    g.bound_min[:] = meta.bound_min
+    g.bound_max[:] = meta.bound_max
+    return g
+
+
 def _fill_grid(features: Sequence[torch.Tensor], meta: GridMeta,
                grads: Optional[Sequence[Optional[torch.Tensor]]] = None,
                data: bool = True, touched: Optional[Sequence[Optional[torch.Tensor]]] = None) -> _lib.Grid:
@@ -103,13 +111,11 @@ def _fill_grid(features: Sequence[torch.Tensor], meta: GridMeta,
     non-zero into ``grads[l]`` (miso_level_t.grad_touched) -- the gradient must then be a dense storage."""
     if not 1 <= len(features) <= _lib.MAX_LEVELS:
         raise ValueError(f"1..{_lib.MAX_LEVELS} levels supported, got {len(features)}")
-    g = _lib.Grid()
+    g = _grid_header(meta)
     g.n_levels = len(features)
     g.ignore_mask = meta.ignore_mask
-    g.flags = meta.flags | (_lib.F_EXACT_F32 if _EXACT_F32 else 0)
-    for a in range(3):
-        g.bound_min[a] = meta.bound_min[a]
-        g.bound_max[a] = meta.bound_max[a]
+    if _EXACT_F32:
+        g.flags |= _lib.F_EXACT_F32
     for l, f in enumerate(features):
         assert f.ndim == 5 and f.shape[0] == 1, f"feature must be (1,C,Z,Y,X), got {tuple(f.shape)}"
         lv = g.level[l]
@@ -124,11 +130,6 @@ def _fill_grid(features: Sequence[torch.Tensor], meta: GridMeta,
                 assert gr.is_contiguous() or gr.is_contiguous(memory_format=torch.channels_last_3d), \
                     "touched flags index the gradient's dense storage"
                 lv.grad_touched = tc.data_ptr()
-            else:
-                lv.grad_touched = 0
-        else:
-            lv.grad = 0
-            lv.grad_touched = 0
         lv.C, lv.Z, lv.Y, lv.X = f.shape[1], f.shape[2], f.shape[3], f.shape[4]
         lv.sC, lv.sZ, lv.sY, lv.sX = f.stride(1), f.stride(2), f.stride(3), f.stride(4)
     return g
@@ -178,6 +179,23 @@ def encode_pull_applies(n: int, meta: GridMeta) -> bool:
             and not meta.flags & (_lib.F_ALIGN_CORNERS | _lib.F_PAD_BORDER))
 
 
+def _pull_split(x, features, meta: GridMeta, gout, want: Sequence[bool], sorted_batch):
+    """The pull / scatter split of an encode backward over the rows ``gout``: -> (bit mask of the levels in ``want`` that
+    the owner-computes pull forms, their uninitialised gradient buffers -- None for every other level -- and the binned
+    batch, sorted here if nobody has).  Mask 0: encode_pull_applies says no (the library's plan owns nothing under
+    align_corners / border padding either), the rows are not float4-aligned, or no level's bricks fit."""
+    pulled = 0
+    if any(want) and encode_pull_applies(x.shape[0], meta) and gout.stride(0) % 4 == 0 and gout.data_ptr() % 16 == 0:
+        cand = [torch.empty_like(f) if w else None for f, w in zip(features, want)]
+        pulled = int(_lib.load().miso_grad_pull_levels(C.byref(_fill_grid(features, meta, cand, data=False)),
+                                                       SortedBatch.TILES))
+    if not pulled:
+        return 0, [None] * len(features), sorted_batch
+    if sorted_batch is None:
+        sorted_batch = SortedBatch(x.shape[0], x.device).sort(x, meta)
+    return pulled, [c if (pulled >> l) & 1 else None for l, c in enumerate(cand)], sorted_batch
+
+
 def encode_bwd_raw(x, features, meta: GridMeta, gout, need_x: bool, need_f: Sequence[bool],
                    sorted_batch: Optional["SortedBatch"] = None):
     """sorted_batch: the SortedBatch of the forward, if it binned the batch (saves the sort)."""
@@ -186,19 +204,9 @@ def encode_bwd_raw(x, features, meta: GridMeta, gout, need_x: bool, need_f: Sequ
     gout = _rows(gout)
     n = x.shape[0]
     lib = _lib.load()
-    pulled = 0
-    grads: List[Optional[torch.Tensor]] = [None] * len(features)
-    if (ENCODE_PULL_MIN_POINTS is not None and n >= ENCODE_PULL_MIN_POINTS and any(need_f)
-            and gout.stride(0) % 4 == 0 and gout.data_ptr() % 16 == 0):
-        want = [torch.empty_like(f) if nf else None for f, nf in zip(features, need_f)]
-        pulled = int(lib.miso_grad_pull_levels(C.byref(_fill_grid(features, meta, want, data=False)),
-                                               SortedBatch.TILES))
-        if pulled:
-            if sorted_batch is None:
-                sorted_batch = SortedBatch(n, x.device).sort(x, meta)
-            mine = [w if (pulled >> l) & 1 else None for l, w in enumerate(want)]
-            grad_pull_raw(features, meta, sorted_batch, gout, mine, overwrite=True, caller_order=True)
-            grads = mine
+    pulled, grads, sorted_batch = _pull_split(x, features, meta, gout, need_f, sorted_batch)
+    if pulled:
+        grad_pull_raw(features, meta, sorted_batch, gout, grads, overwrite=True, caller_order=True)
     rest = [bool(nf) and not (pulled >> l) & 1 for l, nf in enumerate(need_f)]
     gx = None
     if need_x or any(rest):
@@ -228,20 +236,12 @@ def encode_bwd2_raw(x, features, meta: GridMeta, gout, ggx, ggf, need_x: bool, n
     n = x.shape[0]
     F = _feature_dim(features)
     want = [bool(nf) and ggx is not None for nf in need_f]
-    grads: List[Optional[torch.Tensor]] = [None] * len(features)
-    pulled = 0
-    if (any(want) and encode_pull_applies(n, meta) and gout.stride(0) % 4 == 0 and gout.data_ptr() % 16 == 0):
-        cand = [torch.empty_like(f) if w else None for f, w in zip(features, want)]
-        pulled = int(_lib.load().miso_grad_pull_levels(C.byref(_fill_grid(features, meta, cand, data=False)),
-                                                       SortedBatch.TILES))
-        if pulled:
-            sorted_batch = sorted_batch if sorted_batch is not None else SortedBatch(n, x.device).sort(x, meta)
-            mine = [c if (pulled >> l) & 1 else None for l, c in enumerate(cand)]
-            gp = _fill_grid(features, meta, mine, data=False)
-            gp.flags |= _lib.F_GRAD_OVERWRITE
-            _lib.check(_lib.load().miso_grad_pull_dx(C.byref(gp), C.byref(sorted_batch.struct), n, _ptr(gout), gout.stride(0),
-                                                     _ptr(ggx.contiguous()), _stream(x)), "miso_grad_pull_dx")
-            grads = mine
+    pulled, grads, sorted_batch = _pull_split(x, features, meta, gout, want, sorted_batch)
+    if pulled:
+        gp = _fill_grid(features, meta, grads, data=False)
+        gp.flags |= _lib.F_GRAD_OVERWRITE
+        _lib.check(_lib.load().miso_grad_pull_dx(C.byref(gp), C.byref(sorted_batch.struct), n, _ptr(gout), gout.stride(0),
+                                                 _ptr(ggx.contiguous()), _stream(x)), "miso_grad_pull_dx")
     for l, w in enumerate(want):
         if w and not (pulled >> l) & 1:
             grads[l] = torch.zeros_like(features[l])
@@ -401,17 +401,24 @@ class DecoderPack:
             tuple((0, 0) if b is None else (b.data_ptr(), b._version) for b in self.biases)
         if key == self._key:
             return self._mlp, self._packed
-        _require_hip(*self.weights)
         m, keep = self._struct()
+        # (the shape is judged on the host: a decoder the kernels do not cover is refused wherever its tensors live)
+        nf = 0 if m is None else _lib.load().miso_mlp_packed_floats(C.byref(m))
+        if nf:
+            _require_hip(*self.weights)
         self._key, self._mlp, self._packed, self._keep = key, None, None, None
-        if m is None:
-            return None, None
-        nf = _lib.load().miso_mlp_packed_floats(C.byref(m))
         if nf == 0:
             return None, None
         packed = torch.empty(nf, device=self.weights[0].device, dtype=torch.float32)
         _lib.check(_lib.load().miso_mlp_pack(C.byref(m), _ptr(packed), _stream(packed)), "miso_mlp_pack")
         self._mlp, self._packed, self._keep = m, packed, keep
+        return m, packed
+
+    def require(self):
+        """get() for a caller that has no other path: (Mlp struct, packed tensor), or NotCovered."""
+        m, packed = self.get()
+        if m is None:
+            raise NotCovered("decoder shape is not covered by the fused kernels", _lib.E_UNSUPPORTED, "DecoderPack")
         return m, packed
 
     def trainable(self) -> bool:
@@ -516,12 +523,8 @@ class SortedBatch:
         _require_hip(x)
         x = x.contiguous()
         assert x.shape == (self.n, 3)
-        g = _lib.Grid()
+        g = _grid_header(meta)      # (not _fill_grid: the sort has no decoder, _EXACT_F32 is not its business)
         g.n_levels = 1
-        g.flags = meta.flags
-        for a in range(3):
-            g.bound_min[a] = meta.bound_min[a]
-            g.bound_max[a] = meta.bound_max[a]
         lv = g.level[0]
         lv.C = lv.X = lv.Y = lv.Z = 1
         lv.sC = lv.sX = lv.sY = lv.sZ = 1
@@ -535,17 +538,14 @@ def sdf_fwd_raw(x, features, meta, pack: DecoderPack, want_mask: bool, out=None,
                 sorted_batch: Optional[SortedBatch] = None):
     """sorted_batch: a SortedBatch already sorted for these points (x is then ignored)."""
     _require_hip(x, *features)
-    m, packed = pack.get()
-    if m is None:
-        raise RuntimeError("decoder shape is not covered by the fused kernels")
+    m, packed = pack.require()
     x = x.contiguous()
     n = x.shape[0]
     sdf = torch.empty((n, 1), device=x.device, dtype=torch.float32) if out is None else out
-    if want_mask and mask is None:
-        mw = _lib.load().miso_sdf_mask_words(C.byref(m))
-        mask = torch.empty(((n + 63) // 64) * 64 * mw, device=x.device, dtype=torch.int32)
     if not want_mask:
         mask = None
+    elif mask is None:
+        mask = sdf_mask_buffer(pack, n, x.device)
     g = _fill_grid(features, meta)
     if sorted_batch is not None:
         _lib.check(_lib.load().miso_sdf_fwd_sorted(C.byref(g), C.byref(m), _ptr(packed),
@@ -566,7 +566,7 @@ def sdf_bwd_raw(x, features, meta, pack: DecoderPack, gsdf, mask, need_x, need_f
     zeroed (with overwrite): the levels the call adds to with atomics (sdf_bwd_scattered_levels) are zero already --
     the Adam launch that consumed them cleared them -- so the library's fill is skipped (MISO_F_GRAD_ZEROED)."""
     _require_hip(x, gsdf, *features)
-    m, packed = pack.get()
+    m, packed = pack.require()
     x = x.contiguous()
     gsdf = gsdf.contiguous()
     n = x.shape[0]
@@ -601,9 +601,7 @@ def sdf_wgrad_raw(x, features, meta, pack: DecoderPack, gsdf, mask, sorted_batch
     forward (sdf_fwd_raw) over the same points -- with ``sorted_batch`` in the binned order, ``gsdf`` then in the
     caller's order or (gsdf_sorted) the binned one.  Deterministic; the results are written, not accumulated."""
     _require_hip(x, gsdf, *features)
-    m, packed = pack.get()
-    if m is None:
-        raise RuntimeError("decoder shape is not covered by the fused kernels")
+    m, packed = pack.require()
     x = x.contiguous()
     gsdf = gsdf.contiguous()
     n = x.shape[0]
@@ -619,7 +617,7 @@ def sdf_wgrad_raw(x, features, meta, pack: DecoderPack, gsdf, mask, sorted_batch
     lib = _lib.load()
     floats = int(lib.miso_sdf_wgrad_workspace_floats(C.byref(g), C.byref(m), n))
     if floats == 0 and n > 0:
-        raise RuntimeError("decoder / grid shape is not covered by the fused kernels")
+        raise NotCovered("decoder / grid shape is not covered by the fused kernels", _lib.E_UNSUPPORTED, "miso_sdf_wgrad")
     stream = _stream(x)
     ws = pack.wgrad_workspace(floats, stream.value)
     _lib.check(lib.miso_sdf_wgrad(C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _ptr(gsdf), _ptr(mask),
@@ -633,7 +631,7 @@ def sdf_bwd_rows_raw(x, features, meta, pack: DecoderPack, gsdf, mask, need_x, n
     """sdf_bwd_raw (caller-order points) that also returns the d-feat rows (N,F) of the decoder backward
     (miso_sdf_bwd_rows): -> (gx, grads, rows)."""
     _require_hip(x, gsdf, *features)
-    m, packed = pack.get()
+    m, packed = pack.require()
     x = x.contiguous()
     gsdf = gsdf.contiguous()
     n = x.shape[0]
@@ -657,10 +655,19 @@ def sdf_bwd_scattered_levels(features, meta, grads, n: int, tiles=None) -> int:
 
 def sdf_mask_words(pack: DecoderPack) -> int:
     """32-bit words of ReLU sign bits per point slot (miso_sdf_mask_words)."""
-    m, _ = pack.get()
-    if m is None:
-        raise RuntimeError("decoder shape is not covered by the fused kernels")
-    return int(_lib.load().miso_sdf_mask_words(C.byref(m)))
+    return int(_lib.load().miso_sdf_mask_words(C.byref(pack.require()[0])))
+
+
+def sdf_mask_buffer(pack: DecoderPack, n: int, device) -> torch.Tensor:
+    """Room for the ReLU sign bits of n points: sdf_mask_words per point slot, slots in whole blocks of 64."""
+    return torch.empty(((n + 63) // 64) * 64 * sdf_mask_words(pack), device=device, dtype=torch.int32)
+
+
+def _check_loss_args(n: int, loss_inputs, loss_slots, n_live=None):
+    """Label rows (n,4), per-workgroup sums (LOSS_SLOTS,2) and, for a padded batch, the live count: one device int32."""
+    assert loss_inputs.shape == (n, 4) and loss_inputs.is_contiguous()
+    assert loss_slots.is_contiguous() and loss_slots.numel() == _lib.LOSS_SLOTS * 2
+    assert n_live is None or (n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() == 1)
 
 
 def sdf_fwd_loss_raw(features, meta, pack: DecoderPack, sorted_batch: SortedBatch, loss_inputs, mask, gsdf_sorted,
@@ -673,13 +680,10 @@ def sdf_fwd_loss_raw(features, meta, pack: DecoderPack, sorted_batch: SortedBatc
     sdf_out (N,1), caller order, is optional.  n_live: one int32 on the device = live rows of a padded batch
     (the means divide by it instead of N)."""
     _require_hip(loss_inputs, gsdf_sorted, loss_slots, *features)
-    if n_live is not None:
-        assert n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() == 1
-    m, packed = pack.get()
+    m, packed = pack.require()
     n = sorted_batch.n
-    assert loss_inputs.shape == (n, 4) and loss_inputs.is_contiguous()
+    _check_loss_args(n, loss_inputs, loss_slots, n_live)
     assert gsdf_sorted.is_contiguous() and gsdf_sorted.numel() == n
-    assert loss_slots.is_contiguous() and loss_slots.numel() == _lib.LOSS_SLOTS * 2
     g = _fill_grid(features, meta)
     _lib.check(_lib.load().miso_sdf_fwd_sorted_loss(
         C.byref(g), C.byref(m), _ptr(packed), C.byref(sorted_batch.struct), n, _LOSS_TYPES[loss_type],
@@ -724,12 +728,9 @@ def sdf_train_raw(features, meta, pack: DecoderPack, sorted_batch: SortedBatch, 
     atomics -- then the pull / push of the other levels' gradient (overwrite semantics: ``grads`` need no zero-fill).
     Same results as sdf_fwd_loss_raw + sdf_bwd_raw(gsdf_sorted=True, overwrite=True)."""
     _require_hip(loss_inputs, loss_slots, *features)
-    if n_live is not None:
-        assert n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() == 1
-    m, packed = pack.get()
+    m, packed = pack.require()
     n = sorted_batch.n
-    assert loss_inputs.shape == (n, 4) and loss_inputs.is_contiguous()
-    assert loss_slots.is_contiguous() and loss_slots.numel() == _lib.LOSS_SLOTS * 2
+    _check_loss_args(n, loss_inputs, loss_slots, n_live)
     g = _fill_grid(features, meta, grads, touched=touched)
     g.flags |= _lib.F_GRAD_OVERWRITE
     if zeroed:
@@ -747,10 +748,10 @@ def sdf_train_unsorted_raw(x, features, meta, pack: DecoderPack, loss_inputs, lo
     forward + mapping loss + decoder backward + the atomic scatter of every level's gradient, ADDED to ``grads``.
     Same results as sdf_fwd_loss_unsorted_raw + sdf_bwd_raw up to the order of the float atomics."""
     _require_hip(x, loss_inputs, loss_slots, *features)
-    m, packed = pack.get()
+    m, packed = pack.require()
     n = x.shape[0]
-    assert x.is_contiguous() and loss_inputs.shape == (n, 4) and loss_inputs.is_contiguous()
-    assert loss_slots.is_contiguous() and loss_slots.numel() == _lib.LOSS_SLOTS * 2
+    assert x.is_contiguous()
+    _check_loss_args(n, loss_inputs, loss_slots)
     g = _fill_grid(features, meta, grads, touched=touched)
     _lib.check(_lib.load().miso_sdf_train(
         C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _LOSS_TYPES[loss_type], float(weight_sdf), float(weight_fs),
@@ -761,11 +762,10 @@ def sdf_fwd_loss_unsorted_raw(x, features, meta, pack: DecoderPack, loss_inputs,
                               weight_sdf=1.0, weight_fs=0.0, trunc_dist=0.0, sdf_out=None):
     """sdf_fwd_loss_raw for an unbinned (small) batch: everything in the caller's order (miso_sdf_fwd_loss)."""
     _require_hip(x, loss_inputs, gsdf, loss_slots, *features)
-    m, packed = pack.get()
+    m, packed = pack.require()
     n = x.shape[0]
-    assert x.is_contiguous() and loss_inputs.shape == (n, 4) and loss_inputs.is_contiguous()
-    assert gsdf.is_contiguous() and gsdf.numel() == n and loss_slots.is_contiguous()
-    assert loss_slots.numel() == _lib.LOSS_SLOTS * 2
+    _check_loss_args(n, loss_inputs, loss_slots)
+    assert x.is_contiguous() and gsdf.is_contiguous() and gsdf.numel() == n
     g = _fill_grid(features, meta)
     _lib.check(_lib.load().miso_sdf_fwd_loss(
         C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _LOSS_TYPES[loss_type], float(weight_sdf), float(weight_fs),
@@ -796,20 +796,19 @@ _BWD2_TORCH = os.environ.get("MISO_BWD2_TORCH", "0") not in ("", "0")
 # requires grad reads True) -- it would form the grid gradients too, a zero fill and an atomic scatter of every level,
 # to have autograd drop them.  The mirror's own gradient helpers (grid_opt/diff.py, loss_isdf.py, models/encoder.py)
 # wrap their call in coordinate_gradient_only(): inside it a differentiable (create_graph) first backward of encode /
-# sdf_fused skips the grids.
+# sdf_fused skips the grids.  It stays a process-wide switch: the backward of a device node runs on autograd's device
+# thread, so a thread-local set by the caller would not be seen there.
 _ONLY_X = False
 
 
-class coordinate_gradient_only:
-    def __enter__(self):
-        global _ONLY_X
-        self.prev, _ONLY_X = _ONLY_X, True
-        return self
-
-    def __exit__(self, *exc):
-        global _ONLY_X
-        _ONLY_X = self.prev
-        return False
+@contextlib.contextmanager
+def coordinate_gradient_only():
+    global _ONLY_X
+    prev, _ONLY_X = _ONLY_X, True
+    try:
+        yield
+    finally:
+        _ONLY_X = prev
 
 
 def _mlp_torch(feats, weights, biases):
@@ -871,15 +870,18 @@ class _SdfFusedBackward(torch.autograd.Function):
         return (g_gsdf, g_x, None, None, None, None, None, None, *g_f)
 
 
+def _binned_if_training_size(x, meta, grids_take_gradient: bool):
+    """sdf_fused over a training-size batch whose grids take a gradient: the points binned once, for both passes."""
+    if grids_take_gradient and SortedBatch.AUTO_MIN_POINTS is not None and x.shape[0] >= SortedBatch.AUTO_MIN_POINTS:
+        return SortedBatch(x.shape[0], x.device).sort(x, meta)
+    return None
+
+
 class _SdfFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, meta, pack, *features):
         need = any(ctx.needs_input_grad)
-        sb = None
-        if (any(ctx.needs_input_grad[3:]) and SortedBatch.AUTO_MIN_POINTS is not None
-                and x.shape[0] >= SortedBatch.AUTO_MIN_POINTS):
-            # training-size batch: bin the points once, both passes use the binned order
-            sb = SortedBatch(x.shape[0], x.device).sort(x, meta)
+        sb = _binned_if_training_size(x, meta, any(ctx.needs_input_grad[3:]))
         sdf, mask = sdf_fwd_raw(x, features, meta, pack, want_mask=need, sorted_batch=sb)
         ctx.save_for_backward(x, mask, *features)
         ctx.meta, ctx.pack, ctx.sb = meta, pack, sb
@@ -922,10 +924,7 @@ class _SdfFusedTrainable(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, meta, pack, n_feat, *tensors):
         features = tensors[:n_feat]
-        sb = None
-        if (any(ctx.needs_input_grad[4:4 + n_feat]) and SortedBatch.AUTO_MIN_POINTS is not None
-                and x.shape[0] >= SortedBatch.AUTO_MIN_POINTS):
-            sb = SortedBatch(x.shape[0], x.device).sort(x, meta)      # as _SdfFused: both passes use the binned order
+        sb = _binned_if_training_size(x, meta, any(ctx.needs_input_grad[4:4 + n_feat]))
         sdf, mask = sdf_fwd_raw(x, features, meta, pack, want_mask=any(ctx.needs_input_grad), sorted_batch=sb)
         ctx.save_for_backward(x, mask, *tensors)      # (the weights too: an in-place step before backward() is an error)
         ctx.meta, ctx.pack, ctx.sb, ctx.n_feat = meta, pack, sb, n_feat
@@ -1049,25 +1048,36 @@ class AtlasQuery:
             tuple((m.bound_min, m.bound_max, m.flags, m.ignore_mask) for m in metas)
         if key == self._key:
             return
-        S = len(features)
+        self._plan = self._build_plan(features, metas)
+        self._shape = _fill_grid(features[0], metas[0])
+        self._key = key
+
+    @staticmethod
+    def _build_plan(features, metas, grads=None, pinned=False) -> torch.Tensor:
+        """The device-resident table of the S submaps' grids (miso_atlas_plan_build), the addresses of ``grads`` (per submap,
+        per level, or None) in it.  pinned: uploaded from pinned memory on the stream -- neither side waits for the other."""
+        S, lib = len(features), _lib.load()
         grids = (_lib.Grid * S)()
         for s, (fs, m) in enumerate(zip(features, metas)):
             _require_hip(*fs)
-            g = _fill_grid(fs, m)
+            g = _fill_grid(fs, m, grads=None if grads is None else grads[s])
             C.memmove(C.addressof(grids[s]), C.addressof(g), C.sizeof(_lib.Grid))
-        nbytes = int(_lib.load().miso_atlas_plan_bytes(S))
-        host = (C.c_char * nbytes)()
-        _lib.check(_lib.load().miso_atlas_plan_build(grids, S, C.cast(host, C.c_void_p)), "miso_atlas_plan_build")
+        host = (C.c_char * int(lib.miso_atlas_plan_bytes(S)))()
+        _lib.check(lib.miso_atlas_plan_build(grids, S, C.cast(host, C.c_void_p)), "miso_atlas_plan_build")
+        plan = torch.frombuffer(host, dtype=torch.uint8).clone()
         dev = features[0][0].device
-        self._plan = torch.frombuffer(host, dtype=torch.uint8).clone().to(dev)
-        self._shape = _fill_grid(features[0], metas[0])
-        self._key = key
+        return plan.pin_memory().to(dev, non_blocking=True) if pinned else plan.to(dev)
+
+    @staticmethod
+    def _flags(no_bound=False) -> int:
+        return (_lib.F_EXACT_F32 if _EXACT_F32 else 0) | (_lib.F_ATLAS_NO_BOUND if no_bound else 0)
 
     def __call__(self, features, metas, poses, pack: Optional["DecoderPack"], x=None, axes=None, want_sdf=True,
                  want_feats=False, no_bound=False):
         """poses: (S,12) device floats, per submap R_submap_world row-major then t_submap_world.  x: (N,3) world points,
         or axes = (xs, ys, zs) device vectors of a lattice (point (i,j,k) -> index (i ny + j) nz + k).
         -> (sdf (N,1) or None, feats (N,F) or None)."""
+        m, packed = pack.require() if want_sdf else (None, None)
         self._prepare(features, metas)
         S = len(features)
         assert poses.shape == (S, 12) and poses.is_contiguous() and poses.dtype == torch.float32
@@ -1084,16 +1094,10 @@ class AtlasQuery:
         F_ = _feature_dim(features[0])
         sdf = torch.empty((n, 1), device=dev, dtype=torch.float32) if want_sdf else None
         feats = torch.empty((n, F_), device=dev, dtype=torch.float32) if want_feats else None
-        m = packed = None
-        if want_sdf:
-            m, packed = pack.get()
-            if m is None:
-                raise RuntimeError("decoder shape is not covered by the fused kernels")
-        flags = (_lib.F_EXACT_F32 if _EXACT_F32 else 0) | (_lib.F_ATLAS_NO_BOUND if no_bound else 0)
         _lib.check(_lib.load().miso_atlas_sdf_fwd(
             _ptr(self._plan), S, C.byref(self._shape), _ptr(poses), C.byref(m) if m is not None else None, _ptr(packed),
             _ptr(x), n, _ptr(ax[0]), _ptr(ax[1]), _ptr(ax[2]), dims[0], dims[1], dims[2], _ptr(sdf), _ptr(feats), F_,
-            flags, _stream(poses)), "miso_atlas_sdf_fwd")
+            self._flags(no_bound), _stream(poses)), "miso_atlas_sdf_fwd")
         return sdf, feats
 
     def differentiable(self, features, metas, poses, pack: "DecoderPack", x):
@@ -1124,6 +1128,8 @@ class AtlasQuery:
         """-> (gx or None, gposes or None, per submap the list of level gradients / None).  grads: buffers to ADD the
         level gradients into (the layout of the features; None per level: no gradient), instead of new zero-filled ones."""
         S, n, dev = len(features), x.shape[0], poses.device
+        if n > 0:
+            m, packed = pack.require()      # (asked before anything is filled or uploaded)
         if grads is None:
             grads = [[torch.zeros_like(f) if nd else None for f, nd in zip(fs, nds)]
                      for fs, nds in zip(features, need_feats)]
@@ -1134,18 +1140,8 @@ class AtlasQuery:
                 gposes.zero_()
             return gx, gposes, grads
         # the plan again, with the gradients' addresses in it (they are new tensors in every backward)
-        grids = (_lib.Grid * S)()
-        for s, (fs, gs, m) in enumerate(zip(features, grads, metas)):
-            g = _fill_grid(fs, m, grads=gs)
-            C.memmove(C.addressof(grids[s]), C.addressof(g), C.sizeof(_lib.Grid))
+        plan = self._build_plan(features, metas, grads, pinned=True)
         lib = _lib.load()
-        host = (C.c_char * int(lib.miso_atlas_plan_bytes(S)))()
-        _lib.check(lib.miso_atlas_plan_build(grids, S, C.cast(host, C.c_void_p)), "miso_atlas_plan_build")
-        # (pinned, on the stream: the upload does not wait for the device, and the host does not wait for the upload)
-        plan = torch.frombuffer(host, dtype=torch.uint8).clone().pin_memory().to(dev, non_blocking=True)
-        m, packed = pack.get()
-        if m is None:
-            raise RuntimeError("decoder shape is not covered by the fused kernels")
         ws = None
         if need_poses:
             ws = torch.empty(int(lib.miso_atlas_bwd_workspace_bytes(n, S)) // 4, device=dev, dtype=torch.float32)
@@ -1165,15 +1161,13 @@ class AtlasQuery:
         if int(max_iters) < 1:
             raise ValueError(f"max_iters must be at least 1, got {max_iters}")
         _require_hip(origins, dirs, poses)
+        m, packed = pack.require()
         self._prepare(features, metas)
         S = len(features)
         assert poses.shape == (S, 12) and poses.is_contiguous() and poses.dtype == torch.float32
         assert origins.ndim == 2 and origins.shape[1] == 3 and dirs.shape == origins.shape
         origins, dirs = origins.detach().contiguous(), dirs.detach().contiguous()
         n, dev = origins.shape[0], poses.device
-        m, packed = pack.get()
-        if m is None:
-            raise RuntimeError("decoder shape is not covered by the fused kernels")
         points = torch.empty((n, 3), device=dev, dtype=torch.float32)
         mask = torch.empty((n, 1), device=dev, dtype=torch.bool)
         extras = {}
@@ -1185,12 +1179,12 @@ class AtlasQuery:
             extras['grad'] = torch.empty((n, 3), device=dev, dtype=torch.float32)
         if n == 0:          # (an empty tensor has no address to hand over; nothing to launch)
             return points, mask, extras
-        flags = (_lib.F_EXACT_F32 if _EXACT_F32 else 0) | (_lib.F_ATLAS_NO_BOUND if no_bound else 0)
         _lib.check(_lib.load().miso_atlas_sphere_trace(
             _ptr(self._plan), S, C.byref(self._shape), _ptr(poses), C.byref(m), _ptr(packed), _ptr(origins), _ptr(dirs),
             n, float(min_dist), float(max_dist), int(max_iters), float(epsilon),
             0.0 if grad_step is None else float(grad_step), _ptr(points), _ptr(mask), _ptr(extras.get('sdf')),
-            _ptr(extras.get('steps')), _ptr(extras.get('grad')), flags, _stream(poses)), "miso_atlas_sphere_trace")
+            _ptr(extras.get('steps')), _ptr(extras.get('grad')), self._flags(no_bound), _stream(poses)),
+            "miso_atlas_sphere_trace")
         return points, mask, extras
 
 
@@ -1235,12 +1229,21 @@ class _AtlasSdf(torch.autograd.Function):
 # --------------------------------------------------------------------------- #
 # dense Adam
 # --------------------------------------------------------------------------- #
+def _check_adam_state(param, grad, exp_avg, exp_avg_sq, active=None, touched=None):
+    """Gradient and moments in the parameter's layout; a flag byte per ADAM_CHUNK floats; ``touched`` sized as ``active``."""
+    for t in (grad, exp_avg, exp_avg_sq):
+        assert t.shape == param.shape and t.stride() == param.stride(), "Adam state must share the param layout"
+    if active is not None:
+        assert active.dtype == torch.uint8 and active.numel() * _lib.ADAM_CHUNK >= param.numel()
+    if touched is not None:
+        assert touched.dtype == torch.uint8 and touched.numel() == active.numel() and touched.is_contiguous()
+
+
 def adam_dense_(param, grad, exp_avg, exp_avg_sq, step: int, lr: float, beta1: float = 0.9,
                 beta2: float = 0.999, eps: float = 1e-8, zero_grad: bool = False):
     """In-place torch.optim.Adam step (amsgrad=False, weight_decay=0) on one dense tensor."""
     _require_hip(param, grad, exp_avg, exp_avg_sq)
-    for t in (grad, exp_avg, exp_avg_sq):
-        assert t.shape == param.shape and t.stride() == param.stride(), "Adam state must share the param layout"
+    _check_adam_state(param, grad, exp_avg, exp_avg_sq)
     _lib.check(_lib.load().miso_adam_dense(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
                                            param.numel(), lr, beta1, beta2, eps, step, int(zero_grad),
                                            _stream(param)), "miso_adam_dense")
@@ -1261,11 +1264,8 @@ def adam_active_(param, grad, exp_avg, exp_avg_sq, active, step: int, lr: float,
     them instead of the gradient (miso_adam_touched) and clears them -- only valid when nothing but those kernels
     wrote the gradient since the last step."""
     _require_hip(param, grad, exp_avg, exp_avg_sq, guard)
-    for t in (grad, exp_avg, exp_avg_sq):
-        assert t.shape == param.shape and t.stride() == param.stride(), "Adam state must share the param layout"
-    assert active.dtype == torch.uint8 and active.numel() * _lib.ADAM_CHUNK >= param.numel()
+    _check_adam_state(param, grad, exp_avg, exp_avg_sq, active, touched)
     if touched is not None:
-        assert touched.dtype == torch.uint8 and touched.numel() == active.numel() and touched.is_contiguous()
         _lib.check(_lib.load().miso_adam_touched(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(active),
                                                  _ptr(touched), param.numel(), lr, beta1, beta2, eps, step,
                                                  int(zero_grad), _ptr(guard), _stream(param)), "miso_adam_touched")
@@ -1285,11 +1285,7 @@ def adam_tensors(tensors):
         p, g, m, v, act, zero = t7[:6]
         tch = t7[6] if len(t7) > 6 else None
         _require_hip(p, g, m, v)
-        for t in (g, m, v):
-            assert t.shape == p.shape and t.stride() == p.stride(), "Adam state must share the param layout"
-        assert act.dtype == torch.uint8 and act.numel() * _lib.ADAM_CHUNK >= p.numel()
-        if tch is not None:
-            assert tch.dtype == torch.uint8 and tch.numel() == act.numel() and tch.is_contiguous()
+        _check_adam_state(p, g, m, v, act, tch)
         a.param, a.grad, a.exp_avg, a.exp_avg_sq = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
         a.active, a.numel, a.zero_grad = act.data_ptr(), p.numel(), int(bool(zero))
         a.touched = None if tch is None else tch.data_ptr()
@@ -1382,10 +1378,7 @@ class AdamDeviceStep:
                                                   _ptr(self.step), int(zero_grad), _ptr(guard), _stream(param)),
                    "miso_adam_step_dev")
 
-
-    def multi(self, tensors):
-        """adam_tensors(tensors): the argument block of step_multi_."""
-        return adam_tensors(tensors)
+    multi = staticmethod(adam_tensors)      # the argument block of step_multi_
 
     def step_multi_(self, packed, guard=None):
         """step_ for several tensors in one launch (miso_adam_step_dev_multi); ``packed`` from multi()."""
@@ -1437,9 +1430,6 @@ def mapping_batch(R, t, table, frame_ids, coords_frame, target, valid, sign, wei
 # --------------------------------------------------------------------------- #
 # mapping loss (value + gradient w.r.t. the prediction)
 # --------------------------------------------------------------------------- #
-_LOSS_TYPES = {"L1": 1, "L2": 2}
-
-
 def mapping_loss_raw(pred, target, valid, sign, weight, loss_type: str, weight_sdf: float,
                      weight_fs: float, trunc_dist: float, grad_pred=None, loss_out=None, grad_pred_fs=None):
     """miso_loss_regression + miso_loss_free_space (grid_opt/loss.py:594-635, :668-700) and
@@ -1842,13 +1832,12 @@ class LmTrackStep:
     def __init__(self, n: int, device, pack: DecoderPack):
         self.n = int(n)
         f32 = dict(device=device, dtype=torch.float32)
-        mw = sdf_mask_words(pack)
         self.pose = torch.empty(12, **f32)
         self.xw = torch.empty((self.n, 3), **f32)
         self.sdf = torch.empty(self.n, **f32)
         self.grad = torch.empty((self.n, 3), **f32)
         self.ones = torch.ones(self.n, **f32)
-        self.mask = torch.empty(((self.n + 63) // 64) * 64 * mw, device=device, dtype=torch.int32)
+        self.mask = sdf_mask_buffer(pack, self.n, device)
         self.sums = torch.empty(36, **f32)
         self.info = torch.empty(8, **f32)
         self.clean = torch.empty(5 * max(self.n, 1), **f32)       # nan_to_num'ed coords / target / valid (sanitize=True)
@@ -1894,11 +1883,11 @@ class LmTrackStep:
         """-> [|delta_R| rad, |delta_t|, |g|, rows in bound, rows kept, wrong frame ids, invalid rows, 0] (host floats).
         rot_correction / trans_correction: 3-float views of the pose parameters, updated in place.
         sanitize: torch.nan_to_num on the batch first (prepare_batch folded in)."""
+        m, packed = pack.require()
         a = _lib.LmTrack()
         cf = self._fill(a, coords_frame, target, valid, frame_ids, keyframe_id, trunc_dist, R_base, t_base, rot_correction,
                         trans_correction, sanitize)
         a.loss_type, a.gm_scale, a.lm_lambda = {"L2": 2, "GM": 3}[loss_type], float(gm_scale), float(lm_lambda)
-        m, packed = pack.get()
         g = _fill_grid([f.detach() for f in features], meta)
         _lib.check(_lib.load().miso_lm_track_step(C.byref(g), C.byref(m), _ptr(packed), C.byref(a), _stream(cf)),
                    "miso_lm_track_step")
@@ -1930,13 +1919,13 @@ class TrackAdamWindow(LmTrackStep):
     def step(self, features, meta: GridMeta, pack: DecoderPack, coords_frame, target, valid, frame_ids, keyframe_id,
              trunc_dist, R_base, t_base, rot_correction, trans_correction, loss_type: str, weight_sdf: float,
              gm_scale: float, sanitize: bool = False):
+        m, packed = pack.require()
         t = _lib.TrackAdam()
         cf = self._fill(t.s, coords_frame, target, valid, frame_ids, keyframe_id, trunc_dist, R_base, t_base,
                         rot_correction, trans_correction, sanitize)
         t.loss_type, t.weight_sdf, t.gm_scale = {"L1": 1, "L2": 2, "GM": 3}[loss_type], float(weight_sdf), float(gm_scale)
         t.grad_pred, t.adam_table, t.adam_table_len = self.gpred.data_ptr(), self.table.data_ptr(), self.table.shape[0]
         t.state, t.loss_ring, t.ring_len = self.state.data_ptr(), self.ring.data_ptr(), self.ring.shape[0]
-        m, packed = pack.get()
         g = _fill_grid([f.detach() for f in features], meta)
         _lib.check(_lib.load().miso_track_adam_step(C.byref(g), C.byref(m), _ptr(packed), C.byref(t), _stream(cf)),
                    "miso_track_adam_step")

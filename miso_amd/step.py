@@ -62,7 +62,8 @@ class MappingStep:
         self.loss_cfg = (loss_type, float(weight_sdf), float(weight_fs), float(trunc_dist))
         dev = self.features[0].device
         if not ops.sdf_fused_supported(self.features, meta, pack):
-            raise RuntimeError("MappingStep needs a (grid, decoder) shape covered by the fused kernels")
+            raise ops.NotCovered("MappingStep needs a (grid, decoder) shape covered by the fused kernels",
+                                 ops._lib.E_UNSUPPORTED, "MappingStep")
         f32 = dict(device=dev, dtype=torch.float32)
         # static buffers (graph-safe): inputs are copied into these
         self.x = torch.zeros((self.n, 3), **f32)
@@ -95,12 +96,19 @@ class MappingStep:
         # launch is ~5 % slower than the scan (tools/adam_bench.py), and a level sized to the scene ends up there.
         self.touched = [ops.adam_active_flags(f) if nd and f.numel() >= self.TOUCHED_MIN_NUMEL else None
                         for f, nd in zip(self.features, need)]
-        self.adam = adam
+        # the optimizer inside the step, two drivers: adam=dict(lr=...) -- host scalars, the step's own moments -- or
+        # adam_device + adam_state -- the caller's moments, scalars and step count on the device
+        self.adam, self.adam_device, self.adam_state = adam, adam_device, adam_state
         if adam is not None:
             self.exp_avg = [torch.zeros_like(f) if nd else None for f, nd in zip(self.features, need)]
             self.exp_avg_sq = [torch.zeros_like(f) if nd else None for f, nd in zip(self.features, need)]
             self.active = [ops.adam_active_flags(f) if nd else None for f, nd in zip(self.features, need)]
+            self.adam_state = list(zip(self.exp_avg, self.exp_avg_sq, self.active))
             self.t = 0
+        if adam_device is not None:
+            assert adam is None and adam_state is not None and len(adam_state) == len(self.features)
+            assert all((st is not None) == nd for st, nd in zip(adam_state, need))
+        self._adam_key = None
         self.live_rows = torch.full((1,), self.n, device=dev, dtype=torch.int32) if padded else None
         if padded:
             sort = True        # the live count is read by the binned forward
@@ -113,7 +121,6 @@ class MappingStep:
         # the bound): 412 us per trainer step against 324 us with the fine level scattered from the train kernel and the
         # coarse one pushed -- a crowded block works its table off in epochs on ONE workgroup while most of the chip has
         # no block to work on (tools/experiments/README.md) -- so it is not the default.
-        import os
         env = os.environ.get("MISO_STEP_TILES")
         self.tiles = ops.choose_tiles(self.features) if env == "auto" else ops.pack_tiles(int(env or ops.SortedBatch.TILES))
         # the fused step (sort -> sdf_train_kernel -> pull) reads a point's original index out of xn[p].w: no perm[] array,
@@ -125,10 +132,9 @@ class MappingStep:
             for g in self.grads:
                 if g is not None:
                     g.zero_()
-        self.adam_device, self.adam_state = adam_device, adam_state
-        if adam_device is not None:
-            assert adam is None and adam_state is not None and len(adam_state) == len(self.features)
-            assert all((st is not None) == nd for st, nd in zip(adam_state, need))
+        # ReLU bits handed from the forward to the backward where they are two launches (see _forward_backward)
+        one_launch = self._fused_train() and (self.sorted is not None or self.live_rows is None)
+        self._mask = None if one_launch else ops.sdf_mask_buffer(pack, self.n, dev)
         self.total = torch.zeros((), **f32)
         # binned step with the optimizer inside: the levels the backward ADDS to (atomic scatter, push) are cleared by
         # the Adam launch that consumes them instead of by a fill in front of every backward (64 MB at the ScanNet shape)
@@ -168,98 +174,87 @@ class MappingStep:
                 buf.copy_(src.reshape(self.n, 1))
 
     def _launch(self):
+        self._forward_backward()
+        if self.adam is not None or self.adam_device is not None:
+            self._optimize()
+
+    def _forward_backward(self):
+        """Loss sums into ``loss_slots``, gradients into ``grads``: four forms, by binning and by what the train kernel takes."""
         lt, ws, wf, td = self.loss_cfg
+        sdf_out = self.sdf if self.keep_sdf else None
         # binned path: gradients are written owner-computes, nothing to clear
         need_zero = self.sorted is None and (self.adam is None or self.t == 0) and not self.external_clear
         if need_zero:
             for g in self.grads:
                 if g is not None:
                     g.zero_()
-        L = len(self.features)
         if self.sorted is not None and self._fused_train():
             # binned path: forward + loss + decoder backward are ONE launch (sdf_train_kernel, which also scatters the
             # levels whose bricks are beyond the pull's reach), then the pull / push of the other levels
             self.sorted.sort(self.x, self.meta)   # part of the step: a new batch arrives every iteration
             ops.sdf_train_raw(self.features, self.meta, self.pack, self.sorted, self.aux, self.loss_slots, self.grads,
-                              lt, ws, wf, td, sdf_out=self.sdf if self.keep_sdf else None, n_live=self.live_rows,
+                              lt, ws, wf, td, sdf_out=sdf_out, n_live=self.live_rows,
                               touched=self.touched, zeroed=self.adam_device is not None)
         elif self.sorted is not None:
             # binned path, a level still scattered from the backward kernel (bricks beyond what the pull owns)
             self.sorted.sort(self.x, self.meta)
-            if getattr(self, "_mask", None) is None:
-                mw = ops.sdf_mask_words(self.pack)
-                self._mask = torch.empty(((self.n + 63) // 64) * 64 * mw, device=self.x.device, dtype=torch.int32)
             # forward + mapping loss: sdf, ReLU bits, d loss / d sdf (binned order) in one launch
             ops.sdf_fwd_loss_raw(self.features, self.meta, self.pack, self.sorted, self.aux, self._mask,
-                                 self.gpred, self.loss_slots, lt, ws, wf, td,
-                                 sdf_out=self.sdf if self.keep_sdf else None, n_live=self.live_rows)
+                                 self.gpred, self.loss_slots, lt, ws, wf, td, sdf_out=sdf_out, n_live=self.live_rows)
             ops.sdf_bwd_raw(self.x, self.features, self.meta, self.pack, self.gpred, self._mask, False,
                             self.need_levels, self.grads, sorted_batch=self.sorted, overwrite=True, gsdf_sorted=True,
                             touched=self.touched, zeroed=self.adam_device is not None)
         elif self._fused_train() and self.live_rows is None:
             # unbinned (small) batch: forward + loss + decoder backward + the atomic scatter of every level, one launch
             ops.sdf_train_unsorted_raw(self.x, self.features, self.meta, self.pack, self.aux, self.loss_slots, self.grads,
-                                       lt, ws, wf, td, sdf_out=self.sdf if self.keep_sdf else None, touched=self.touched)
+                                       lt, ws, wf, td, sdf_out=sdf_out, touched=self.touched)
         else:
             # forward + mapping loss in one launch here too (the label rows are read by the forward itself)
-            if getattr(self, "_mask", None) is None:
-                mw = ops.sdf_mask_words(self.pack)
-                self._mask = torch.empty(((self.n + 63) // 64) * 64 * mw, device=self.x.device, dtype=torch.int32)
-            mask = self._mask
-            ops.sdf_fwd_loss_unsorted_raw(self.x, self.features, self.meta, self.pack, self.aux, mask, self.gpred,
-                                          self.loss_slots, lt, ws, wf, td, sdf_out=self.sdf if self.keep_sdf else None)
-            ops.sdf_bwd_raw(self.x, self.features, self.meta, self.pack, self.gpred, mask, False,
+            ops.sdf_fwd_loss_unsorted_raw(self.x, self.features, self.meta, self.pack, self.aux, self._mask, self.gpred,
+                                          self.loss_slots, lt, ws, wf, td, sdf_out=sdf_out)
+            ops.sdf_bwd_raw(self.x, self.features, self.meta, self.pack, self.gpred, self._mask, False,
                             self.need_levels, self.grads, touched=self.touched)
-        if self.adam_device is not None:
-            self.adam_device.total_and_bump(self.loss_slots, self.total)      # loss sum + step count: one launch
-            # all levels share ONE launch (each stepped by its gradient or by its `touched` flags): as launches of their own the coarse
-            # levels of a pyramid are all ramp and tail (cfg-2: 8.5 + 13.4 us for 67 MB next to 74.5 us for 469 MB)
-            # (the block bakes raw pointers in: keyed by them, so a level whose storage was rebound -- f.data = ..., a replaced
-            # gradient or moment buffer -- gets a new block instead of an update of stale memory)
-            akey = tuple(t.data_ptr() for p, g, st, tch in zip(self.features, self.grads, self.adam_state, self.touched)
-                         if g is not None for t in (p, g, st[0], st[1], st[2]))
-            multi = self.__dict__.get("_adam_multi")
-            if multi is None or self.__dict__.get("_adam_multi_key") != akey:
-                dense = [(p, g, st[0], st[1], st[2], self.sorted is None or bool((self._adam_clears >> l) & 1), tch)
-                         for l, (p, g, st, tch) in enumerate(zip(self.features, self.grads, self.adam_state, self.touched))
-                         if g is not None]
-                multi = self._adam_multi = (self.adam_device.multi(dense) if 2 <= len(dense) <= ops._lib.ADAM_MAX_TENSORS
-                                            and os.environ.get("MISO_ADAM_PER_LEVEL") is None else False)
-                self._adam_multi_key = akey
-            if multi:
-                self.adam_device.step_multi_(multi, guard=self.total)
-            for l, (p, g, st, tch) in enumerate(zip(self.features, self.grads, self.adam_state, self.touched)):
-                if g is None or multi:
-                    continue
-                self.adam_device.step_(p, g, st[0], st[1], st[2], touched=tch, guard=self.total,
-                                       zero_grad=self.sorted is None or bool((self._adam_clears >> l) & 1))
-        if self.adam is not None:
+
+    def _adam_block(self):
+        """-> (multi, rows) of both Adam drivers.  rows: per level with a gradient (param, grad, exp_avg, exp_avg_sq, active,
+        zero_grad, touched); zero_grad: the Adam launch clears the gradient, the next backward that ADDS to it needs no
+        fill.  multi: the argument block that steps all of them in ONE launch (each by its gradient or by its `touched`
+        flags), or False: a launch per level -- as launches of their own the coarse levels of a pyramid are all ramp and
+        tail (cfg-2: 8.5 + 13.4 us for 67 MB next to 74.5 us for 469 MB).  The block bakes raw pointers in: it is keyed by
+        them, so a level whose storage was rebound -- f.data = ..., a replaced gradient or moment buffer -- gets a new
+        block instead of an update of stale memory."""
+        key = tuple(t.data_ptr() for p, g, st in zip(self.features, self.grads, self.adam_state) if g is not None
+                    for t in (p, g, st[0], st[1], st[2]))
+        if key != self._adam_key:
+            rows = [(p, g, st[0], st[1], st[2], self.sorted is None or bool((self._adam_clears >> l) & 1), tch)
+                    for l, (p, g, st, tch) in enumerate(zip(self.features, self.grads, self.adam_state, self.touched))
+                    if g is not None]
+            one = 2 <= len(rows) <= ops._lib.ADAM_MAX_TENSORS and os.environ.get("MISO_ADAM_PER_LEVEL") is None
+            self._adam_key, self._adam_rows, self._adam_multi = key, rows, ops.adam_tensors(rows) if one else False
+        return self._adam_multi, self._adam_rows
+
+    def _optimize(self):
+        dev = self.adam_device
+        if dev is not None:
+            dev.total_and_bump(self.loss_slots, self.total)      # loss sum + step count: one launch
+        else:
             self.t += 1
-            akey = tuple(t.data_ptr() for p, g, m, v, act in zip(self.features, self.grads, self.exp_avg, self.exp_avg_sq,
-                                                               self.active) if g is not None for t in (p, g, m, v, act))
-            multi = self.__dict__.get("_adam_multi")
-            if multi is None or self.__dict__.get("_adam_multi_key") != akey:
-                self._adam_multi_key = akey
-                dense = [(p.data, g, m, v, act, self.sorted is None, tch)
-                         for p, g, m, v, act, tch in zip(self.features, self.grads, self.exp_avg, self.exp_avg_sq,
-                                                         self.active, self.touched) if g is not None]
-                multi = self._adam_multi = (ops.adam_tensors(dense) if 2 <= len(dense) <= ops._lib.ADAM_MAX_TENSORS
-                                            and os.environ.get("MISO_ADAM_PER_LEVEL") is None else False)
-            if multi:
-                ops.adam_active_multi_(multi, self.t, **self.adam)
-            for p, g, m, v, act, tch in zip(self.features, self.grads, self.exp_avg, self.exp_avg_sq, self.active,
-                                            self.touched):
-                if g is None or multi:
-                    continue
-                # zero_grad=True: the gradient is cleared in the same pass, so the next
-                # iteration needs no memset
-                ops.adam_active_(p.data, g, m, v, act, self.t, zero_grad=self.sorted is None, touched=tch, **self.adam)
+        multi, rows = self._adam_block()
+        if multi and dev is not None:
+            dev.step_multi_(multi, guard=self.total)
+        elif multi:
+            ops.adam_active_multi_(multi, self.t, **self.adam)
+        else:
+            for p, g, m, v, act, zero, tch in rows:
+                if dev is not None:
+                    dev.step_(p, g, m, v, act, touched=tch, guard=self.total, zero_grad=zero)
+                else:
+                    ops.adam_active_(p, g, m, v, act, self.t, zero_grad=zero, touched=tch, **self.adam)
 
     def _fused_train(self) -> bool:
         """Whether the binned step runs as sort -> sdf_train_kernel -> pull (decided once: the grids do not change)."""
         ok = self.__dict__.get("_fused_train_ok")
         if ok is None:
-            import os
             ok = self._fused_train_ok = (os.environ.get("MISO_NO_FUSED_TRAIN") is None      # dev: the two-launch form
                                          and ops.sdf_train_supported(self.features, self.meta, self.grads, self.pack))
         return ok

@@ -81,6 +81,34 @@ def test_argument_validation_without_gpu():
     assert lib.miso_mlp_packed_floats(ctypes.byref(m)) == 0
 
 
+def test_refusals_are_typed_without_gpu():
+    """_lib.check turns MISO_E_UNSUPPORTED into NotCovered and every other code into a plain MisoError, the message as
+    it always was; a decoder the library does not pack is NotCovered for a caller that demands it (require) and
+    (None, None) for one that asks (get) -- decided by host code, so on host tensors too."""
+    from miso_amd import _lib, ops
+    assert ops.NotCovered is _lib.NotCovered and ops.MisoError is _lib.MisoError
+    assert issubclass(_lib.NotCovered, _lib.MisoError) and issubclass(_lib.MisoError, RuntimeError)
+    with pytest.raises(_lib.NotCovered) as e:
+        _lib.check(_lib.E_UNSUPPORTED, "x")
+    assert e.value.code == _lib.E_UNSUPPORTED == 2002 and e.value.what == "x"
+    assert str(e.value) == "x failed: shape not covered by the fused kernels (code 2002)"
+    with pytest.raises(_lib.MisoError) as e:
+        _lib.check(_lib.E_BADARG, "x")
+    assert not isinstance(e.value, _lib.NotCovered) and e.value.code == 2001
+    assert str(e.value) == "x failed: bad argument (code 2001)"
+    assert _lib.check(0, "x") is None
+    pack = ops.DecoderPack([torch.zeros(48, 12), torch.zeros(48, 48), torch.zeros(1, 48)], [None, None, None])
+    with pytest.raises(ops.NotCovered, match="decoder shape is not covered by the fused kernels") as e:
+        pack.require()
+    assert e.value.code == _lib.E_UNSUPPORTED
+    assert pack.get() == (None, None)
+    # a decoder that would pack is still refused on the host for what it is: no device
+    ok = ops.DecoderPack([torch.zeros(64, 24), torch.zeros(64, 64), torch.zeros(1, 64)], [None, None, None])
+    for _ in range(2):
+        with pytest.raises(RuntimeError, match="HIP device only"):
+            ok.get()
+
+
 def test_round2_entry_points_validate_arguments_without_gpu():
     """The entry points added for the captured trainer step, the tracker and the batch prologue refuse bad arguments
     before any launch; miso_adam_scalars_table is a host function and can be checked against the formula here."""
