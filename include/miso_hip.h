@@ -55,6 +55,10 @@
  *                     PosedSdfRgbd.getitem_sdf runs it on the host in every iteration (grid_opt/datasets/
  *                     sdf_rgbd.py:460-470: .cpu(), unique + scatter_reduce, six indexed gathers) and the LiDAR
  *                     dataset per loaded frame (grid_opt/datasets/sdf_3d_lidar.py:108-122).
+ *   miso_nn_plan / miso_nn_build / miso_nn_query / miso_nn_all_pairs
+ *                     utils_eval.nn_correspondance, grid_opt/utils/utils_eval.py:14-36: pytorch3d.ops.knn_points with
+ *                     K = 1 (an all-pairs search) under compute_chamfer_metrics (:74-108), the last step of
+ *                     demo/full_slam_scannet.py:161-191 and grid_opt/utils/utils_ncd.py:121-128.
  *
  * This file is also the ONLY statement of the ABI for Python: miso_amd/_lib.py reads its structs, integer constants and
  * prototypes at import and refuses what it cannot read.  Keep the declarations in the style used below: block comments,
@@ -762,6 +766,48 @@ int miso_voxel_down_sample(const float* points, int64_t ld, int64_t capacity, co
 int miso_voxel_select_rows(const float* src_coords, const int64_t* src_ids, const float* src_aux, const int64_t* out_idx,
                            const int32_t* out_count, int64_t capacity, float* dst_coords, int64_t* dst_ids, float* dst_aux,
                            int32_t* live_rows, void* stream);
+
+/* --- exact nearest neighbour on a uniform cell list -----------------------------------------------------------------------
+ * For every query the target with the smallest (d2, index) pair, compared lexicographically, where
+ * d2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2 in fp32 with one rounding per operation: the same bits from the index
+ * route and from the all-pairs route, from run to run, and whatever order the build's atomics left inside a cell.  A
+ * query or target with a non-finite coordinate gives or takes no match; a query without a match gets d2 = +inf, idx = -1.
+ *   miso_nn_plan  host only.  bound_min / bound_max: three host floats each, the box of the (finite) targets; cell > 0;
+ *       dims[a] = floor((max - min) / cell) + 1, and while dims_x dims_y dims_z > MISO_NN_MAX_CELLS the cell is doubled:
+ *       plan.cell is the one used.  max_rings in [0, MISO_NN_MAX_RINGS].  coord_mag: the largest |coordinate| of the
+ *       grid plus its largest extent, which the query's stop test scales its rounding slack with.  n_tgt == 0 is a
+ *       valid plan (the bounds are not read).  MISO_E_BADARG: non-finite or non-positive cell, non-finite bounds,
+ *       max < min, negative sizes; MISO_E_TOOLARGE: n_tgt >= 2^31.
+ *   miso_nn_workspace_bytes  the device workspace of a plan (16-byte aligned): the offset table (cells + 1 int32), the
+ *       targets as 16-byte rows in cell order, and a fixed part for the queries (the list of one chunk of
+ *       MISO_NN_CHUNK queries and a counter per chunk); 0 for a plan the library did not write.
+ *   miso_nn_build  tgt (n_tgt, 3) fp32 with row stride ld >= 3 -> the index in `workspace` (the library clears its own
+ *       counters).  n_tgt == 0 launches nothing.
+ *   miso_nn_query  src (n, 3) with row stride ld >= 3, n < 2^31 -> out_d2 (n) fp32, out_idx (n) int64, stats (2 int32 on the
+ *       device) = {queries finished by the shells of cells up to max_rings, queries sent to the all-pairs kernel}.  No
+ *       host read, no allocation: the call replays inside a captured graph.  One query at a time per workspace.
+ *   miso_nn_all_pairs  the all-pairs kernel for every query over the caller's arrays, no index (m < 2^31). */
+#define MISO_NN_MAX_CELLS 16777216
+#define MISO_NN_MAX_RINGS 64
+#define MISO_NN_CHUNK 1048576
+#define MISO_NN_MAX_CHUNKS 2048
+typedef struct {
+  float bound_min[3];
+  float cell;
+  float coord_mag;
+  int32_t dims[3];
+  int32_t max_rings;
+  int64_t n_tgt;
+  int64_t cells;
+} miso_nn_plan_t;
+int miso_nn_plan(const float* bound_min, const float* bound_max, float cell, int64_t n_tgt, int32_t max_rings,
+                 miso_nn_plan_t* plan);
+int64_t miso_nn_workspace_bytes(const miso_nn_plan_t* plan);
+int miso_nn_build(const miso_nn_plan_t* plan, const float* tgt, int64_t ld, void* workspace, void* stream);
+int miso_nn_query(const miso_nn_plan_t* plan, void* workspace, const float* src, int64_t ld, int64_t n, float* out_d2,
+                  int64_t* out_idx, int32_t* stats, void* stream);
+int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, float* out_d2,
+                      int64_t* out_idx, void* stream);
 
 /* --- fused atlas query: GridAtlas.query_feature / GridAtlas.forward in one launch (round 6) ---------------------------
  * Replaces the per-submap loop of grid_opt/models/grid_atlas.py:374-399 (for each active submap: transfrom_points_from,

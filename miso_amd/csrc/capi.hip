@@ -1009,6 +1009,83 @@ int miso_voxel_select_rows(const float* src_coords, const int64_t* src_ids, cons
                                        dst_aux, live_rows, (hipStream_t)stream);
 }
 
+// ---- exact nearest neighbour (nn.hip) --------------------------------------------------------------------------------------
+int miso_nn_plan(const float* bound_min, const float* bound_max, float cell, int64_t n_tgt, int32_t max_rings,
+                 miso_nn_plan_t* plan) {
+  const float inf = __builtin_huge_valf();
+  if (!plan || !bound_min || !bound_max || n_tgt < 0 || max_rings < 0 || max_rings > MISO_NN_MAX_RINGS) return MISO_E_BADARG;
+  if (!(cell > 0.0f) || !(cell < inf)) return MISO_E_BADARG;
+  if (n_tgt >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  memset(plan, 0, sizeof(*plan));
+  plan->n_tgt = n_tgt; plan->max_rings = max_rings; plan->cell = cell;
+  plan->dims[0] = plan->dims[1] = plan->dims[2] = 1; plan->cells = 1;
+  if (n_tgt == 0) return MISO_OK;
+  // dims in the kernels' arithmetic (fp32 difference, fp32 division, floor): the cell index of the largest coordinate is
+  // dims - 1 without the clamp
+  float ext[3];
+  double mag = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    if (!(fabsf(bound_min[a]) < inf) || !(fabsf(bound_max[a]) < inf) || bound_max[a] < bound_min[a]) return MISO_E_BADARG;
+    ext[a] = bound_max[a] - bound_min[a];
+    if (!(ext[a] < inf)) return MISO_E_BADARG;
+    plan->bound_min[a] = bound_min[a];
+  }
+  float c = cell;
+  for (;;) {
+    double cells = 1.0;
+    for (int a = 0; a < 3; ++a) cells *= (double)floorf(ext[a] / c) + 1.0;
+    if (cells <= (double)MISO_NN_MAX_CELLS) break;
+    c *= 2.0f;
+    if (!(c < inf)) return MISO_E_BADARG;
+  }
+  plan->cell = c;
+  plan->cells = 1;
+  for (int a = 0; a < 3; ++a) {
+    plan->dims[a] = (int32_t)floorf(ext[a] / c) + 1;
+    plan->cells *= plan->dims[a];
+    const double top = fmax(fabs((double)bound_min[a]), fabs((double)bound_min[a] + (double)plan->dims[a] * c));
+    mag = fmax(mag, top + (double)plan->dims[a] * c);
+  }
+  plan->coord_mag = (float)fmin(mag * (1.0 + 1e-6), 3.0e38);
+  return MISO_OK;
+}
+
+// a plan as miso_nn_plan writes it (the struct is the caller's memory: the kernels index by it)
+static bool nn_plan_ok(const miso_nn_plan_t* p) {
+  if (!p || p->n_tgt < 0 || p->n_tgt >= ((int64_t)1 << 31) || p->max_rings < 0 || p->max_rings > MISO_NN_MAX_RINGS) return false;
+  if (p->dims[0] < 1 || p->dims[1] < 1 || p->dims[2] < 1 || p->cells < 1 || p->cells > MISO_NN_MAX_CELLS) return false;
+  if ((int64_t)p->dims[0] * p->dims[1] > MISO_NN_MAX_CELLS || (int64_t)p->dims[0] * p->dims[1] * p->dims[2] != p->cells) return false;
+  return p->cell > 0.0f && p->cell < __builtin_huge_valf() && p->coord_mag >= 0.0f;
+}
+
+int64_t miso_nn_workspace_bytes(const miso_nn_plan_t* plan) {
+  return nn_plan_ok(plan) ? nn_workspace_bytes(*plan) : 0;
+}
+
+int miso_nn_build(const miso_nn_plan_t* plan, const float* tgt, int64_t ld, void* workspace, void* stream) {
+  if (!nn_plan_ok(plan) || ld < 3) return MISO_E_BADARG;
+  if (plan->n_tgt == 0) return MISO_OK;
+  if (!tgt || !workspace || ((uintptr_t)workspace & 15u)) return MISO_E_BADARG;
+  return (int)launch_nn_build(*plan, tgt, ld, workspace, (hipStream_t)stream);
+}
+
+int miso_nn_query(const miso_nn_plan_t* plan, void* workspace, const float* src, int64_t ld, int64_t n, float* out_d2,
+                  int64_t* out_idx, int32_t* stats, void* stream) {
+  if (!nn_plan_ok(plan) || ld < 3 || n < 0 || !stats) return MISO_E_BADARG;
+  if (n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (n > 0 && (!src || !out_d2 || !out_idx)) return MISO_E_BADARG;
+  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  return (int)launch_nn_query(*plan, workspace, src, ld, n, out_d2, out_idx, stats, (hipStream_t)stream);
+}
+
+int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, float* out_d2,
+                      int64_t* out_idx, void* stream) {
+  if (m < 0 || n < 0 || ld_t < 3 || ld_s < 3) return MISO_E_BADARG;
+  if (m >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if ((m > 0 && !tgt) || (n > 0 && (!src || !out_d2 || !out_idx))) return MISO_E_BADARG;
+  return (int)launch_nn_all_pairs(tgt, ld_t, m, src, ld_s, n, out_d2, out_idx, (hipStream_t)stream);
+}
+
 // ---- fused atlas query (atlas.hip) ------------------------------------------------------------------------------------
 int64_t miso_atlas_plan_bytes(int32_t n_submaps) {
   return n_submaps < 1 ? 0 : (int64_t)n_submaps * (int64_t)sizeof(GridK);

@@ -156,4 +156,12 @@ hipError_t launch_voxel_select_rows(const float* src_coords, const int64_t* src_
                                     const int64_t* out_idx, const int32_t* out_count, int64_t capacity, float* dst_coords,
                                     int64_t* dst_ids, float* dst_aux, int32_t* live_rows, hipStream_t s);
 
+// ---- nn.hip
+int64_t nn_workspace_bytes(const miso_nn_plan_t& plan);
+hipError_t launch_nn_build(const miso_nn_plan_t& plan, const float* tgt, int64_t ld, void* workspace, hipStream_t s);
+hipError_t launch_nn_query(const miso_nn_plan_t& plan, void* workspace, const float* src, int64_t ld, int64_t n, float* out_d2,
+                           int64_t* out_idx, int32_t* stats, hipStream_t s);
+hipError_t launch_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n,
+                               float* out_d2, int64_t* out_idx, hipStream_t s);
+
 }  // namespace miso

@@ -1,0 +1,409 @@
+// Exact nearest neighbour of every query among a target cloud: what utils_eval.nn_correspondance (grid_opt/utils/
+// utils_eval.py:14-36) asks of pytorch3d's knn_points with K = 1, an all-pairs search.  Here a uniform cell list over the
+// targets' bounding box answers a query from the shells of cells around it, and the queries it cannot finish within
+// max_rings shells go to an all-pairs kernel.  Both compute
+//     d2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2        fp32, one rounding per operation
+// and the winner is the smallest (d2, original target index) pair, compared lexicographically: the answer depends neither
+// on the order in which candidates are visited, nor on the order atomics left inside a cell, nor on the kernel.  A NaN
+// or +inf d2 never wins (both comparisons below are false for it), so a query or target with a non-finite coordinate gives
+// or takes no match: (d2, idx) = (+inf, -1).
+//
+// Index (miso_nn_build; workspace layout in nn_layout):
+//   table  cells + 1 int32.  count: table[c + 1] += 1 per target of cell c.  scan: table[c + 1] = targets in cells < c
+//          (three launches: block sums of 16 384, a scan of up to 1024 sums, the blocks again).  scatter: a target takes
+//          row atomicAdd(&table[c + 1], 1), which leaves table[c] = first row of cell c and table[c + 1] = one past its last.
+//   rows   {x, y, z, original index bits} per target in cell order, 16 bytes: a candidate is one dwordx4 load.
+//   cell   c_a = int(clamp(floor((p_a - min_a) / cell), 0, dims_a - 1)), clamped as a float (fmaxf / fminf drop a NaN), so
+//          any input indexes inside the table; linear index (z dims_y + y) dims_x + x: the cells of an x run are one run
+//          of rows.
+// Query (miso_nn_query), a lane per query, chunks of NN_CHUNK queries:
+//   rings  shell r = 0, 1, .. max_rings of cells at Chebyshev distance r from the query's (clamped) cell, then the stop
+//          test (ring_finished).  Unfinished queries append themselves to the chunk's list (one atomic per wavefront).
+//   rest   blocks of 256 listed queries against the rows, staged through LDS in tiles, the rows split over grid.y and merged
+//          with a 64-bit atomicMin on the packed (d2, idx); a block whose first list slot is at or beyond the device
+//          counter leaves, so the launch is sized for the worst case and the host reads nothing.  Then the pairs are unpacked.
+// miso_nn_all_pairs is the second kernel over the caller's arrays, every query, no index.
+#include "common.hpp"
+#include "launch.hpp"
+#include "nn.hpp"
+
+// plain operators, one rounding each (see voxel.hip on why not the __fmul_rn / __fadd_rn wrappers)
+#pragma clang fp contract(off)
+
+namespace miso {
+namespace {
+
+constexpr int NN_SCAN_THREADS = 1024;
+constexpr int NN_SCAN_ITEMS = 16;
+constexpr int NN_SCAN_TILE = NN_SCAN_THREADS * NN_SCAN_ITEMS;      // 16 384 table entries per block; 1024 blocks = the cap
+static_assert((int64_t)NN_SCAN_TILE * 1024 >= MISO_NN_MAX_CELLS, "one block scans the block sums");
+constexpr int NN_TILE = 1024;                                      // targets per LDS tile of the all-pairs kernel (16 KB)
+constexpr int NN_SEG_TILES = 8;                                    // the listed queries' all-pairs: at least 8 tiles a segment,
+constexpr int NN_SEGMENTS = 64;                                    // at most 64 segments (grid.y)
+
+struct Best {
+  float d2;
+  int idx;
+};
+
+__device__ __forceinline__ float nn_dist2(float ax, float ay, float az, float bx, float by, float bz) {
+  const float dx = ax - bx, dy = ay - by, dz = az - bz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// smallest (d2, idx); false for a NaN d2, and for d2 = +inf against the initial (+inf, -1)
+__device__ __forceinline__ void nn_take(Best& b, float d2, int idx) {
+  if (d2 < b.d2 || (d2 == b.d2 && idx < b.idx)) { b.d2 = d2; b.idx = idx; }
+}
+
+// (d2, idx) as one unsigned 64-bit key that orders like the pair: d2 >= +0 (floats then order like their bits), idx as
+// uint32 (-1 = the largest: no match).  The all-pairs kernel behind the rings merges its target segments with atomicMin.
+__device__ __forceinline__ unsigned long long nn_pack(const Best& b) {
+  return ((unsigned long long)__float_as_uint(b.d2) << 32) | (unsigned long long)(uint32_t)b.idx;
+}
+
+__device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
+  const float inf = __builtin_huge_valf();
+  return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;       // false for NaN
+}
+
+__device__ __forceinline__ int nn_cell_axis(float p, float lo, float cell, int dim) {
+  const float c = floorf(__fdiv_rn(p - lo, cell));
+  return (int)fminf(fmaxf(c, 0.0f), (float)(dim - 1));              // fmaxf(NaN, 0) = 0
+}
+
+__device__ __forceinline__ int nn_cell_of(const NnK& k, float x, float y, float z, int c[3]) {
+  c[0] = nn_cell_axis(x, k.lo[0], k.cell, k.dims[0]);
+  c[1] = nn_cell_axis(y, k.lo[1], k.cell, k.dims[1]);
+  c[2] = nn_cell_axis(z, k.lo[2], k.cell, k.dims[2]);
+  return (c[2] * k.dims[1] + c[1]) * k.dims[0] + c[0];
+}
+
+// ---- build -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void nn_count_kernel(NnK k, const float* __restrict__ tgt, int64_t ld, int* __restrict__ table) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= k.n_tgt) return;
+  int c[3];
+  const int cell = nn_cell_of(k, tgt[i * ld], tgt[i * ld + 1], tgt[i * ld + 2], c);
+  atomicAdd(&table[cell + 1], 1);
+}
+
+// sums of the blocks' NN_SCAN_TILE entries of t[0 .. n)
+__global__ __launch_bounds__(NN_SCAN_THREADS) void nn_scan_sums_kernel(const int* __restrict__ t, int n, int* __restrict__ sums) {
+  __shared__ int ws[NN_SCAN_THREADS / 64];
+  const int base = blockIdx.x * NN_SCAN_TILE + threadIdx.x * NN_SCAN_ITEMS;
+  int s = 0;
+#pragma unroll
+  for (int j = 0; j < NN_SCAN_ITEMS; ++j) s += base + j < n ? t[base + j] : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int w = 0; w < NN_SCAN_THREADS / 64; ++w) tot += ws[w];
+    sums[blockIdx.x] = tot;
+  }
+}
+
+// exclusive scan of `v` over the block's 1024 threads; returns the prefix of this thread
+__device__ __forceinline__ int nn_block_exclusive(int v, int* ws) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int w = __shfl_up(inc, o); if (lane >= o) inc += w; }
+  if (lane == 63) ws[wave] = inc;
+  __syncthreads();
+  int base = 0;
+  for (int w = 0; w < wave; ++w) base += ws[w];
+  return base + inc - v;
+}
+
+__global__ __launch_bounds__(NN_SCAN_THREADS) void nn_scan_blocks_kernel(int* __restrict__ sums, int nb) {
+  __shared__ int ws[NN_SCAN_THREADS / 64];
+  const int v = (int)threadIdx.x < nb ? sums[threadIdx.x] : 0;
+  const int pre = nn_block_exclusive(v, ws);
+  if ((int)threadIdx.x < nb) sums[threadIdx.x] = pre;
+}
+
+__global__ __launch_bounds__(NN_SCAN_THREADS) void nn_scan_apply_kernel(int* __restrict__ t, int n, const int* __restrict__ sums) {
+  __shared__ int ws[NN_SCAN_THREADS / 64];
+  const int base = blockIdx.x * NN_SCAN_TILE + threadIdx.x * NN_SCAN_ITEMS;
+  int v[NN_SCAN_ITEMS], s = 0;
+#pragma unroll
+  for (int j = 0; j < NN_SCAN_ITEMS; ++j) { v[j] = base + j < n ? t[base + j] : 0; s += v[j]; }
+  int run = nn_block_exclusive(s, ws) + sums[blockIdx.x];
+#pragma unroll
+  for (int j = 0; j < NN_SCAN_ITEMS; ++j) {
+    if (base + j < n) t[base + j] = run;
+    run += v[j];
+  }
+}
+
+__global__ __launch_bounds__(256) void nn_scatter_kernel(NnK k, const float* __restrict__ tgt, int64_t ld, int* __restrict__ table,
+                                                         float4* __restrict__ rows) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= k.n_tgt) return;
+  const float x = tgt[i * ld], y = tgt[i * ld + 1], z = tgt[i * ld + 2];
+  int c[3];
+  const int cell = nn_cell_of(k, x, y, z, c);
+  const int at = atomicAdd(&table[cell + 1], 1);
+  if (at >= 0 && (int64_t)at < k.n_tgt) rows[at] = make_float4(x, y, z, __int_as_float((int)i));
+}
+
+// ---- query: rings ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void nn_scan_rows(const float4* __restrict__ rows, int n_rows, int s, int e, float qx, float qy, float qz,
+                                             Best& b) {
+  e = min(e, n_rows);                            // (a table that no build wrote must not lead outside the rows)
+  for (int j = max(s, 0); j < e; ++j) {
+    const float4 t = rows[j];
+    nn_take(b, nn_dist2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
+  }
+}
+
+// After ring r the examined box is [c - r, c + r] (clamped to the grid).  A target outside it lies beyond a face of the box
+// that is not on the grid's edge, so in real arithmetic it is at least g away, g the smallest distance from the query to
+// such a face; with every face on the edge nothing is left.  In fp32 three things move that bound:
+//   * membership.  A target t is below the face of cell k when floor(fl(fl(t - lo) / cell)) < k, which allows
+//     t - lo < k cell (1 + 2.1 u), u = 2^-24: it may sit up to 2.1 u (k cell) beyond the plane lo + k cell.
+//   * the face.  fl(q - fl(lo + fl(k cell))) is off by at most u (k cell + |lo + k cell| + g).
+//   * the distance.  A computed d2 is within 5.1 u (relative) of the true one.
+// With A = the largest coordinate magnitude of the grid plus its largest extent (NnK.mag, from the host plan) the first two
+// are below u (4.1 A + g); the test takes 8 u (A + g) = 2^-21 (A + g) off g, which also covers the roundings of the test
+// itself, and 16 u = 2^-20 (relative) off its square.  The comparison is strict: a target left out has a computed d2
+// above `best`, so it loses whatever its index.
+__device__ __forceinline__ bool ring_finished(const NnK& k, const float q[3], const int c[3], int r, float best) {
+  const float inf = __builtin_huge_valf();
+  float g = inf;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (c[a] - r > 0) g = fminf(g, q[a] - (k.lo[a] + (float)(c[a] - r) * k.cell));
+    if (c[a] + r < k.dims[a] - 1) g = fminf(g, (k.lo[a] + (float)(c[a] + r + 1) * k.cell) - q[a]);
+  }
+  if (g == inf) return true;                      // the box is the grid
+  const float gs = g - 0x1p-21f * (k.mag + g);
+  if (!(gs > 0.0f)) return false;
+  return best < (gs * gs) * (1.0f - 0x1p-20f);
+}
+
+__global__ __launch_bounds__(256) void nn_rings_kernel(NnK k, const int* __restrict__ table, const float4* __restrict__ rows,
+                                                       const float* __restrict__ src, int64_t ld, int64_t first, int count,
+                                                       float* __restrict__ out_d2, int64_t* __restrict__ out_idx,
+                                                       int* __restrict__ list, int* __restrict__ list_n, int* __restrict__ stats) {
+  const int li = blockIdx.x * 256 + threadIdx.x;
+  const bool live = li < count;
+  const int64_t i = first + li;
+  bool done = true;
+  if (live) {
+    const float q[3] = {src[i * ld], src[i * ld + 1], src[i * ld + 2]};
+    Best b = {__builtin_huge_valf(), -1};
+    if (nn_finite3(q[0], q[1], q[2])) {
+      int c[3];
+      nn_cell_of(k, q[0], q[1], q[2], c);
+      done = false;
+      for (int r = 0; r <= k.max_rings && !done; ++r) {
+        const int xlo = max(c[0] - r, 0), xhi = min(c[0] + r, k.dims[0] - 1);
+        const int ylo = max(c[1] - r, 0), yhi = min(c[1] + r, k.dims[1] - 1);
+        const int zlo = max(c[2] - r, 0), zhi = min(c[2] + r, k.dims[2] - 1);
+        for (int z = zlo; z <= zhi; ++z)
+          for (int y = ylo; y <= yhi; ++y) {
+            const int row = (z * k.dims[1] + y) * k.dims[0];
+            if (abs(z - c[2]) == r || abs(y - c[1]) == r) {          // a whole x run of the shell: one run of rows
+              nn_scan_rows(rows, (int)k.n_tgt, table[row + xlo], table[row + xhi + 1], q[0], q[1], q[2], b);
+            } else {                                                  // (r > 0 here) the two end cells of the run
+              if (c[0] - r >= 0) nn_scan_rows(rows, (int)k.n_tgt, table[row + c[0] - r], table[row + c[0] - r + 1], q[0], q[1], q[2], b);
+              if (c[0] + r < k.dims[0]) nn_scan_rows(rows, (int)k.n_tgt, table[row + c[0] + r], table[row + c[0] + r + 1], q[0], q[1], q[2], b);
+            }
+          }
+        done = ring_finished(k, q, c, r, b.d2);
+      }
+    }
+    if (done) { out_d2[i] = b.d2; out_idx[i] = (int64_t)b.idx; }
+    else out_idx[i] = (int64_t)nn_pack(b);        // the best of the rings so far: the accumulator of the all-pairs blocks
+  }
+  // one atomic per wavefront and counter
+  const uint64_t fin = __ballot(live && done), rest = __ballot(live && !done);
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) {
+    if (fin) atomicAdd(&stats[0], __popcll(fin));
+    if (rest) { atomicAdd(&stats[1], __popcll(rest)); base = atomicAdd(list_n, __popcll(rest)); }
+  }
+  base = __shfl(base, 0);
+  if (live && !done) {
+    const int at = base + __popcll(rest & ((1ull << lane) - 1));
+    if (at >= 0 && at < count) list[at] = li;
+  }
+}
+
+// ---- all pairs ---------------------------------------------------------------------------------------------------------
+// LISTED: the kernel behind the rings.  Targets are the index's rows (the original index in .w), queries list[slot] of the
+// chunk for slot < *list_n, and blockIdx.y takes the targets [y seg_len, (y + 1) seg_len): a few hundred listed queries
+// against all targets are a few blocks, each bound by its own latency, unless the targets are spread over the device.
+// The segments merge with a 64-bit atomicMin on the packed pair in out_idx[i] (seeded by the rings kernel), which
+// nn_unpack_kernel turns into (d2, idx).  Else: the caller's (m, 3) targets with row stride ld_t, query `slot` of n, one
+// segment, results written directly.
+template <bool LISTED>
+__global__ __launch_bounds__(256) void nn_all_pairs_kernel(const float4* __restrict__ rows, const float* __restrict__ tgt, int64_t ld_t,
+                                                           int64_t m, int64_t seg_len, const float* __restrict__ src, int64_t ld_s,
+                                                           int64_t first, int64_t n, const int* __restrict__ list,
+                                                           const int* __restrict__ list_n, float* __restrict__ out_d2,
+                                                           int64_t* __restrict__ out_idx) {
+  __shared__ float4 tile[NN_TILE];
+  int64_t count = n;
+  if (LISTED) { const int c = *list_n; count = c < 0 ? 0 : (c > n ? n : c); }
+  if ((int64_t)blockIdx.x * 256 >= count) return;                     // the whole block: no barrier is left waiting
+  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = slot < count;
+  int64_t i = 0;
+  if (live) {
+    i = slot;
+    if (LISTED) { const int li = list[slot]; i = li < 0 ? 0 : (li >= n ? n - 1 : li); }
+    i += first;
+  }
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  if (live) { qx = src[i * ld_s]; qy = src[i * ld_s + 1]; qz = src[i * ld_s + 2]; }
+  Best b = {__builtin_huge_valf(), -1};
+  const int64_t t_begin = (int64_t)blockIdx.y * seg_len, t_end = t_begin + seg_len < m ? t_begin + seg_len : m;
+  for (int64_t t0 = t_begin; t0 < t_end; t0 += NN_TILE) {
+    const int len = (int)(t_end - t0 < NN_TILE ? t_end - t0 : NN_TILE);
+    __syncthreads();
+    for (int j = threadIdx.x; j < len; j += 256) {
+      if (LISTED) tile[j] = rows[t0 + j];
+      else tile[j] = make_float4(tgt[(t0 + j) * ld_t], tgt[(t0 + j) * ld_t + 1], tgt[(t0 + j) * ld_t + 2], __int_as_float((int)(t0 + j)));
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int j = 0; j < len; ++j) {
+      const float4 t = tile[j];                                       // one address per wavefront: a broadcast
+      nn_take(b, nn_dist2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
+    }
+  }
+  if (!live) return;
+  if (LISTED) {
+    if (b.idx >= 0) atomicMin(reinterpret_cast<unsigned long long*>(out_idx + i), nn_pack(b));
+  } else {
+    out_d2[i] = b.d2; out_idx[i] = (int64_t)b.idx;
+  }
+}
+
+// the merged pairs of the listed queries -> (d2, idx)
+__global__ __launch_bounds__(256) void nn_unpack_kernel(int64_t first, int n, const int* __restrict__ list, const int* __restrict__ list_n,
+                                                        float* __restrict__ out_d2, int64_t* __restrict__ out_idx) {
+  const int c = *list_n, count = c < 0 ? 0 : (c > n ? n : c);
+  const int slot = blockIdx.x * 256 + threadIdx.x;
+  if (slot >= count) return;
+  const int li = list[slot];
+  const int64_t i = first + (li < 0 ? 0 : (li >= n ? n - 1 : li));
+  const unsigned long long key = (unsigned long long)out_idx[i];
+  out_d2[i] = __uint_as_float((uint32_t)(key >> 32));
+  out_idx[i] = (int64_t)(int32_t)(uint32_t)key;
+}
+
+__global__ __launch_bounds__(256) void nn_fill_kernel(int64_t n, float* __restrict__ out_d2, int64_t* __restrict__ out_idx) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) { out_d2[i] = __builtin_huge_valf(); out_idx[i] = -1; }
+}
+
+__global__ void nn_set_stats_kernel(int* __restrict__ stats, int a, int b) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) { stats[0] = a; stats[1] = b; }
+}
+
+inline int64_t a256(int64_t v) { return (v + 255) / 256 * 256; }
+
+struct NnLayout {
+  int64_t table, sums, counters, list, rows, total;
+};
+
+// byte offsets inside the workspace
+inline NnLayout nn_layout(const miso_nn_plan_t& p) {
+  NnLayout l;
+  int64_t at = 0;
+  l.table = at;    at += a256((p.cells + 1) * 4);
+  l.sums = at;     at += a256(1024 * 4);
+  l.counters = at; at += a256((int64_t)MISO_NN_MAX_CHUNKS * 4);
+  l.list = at;     at += a256((int64_t)MISO_NN_CHUNK * 4);
+  l.rows = at;     at += a256(p.n_tgt * 16);
+  l.total = at;
+  return l;
+}
+
+inline NnK nn_k(const miso_nn_plan_t& p) {
+  NnK k;
+  for (int a = 0; a < 3; ++a) { k.lo[a] = p.bound_min[a]; k.dims[a] = p.dims[a]; }
+  k.cell = p.cell; k.mag = p.coord_mag; k.max_rings = p.max_rings; k.n_tgt = p.n_tgt;
+  return k;
+}
+
+}  // namespace
+
+int64_t nn_workspace_bytes(const miso_nn_plan_t& p) { return nn_layout(p).total; }
+
+hipError_t launch_nn_build(const miso_nn_plan_t& p, const float* tgt, int64_t ld, void* ws, hipStream_t s) {
+  if (p.n_tgt == 0) return hipSuccess;
+  const NnLayout l = nn_layout(p);
+  char* w = reinterpret_cast<char*>(ws);
+  int* table = reinterpret_cast<int*>(w + l.table);
+  int* sums = reinterpret_cast<int*>(w + l.sums);
+  float4* rows = reinterpret_cast<float4*>(w + l.rows);
+  const NnK k = nn_k(p);
+  const int cells = (int)p.cells, nb = (cells + NN_SCAN_TILE - 1) / NN_SCAN_TILE;
+  const unsigned g = (unsigned)((p.n_tgt + 255) / 256);
+  hipError_t e = launch_zero_words(table, cells + 1, s);
+  if (e != hipSuccess) return e;
+  nn_count_kernel<<<g, 256, 0, s>>>(k, tgt, ld, table);
+  nn_scan_sums_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(table + 1, cells, sums);
+  nn_scan_blocks_kernel<<<1, NN_SCAN_THREADS, 0, s>>>(sums, nb);
+  nn_scan_apply_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(table + 1, cells, sums);
+  nn_scatter_kernel<<<g, 256, 0, s>>>(k, tgt, ld, table, rows);
+  return hipGetLastError();
+}
+
+hipError_t launch_nn_query(const miso_nn_plan_t& p, void* ws, const float* src, int64_t ld, int64_t n, float* out_d2,
+                           int64_t* out_idx, int32_t* stats, hipStream_t s) {
+  if (p.n_tgt == 0) {
+    nn_set_stats_kernel<<<1, 64, 0, s>>>(stats, (int)n, 0);
+    if (n > 0) nn_fill_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, out_d2, out_idx);
+    return hipGetLastError();
+  }
+  hipError_t e = launch_zero_words(stats, 2, s);
+  if (e != hipSuccess || n == 0) return e;
+  const NnLayout l = nn_layout(p);
+  char* w = reinterpret_cast<char*>(ws);
+  const int* table = reinterpret_cast<const int*>(w + l.table);
+  int* counters = reinterpret_cast<int*>(w + l.counters);
+  int* list = reinterpret_cast<int*>(w + l.list);
+  const float4* rows = reinterpret_cast<const float4*>(w + l.rows);
+  const NnK k = nn_k(p);
+  const int chunks = (int)((n + MISO_NN_CHUNK - 1) / MISO_NN_CHUNK);
+  // the listed queries see the targets in up to NN_SEGMENTS segments of at least NN_SEG_TILES tiles
+  const int64_t tiles = (p.n_tgt + NN_TILE - 1) / NN_TILE;
+  const unsigned segs = (unsigned)(tiles / NN_SEG_TILES < 1 ? 1 : (tiles / NN_SEG_TILES > NN_SEGMENTS ? NN_SEGMENTS : tiles / NN_SEG_TILES));
+  const int64_t seg_len = (tiles + segs - 1) / segs * NN_TILE;
+  e = launch_zero_words(counters, chunks, s);
+  if (e != hipSuccess) return e;
+  for (int c = 0; c < chunks; ++c) {
+    const int64_t first = (int64_t)c * MISO_NN_CHUNK;
+    const int count = (int)(n - first < MISO_NN_CHUNK ? n - first : MISO_NN_CHUNK);
+    const unsigned g = (unsigned)((count + 255) / 256);
+    nn_rings_kernel<<<g, 256, 0, s>>>(k, table, rows, src, ld, first, count, out_d2, out_idx, list, counters + c, stats);
+    nn_all_pairs_kernel<true><<<dim3(g, segs), 256, 0, s>>>(rows, nullptr, 0, p.n_tgt, seg_len, src, ld, first, (int64_t)count, list,
+                                                            counters + c, out_d2, out_idx);
+    nn_unpack_kernel<<<g, 256, 0, s>>>(first, count, list, counters + c, out_d2, out_idx);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n,
+                               float* out_d2, int64_t* out_idx, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  // (m == 0: no tile is loaded and every query keeps (+inf, -1))
+  for (int64_t first = 0; first < n; first += MISO_NN_CHUNK) {
+    const int64_t count = n - first < MISO_NN_CHUNK ? n - first : MISO_NN_CHUNK;
+    nn_all_pairs_kernel<false><<<(unsigned)((count + 255) / 256), 256, 0, s>>>(nullptr, tgt, ld_t, m, m, src, ld_s, first, count,
+                                                                               nullptr, nullptr, out_d2, out_idx);
+  }
+  return hipGetLastError();
+}
+
+}  // namespace miso

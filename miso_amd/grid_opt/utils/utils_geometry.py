@@ -188,6 +188,23 @@ def voxel_down_sample_torch_ops(points: torch.Tensor, voxel_size: float):
     return best % base
 
 
+def voxel_centroid_down_sample(points: torch.Tensor, voxel_size: float) -> torch.Tensor:
+    """Open3D's ``PointCloud.voxel_down_sample``: the centroid of the points of every occupied voxel, voxels of edge
+    ``voxel_size`` with their origin at ``min_bound - 0.5 voxel_size`` (``unique`` over the voxel indices, ``index_add``
+    of the coordinates in float64).  (N, 3) -> (K, 3) in the order of the sorted voxel keys, which is not Open3D's
+    (a hash map's).  Works on whatever device ``points`` is on."""
+    if points.shape[0] == 0:
+        return points.reshape(0, 3)
+    p = points.to(torch.float64)
+    origin = p.min(dim=0)[0] - 0.5 * voxel_size
+    ijk = torch.floor((p - origin) / voxel_size).long()
+    dims = ijk.max(dim=0)[0] + 1
+    key = (ijk[:, 0] * dims[1] + ijk[:, 1]) * dims[2] + ijk[:, 2]
+    _, inverse, counts = torch.unique(key, return_inverse=True, return_counts=True)
+    acc = torch.zeros((counts.shape[0], 3), dtype=torch.float64, device=points.device).index_add_(0, inverse, p)
+    return (acc / counts[:, None].to(torch.float64)).to(points.dtype)
+
+
 def crop_points(points: torch.Tensor, ts: torch.Tensor, min_z_th=-3.0, max_z_th=100.0, min_range=2.75,
                 max_range=100.0):
     """Range and height gate of a lidar scan (strict inequalities); ts rows follow (reference :337-358)."""

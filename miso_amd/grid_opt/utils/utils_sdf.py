@@ -129,21 +129,111 @@ class TriangleMesh:
             fh.write(f.tobytes())
 
 
+def box_mesh(bound) -> TriangleMesh:
+    """The six rectangles of the axis-aligned box ``bound`` ((3, 2) rows [min, max]) as twelve triangles."""
+    b = np.asarray(bound, dtype=np.float64).reshape(3, 2)
+    v = np.array([[x, y, z] for x in b[0] for y in b[1] for z in b[2]])
+    quads = [(0, 1, 3, 2), (4, 6, 7, 5), (0, 4, 5, 1), (2, 3, 7, 6), (0, 2, 6, 4), (1, 5, 7, 3)]
+    return TriangleMesh(v, [t for a, c, d, e in quads for t in ((a, c, d), (a, d, e))])
+
+
+_PLY_SCALARS = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2',
+                'uint16': 'u2', 'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4',
+                'double': 'f8', 'float64': 'f8'}
+
+
+def _ply_header(fh):
+    """-> (format, [(element name, count, [(property name, scalar dtype) | (name, count dtype, item dtype)])])"""
+    if fh.readline().strip() != b'ply':
+        raise ValueError("not a PLY file")
+    fmt, elements = None, []
+    while True:
+        raw = fh.readline()
+        if not raw:
+            raise ValueError("PLY header without end_header")
+        w = raw.decode('ascii', 'replace').split()
+        if not w or w[0] in ('comment', 'obj_info'):
+            continue
+        if w[0] == 'format':
+            fmt = w[1]
+        elif w[0] == 'element':
+            elements.append((w[1], int(w[2]), []))
+        elif w[0] == 'property':
+            if not elements:
+                raise ValueError("PLY property before any element")
+            types = w[2:4] if w[1] == 'list' else w[1:2]
+            if any(t not in _PLY_SCALARS for t in types):
+                raise ValueError(f"PLY property of unknown type: {' '.join(w)}")
+            elements[-1][2].append((w[-1],) + tuple(_PLY_SCALARS[t] for t in types))
+        elif w[0] == 'end_header':
+            break
+        else:
+            raise ValueError(f"cannot read PLY header line '{' '.join(w)}'")
+    if fmt not in ('binary_little_endian', 'ascii'):
+        raise ValueError(f"PLY format '{fmt}' is not read (binary_little_endian and ascii are)")
+    return fmt, elements
+
+
 def read_ply(path) -> TriangleMesh:
-    """Reads back what TriangleMesh.export_ply wrote."""
+    """A PLY mesh or point cloud -> TriangleMesh (no face element: zero triangles).  Reads ``binary_little_endian`` and
+    ``ascii`` files whose vertex element has x, y, z and any further scalar properties of any PLY scalar type (ScanNet's
+    colours, normals ...), which are skipped, and whose faces are uchar- or int-counted index lists of three; that
+    includes what TriangleMesh.export_ply writes.  ValueError: a face that is not a triangle, another format
+    (big-endian), a list property on the vertices, or an element that cannot be skipped (a list in a binary file)."""
     with open(path, 'rb') as fh:
-        nv = nf = None
-        while True:
-            line = fh.readline().decode('ascii').strip()
-            if line.startswith('element vertex'):
-                nv = int(line.split()[-1])
-            elif line.startswith('element face'):
-                nf = int(line.split()[-1])
-            elif line == 'end_header':
-                break
-        v = np.frombuffer(fh.read(12 * nv), dtype='<f4').reshape(nv, 3)
-        f = np.frombuffer(fh.read(13 * nf), dtype=[('n', 'u1'), ('idx', '<i4', (3,))])
-    return TriangleMesh(v, f['idx'])
+        fmt, elements = _ply_header(fh)
+        verts, tris = None, np.zeros((0, 3), dtype=np.int64)
+        tokens = fh.read().split() if fmt == 'ascii' else None
+        at = 0
+        for name, count, props in elements:
+            lists = [p for p in props if len(p) == 3]
+            if name == 'face' and len(props) >= 1 and len(lists) == 1 and props[0] is lists[0]:
+                extra = props[1:]
+                if any(len(p) == 3 for p in extra):
+                    raise ValueError("PLY face element with more than one list")
+                if fmt == 'ascii':
+                    width = 4 + len(extra)
+                    chunk = tokens[at:at + count * width]
+                    if len(chunk) < count * width or any(int(float(v)) != 3 for v in chunk[::width]):
+                        raise ValueError("PLY faces must be triangles")
+                    if count:
+                        tris = np.asarray(chunk, dtype=np.float64).reshape(count, width)[:, 1:4].astype(np.int64)
+                    at += count * width
+                else:
+                    dt = np.dtype([('n', '<' + lists[0][1]), ('idx', '<' + lists[0][2], (3,))] +
+                                  [(f'_{i}', '<' + p[1]) for i, p in enumerate(extra)])
+                    data = fh.read(dt.itemsize * count)
+                    n_ok = len(data) // dt.itemsize
+                    f = np.frombuffer(data[:n_ok * dt.itemsize], dtype=dt)
+                    if n_ok < count or (count and not (f['n'] == 3).all()):
+                        raise ValueError("PLY faces must be triangles")
+                    tris = f['idx'].astype(np.int64)
+                continue
+            if lists:
+                if name == 'vertex' or fmt != 'ascii':
+                    raise ValueError(f"PLY element '{name}' has a list property and cannot be " +
+                                     ("read" if name == 'vertex' else "skipped"))
+                for _ in range(count):                       # ascii: every list states its length
+                    for p in props:
+                        at += 1 + int(float(tokens[at])) if len(p) == 3 else 1
+                continue
+            if fmt == 'ascii':
+                block = np.asarray(tokens[at:at + count * len(props)], dtype=np.float64).reshape(count, len(props))
+                at += count * len(props)
+                cols = {p[0]: block[:, i] for i, p in enumerate(props)}
+            else:
+                dt = np.dtype([(p[0], '<' + p[1]) for p in props])
+                data = fh.read(dt.itemsize * count)
+                if len(data) < dt.itemsize * count:
+                    raise ValueError(f"PLY element '{name}' is cut short")
+                cols = np.frombuffer(data, dtype=dt)
+            if name == 'vertex':
+                if any(k not in [p[0] for p in props] for k in 'xyz'):
+                    raise ValueError("PLY vertex element without x, y, z")
+                verts = np.stack([np.asarray(cols[k], dtype=np.float64) for k in 'xyz'], axis=1)
+        if verts is None:
+            raise ValueError("PLY file without a vertex element")
+    return TriangleMesh(verts, tris)
 
 
 def save_mesh(model, bounds: torch.Tensor, save_path=None, resolution=256, device='cuda:0', flip_face=True,

@@ -1027,6 +1027,115 @@ def voxel_down_sample(points, voxel_size: float, n_live: Optional[torch.Tensor] 
 
 
 # --------------------------------------------------------------------------- #
+# exact nearest neighbour (utils_eval.nn_correspondance: pytorch3d knn_points, K = 1)
+# --------------------------------------------------------------------------- #
+NN_CELL_SPACINGS = 2.0       # default cell = this many point spacings
+NN_MAX_RINGS = 4             # default number of shells around a query's cell before the all-pairs kernel takes it
+NN_ALL_PAIRS_BELOW = 1 << 22  # nearest(): N * M below this goes to the all-pairs kernel (the index costs ~8 more launches)
+
+
+def _cloud(t: torch.Tensor, what: str) -> torch.Tensor:
+    """(N, 3) fp32 on the device, a row-strided view read in place (-> the tensor and its row stride in elements)"""
+    _require_hip(t)
+    assert t.ndim == 2 and t.shape[1] == 3, f"{what} is an (N, 3) cloud"
+    t = t.detach()
+    if t.shape[0] <= 1 or t.stride(1) != 1 or t.stride(0) < 3:
+        t = t.contiguous()
+    return t
+
+
+def _ld(t: torch.Tensor) -> int:
+    return t.stride(0) if t.shape[0] > 1 else 3
+
+
+def nn_default_cell(lo, hi, m: int) -> float:
+    """The cell of NearestIndex(cell=None): NN_CELL_SPACINGS point spacings, the spacing that of ``m`` points spread over
+    the surface of their bounding box (a sampled mesh fills surfaces, not the volume); a flat or linear cloud falls back
+    to its area or length, a single point to 1."""
+    e = [max(float(h) - float(l), 0.0) for l, h in zip(lo, hi)]
+    area = 2.0 * (e[0] * e[1] + e[1] * e[2] + e[2] * e[0])
+    if area > 0.0:
+        s = (area / max(m, 1)) ** 0.5
+    elif max(e) > 0.0:
+        s = max(e) / max(m, 1)
+    else:
+        return 1.0
+    return max(NN_CELL_SPACINGS * s, 1e-6 * max(max(e), 1e-30))
+
+
+class NearestIndex:
+    """A uniform cell list over ``tgt`` (M, 3) for exact 1-nearest-neighbour queries (miso_nn_plan / miso_nn_build,
+    csrc/nn.hip).  Building reads the targets' bounds back -- six floats, ONE device-to-host read per build -- to plan
+    the grid on the host; queries read nothing back.  ``cell=None``: nn_default_cell; ``max_rings=None``: NN_MAX_RINGS.
+    Rows with a non-finite coordinate are never a match and do not widen the bounds."""
+
+    def __init__(self, tgt: torch.Tensor, cell: Optional[float] = None, max_rings: Optional[int] = None):
+        tgt = _cloud(tgt, "tgt")
+        self.tgt, self.m = tgt, int(tgt.shape[0])
+        lib = _lib.load()
+        lo, hi = [0.0] * 3, [0.0] * 3
+        if self.m:
+            ok = torch.isfinite(tgt).all(dim=1, keepdim=True)
+            inf = float("inf")
+            b = torch.cat([torch.where(ok, tgt, inf).amin(dim=0), torch.where(ok, tgt, -inf).amax(dim=0)]).tolist()   # the one read
+            if all(abs(v) < inf for v in b):
+                lo, hi = b[:3], b[3:]
+        if cell is None:
+            cell = nn_default_cell(lo, hi, self.m)
+        self.plan = _lib.NnPlan()
+        _lib.check(lib.miso_nn_plan((C.c_float * 3)(*lo), (C.c_float * 3)(*hi), float(cell), self.m,
+                                    int(NN_MAX_RINGS if max_rings is None else max_rings), C.byref(self.plan)), "miso_nn_plan")
+        self.cell = float(self.plan.cell)
+        self.dims = tuple(int(d) for d in self.plan.dims)
+        self.workspace = None
+        if self.m:
+            self.workspace = torch.empty(int(lib.miso_nn_workspace_bytes(C.byref(self.plan))), device=tgt.device,
+                                         dtype=torch.uint8)
+            _lib.check(lib.miso_nn_build(C.byref(self.plan), _ptr(tgt), _ld(tgt), _ptr(self.workspace), _stream(tgt)),
+                       "miso_nn_build")
+
+    def query(self, src: torch.Tensor, out=None):
+        """-> (d2 (N,) fp32, idx (N,) int64, stats (2,) int32 = {finished by the shells, sent to the all-pairs kernel}), all
+        on the device; nothing is read back, so with ``out`` = (d2, idx, stats) the call replays inside a captured graph.
+        (+inf, -1) for a query without a match.  One query at a time per index: the workspace holds the query's list."""
+        src = _cloud(src, "src")
+        n = int(src.shape[0])
+        if out is None:
+            out = (torch.empty(n, device=src.device, dtype=torch.float32), torch.empty(n, device=src.device, dtype=torch.int64),
+                   torch.empty(2, device=src.device, dtype=torch.int32))
+        d2, idx, stats = out
+        assert d2.is_cuda and d2.dtype == torch.float32 and d2.is_contiguous() and d2.numel() >= n
+        assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() >= n
+        assert stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= 2
+        _lib.check(_lib.load().miso_nn_query(C.byref(self.plan), _ptr(self.workspace), _ptr(src), _ld(src), n, _ptr(d2),
+                                             _ptr(idx), _ptr(stats), _stream(src)), "miso_nn_query")
+        return d2, idx, stats
+
+
+def nearest_all_pairs(src: torch.Tensor, tgt: torch.Tensor):
+    """The all-pairs kernel for every query (miso_nn_all_pairs): -> (d2, idx), the bits NearestIndex.query returns."""
+    src, tgt = _cloud(src, "src"), _cloud(tgt, "tgt")
+    n, m = int(src.shape[0]), int(tgt.shape[0])
+    d2 = torch.empty(n, device=src.device, dtype=torch.float32)
+    idx = torch.empty(n, device=src.device, dtype=torch.int64)
+    _lib.check(_lib.load().miso_nn_all_pairs(_ptr(tgt), _ld(tgt), m, _ptr(src), _ld(src), n, _ptr(d2), _ptr(idx),
+                                             _stream(src)), "miso_nn_all_pairs")
+    return d2, idx
+
+
+def nearest(src: torch.Tensor, tgt: torch.Tensor, cell: Optional[float] = None):
+    """For every row of ``src`` (N, 3) the squared distance to, and the index of, its nearest row of ``tgt`` (M, 3): the
+    smallest (d2, index) pair, d2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2 in fp32.  -> (d2 (N,) fp32, idx (N,) int64) on
+    the device; (+inf, -1) where there is no match.  Small problems (N M < NN_ALL_PAIRS_BELOW) take the all-pairs kernel,
+    the rest a NearestIndex: the same bits either way."""
+    _require_hip(src, tgt)
+    if int(src.shape[0]) * int(tgt.shape[0]) < NN_ALL_PAIRS_BELOW:
+        return nearest_all_pairs(src, tgt)
+    d2, idx, _ = NearestIndex(tgt, cell=cell).query(src)
+    return d2, idx
+
+
+# --------------------------------------------------------------------------- #
 # fused atlas query (GridAtlas.query_feature / forward in one launch)
 # --------------------------------------------------------------------------- #
 class AtlasQuery:

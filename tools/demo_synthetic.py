@@ -207,6 +207,24 @@ def render_views(grid_atlas, dataset, cam, out_dir):
         print(f"keyframe {k}: {int(mask.sum())} of {mask.numel()} pixels hit, images in {out_dir}")
 
 
+def evaluate_mapping_quality(grid_atlas, save_dir, resolution):
+    """demo/full_slam_scannet.py:161-191 against the analytic room: save_mesh (per submap, at its aligned pose) ->
+    sample_points_from_mesh -> filter_points_by_oriented_bound -> compute_chamfer_metrics.  None when no submap has a
+    surface (a quick run's first submap may have none)."""
+    # the submaps' meshes in the world frame, as save_submap places them (demo/build_submaps.py:93-103), taken together
+    parts = [save_submap(grid_atlas, i, join(save_dir, 'submaps'), resolution, 'aligned') for i in range(grid_atlas.num_submaps)]
+    offsets = np.cumsum([0] + [len(m.vertices) for m in parts[:-1]])
+    mesh = utils_sdf.TriangleMesh(np.concatenate([m.vertices for m in parts]),
+                                  np.concatenate([m.triangles + o for m, o in zip(parts, offsets)]))
+    if len(mesh.triangles) == 0:
+        print("no submap produced a triangle: nothing to grade")
+        return None
+    gt = utils_eval.sample_points_from_mesh(utils_sdf.box_mesh(ROOM), mesh_sample_point=200000, voxel_down_sample_res=0.02, seed=1)
+    pred = utils_eval.sample_points_from_mesh(mesh, mesh_sample_point=200000, voxel_down_sample_res=0.02, seed=2)
+    pred = utils_eval.filter_points_by_oriented_bound(pred, utils_eval.OrientedBox.from_points(gt, buffer=0.05))
+    return utils_eval.compute_chamfer_metrics(pred, gt, threshold=0.05, truncation_acc=0.50, truncation_com=0.50)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--save_dir', type=str, default='./results/demo/synthetic')
@@ -216,6 +234,8 @@ def main():
                     help='write depth and normal images of the aligned atlas from the first and last keyframe to DIR')
     ap.add_argument('--voxel_size', type=float, default=None,
                     help='voxel down-sample every batch of the dataset (the ScanNet demo maps with 0.01); default: off')
+    ap.add_argument('--eval_mesh', action='store_true',
+                    help="grade the aligned atlas's mesh against the analytic room (Chamfer / F-score), into the JSON")
     args = ap.parse_args()
     if args.quick:
         H, W, n_kf, args.submap_size, n_rays = 60, 80, 12, 4, 120
@@ -256,9 +276,13 @@ def main():
     _, info_sf, sf_bef, sf_aft = perturb_and_align(model_path, cfg, dataset, noise_rot, noise_tra, shared_field=True)
     print("Shared-field features, before:\n", json.dumps(sf_bef, indent=4))
     print("Shared-field features, after:\n", json.dumps(sf_aft, indent=4))
+    result = {'before_alignment': metrics_bef, 'after_alignment': metrics_aft,
+              'shared_field_before': sf_bef, 'shared_field_after': sf_aft}
+    if args.eval_mesh:
+        result['mesh_quality'] = evaluate_mapping_quality(grid_atlas, args.save_dir, args.mesh_res)
+        print("Meshes of the aligned submaps against the room:\n", json.dumps(result['mesh_quality'], indent=4))
     with open(join(args.save_dir, 'alignment_result.json'), 'w') as f:
-        json.dump({'before_alignment': metrics_bef, 'after_alignment': metrics_aft,
-                   'shared_field_before': sf_bef, 'shared_field_after': sf_aft}, f, indent=4)
+        json.dump(result, f, indent=4)
     assert sf_aft['rmse_tran (cm)'] <= 0.2 * sf_bef['rmse_tran (cm)'] and sf_aft['rmse_deg'] <= 0.2 * sf_bef['rmse_deg'], \
         "alignment on the shared field did not bring the submaps back"
     it = align_info['hier_latent_level1_L2']['iteration_results']
