@@ -6,12 +6,12 @@
 // wavefront per 64 world points (lane = point), per chunk
 //   1. the forward again (atlas_mean, atlas_eval.hpp: same frame change, bound test, sum, count and mean) and the
 //      decoder forward with its ReLU signs kept -- nothing is saved between the two launches but the SDF itself;
-//   2. the decoder backward of sdf_bwd_kernel / sdf_train_kernel: d sdf -> d mean in accumulator layout -> the
-//      wavefront's LDS tile -> one row per lane, divided by the lane's count: that row is d feats of EVERY submap the
+//   2. the decoder backward (decoder.hpp): d sdf -> d mean in accumulator layout -> the wavefront's LDS tile
+//      (dfeat_tile.hpp) -> one row per lane, divided by the lane's count: that row is d feats of EVERY submap the
 //      point is inside (the count is a constant, and the bound mask is not differentiated: autograd sees
 //      inside * interp with a boolean mask);
 //   3. per submap that some lane is inside (poses and bounds are wave-uniform):
-//        grid   the row-major float-atomic scatter of sdf_bwd_kernel into the submap's level gradients (levels whose
+//        grid   the row-major float-atomic scatter (scatter_tile) into the submap's level gradients (levels whose
 //               gradient pointer is NULL -- a locked submap -- are skipped);
 //        x      d x_local by the corner loop (lane = point), d x_world += R_sw^T d x_local;
 //        pose   the table row is x_local = R_sw x_world + t_sw: dR_sw[j][k] += d x_local[j] x_world[k],
@@ -39,8 +39,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 template <int C, int L, int H, int NH, bool SPLIT>
 __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK b, const float* __restrict__ packed) {
   constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2, NF = 2 * KS0, MW = (NH + 1) * RT;
-  constexpr int FP = ((F + 3) / 4) * 4 + 4;      // d-feat row pitch in LDS: 16-B aligned, conflict-free b128 writes
-  constexpr int REC = 8;                         // ints per (point, level) cell record
+  constexpr int FP = dfeat_pitch(F), REC = CELL_REC;      // the d-feat tile and the cell records: dfeat_tile.hpp
   constexpr int WAVE_LDS = 64 * FP + 64 * L * REC;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const PackLayout pl(F, H, NH);
@@ -108,15 +107,7 @@ __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK 
     if constexpr (SPLIT) decoder_bwd_split<F, H, NH, false>(s_bwd, lane, maskB, mw, ds, df);
     else decoder_bwd_exact<F, H, NH>(whT, w0T, wo, lane, mw, ds, df);
     // ---- accumulator layout -> LDS tile -> one row per lane; d feats_s = d mean / count ------------------------------
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int gq = 0; gq < (F + 7) / 8; ++gq) {
-        const int f0 = 8 * gq + 4 * hi;
-        if (f0 < F)
-          *reinterpret_cast<float4*>(dF + (32 * t + (lane & 31)) * FP + f0) =
-              make_float4(df[t][4 * gq], df[t][4 * gq + 1], df[t][4 * gq + 2], df[t][4 * gq + 3]);
-      }
+    dfeat_to_tile<F, 2>(df, dF, lane & 31, hi);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -150,16 +141,7 @@ __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK 
         Axis ay = axis_coord(xl[1], g.bmin[1], g.bmax[1], lv.Y, g.flags);
         Axis az = axis_coord(xl[2], g.bmin[2], g.bmax[2], lv.Z, g.flags);
         Cell c = make_cell(ax, ay, az, lv);
-        if ((scatter_mask >> l) & 1u) {      // the cell record of (point, level); a lane outside the submap adds nothing
-          int flags = (c.inx[0] ? 1 : 0) | (c.inx[1] ? 2 : 0) | (c.iny[0] ? 4 : 0) | (c.iny[1] ? 8 : 0) |
-                      (c.inz[0] ? 16 : 0) | (c.inz[1] ? 32 : 0);
-          if (!inside) flags = 0;
-          int* r = rec + (lane * L + l) * REC;
-          *reinterpret_cast<int4*>(r) = make_int4(c.k0 * lv.sZ + c.j0 * lv.sY + c.i0 * lv.sX, flags,
-                                                  __float_as_int(c.wx[1]), __float_as_int(c.wy[1]));
-          *reinterpret_cast<int4*>(r + 4) = make_int4(__float_as_int(c.wz[1]), __float_as_int(c.wx[0]),
-                                                      __float_as_int(c.wy[0]), __float_as_int(c.wz[0]));
-        }
+        if ((scatter_mask >> l) & 1u) write_cell_record(rec + (lane * L + l) * REC, c, lv, inside);
         if (want_x && inside) {      // d x_local of this level: the corner loop of sdf_bwd_kernel, lane = point
           float sx_ = 0.f, sy_ = 0.f, sz_ = 0.f;
 #pragma unroll
@@ -199,38 +181,10 @@ __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK 
         }
       }
       if (scatter_mask) {
-        // the scatter of sdf_bwd_kernel: 2 C consecutive lanes cover the x-pair (i0, i0 + 1) x C channels = one contiguous
-        // run of 2 C floats, one atomic instruction per 64-byte request; cells broadcast from the records
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        constexpr int LPR = 2 * C, SLOTS = 64 / LPR;
-        const int slot = lane / LPR, dx = (lane / C) & 1, ch = lane % C;
-#pragma unroll 1
-        for (int pg = 0; pg < 64 / SLOTS; ++pg) {
-          const int pt = pg * SLOTS + slot;
-#pragma unroll
-          for (int l = 0; l < L; ++l) {
-            if (!((scatter_mask >> l) & 1u)) continue;
-            const LevelK& lv = g.lv[l];
-            const int* r = rec + (pt * L + l) * REC;
-            const int4 r0 = *reinterpret_cast<const int4*>(r);
-            const int4 r1 = *reinterpret_cast<const int4*>(r + 4);
-            const int fl = r0.y;
-            if (!((fl >> dx) & 1)) continue;
-            const float v = dF[pt * FP + l * C + ch];
-            const float cwx = dx ? __int_as_float(r0.z) : __int_as_float(r1.y);
-            const float cwy[2] = {__int_as_float(r1.z), __int_as_float(r0.w)};
-            const float cwz[2] = {__int_as_float(r1.w), __int_as_float(r1.x)};
-            float* base = lv.grad + r0.x + dx * lv.sX + ch;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int dy = q & 1, dz = q >> 1;
-              if (((fl >> (2 + dy)) & 1) && ((fl >> (4 + dz)) & 1))
-                atomic_add_f32(base + dy * lv.sY + dz * lv.sZ, v * ((cwx * cwy[dy]) * cwz[dz]));
-            }
-          }
-        }
+        scatter_tile<C, L, false, const GridK&>(g, scatter_mask, dF, rec, 64, lane);      // (no touched flags: the atlas keeps none)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();      // the next submap overwrites the records
       }
@@ -279,7 +233,7 @@ struct AtlasBwdPlan {
 };
 static AtlasBwdPlan plan_atlas_bwd(int C, int L, int H, int NH, bool split, int n_submaps, bool poses) {
   const PackLayout pl(C * L, H, NH);
-  const int F = C * L, FP = ((F + 3) / 4) * 4 + 4, wave_lds = 64 * FP + 64 * L * 8;
+  const int F = C * L, wave_lds = 64 * dfeat_pitch(F) + 64 * L * CELL_REC;
   const int pack = split ? pl.total_all - pl.s_w0 + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
   const int pose = poses ? (n_submaps * 12 + 3) / 4 * 4 : 0;
   const auto bytes = [&](int wavefronts) { return (size_t)(pack + wavefronts * wave_lds + pose) * sizeof(float); };

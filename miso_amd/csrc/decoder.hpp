@@ -1,6 +1,17 @@
 // Frozen-decoder MLP (MLPNet: grid_opt/models/modules.py:11-32) on the matrix cores: the packed-weight layout shared by
-// mlp_pack_kernel and every kernel that decodes (sdf_fused.hip, sdf_train.hip, atlas.hip), the register-level helpers of the ReLU / gate
-// passes, and the split-precision (bf16x3, mlp_split.hpp) forward and backward chains.
+// mlp_pack_kernel and every kernel that decodes, the register-level helpers of the ReLU / gate passes, and the decoder
+// chains:
+//   decoder_fwd_split / decoder_bwd_split   bf16x3 split products (mlp_split.hpp), the default arithmetic
+//   decoder_fwd_exact / decoder_bwd_exact   exact fp32 chains, behind MISO_F_EXACT_F32
+// Who runs them:       forward                                backward
+//   sdf_fused.hip      sdf_fwd_kernel                         sdf_bwd_kernel
+//   sdf_train.hip      sdf_train_kernel: the split chains (HALF: 32-point trips too); its exact chains are written out
+//                      in the kernel -- through decoder_*_exact ten of its exact instantiations took 1 .. 28 VGPRs more
+//                      and the step was 0.3 - 0.6 % slower (profiles/decoder_shared.json)
+//   atlas_eval.hpp     its decode() (atlas.hip, trace.hip)    --
+//   atlas_bwd.hip      atlas_sdf_bwd_kernel                   the same kernel
+// decoder_wgrad.hip keeps chains of its own: it holds every layer's activations and interleaves the outer products of the
+// weight gradients, a different computation.  What happens to d feats behind a backward chain is in dfeat_tile.hpp.
 #pragma once
 #include "common.hpp"
 #include "mlp_split.hpp"
@@ -394,9 +405,20 @@ __device__ __forceinline__ void decoder_bwd_split(const uint32_t* __restrict__ s
   }
 }
 
-// The exact fp32 chains of the forward (v_mfma_f32_32x32x2_f32; the accumulators of a layer ARE the next layer's B operand:
-// sdf_fused.hip's header), as sdf_fwd_kernel and atlas_sdf_kernel run them behind MISO_F_EXACT_F32.  w0p / whp / b0 / bh / wo:
-// the fp32 pack's forward part in LDS.  Same outputs as decoder_fwd_split (p0 / p1: this lane's partial output sums).
+// A lane index the compiler takes for a new value at this point, for decoder_bwd_exact inside sdf_bwd_kernel's chunk
+// loop.  The chain forms every LDS address of its weights from `lane`; given the kernel's own lane index, those addresses
+// (one per k-step and output-weight row) are hoisted out of the loop and stay live across it: sdf_bwd_kernel<4, 4, 64, 1,
+// true, false, false> then takes 211 VGPRs (205 with the chain written out in the kernel), 170 with kept_in_loop(lane),
+// where the addresses are one base register and immediate offsets (profiles/decoder_shared.json lists every shape).
+// sdf_fwd_kernel and the atlas kernels pass their lane index as it is: they called these chains before there was a
+// kept_in_loop, their registers are what they were, and with it their instruction streams would change for no gain.
+__device__ __forceinline__ int kept_in_loop(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// The exact fp32 chains of the forward (v_mfma_f32_32x32x2_f32, behind MISO_F_EXACT_F32; the accumulators of a layer ARE the
+// next layer's B operand: sdf_fused.hip's header).  w0p / whp / b0 / bh / wo: the fp32 pack's forward part in LDS.  Same outputs as decoder_fwd_split (p0 / p1: this lane's partial output sums).
 template <int F, int H, int NH, bool PIN_FMA = false, int FN = 0>
 __device__ __forceinline__ void decoder_fwd_exact(const float* __restrict__ w0p, const float* __restrict__ whp,
                                                   const float* __restrict__ b0, const float* __restrict__ bh,
@@ -518,7 +540,7 @@ __device__ __forceinline__ void decoder_fwd_exact(const float* __restrict__ w0p,
   }
 }
 
-// The exact fp32 chains of the backward, as sdf_bwd_kernel runs them: d sdf of the two point tiles (ds[t]) -> d feats in
+// The exact fp32 chains of the backward: d sdf of the two point tiles (ds[t]) -> d feats in
 // accumulator layout, gated by the sign words mw of decoder_fwd_exact.  whT / w0T / wo: the fp32 pack's transposed weights
 // and output weights in LDS.  Same outputs as decoder_bwd_split.
 template <int F, int H, int NH>

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
   // defer_mask are NOT scattered here: grad_pull_kernel (grad_pull.hip) forms their gradient owner-computes.
   // debug: ablation switches (MISO_DEBUG_BWD, dev only): 1 = no atomics, 8 = no scatter; bit 16 (set by the
   // launcher for MISO_F_GRAD_SDF_SORTED): gsdf is already in the binned order.
-  constexpr int F = C * L, RT = H / 32, KS1 = H / 2;
+  constexpr int F = C * L, RT = H / 32;
   constexpr int MW = (NH + 1) * RT;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const PackLayout pl(F, H, NH);
@@ -269,8 +269,7 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
   const float* w0T = smem + (pl.o_w0T - pl.o_whT);
   const float* wo = smem + nb;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
-  constexpr int FP = ((F + 3) / 4) * 4 + 4;  // d-feat row pitch: 16-B aligned, conflict-free b128 writes
-  constexpr int REC = 8;                     // ints per (point, level) cell record
+  constexpr int FP = dfeat_pitch(F), REC = CELL_REC;      // the tile and the cell records: dfeat_tile.hpp
   constexpr int WAVE_LDS = 64 * FP + 64 * L * REC;
   // debug bit 32 (set by the launcher when nothing is scattered from here): only the d-feat tile is
   // allocated per wave -- 50 KB per workgroup instead of 74, i.e. three workgroups per CU
@@ -303,79 +302,16 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
       mask_operand_from_bits<H, NH, false>(mw, maskB);
       decoder_bwd_split<F, H, NH, false>(reinterpret_cast<const uint32_t*>(smem), lane, maskB, mw, ds, df);
     } else {
-    // d(last hidden) = wo * ds, gated.  Two accumulator sets ping-pong.
-    f32x16 dbuf[2][RT][2];
-#pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        float wv = wo[32 * r + row_of(j, hi)];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-          dbuf[0][r][t][j] = gate(wv * ds[t], mw[NH * RT + r], t, j);
-      }
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh) {
-      const int h = NH - 1 - hh;
-      const int ci = hh & 1, ni = ci ^ 1;
-#pragma unroll
-      for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) { dbuf[ni][r][0][j] = 0.0f; dbuf[ni][r][1][j] = 0.0f; }
-#pragma unroll
-      for (int rp = 0; rp < RT; ++rp)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          const int ks = rp * 16 + j;
-#pragma unroll
-          for (int r = 0; r < RT; ++r) {
-            float a = whT[((h * KS1 + ks) * 64 + lane) * RT + r];
-            dbuf[ni][r][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, dbuf[ci][rp][0][j], dbuf[ni][r][0], 0, 0, 0);
-            dbuf[ni][r][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, dbuf[ci][rp][1][j], dbuf[ni][r][1], 0, 0, 0);
-          }
-        }
-#pragma unroll
-      for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int j = 0; j < 16; ++j)
-            dbuf[ni][r][t][j] = gate(dbuf[ni][r][t][j], mw[h * RT + r], t, j);
-    }
-    f32x16 (&d)[RT][2] = dbuf[NH & 1];
-    // d feats = W0^T d   (one 32-row tile; rows >= F are zero)
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { df[0][j] = 0.0f; df[1][j] = 0.0f; }
-#pragma unroll
-    for (int rp = 0; rp < RT; ++rp)
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        float a = w0T[(rp * 16 + j) * 64 + lane];
-        df[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, d[rp][0][j], df[0], 0, 0, 0);
-        df[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, d[rp][1][j], df[1], 0, 0, 0);
-      }
+      decoder_bwd_exact<F, H, NH>(whT, w0T, wo, kept_in_loop(lane), mw, ds, df);
     }      // exact fp32 chains
-    // ---- scatter into the level gradients ----------------------------------------
-    // The L2 executes fp32 atomics per 64-byte request (~21 G requests/s on MI355X,
-    // tools/ubench/atomics.hip), however many of its 16 dwords carry data.  So the
-    // scatter runs "row-major": the 2*C consecutive lanes of a group cover the
-    // x-pair (i0, i0+1) x C channels = one contiguous run of 2*C floats, and one
-    // atomic instruction serves 64/(2C) (point, row) pairs.  d feats move from the
-    // accumulator layout to that lane order through a per-wave LDS tile; the cell
+    // ---- scatter into the level gradients (dfeat_tile.hpp) ------------------------
+    // d feats move from the accumulator layout to the scatter's lane order through a per-wave LDS tile; the cell
     // of every (point, level) is computed once (lane = point) and broadcast from LDS.
     memory_phase(true, g.tune);
     if (WANT_GRID && !(debug & 8)) {
       float* dF = wave_lds;                         // [64][FP]
       int* rec = reinterpret_cast<int*>(wave_lds + 64 * FP);   // [64][L][REC]
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int gq = 0; gq < (F + 7) / 8; ++gq) {
-          const int f0 = 8 * gq + 4 * hi;
-          if (f0 < F)
-            *reinterpret_cast<float4*>(dF + (32 * t + (lane & 31)) * FP + f0) =
-                make_float4(df[t][4 * gq], df[t][4 * gq + 1], df[t][4 * gq + 2], df[t][4 * gq + 3]);
-        }
+      dfeat_to_tile<F, 2>(df, dF, lane & 31, hi);
       if (scatter_mask) {     // cell records only where a level is still scattered from here
         const int64_t p = chunk * 64 + lane;
         const bool valid = p < n;
@@ -388,58 +324,14 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
           Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
           Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
           Cell c = make_cell(ax, ay, az, lv);
-          int flags = (c.inx[0] ? 1 : 0) | (c.inx[1] ? 2 : 0) | (c.iny[0] ? 4 : 0) | (c.iny[1] ? 8 : 0) |
-                      (c.inz[0] ? 16 : 0) | (c.inz[1] ? 32 : 0);
-          if (!valid) flags = 0;
-          int* r = rec + (lane * L + l) * REC;
-          *reinterpret_cast<int4*>(r) = make_int4(c.k0 * lv.sZ + c.j0 * lv.sY + c.i0 * lv.sX, flags,
-                                                  __float_as_int(c.wx[1]), __float_as_int(c.wy[1]));
-          *reinterpret_cast<int4*>(r + 4) = make_int4(__float_as_int(c.wz[1]), __float_as_int(c.wx[0]),
-                                                      __float_as_int(c.wy[0]), __float_as_int(c.wz[0]));
+          write_cell_record(rec + (lane * L + l) * REC, c, lv, valid);
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (dfeat_out) {
-        // the chunk's 64 rows are contiguous in the (N,F) buffer: coalesced 16-B stores
-        float* dst = dfeat_out + chunk * 64 * F;
-        const int64_t rows_left = n - chunk * 64;
-        for (int i = lane; i < 64 * F / 4; i += 64) {
-          const int row = (i * 4) / F, col = (i * 4) % F;
-          if (row < rows_left)
-            *reinterpret_cast<float4*>(dst + row * F + col) = *reinterpret_cast<const float4*>(dF + row * FP + col);
-        }
-      }
-      constexpr int LPR = 2 * C, SLOTS = 64 / LPR;
-      const int slot = lane / LPR, dx = (lane / C) & 1, ch = lane % C;
-#pragma unroll 1
-      for (int pg = 0; pg < (scatter_mask ? 64 / SLOTS : 0); ++pg) {
-        const int pt = pg * SLOTS + slot;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-          const LevelK& lv = g.lv[l];
-          if (!lv.grad || ((g.ignore_mask >> l) & 1u) || ((defer_mask >> l) & 1u)) continue;
-          const int* r = rec + (pt * L + l) * REC;
-          const int4 r0 = *reinterpret_cast<const int4*>(r);
-          const int4 r1 = *reinterpret_cast<const int4*>(r + 4);
-          const int fl = r0.y;
-          if (!((fl >> dx) & 1)) continue;
-          const float v = dF[pt * FP + l * C + ch];
-          const float wx = dx ? __int_as_float(r0.z) : __int_as_float(r1.y);
-          const float wy[2] = {__int_as_float(r1.z), __int_as_float(r0.w)};
-          const float wz[2] = {__int_as_float(r1.w), __int_as_float(r1.x)};
-          float* base = lv.grad + r0.x + dx * lv.sX + ch;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int dy = q & 1, dz = q >> 1;
-            if (((fl >> (2 + dy)) & 1) && ((fl >> (4 + dz)) & 1) && !(debug & 1)) {
-              atomic_add_f32(base + dy * lv.sY + dz * lv.sZ, v * ((wx * wy[dy]) * wz[dz]));
-              if (ch == 0) touch_chunk(lv, r0.x + dx * lv.sX + dy * lv.sY + dz * lv.sZ);   // C floats: one chunk
-            }
-          }
-        }
-      }
+      if (dfeat_out) tile_to_rows<F, 64>(dF, dfeat_out + chunk * 64 * F, n - chunk * 64, lane);
+      scatter_tile<C, L, true, GridK>(g, scatter_mask, dF, rec, 64, lane, (debug & 1) != 0);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
@@ -530,7 +422,7 @@ static hipError_t launch_bwd_t(FusedShape<C, L, H, NH>, const GridK& g, const fl
                                const int* perm, float* dfeat_out, uint32_t defer_mask, bool gsdf_sorted,
                                hipStream_t s) {
   PackLayout pl(C * L, H, NH);
-  constexpr int F = C * L, FP = ((F + 3) / 4) * 4 + 4, WAVE_LDS = 64 * FP + 64 * L * 8;
+  constexpr int F = C * L, FP = dfeat_pitch(F), WAVE_LDS = 64 * FP + 64 * L * CELL_REC;
   bool lean = want_grid && !gx && dfeat_out != nullptr;      // every gradient level deferred to the pull?
   for (int l = 0; l < L && lean; ++l)
     if (g.lv[l].grad && !((g.ignore_mask >> l) & 1u) && !((defer_mask >> l) & 1u)) lean = false;

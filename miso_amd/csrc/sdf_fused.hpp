@@ -1,11 +1,13 @@
 // What the fused decoder kernels share across their translation units -- sdf_fused.hip (forward, backward, weight pack),
 // sdf_train.hip (the one-launch training step) and atlas.hip (the atlas query, which uses the host part only): the
-// wavefront priority of a memory phase, the chunk schedule of the persistent waves, the list of instantiated decoder
-// shapes with its dispatcher, and the choice between the two decoder arithmetics.
+// decoder chains (decoder.hpp), the d-feat tile and scatter behind a backward chain (dfeat_tile.hpp), the wavefront
+// priority of a memory phase, the chunk schedule of the persistent waves, the list of instantiated decoder shapes with
+// its dispatcher, and the choice between the two decoder arithmetics.
 #pragma once
 #include <stdlib.h>
 
 #include "decoder.hpp"
+#include "dfeat_tile.hpp"
 #include "launch.hpp"
 
 namespace miso {

@@ -7,14 +7,16 @@
 // of its matrix and vector clocks, but a wavefront waiting for its corner gathers costs the neighbour's matrix chain
 // nothing.  The backward pass is ~all matrix work (it reads 20 B per point), the forward has the long memory phase:
 // with both in one kernel a wavefront's gathers hide behind TWICE the matrix work of its neighbour.
-// The bodies are those of sdf_fwd_kernel and sdf_bwd_kernel (sdf_fused.hip; kept separate: they also serve inference, the unsorted path, the
-// coordinate backward and levels scattered from the backward); the sign bits stay in the registers they were formed
-// in, d loss / d sdf moves between the point-per-lane layout of the loss and the two 32-point tiles of the backward
-// with two lane reads.
+// The split decoder chains (decoder.hpp) and the d-feat tile, cell records and scatter (dfeat_tile.hpp) are those of
+// sdf_fwd_kernel and sdf_bwd_kernel (sdf_fused.hip; the kernels stay separate: those two also serve inference, the
+// unsorted path, the coordinate backward and levels scattered from the backward).  The exact fp32 chains are written out
+// here, each tile-1 statement under `if (!HALF)`: through decoder_fwd_exact / decoder_bwd_exact this kernel's exact
+// instantiations took more VGPRs and more time (decoder.hpp's header).  The sign bits stay in the registers they were
+// formed in, d loss / d sdf moves between the point-per-lane layout of the loss and the two 32-point tiles of the
+// backward with two lane reads.
 // SCAT: levels with a gradient that are NOT in defer_mask (bricks beyond what the pull owns: cfg-3's fine level; or
-// every level of an unbinned batch, perm == nullptr) are scattered from here with float atomics exactly as
-// sdf_bwd_kernel<.., true, false> does it -- per-point cell records kept in LDS from the forward's gather, lanes
-// (point slot, dx, channel) walking the chunk's d-feat tile.  dfeat_out may then be null (nothing deferred).
+// every level of an unbinned batch, perm == nullptr) are scattered from here with float atomics (scatter_tile) -- the
+// per-point cell records are kept in LDS from the forward's gather.  dfeat_out may then be null (nothing deferred).
 // HALF: 32 points per wavefront and trip instead of 64 -- lanes 32..63 mirror lanes 0..31 (the same point, the same gather),
 // only the first of the two 32-point matrix tiles is computed.  For batches that are one chunk per wavefront anyway (a
 // few thousand samples: Newer College's 6 144, the tracker's windows): the wavefront's chain of matrix instructions halves,
@@ -30,9 +32,8 @@ namespace miso {
 #define MISO_TRAIN_GATHER_LEVEL(lv, c, fo) gather_level<C>(lv, c, fo)
 #endif
 // A chunk's input side (sdf_train_kernel): its point, label row and corner gathers (-> f) and, scattering, its cell records
-// (-> recw: base offset, in-bound bits, the six weights, as sdf_bwd_kernel forms them from the point again).  A macro, not a
-// lambda: the non-scattering instantiations must compile to the loop they had before the scattering ones learnt to
-// request a chunk's gathers one chunk early.
+// (-> recw: write_cell_record).  A macro, not a lambda: the non-scattering instantiations must compile to the loop they
+// had before the scattering ones learnt to request a chunk's gathers one chunk early.
 #define MISO_TRAIN_GATHER(CHUNK_, RECW_, P_O_, PO_O_, VALID_O_, LIN_O_)                                        \
   {                                                                                                         \
     const int64_t gp_ = HALF ? (CHUNK_) * 32 + (lane & 31) : (CHUNK_) * 64 + lane; \
@@ -61,18 +62,12 @@ _Pragma("unroll") \
         Cell c = make_cell(ax, ay, az, lv); \
       MISO_TRAIN_GATHER_LEVEL(lv, c, &f[l * C]); \
         if (SCAT && ((scatter_mask >> l) & 1u)) { \
-          const int flags = (c.inx[0] ? 1 : 0) | (c.inx[1] ? 2 : 0) | (c.iny[0] ? 4 : 0) | (c.iny[1] ? 8 : 0) | \
-                            (c.inz[0] ? 16 : 0) | (c.inz[1] ? 32 : 0); \
-          int* r = (RECW_) + (row_l * L + l) * REC; \
-          *reinterpret_cast<int4*>(r) = make_int4(c.k0 * lv.sZ + c.j0 * lv.sY + c.i0 * lv.sX, flags, \
-                                                  __float_as_int(c.wx[1]), __float_as_int(c.wy[1])); \
-          *reinterpret_cast<int4*>(r + 4) = make_int4(__float_as_int(c.wz[1]), __float_as_int(c.wx[0]), \
-                                                      __float_as_int(c.wy[0]), __float_as_int(c.wz[0])); \
+          write_cell_record((RECW_) + (row_l * L + l) * REC, c, lv, true); \
         } \
       } \
     } else if (SCAT) { \
 _Pragma("unroll") \
-      for (int l = 0; l < L; ++l) (RECW_)[(row_l * L + l) * REC + 1] = 0; \
+      for (int l = 0; l < L; ++l) (RECW_)[(row_l * L + l) * REC + CELL_REC_FLAGS] = 0; \
     } \
     memory_phase(false, g.tune, wave < NW / 2); \
     P_O_ = gp_; PO_O_ = gpo_; VALID_O_ = gvalid_; LIN_O_ = glin_; \
@@ -85,8 +80,7 @@ __global__ __launch_bounds__(64 * NW, 2) MISO_FUSED_KERNEL_ATTR void sdf_train_k
                                                           uint32_t defer_mask) {
   constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2, KS1 = H / 2;
   constexpr int MW = (NH + 1) * RT;
-  constexpr int FP = ((F + 3) / 4) * 4 + 4;      // d-feat row pitch in LDS: 16-B aligned, conflict-free b128 writes
-  constexpr int REC = 8;                         // ints per (point, level) cell record (SCAT)
+  constexpr int FP = dfeat_pitch(F), REC = CELL_REC;      // the d-feat tile and (SCAT) the cell records: dfeat_tile.hpp
   // SCAT: the cell records are double-buffered when the launcher found room for a second block (MISO_TUNE_ROTATE) -- the
   // next chunk's gathers are then issued in FRONT of this chunk's atomics, see the loop
   const bool rotate = SCAT && C * L <= MISO_ROTATE_MAX_F && (g.tune & MISO_TUNE_ROTATE) != 0;
@@ -344,64 +338,13 @@ __global__ __launch_bounds__(64 * NW, 2) MISO_FUSED_KERNEL_ATTR void sdf_train_k
     }
     // ---- d-feat rows: accumulator layout -> LDS tile -> 64 contiguous rows of the (N, F) buffer, 16-B stores --------
     memory_phase(true, g.tune);
-#pragma unroll
-    for (int t = 0; t < (HALF ? 1 : 2); ++t)
-#pragma unroll
-      for (int gq = 0; gq < (F + 7) / 8; ++gq) {
-        const int f0 = 8 * gq + 4 * hi;
-        if (f0 < F)
-          *reinterpret_cast<float4*>(dF + (32 * t + (lane & 31)) * FP + f0) =
-              make_float4(df[t][4 * gq], df[t][4 * gq + 1], df[t][4 * gq + 2], df[t][4 * gq + 3]);
-      }
+    dfeat_to_tile<F, HALF ? 1 : 2>(df, dF, lane & 31, hi);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (!SCAT || dfeat_out) {
-      float* dst = dfeat_out + chunk * PTS * F;
-      const int64_t rows_left = n - chunk * PTS;
-      for (int i = lane; i < PTS * F / 4; i += 64) {
-        const int row = (i * 4) / F, col = (i * 4) % F;
-        if (row < rows_left)
-          *reinterpret_cast<float4*>(dst + row * F + col) = *reinterpret_cast<const float4*>(dF + row * FP + col);
-      }
-    }
+    if (!SCAT || dfeat_out) tile_to_rows<F, PTS>(dF, dfeat_out + chunk * PTS * F, n - chunk * PTS, lane);
     if (rotate && chunk + sched.step < sched.end) MISO_TRAIN_GATHER(chunk + sched.step, rec_nxt, p_n, po_n, valid_n, l_in_n)
-    if (SCAT) {
-      // the scatter of sdf_bwd_kernel: 64 / SLOTS trips, lane = (point slot, dx, channel), four (dy, dz) atomics each
-      constexpr int LPR = 2 * C, SLOTS = 64 / LPR;
-      const int slot = lane / LPR, dx = (lane / C) & 1, ch = lane % C;
-#pragma unroll 1
-      for (int pg = 0; pg < (scatter_mask ? PTS / SLOTS : 0); ++pg) {
-        const int pt = pg * SLOTS + slot;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-          const LevelK& lv = g.lv[l];
-          if (!((scatter_mask >> l) & 1u)) continue;
-          const int* r = rec_cur + (pt * L + l) * REC;
-          const int4 r0 = *reinterpret_cast<const int4*>(r);
-          const int4 r1 = *reinterpret_cast<const int4*>(r + 4);
-          const int fl = r0.y;
-          if (!((fl >> dx) & 1)) continue;
-          const float v = dF[pt * FP + l * C + ch];
-          const float wx = dx ? __int_as_float(r0.z) : __int_as_float(r1.y);
-          const float wy[2] = {__int_as_float(r1.z), __int_as_float(r0.w)};
-          const float wz[2] = {__int_as_float(r1.w), __int_as_float(r1.x)};
-          float* base = lv.grad + r0.x + dx * lv.sX + ch;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int dy = q & 1, dz = q >> 1;
-            if (((fl >> (2 + dy)) & 1) && ((fl >> (4 + dz)) & 1)) {
-#ifndef MISO_ABL_NO_SCATTER      // dev ablation (wrong results): everything of the scatter but the atomics
-              atomic_add_f32(base + dy * lv.sY + dz * lv.sZ, v * ((wx * wy[dy]) * wz[dz]));
-#else
-              asm volatile("" ::"v"(base + dy * lv.sY + dz * lv.sZ), "v"(v * ((wx * wy[dy]) * wz[dz])));
-#endif
-              if (ch == 0) touch_chunk(lv, r0.x + dx * lv.sX + dy * lv.sY + dz * lv.sZ);   // C floats: one chunk
-            }
-          }
-        }
-      }
-    }
+    if (SCAT) scatter_tile<C, L, true, GridK>(g, scatter_mask, dF, rec_cur, PTS, lane);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();      // the next chunk overwrites the tile (and the records)
     memory_phase(false, g.tune, wave < NW / 2);
@@ -456,7 +399,7 @@ struct TrainPlan {
 
 static TrainPlan plan_train(int C, int L, int H, int NH, const TrainCase& c, const TrainToggles& t) {
   const PackLayout pl(C * L, H, NH);
-  const int F = C * L, FP = ((F + 3) / 4) * 4 + 4, tile = 64 * FP, records = 64 * L * 8;
+  const int F = C * L, FP = dfeat_pitch(F), tile = 64 * FP, records = 64 * L * CELL_REC;
   const int pack = c.split ? pl.total_all - pl.s_w0 + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
   const auto bytes = [&](int wavefronts, int record_blocks) {
     return (size_t)(pack + wavefronts * (tile + record_blocks * records)) * sizeof(float);

@@ -120,13 +120,24 @@ def test_split_decoder_error_within_twice_the_exact_fp32_kernels(name, levels, C
 
 def test_exact_fp32_form_still_passes_its_parity_checks():
     """The exact chains stay in the library behind MISO_F_EXACT_F32: the checks the default (split) form passes in
-    tests/test_train_fused.py and tests/test_hip_parity.py, re-run on the exact form."""
+    tests/test_train_fused.py and tests/test_hip_parity.py, re-run on the exact form.  Every family of exact
+    sdf_train_kernel instantiations the launch plan can name is reached (sdf_train.hip, plan_train): 32-point trips
+    (unbinned, at most 1024 chunks), their 64-point form, eight wavefronts with nothing scattered (binned), eight
+    wavefronts with the rotated scatter (binned, narrow rows) -- against the two launches, and, binned and unbinned,
+    scattering and not, against the CPU oracle, which shares no code with either."""
     from miso_amd import ops
     import test_train_fused as T
     with ops.exact_fp32():
         T.test_unbinned_train_kernel_equals_forward_plus_backward((8, (32, 64, 128), 64), 3000)
         T.test_unbinned_train_kernel_equals_forward_plus_backward((4, (16, 80), 64), 65)
         T.test_unbinned_train_kernel_equals_forward_plus_backward((4, (48,), 32), 3000)
+        T.test_train_kernel_equals_forward_plus_backward(2, "L1")              # binned, nothing scattered: (4, (48,), 32)
+        T.test_train_kernel_vs_cpu_oracle(2, "L2")
+        T.test_train_kernel_vs_cpu_oracle("scat", "L2")                        # binned, eight wavefronts, rotated scatter
+        T.test_unbinned_train_kernel_vs_cpu_oracle(65)                         # 32-point trips, a ragged last one
+        for n in (1, 65, 40000):      # a wavefront without a chunk, one ragged chunk, several chunks per wavefront
+            T.test_rotated_scattering_kernel_on_small_and_ragged_binned_batches(n)
+        T.test_small_batch_32_point_trips_equal_64_point_trips((4, (16, 80), 64))
 
 
 @pytest.mark.parametrize("n", [3000, 70000])
