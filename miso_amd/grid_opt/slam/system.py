@@ -13,6 +13,7 @@ import torch
 from torch import Tensor
 
 import miso_amd.grid_opt.utils.utils_geometry as utils_geometry
+from miso_amd.grid_opt.captured_mapping import forget_plans
 from miso_amd.grid_opt.datasets.submap_dataset import SubmapDataset
 from miso_amd.grid_opt.models.grid_atlas import GridAtlas
 from miso_amd.grid_opt.models.grid_net import GridNet
@@ -54,7 +55,7 @@ class System:
         # (gradient, Adam and binning buffers -- three quarters of a GB per ScanNet-sized submap)
         old = getattr(getattr(self, 'mapper', None), 'grid', None)
         if old is not None and old is not self.currrent_submap():
-            old.__dict__.pop('_fast_plans', None)
+            forget_plans(old)
         self.tracker = Tracker(model=self.currrent_submap(), dataset=self.dataset_track, cfg=self.cfg)
         self.mapper = Mapper(model=self.currrent_submap(), dataset=self.dataset_map, cfg=self.cfg)
         self.mapper.mapping(mapping_kfs=[self.current_kf_id()], iterations=self.init_iterations,

@@ -53,6 +53,7 @@ class MappingStep:
         in ``self.sdf`` (caller order); a training loop only needs the loss and the gradients, and on
         the binned path the scattered write costs 1.6 us."""
         self.keep_sdf = bool(keep_sdf)
+        self._fused_train_ok = None       # _fused_train(): decided at its first call
         self.external_clear = bool(grads_cleared_by_optimizer)
         self.features = list(features)
         if crowded and not meta.flags & ops._lib.F_CROWDED:
@@ -83,10 +84,10 @@ class MappingStep:
         self.need_levels = need
         # share_grads: gradient buffers of a previous step over the same grids (a trainer whose batch size changes
         # builds a step per size; the dense buffers -- the size of the grids -- are not re-allocated each time)
-        if share_grads is not None and all((g is not None) == nd and (g is None or g.shape == f.shape)
-                                           for g, f, nd in zip(share_grads, self.features, need)):
+        self._shared_grads = share_grads is not None and all((g is not None) == nd and (g is None or g.shape == f.shape)
+                                                             for g, f, nd in zip(share_grads, self.features, need))
+        if self._shared_grads:
             self.grads = list(share_grads)
-            self._shared_grads = True
         else:
             self.grads = [torch.zeros_like(f) if nd else None for f, nd in zip(self.features, need)]
         # one flag byte per ADAM_CHUNK (64) gradient floats, set by the scatter kernels where they put a non-zero: Adam finds the
@@ -126,7 +127,7 @@ class MappingStep:
         # the fused step (sort -> sdf_train_kernel -> pull) reads a point's original index out of xn[p].w: no perm[] array,
         # one scattered store per point less in the sort (sort_scatter_kernel 11.2 -> 8.6 us at 262 144 points)
         self.sorted = ops.SortedBatch(self.n, dev, tiles=self.tiles, need_perm=not self._fused_train()) if sort else None
-        if getattr(self, "_shared_grads", False) and self.sorted is None:
+        if self._shared_grads and self.sorted is None:
             # the small-batch path accumulates onto buffers it expects zeroed; the previous owner may have been a
             # binned step, which overwrites and never clears
             for g in self.grads:
@@ -141,11 +142,11 @@ class MappingStep:
         self._adam_clears = 0
         if adam_device is not None and self.sorted is not None:
             self._adam_clears = ops.sdf_bwd_scattered_levels(self.features, meta, self.grads, self.n, tiles=self.tiles)
-            for l, g in enumerate(self.grads):
-                if g is not None and (self._adam_clears >> l) & 1:
-                    g.zero_()
+            self.clear_added_levels()
         self._graph = None
-        if use_graph is None:
+        if use_graph is not None:
+            self._use_graph = use_graph and adam is None  # the Adam step count changes per call (adam_device: on the device)
+        else:
             # a graph replay saves the host's launch work (decisive for small batches: the step is launch-bound) and
             # costs ~6 us of device idle time between two replays (measured on the cfg-2 step: 163.3 us per replay,
             # 157.0 us as plain stream launches with the host 35 us per step, tools/graph_vs_eager.py) -- from
@@ -153,8 +154,20 @@ class MappingStep:
             # host may run ahead as far as the runtime's queue lets it, ~47 steps; what does starve the device is a
             # full collection of Python's garbage collector, ~45 ms over the objects `import torch` leaves behind:
             # a long-running loop calls gc.freeze() after its setup, as bench.py does.)
-            use_graph = self.n < self.STREAM_MIN_POINTS
-        self._use_graph = use_graph and adam is None  # the Adam step count changes per call (adam_device: on the device)
+            self.graph_by_size()
+
+    def graph_by_size(self):
+        """From now on: one graph replay per step below STREAM_MIN_POINTS samples, plain stream launches from there."""
+        self._use_graph = self.n < self.STREAM_MIN_POINTS and self.adam is None
+
+    def clear_added_levels(self):
+        """Zero the levels the backward ADDS to where Adam clears behind it (_adam_clears), with their touched flags: what
+        the step relies on finding when nothing but its own Adam launch has written them since."""
+        for l, g in enumerate(self.grads):
+            if g is not None and (self._adam_clears >> l) & 1:
+                g.zero_()
+                if self.touched[l] is not None:
+                    self.touched[l].zero_()
 
     def set_batch(self, x, target, valid=None, sign=None, weight=None, live_rows=None):
         if self.live_rows is not None:
@@ -253,7 +266,7 @@ class MappingStep:
 
     def _fused_train(self) -> bool:
         """Whether the binned step runs as sort -> sdf_train_kernel -> pull (decided once: the grids do not change)."""
-        ok = self.__dict__.get("_fused_train_ok")
+        ok = self._fused_train_ok
         if ok is None:
             ok = self._fused_train_ok = (os.environ.get("MISO_NO_FUSED_TRAIN") is None      # dev: the two-launch form
                                          and ops.sdf_train_supported(self.features, self.meta, self.grads, self.pack))
