@@ -59,6 +59,10 @@
  *                     utils_eval.nn_correspondance, grid_opt/utils/utils_eval.py:14-36: pytorch3d.ops.knn_points with
  *                     K = 1 (an all-pairs search) under compute_chamfer_metrics (:74-108), the last step of
  *                     demo/full_slam_scannet.py:161-191 and grid_opt/utils/utils_ncd.py:121-128.
+ *   miso_icp_transform / miso_icp_sums / miso_nn_normals
+ *                     Open3D's registration_icp and estimate_normals as utils_scannet.align_mesh_to_ref
+ *                     (grid_opt/utils/utils_scannet.py:115-156) and align_submap_pair (grid_opt/align/icp.py:51-118)
+ *                     call them: the per-point work of an iteration; the loop and the solve are host code.
  *
  * This file is also the ONLY statement of the ABI for Python: miso_amd/_lib.py reads its structs, integer constants and
  * prototypes at import and refuses what it cannot read.  Keep the declarations in the style used below: block comments,
@@ -808,6 +812,44 @@ int miso_nn_query(const miso_nn_plan_t* plan, void* workspace, const float* src,
                   int64_t* out_idx, int32_t* stats, void* stream);
 int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, float* out_d2,
                       int64_t* out_idx, void* stream);
+
+/* --- ICP on the nearest-neighbour index: the per-point work of Open3D's registration_icp, and normals -------------------
+ * Users: grid_opt/utils/utils_registration.py (registration_icp), utils_scannet.align_mesh_to_ref, grid_opt/align/icp.py.
+ * One iteration = miso_icp_transform, miso_nn_query on its output, miso_icp_sums; the host reads MISO_ICP_SUMS doubles
+ * and solves in float64.  All launches go on `stream`; nothing allocates or synchronises.  Arithmetic, orders of
+ * operations and the layout of the sums: the header comment of csrc/icp.hip.
+ *   miso_icp_transform  src (n, 3) fp32 with row stride ld >= 3 -> out (n, 3) contiguous, p' = ((R0 x + R1 y) + R2 z) + t
+ *       per component in fp32, one rounding per operation.  pose: 12 HOST floats, R row-major then t, passed to the
+ *       kernel by value.
+ *   miso_icp_workspace_bytes  the device workspace of miso_icp_sums for n pairs (one partial block of sums per thread
+ *       block, at most MISO_ICP_MAX_BLOCKS), 8-byte aligned; 0 for n < 0.
+ *   miso_icp_sums  moved (n, 3) contiguous (the output of miso_icp_transform), d2 (n) fp32 and idx (n) int64 as
+ *       miso_nn_query / miso_nn_all_pairs wrote them for `moved`, tgt (m, 3) with row stride ld_t, normals (m, 3) with row
+ *       stride ld_n (needed for kind 1 only) -> out: MISO_ICP_SUMS doubles on the device.  A pair is an inlier when
+ *       0 <= idx < m and d2 <= max_dist^2 (`<=`).  kind: MISO_ICP_POINT_TO_POINT / MISO_ICP_POINT_TO_PLANE; loss:
+ *       MISO_ICP_LOSS_L2 / MISO_ICP_LOSS_TUKEY with parameter tukey_k > 0 (point to plane only: Open3D's point-to-point
+ *       estimate takes no kernel, and kind 0 ignores `loss`).  origin: three HOST doubles the point-to-point sums are
+ *       taken relative to (NULL = 0).  out[0] = inlier count, out[1] = sum of d2; then for kind 1 the 21 upper-triangle
+ *       entries of sum w J J^T, the 6 of sum w J r and sum w r^2 (r = (p' - q) . n, J = [p' x n, n]); for kind 0
+ *       sum (p' - o), sum (q - o) and the 9 entries of sum (q - o)(p' - o)^T, row-major.  Float64 accumulation in a fixed
+ *       order, no atomics: the same inputs give the same bits.  n == 0 writes zeros.
+ *   miso_nn_normals  for every row of pts (n, 3) (row stride ld), over the targets of a built index within `radius`
+ *       (d2 <= radius^2, d2 in float64): counts (n) int32 and normals (n, 3) fp32 contiguous, the unit eigenvector of the
+ *       smallest eigenvalue of the neighbours' covariance (closed form; sign not fixed).  Fewer than three neighbours or
+ *       a neighbourhood on a line gives (0, 0, 1), Open3D's fallback.  A radius search, not Open3D's default 30-NN. */
+#define MISO_ICP_SUMS 32
+#define MISO_ICP_MAX_BLOCKS 512
+#define MISO_ICP_POINT_TO_POINT 0
+#define MISO_ICP_POINT_TO_PLANE 1
+#define MISO_ICP_LOSS_L2 0
+#define MISO_ICP_LOSS_TUKEY 1
+int miso_icp_transform(const float* src, int64_t ld, int64_t n, const float* pose, float* out, void* stream);
+int64_t miso_icp_workspace_bytes(int64_t n);
+int miso_icp_sums(const float* moved, const float* d2, const int64_t* idx, int64_t n, const float* tgt, int64_t ld_t,
+                  int64_t m, const float* normals, int64_t ld_n, double max_dist, int32_t kind, int32_t loss,
+                  double tukey_k, const double* origin, void* workspace, double* out, void* stream);
+int miso_nn_normals(const miso_nn_plan_t* plan, const void* workspace, const float* pts, int64_t ld, int64_t n,
+                    double radius, float* normals, int32_t* counts, void* stream);
 
 /* --- fused atlas query: GridAtlas.query_feature / GridAtlas.forward in one launch (round 6) ---------------------------
  * Replaces the per-submap loop of grid_opt/models/grid_atlas.py:374-399 (for each active submap: transfrom_points_from,

@@ -1086,6 +1086,39 @@ int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* sr
   return (int)launch_nn_all_pairs(tgt, ld_t, m, src, ld_s, n, out_d2, out_idx, (hipStream_t)stream);
 }
 
+// ---- ICP and normals on the index (icp.hip) ----------------------------------------------------------------------------------
+int miso_icp_transform(const float* src, int64_t ld, int64_t n, const float* pose, float* out, void* stream) {
+  if (n < 0 || ld < 3 || !pose) return MISO_E_BADARG;
+  if (n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (n > 0 && (!src || !out)) return MISO_E_BADARG;
+  return (int)launch_icp_transform(pose, src, ld, n, out, (hipStream_t)stream);
+}
+
+int64_t miso_icp_workspace_bytes(int64_t n) { return n < 0 ? 0 : icp_workspace_bytes(n); }
+
+int miso_icp_sums(const float* moved, const float* d2, const int64_t* idx, int64_t n, const float* tgt, int64_t ld_t,
+                  int64_t m, const float* normals, int64_t ld_n, double max_dist, int32_t kind, int32_t loss,
+                  double tukey_k, const double* origin, void* workspace, double* out, void* stream) {
+  if (n < 0 || m < 0 || ld_t < 3 || !workspace || !out || ((uintptr_t)workspace & 7u) || ((uintptr_t)out & 7u)) return MISO_E_BADARG;
+  if (n >= ((int64_t)1 << 31) || m >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (kind != MISO_ICP_POINT_TO_POINT && kind != MISO_ICP_POINT_TO_PLANE) return MISO_E_BADARG;
+  if (loss != MISO_ICP_LOSS_L2 && loss != MISO_ICP_LOSS_TUKEY) return MISO_E_BADARG;
+  if (!(max_dist >= 0.0) || (loss == MISO_ICP_LOSS_TUKEY && !(tukey_k > 0.0))) return MISO_E_BADARG;
+  if (n > 0 && (!moved || !d2 || !idx || (m > 0 && !tgt))) return MISO_E_BADARG;
+  if (kind == MISO_ICP_POINT_TO_PLANE && n > 0 && m > 0 && (!normals || ld_n < 3)) return MISO_E_BADARG;
+  return (int)launch_icp_sums(moved, d2, idx, n, tgt, ld_t, m, normals, ld_n, max_dist, kind, loss, tukey_k, origin, workspace,
+                              out, (hipStream_t)stream);
+}
+
+int miso_nn_normals(const miso_nn_plan_t* plan, const void* workspace, const float* pts, int64_t ld, int64_t n,
+                    double radius, float* normals, int32_t* counts, void* stream) {
+  if (!nn_plan_ok(plan) || ld < 3 || n < 0 || !(radius > 0.0) || !(radius < 1e30)) return MISO_E_BADARG;
+  if (n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (n > 0 && (!pts || !normals || !counts)) return MISO_E_BADARG;
+  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  return (int)launch_nn_normals(*plan, workspace, pts, ld, n, radius, normals, counts, (hipStream_t)stream);
+}
+
 // ---- fused atlas query (atlas.hip) ------------------------------------------------------------------------------------
 int64_t miso_atlas_plan_bytes(int32_t n_submaps) {
   return n_submaps < 1 ? 0 : (int64_t)n_submaps * (int64_t)sizeof(GridK);

@@ -164,4 +164,13 @@ hipError_t launch_nn_query(const miso_nn_plan_t& plan, void* workspace, const fl
 hipError_t launch_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n,
                                float* out_d2, int64_t* out_idx, hipStream_t s);
 
+// ---- icp.hip
+hipError_t launch_icp_transform(const float* pose, const float* src, int64_t ld, int64_t n, float* out, hipStream_t s);
+int64_t icp_workspace_bytes(int64_t n);
+hipError_t launch_icp_sums(const float* moved, const float* d2, const int64_t* idx, int64_t n, const float* tgt, int64_t ld_t,
+                           int64_t m, const float* normals, int64_t ld_n, double max_dist, int kind, int loss, double tukey_k,
+                           const double* origin, void* workspace, double* out, hipStream_t s);
+hipError_t launch_nn_normals(const miso_nn_plan_t& plan, const void* workspace, const float* pts, int64_t ld, int64_t n,
+                             double radius, float* normals, int32_t* counts, hipStream_t s);
+
 }  // namespace miso

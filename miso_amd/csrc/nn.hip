@@ -67,17 +67,7 @@ __device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
   return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;       // false for NaN
 }
 
-__device__ __forceinline__ int nn_cell_axis(float p, float lo, float cell, int dim) {
-  const float c = floorf(__fdiv_rn(p - lo, cell));
-  return (int)fminf(fmaxf(c, 0.0f), (float)(dim - 1));              // fmaxf(NaN, 0) = 0
-}
-
-__device__ __forceinline__ int nn_cell_of(const NnK& k, float x, float y, float z, int c[3]) {
-  c[0] = nn_cell_axis(x, k.lo[0], k.cell, k.dims[0]);
-  c[1] = nn_cell_axis(y, k.lo[1], k.cell, k.dims[1]);
-  c[2] = nn_cell_axis(z, k.lo[2], k.cell, k.dims[2]);
-  return (c[2] * k.dims[1] + c[1]) * k.dims[0] + c[0];
-}
+// (nn_cell_axis / nn_cell_of: nn.hpp)
 
 // ---- build -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void nn_count_kernel(NnK k, const float* __restrict__ tgt, int64_t ld, int* __restrict__ table) {
@@ -309,31 +299,7 @@ __global__ void nn_set_stats_kernel(int* __restrict__ stats, int a, int b) {
   if (threadIdx.x == 0 && blockIdx.x == 0) { stats[0] = a; stats[1] = b; }
 }
 
-inline int64_t a256(int64_t v) { return (v + 255) / 256 * 256; }
-
-struct NnLayout {
-  int64_t table, sums, counters, list, rows, total;
-};
-
-// byte offsets inside the workspace
-inline NnLayout nn_layout(const miso_nn_plan_t& p) {
-  NnLayout l;
-  int64_t at = 0;
-  l.table = at;    at += a256((p.cells + 1) * 4);
-  l.sums = at;     at += a256(1024 * 4);
-  l.counters = at; at += a256((int64_t)MISO_NN_MAX_CHUNKS * 4);
-  l.list = at;     at += a256((int64_t)MISO_NN_CHUNK * 4);
-  l.rows = at;     at += a256(p.n_tgt * 16);
-  l.total = at;
-  return l;
-}
-
-inline NnK nn_k(const miso_nn_plan_t& p) {
-  NnK k;
-  for (int a = 0; a < 3; ++a) { k.lo[a] = p.bound_min[a]; k.dims[a] = p.dims[a]; }
-  k.cell = p.cell; k.mag = p.coord_mag; k.max_rings = p.max_rings; k.n_tgt = p.n_tgt;
-  return k;
-}
+// (NnLayout / nn_layout / nn_k: nn.hpp)
 
 }  // namespace
 

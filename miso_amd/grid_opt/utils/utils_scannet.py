@@ -1,11 +1,16 @@
 """ScanNet scene metadata and the RGB-D dataset factory the demos call (reference:
 grid_opt/utils/utils_scannet.py:10-113).  ``create_scannet_dataset`` builds the device-resident ``PosedSdfRgbd`` of
 miso_amd.grid_opt.datasets.sdf_rgbd from the same files the reference reads (``<root>/scene<id>/scene<id>.txt``,
-``frames/pose/*.pose.txt``, ``frames/depth/*.depth.pgm``).  The mesh-to-mesh ICP helper of the reference
-(``align_mesh_to_ref``, an Open3D registration pipeline for evaluation plots) is outside the hot path."""
+``frames/pose/*.pose.txt``, ``frames/depth/*.depth.pgm``).  ``align_mesh_to_ref`` (reference :115-156, an Open3D
+registration pipeline) is the second step of the demo's mesh grading: coarse and fine ICP of the reconstruction onto the
+ground truth, here on ops.NearestIndex and the kernels of csrc/icp.hip (utils_registration.registration_icp)."""
+import copy
 import logging
 from dataclasses import dataclass
 from os.path import join
+
+import numpy as np
+import torch
 
 from miso_amd.grid_opt.datasets.sdf_rgbd import PosedSdfRgbd
 from miso_amd.grid_opt.utils.utils_data import CameraParameters
@@ -75,3 +80,54 @@ def create_scannet_dataset(scannet_root: str, scene_id: str, trunc_dist: float =
                         n_rays=n_rays, min_depth=0.07, max_depth=12.0, n_surf_samples=n_surf_samples,
                         n_strat_samples=n_strat_samples, trunc_dist=trunc_dist, voxel_size=voxel_size, device=device,
                         padded=padded)
+
+
+def _as_mesh(mesh):
+    from miso_amd.grid_opt.utils import utils_sdf
+    return utils_sdf.read_ply(mesh) if isinstance(mesh, (str, bytes)) or hasattr(mesh, '__fspath__') else mesh
+
+
+def _sampled(mesh, count, seed, device, want_normals):
+    """``count`` fp32 surface samples of a TriangleMesh on ``device`` and, if asked, the unit normals of the sampled faces"""
+    from miso_amd.grid_opt.utils import utils_eval
+    verts = torch.from_numpy(np.asarray(mesh.vertices, dtype=np.float64)).to(device)
+    tris = torch.from_numpy(np.asarray(mesh.triangles, dtype=np.int64)).to(device)
+    if tris.shape[0] == 0:
+        raise ValueError("align_mesh_to_ref: a mesh without triangles")
+    gen = torch.Generator(device=device).manual_seed(int(seed))
+    points, face, _ = utils_eval.sample_surface(verts, tris, int(count), gen)
+    normals = None
+    if want_normals:
+        a, b, c = (verts[tris[face, k]] for k in range(3))
+        normals = torch.nn.functional.normalize(torch.cross(b - a, c - a, dim=1), dim=1).to(torch.float32)
+    return points.to(torch.float32).contiguous(), normals
+
+
+def align_mesh_to_ref(est_mesh, ref_mesh, constraint_type='point_to_plane', voxel_size=0.02, threshold_factor_coarse=15,
+                      threshold_factor_fine=1.5, num_iters=100, num_points=1000000, seed=0):
+    """Reference :115-156, same defaults: ``num_points`` surface samples of each mesh (utils_eval.sample_surface, seeds
+    ``seed`` and ``seed + 1``), a coarse ICP with the L2 loss at ``voxel_size * threshold_factor_coarse`` from the identity,
+    then a fine one with TukeyLoss(k=1e-2) at ``voxel_size * threshold_factor_fine`` from the coarse result.  One
+    ops.NearestIndex over the reference's samples serves both passes.  ``est_mesh`` / ``ref_mesh``: utils_sdf.TriangleMesh
+    objects or PLY paths.
+
+    Differences from the reference, on purpose: the target normals of 'point_to_plane' are the FACE NORMALS of the sampled
+    triangles, which are exact, where the reference estimates them from the samples (``estimate_normals``); the samples
+    are not Open3D's; the input mesh is left alone and no viewer is opened.
+    -> (a copy of ``est_mesh`` moved by the fine result, that RegistrationResult; its ``transformation`` is T_ref_est)."""
+    from miso_amd import ops
+    from miso_amd.grid_opt.utils import utils_registration as reg
+    if constraint_type not in ('point_to_plane', 'point_to_point'):
+        raise ValueError(f"Unknown constraint type {constraint_type}")
+    est, ref = _as_mesh(est_mesh), _as_mesh(ref_mesh)
+    device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
+    plane = constraint_type == 'point_to_plane'
+    src, _ = _sampled(est, num_points, seed, device, False)
+    tgt, normals = _sampled(ref, num_points, seed + 1, device, plane)
+    index = ops.NearestIndex(tgt)
+    coarse = reg.registration_icp(src, index, tgt, normals, voxel_size * threshold_factor_coarse, np.eye(4),
+                                  kind=constraint_type, loss=None, max_iteration=num_iters)
+    fine = reg.registration_icp(src, index, tgt, normals, voxel_size * threshold_factor_fine, coarse.transformation,
+                                kind=constraint_type, loss=reg.TukeyLoss(k=1e-2), max_iteration=num_iters)
+    logger.debug(f"Finetuned ICP result: {fine}\n{fine.transformation}")
+    return copy.deepcopy(est).apply_transform(fine.transformation), fine

@@ -1032,6 +1032,7 @@ def voxel_down_sample(points, voxel_size: float, n_live: Optional[torch.Tensor] 
 NN_CELL_SPACINGS = 2.0       # default cell = this many point spacings
 NN_MAX_RINGS = 4             # default number of shells around a query's cell before the all-pairs kernel takes it
 NN_ALL_PAIRS_BELOW = 1 << 22  # nearest(): N * M below this goes to the all-pairs kernel (the index costs ~8 more launches)
+NN_NORMAL_SPACINGS = 4.0     # NearestIndex.normals(radius=None): this many point spacings
 
 
 def _cloud(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -1080,6 +1081,8 @@ class NearestIndex:
             b = torch.cat([torch.where(ok, tgt, inf).amin(dim=0), torch.where(ok, tgt, -inf).amax(dim=0)]).tolist()   # the one read
             if all(abs(v) < inf for v in b):
                 lo, hi = b[:3], b[3:]
+        self.bound_min, self.bound_max = tuple(lo), tuple(hi)
+        self.spacing = nn_default_cell(lo, hi, self.m) / NN_CELL_SPACINGS      # the estimate, whatever cell was asked for
         if cell is None:
             cell = nn_default_cell(lo, hi, self.m)
         self.plan = _lib.NnPlan()
@@ -1111,6 +1114,23 @@ class NearestIndex:
                                              _ptr(idx), _ptr(stats), _stream(src)), "miso_nn_query")
         return d2, idx, stats
 
+    def normals(self, points: Optional[torch.Tensor] = None, radius: Optional[float] = None):
+        """For every row of ``points`` (default: the indexed cloud itself) the normal of its neighbourhood among the
+        indexed targets: the unit eigenvector of the smallest eigenvalue of the covariance of the targets within
+        ``radius`` (miso_nn_normals, csrc/icp.hip).  -> (normals (N, 3) fp32, counts (N,) int32).  This is Open3D's RADIUS
+        search (KDTreeSearchParamRadius), not the 30-nearest-neighbour search estimate_normals() defaults to;
+        ``radius=None``: NN_NORMAL_SPACINGS point spacings (self.spacing, the estimate behind the default cell), about
+        fifty neighbours on a sampled surface.  Fewer than three neighbours, or neighbours on a line, give (0, 0, 1) as in
+        Open3D, and the count shows it.  The sign of a normal is not fixed (point-to-plane ICP does not read it)."""
+        pts = self.tgt if points is None else _cloud(points, "points")
+        n = int(pts.shape[0])
+        radius = NN_NORMAL_SPACINGS * self.spacing if radius is None else float(radius)
+        out = torch.empty((n, 3), device=pts.device, dtype=torch.float32)
+        counts = torch.empty(n, device=pts.device, dtype=torch.int32)
+        _lib.check(_lib.load().miso_nn_normals(C.byref(self.plan), _ptr(self.workspace), _ptr(pts), _ld(pts), n, radius,
+                                               _ptr(out), _ptr(counts), _stream(pts)), "miso_nn_normals")
+        return out, counts
+
 
 def nearest_all_pairs(src: torch.Tensor, tgt: torch.Tensor):
     """The all-pairs kernel for every query (miso_nn_all_pairs): -> (d2, idx), the bits NearestIndex.query returns."""
@@ -1133,6 +1153,102 @@ def nearest(src: torch.Tensor, tgt: torch.Tensor, cell: Optional[float] = None):
         return nearest_all_pairs(src, tgt)
     d2, idx, _ = NearestIndex(tgt, cell=cell).query(src)
     return d2, idx
+
+
+# --------------------------------------------------------------------------- #
+# ICP: the per-point work of Open3D's registration_icp (csrc/icp.hip)
+# --------------------------------------------------------------------------- #
+ICP_KINDS = {"point_to_point": _lib.ICP_POINT_TO_POINT, "point_to_plane": _lib.ICP_POINT_TO_PLANE}
+ICP_SUMS = _lib.ICP_SUMS
+
+
+def _refuse(what: str, message: str):
+    raise MisoError(f"{what} failed: {message} (code {_lib.E_BADARG})", _lib.E_BADARG, what)
+
+
+def _pose12(T) -> "C.Array":
+    """a (4, 4) or (3, 4) pose, array or tensor -> the 12 host floats of miso_icp_transform (R row-major, then t)"""
+    rows = T.tolist() if hasattr(T, "tolist") else T
+    return (C.c_float * 12)(*[float(rows[i][j]) for i in range(3) for j in range(3)], *[float(rows[i][3]) for i in range(3)])
+
+
+def icp_transform(src: torch.Tensor, T, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``R src + t`` for the rows of ``src`` (N, 3), ``T`` a 4 x 4 pose on the host rounded to fp32: p' = ((R0 x + R1 y) +
+    R2 z) + t per component in fp32 (miso_icp_transform).  -> (N, 3) fp32 contiguous (``out`` if given)."""
+    src = _cloud(src, "src")
+    n = int(src.shape[0])
+    if out is None:
+        out = torch.empty((n, 3), device=src.device, dtype=torch.float32)
+    _require_hip(out)
+    assert out.shape == (n, 3) and out.is_contiguous()
+    _lib.check(_lib.load().miso_icp_transform(_ptr(src), _ld(src), n, _pose12(T), _ptr(out), _stream(src)),
+               "miso_icp_transform")
+    return out
+
+
+def icp_sums(moved, d2, idx, tgt, normals=None, *, max_dist: float, kind: str = "point_to_plane",
+             tukey_k: Optional[float] = None, origin=(0.0, 0.0, 0.0), workspace=None, out=None) -> torch.Tensor:
+    """The sums of one ICP iteration over the correspondences ``(d2, idx)`` of ``moved`` (N, 3) among ``tgt`` (M, 3)
+    (miso_icp_sums; layout and arithmetic in csrc/icp.hip): -> ICP_SUMS float64 on the device, [0] the inlier count
+    (idx >= 0 and d2 <= max_dist^2), [1] the sum of d2, then the normal equations of ``kind`` 'point_to_plane' (needs
+    ``normals`` (M, 3); ``tukey_k``: Tukey's weight instead of L2) or the Umeyama sums of 'point_to_point' relative to
+    ``origin``.  Same inputs, same bits.  Nothing is read back."""
+    what = "miso_icp_sums"
+    if kind not in ICP_KINDS:
+        _refuse(what, f"unknown kind '{kind}'")
+    if kind == "point_to_plane" and normals is None:
+        _refuse(what, "point_to_plane needs the targets' normals")
+    _require_hip(moved, d2, tgt, normals)
+    if not idx.is_cuda or idx.dtype != torch.int64:
+        raise RuntimeError(f"{what}: idx is an int64 tensor on the HIP device; got {idx.dtype} on {idx.device}")
+    tgt = _cloud(tgt, "tgt")
+    n, m = int(moved.shape[0]), int(tgt.shape[0])
+    assert moved.shape == (n, 3) and moved.is_contiguous() and d2.is_contiguous() and idx.is_contiguous()
+    assert d2.numel() >= n and idx.numel() >= n
+    if normals is not None:
+        normals = _cloud(normals, "normals")
+        assert normals.shape[0] == m, "one normal per target"
+    lib = _lib.load()
+    if workspace is None:
+        workspace = torch.empty(int(lib.miso_icp_workspace_bytes(n)), device=tgt.device, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty(ICP_SUMS, device=tgt.device, dtype=torch.float64)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() >= ICP_SUMS
+    assert workspace.is_cuda and workspace.numel() * workspace.element_size() >= lib.miso_icp_workspace_bytes(n)
+    _lib.check(lib.miso_icp_sums(_ptr(moved), _ptr(d2), _ptr(idx), n, _ptr(tgt), _ld(tgt), m, _ptr(normals),
+                                 _ld(normals) if normals is not None else 0, float(max_dist), ICP_KINDS[kind],
+                                 _lib.ICP_LOSS_L2 if tukey_k is None else _lib.ICP_LOSS_TUKEY,
+                                 0.0 if tukey_k is None else float(tukey_k), (C.c_double * 3)(*[float(v) for v in origin]),
+                                 _ptr(workspace), _ptr(out), _stream(tgt)), what)
+    return out
+
+
+class IcpWorkspace:
+    """The buffers of an ICP run of ``src`` (N, 3) against an indexed target cloud, allocated once: the transformed cloud,
+    the (d2, idx, stats) of the search, the partial sums and the block of ICP_SUMS doubles.  ``normals``: the targets'
+    (M, 3), needed for 'point_to_plane'.  ``step(T, ...)`` is one iteration's device work -- transform, one search on the
+    index, the sums -- and ONE device-to-host read: the block of doubles, returned as a float64 numpy array.  The
+    point-to-point sums are taken relative to the centre of the targets' bounds."""
+
+    def __init__(self, src: torch.Tensor, index: "NearestIndex", normals: Optional[torch.Tensor] = None):
+        self.src, self.index = _cloud(src, "src"), index
+        _require_hip(normals)
+        self.normals = None if normals is None else _cloud(normals, "normals")
+        n, dev = int(self.src.shape[0]), self.src.device
+        self.n = n
+        self.moved = torch.empty((n, 3), device=dev, dtype=torch.float32)
+        self.search = (torch.empty(n, device=dev, dtype=torch.float32), torch.empty(n, device=dev, dtype=torch.int64),
+                       torch.empty(2, device=dev, dtype=torch.int32))
+        self.partials = torch.empty(int(_lib.load().miso_icp_workspace_bytes(n)), device=dev, dtype=torch.uint8)
+        self.sums = torch.empty(ICP_SUMS, device=dev, dtype=torch.float64)
+        self.origin = tuple(0.5 * (a + b) for a, b in zip(index.bound_min, index.bound_max))
+
+    def step(self, T, max_dist: float, kind: str = "point_to_plane", tukey_k: Optional[float] = None):
+        icp_transform(self.src, T, out=self.moved)
+        d2, idx, _ = self.index.query(self.moved, out=self.search)
+        icp_sums(self.moved, d2, idx, self.index.tgt, self.normals, max_dist=max_dist, kind=kind, tukey_k=tukey_k,
+                 origin=self.origin, workspace=self.partials, out=self.sums)
+        return self.sums.cpu().numpy()
 
 
 # --------------------------------------------------------------------------- #
