@@ -865,3 +865,182 @@ def align_epilogue_b64(flat, params, adam_m, adam_v, adam_t, *, lr=1e-2, betas=(
         bc1, bc2 = 1 - b1 ** int(t[s]), 1 - b2 ** int(t[s])
         prm[s] -= lr / bc1 * m[s] / (v[s].sqrt() / math.sqrt(bc2) + eps)
     return total, prm, m, v, t
+
+
+# --------------------------------------------------------------------------- #
+# Keyframe tracker, stage by stage (lm.hip: miso_lm_track_step, miso_track_adam_step)
+# --------------------------------------------------------------------------- #
+def _t64(t):
+    return torch.as_tensor(t).detach().cpu().to(torch.float64)
+
+
+def track_pose64(R_base, t_base, dr, dt):
+    """lm_pose_kernel in fp64: (12,) = R_base Exp(dr) row-major, then t_base + dt (apply_pose_correction; the clamp of
+    |dr|^2 at 1e-4 is so3_exp_map's)."""
+    R = _t64(R_base).reshape(3, 3) @ so3_exp_map(_t64(dr).reshape(1, 3), 1e-4)[0]
+    return torch.cat([R.reshape(9), _t64(t_base).reshape(3) + _t64(dt).reshape(3)])
+
+
+def track_transform32(x, pose12, sanitize=True):
+    """lm_transform_kernel's map in fp32, operation by operation: per output axis j
+    (fma(x2, R[j,2], fma(x1, R[j,1], x0 * R[j,0]))) + t_j, after torch.nan_to_num of x when ``sanitize``.
+    Returns (xw (N,3) fp32, the sanitised x).  _fma32's double rounding: about 1 value in 2^29 may differ by an ulp."""
+    x = torch.as_tensor(x).detach().cpu().to(torch.float32)
+    if sanitize:
+        x = torch.nan_to_num(x)
+    p = torch.as_tensor(pose12).detach().cpu().to(torch.float32).reshape(12)
+    R, t = p[:9].view(3, 3), p[9:]
+    xw = torch.stack([_fma32(x[:, 2], R[j, 2], _fma32(x[:, 1], R[j, 1], x[:, 0] * R[j, 0])) + t[j] for j in range(3)], 1)
+    return xw, x
+
+
+def track_keep32(gt, trunc):
+    """(N,) bool: the truncation filter as the kernels make it, |gt| < trunc in fp32 (trunc None: every row)."""
+    gt = torch.as_tensor(gt).detach().cpu().to(torch.float32).reshape(-1)
+    if trunc is None:
+        return torch.ones_like(gt, dtype=torch.bool)
+    return gt.abs() < torch.tensor(float(trunc), dtype=torch.float32)
+
+
+def track_counts(xw, gt, ok, frame_ids, kf, trunc, bound):
+    """The four counters of lm_transform_kernel, every compare in fp32: (rows kept by the truncation filter, kept rows
+    inside the bound -- faces included --, kept rows with another frame id, kept rows that are not valid).  xw (N,3)
+    fp32 mapped samples, gt (N,) sanitised targets, ok (N,) bool or None, frame_ids (N,) or None, bound (3,2)."""
+    xw = torch.as_tensor(xw).detach().cpu().to(torch.float32)
+    b = torch.as_tensor(bound, dtype=torch.float32)
+    keep = track_keep32(gt, trunc)
+    inb = ((xw >= b[:, 0]) & (xw <= b[:, 1])).all(1)
+    n = lambda m: int((keep & m).sum())
+    wrong = torch.zeros_like(keep) if frame_ids is None else torch.as_tensor(frame_ids).detach().cpu().reshape(-1) != kf
+    bad = torch.zeros_like(keep) if ok is None else ~torch.as_tensor(ok).detach().cpu().reshape(-1).bool()
+    return int(keep.sum()), n(inb), n(wrong), n(bad)
+
+
+def _kernel_fan_in(terms, rows, dtype):
+    """Sum (n,K) per-row terms over the boolean ``rows``: fp64 directly, or -- dtype fp32 -- as the reduction kernels
+    of lm.hip do: row i belongs to workgroup (i // 256) % 128, a workgroup's share is summed in fp64 from fp32 terms
+    and rounded to fp32, and the at most 128 shares are added in fp32 one after the other (the atomics)."""
+    terms = terms.reshape(terms.shape[0], -1)
+    if dtype == torch.float64:
+        return terms[rows].double().sum(0)
+    idx = torch.nonzero(rows).flatten()
+    blk = (idx // 256) % 128
+    part = torch.zeros(128, terms.shape[1], dtype=torch.float64).index_add_(0, blk, terms[idx].double()).float()
+    acc = torch.zeros(terms.shape[1], dtype=torch.float32)
+    for b in range(min(128, (terms.shape[0] + 255) // 256)):
+        acc = acc + part[b]
+    return acc.double()
+
+
+def lm_sums64(x, pose12, grad, sdf, gt, keep, loss_type="L2", gm_scale=0.1, dtype=torch.float64):
+    """The 29 sums of lm_normal_eq_kernel over the rows of ``keep``: the upper triangle of H = J^T W J row-major
+    [0,21), g = J^T W r [21,27), sum w r^2 [27], the row count [28]; J_i = [((R x_i) x grad_i)^T R, grad_i^T],
+    r = sdf - gt, w = 1 (L2) or c / (c + r^2)^2 (GM).  Inputs are the kernel's own fp32 values (sanitised x, its pose,
+    its field gradient and SDF); everything from there on is ``dtype`` (fp64: the oracle; fp32: a careful fp32
+    evaluation, reduced as the kernel reduces).  Returns (sums (29,), A (29,)) fp64: A is the same sum with every
+    factor of every row in absolute value (|R| |x|, the cross product's six products, |c|^T |R|, |grad|, |r|) --
+    what the rounding of one row is relative to.  A[28] = 0: the count is exact."""
+    f = lambda t: torch.as_tensor(t).detach().cpu().to(torch.float32).to(dtype)
+    x, g, sdf, gt = f(x).reshape(-1, 3), f(grad).reshape(-1, 3), f(sdf).reshape(-1), f(gt).reshape(-1)
+    R = f(pose12).reshape(-1)[:9].view(3, 3)
+    keep = torch.as_tensor(keep).detach().cpu().reshape(-1).bool()
+
+    def jac(x, g, R, cross):
+        y = x @ R.T
+        return torch.cat((cross(y, g) @ R, g), dim=1)
+
+    J = jac(x, g, R, lambda y, g: torch.stack([y[:, 1] * g[:, 2] - y[:, 2] * g[:, 1], y[:, 2] * g[:, 0] - y[:, 0] * g[:, 2],
+                                                y[:, 0] * g[:, 1] - y[:, 1] * g[:, 0]], 1))
+    Ja = jac(x.abs(), g.abs(), R.abs(),
+             lambda y, g: torch.stack([y[:, 1] * g[:, 2] + y[:, 2] * g[:, 1], y[:, 2] * g[:, 0] + y[:, 0] * g[:, 2],
+                                       y[:, 0] * g[:, 1] + y[:, 1] * g[:, 0]], 1))
+    r = sdf - gt
+    if loss_type == "L2":
+        w = torch.ones_like(r)
+    elif loss_type == "GM":
+        d = gm_scale + r * r
+        w = gm_scale / (d * d)
+    else:
+        raise ValueError(loss_type)
+    iu = torch.triu_indices(6, 6)
+    wJ, wJa = w[:, None] * J, w[:, None] * Ja
+
+    def rows(wJ, J, r):
+        return torch.cat((wJ[:, iu[0]] * J[:, iu[1]], wJ * r[:, None], (w * r * r)[:, None], torch.ones_like(r)[:, None]), 1)
+
+    sums = _kernel_fan_in(rows(wJ, J, r), keep, dtype)
+    A = _kernel_fan_in(rows(wJa, Ja, r.abs()).double(), keep, torch.float64)
+    A[28] = 0.0
+    return sums, A
+
+
+def lm_unpack(sums):
+    """(H (6,6), g (6,)) from the 29 sums: the triangle row-major, mirrored."""
+    sums = _t64(sums).reshape(-1)
+    iu = torch.triu_indices(6, 6)
+    H = torch.zeros(6, 6, dtype=torch.float64)
+    H[iu[0], iu[1]] = sums[:21]
+    return H + H.triu(1).T, sums[21:27].clone()
+
+
+def lm_solve64(sums, lam):
+    """lm_solve_kernel in fp64: delta = -(H + lam I)^-1 g from given sums, and the infinity-norm condition number of
+    H + lam I.  Returns (delta (6,), cond_inf)."""
+    H, g = lm_unpack(sums)
+    H = H + float(lam) * torch.eye(6, dtype=torch.float64)
+    delta = torch.linalg.solve(H, -g)
+    cond = torch.linalg.matrix_norm(H, float("inf")) * torch.linalg.matrix_norm(torch.linalg.inv(H), float("inf"))
+    return delta, float(cond)
+
+
+def track_loss64(sdf, gt, ok, n, loss_type, weight, gm_scale=0.1):
+    """track_loss_kernel in fp64 (MisoLossTracking, grid_opt/loss.py:517-586): r = sdf - gt on the rows of ``ok``
+    (valid and inside the truncation), 0 elsewhere; loss = weight * mean over ALL n rows of r^2 | |r| | w r^2 with the
+    Geman-McClure weight w = c / (c + r^2)^2 held constant; gpred = d loss / d sdf per row, exactly 0 off ``ok`` and,
+    for L1, at r = 0.  Returns (loss, gpred (n,))."""
+    sdf, gt = _t64(sdf).reshape(-1), _t64(gt).reshape(-1)
+    ok = torch.as_tensor(ok).detach().cpu().reshape(-1).bool()
+    r = torch.where(ok, sdf - gt, torch.zeros_like(sdf))
+    if loss_type == "L2":
+        term, d = r * r, 2 * r
+    elif loss_type == "L1":
+        term, d = r.abs(), torch.sign(r)
+    elif loss_type == "GM":
+        w = gm_scale / (gm_scale + r * r) ** 2
+        term, d = w * r * r, 2 * w * r
+    else:
+        raise ValueError(loss_type)
+    return float(weight) * term.sum() / n, torch.where(ok, float(weight) * d / n, torch.zeros_like(d))
+
+
+def track_pose_sums64(gx, x, dtype=torch.float64):
+    """track_reduce_kernel: sums[3a+b] = sum_i gx_ia x_ib (d loss / d R for y = R x + t), sums[9+a] = sum_i gx_ia
+    (d loss / d t), over all rows, and A, the same with |gx| and |x|.  dtype as in lm_sums64."""
+    f = lambda t: torch.as_tensor(t).detach().cpu().to(torch.float32).to(dtype)
+    gx, x = f(gx).reshape(-1, 3), f(x).reshape(-1, 3)
+    every = torch.ones(gx.shape[0], dtype=torch.bool)
+    rows = lambda g, x: torch.cat(((g[:, :, None] * x[:, None, :]).reshape(-1, 9), g), 1)
+    return _kernel_fan_in(rows(gx, x), every, dtype), _kernel_fan_in(rows(gx.abs(), x.abs()).double(), every, torch.float64)
+
+
+def track_pull_back64(R_base, dr, sums):
+    """track_adam_kernel's chain rule in fp64: for R = R_base Exp(dr), t = t_base + dt and sums = (d loss / d R (9),
+    d loss / d t (3)), G = R_base^T gR pulled through so3_exp_map's backward gives d loss / d dr; d loss / d dt = gt.
+    Returns (g6 (6,), the same map with every entry of every factor in absolute value: the yardstick of g6)."""
+    s = _t64(sums).reshape(-1)
+    Rb = _t64(R_base).reshape(3, 3)
+    gR = s[:9].view(3, 3)
+    J = so3_exp_jacobian64(torch.as_tensor(dr).detach().cpu().to(torch.float32))
+    g6 = torch.cat([torch.einsum("ijk,ij->k", J, Rb.T @ gR), s[9:12]])
+    a6 = torch.cat([torch.einsum("ijk,ij->k", J.abs(), Rb.T.abs() @ gR.abs()), s[9:12].abs()])
+    return g6, a6
+
+
+def adam6_64(param, g, m, v, t, lr, betas=(0.9, 0.999), eps=1e-8):
+    """Step number ``t`` (1-based) of torch.optim.Adam (no amsgrad, no weight decay) in fp64 -> (param, m, v)."""
+    param, g, m, v = _t64(param).reshape(-1), _t64(g).reshape(-1), _t64(m).reshape(-1), _t64(v).reshape(-1)
+    b1, b2 = betas
+    m = b1 * m + (1 - b1) * g
+    v = b2 * v + (1 - b2) * g * g
+    bc1, bc2 = 1 - b1 ** int(t), 1 - b2 ** int(t)
+    return param - lr / bc1 * m / (v.sqrt() / math.sqrt(bc2) + eps), m, v
