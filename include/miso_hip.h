@@ -55,7 +55,7 @@
  *                     PosedSdfRgbd.getitem_sdf runs it on the host in every iteration (grid_opt/datasets/
  *                     sdf_rgbd.py:460-470: .cpu(), unique + scatter_reduce, six indexed gathers) and the LiDAR
  *                     dataset per loaded frame (grid_opt/datasets/sdf_3d_lidar.py:108-122).
- *   miso_nn_plan / miso_nn_build / miso_nn_query / miso_nn_all_pairs
+ *   miso_nn_plan / miso_nn_build / miso_nn_query / miso_nn_all_pairs / miso_nn_knn / miso_nn_knn_all_pairs
  *                     utils_eval.nn_correspondance, grid_opt/utils/utils_eval.py:14-36: pytorch3d.ops.knn_points with
  *                     K = 1 (an all-pairs search) under compute_chamfer_metrics (:74-108), the last step of
  *                     demo/full_slam_scannet.py:161-191 and grid_opt/utils/utils_ncd.py:121-128.
@@ -790,8 +790,28 @@ int miso_voxel_select_rows(const float* src_coords, const int64_t* src_ids, cons
  *   miso_nn_query  src (n, 3) with row stride ld >= 3, n < 2^31 -> out_d2 (n) fp32, out_idx (n) int64, stats (2 int32 on the
  *       device) = {queries finished by the shells of cells up to max_rings, queries sent to the all-pairs kernel}.  No
  *       host read, no allocation: the call replays inside a captured graph.  One query at a time per workspace.
- *   miso_nn_all_pairs  the all-pairs kernel for every query over the caller's arrays, no index (m < 2^31). */
+ *   miso_nn_all_pairs  the all-pairs kernel for every query over the caller's arrays, no index (m < 2^31).
+ * The k nearest (csrc/knn.hip), 1 <= k <= MISO_NN_KNN_MAX (Open3D's default of 30 fits): for every query the k smallest
+ * (d2, index) pairs in the same arithmetic and lexicographic order, listed ascending; the slots beyond the number of
+ * finite targets, and every slot of a query with a non-finite coordinate, hold (+inf, -1).  The same bits from both
+ * routes, from run to run and from build to build.
+ *   miso_nn_knn  src (n, 3) with row stride ld >= 3 -> out_d2 (n, k) fp32 and out_idx (n, k) int64, row-major, stats as
+ *       miso_nn_query's: {finished by the shells, sent to the all-pairs kernel}.  The queries that the shells leave are
+ *       answered by blocks that each scan every target: deterministic, no further buffer.  Uses the query part of the
+ *       workspace (one query of either kind at a time per workspace); no host read, no allocation: it replays inside a
+ *       captured graph.  n == 0 and n_tgt == 0 are valid; n_tgt == 0 writes the padding and stats = {n, 0}.
+ *   miso_nn_knn_all_pairs  the all-pairs kernel for every query over the caller's arrays, no index: the second route.
+ *   miso_nn_knn_normals  for every row of pts (n, 3) (row stride ld) the normal of its k nearest indexed targets:
+ *       1, d and d d^T with d = t - q in float64, added in ascending (d2, index) order -- a function of the clouds
+ *       alone, so the bits do not depend on the build -- then the covariance and the closed-form eigenvector of
+ *       miso_nn_normals.  counts (n) int32 = neighbours used, min(k, finite targets); normals (n, 3) fp32 contiguous.
+ *       A row of the indexed cloud is its own first neighbour, as in Open3D.  Fewer than three neighbours, or that
+ *       kernel's degenerate cases, give (0, 0, 1).  The lists are never materialised: no O(n k) memory.
+ *   All three return MISO_E_BADARG before any launch for k < 1 or k > MISO_NN_KNN_MAX, a NULL pointer with n > 0 (stats
+ *       always), ld < 3, n < 0 or n >= 2^31 (m likewise), a workspace that is NULL or not 16-byte aligned with
+ *       n_tgt > 0, and a plan the library did not write. */
 #define MISO_NN_MAX_CELLS 16777216
+#define MISO_NN_KNN_MAX 32
 #define MISO_NN_MAX_RINGS 64
 #define MISO_NN_CHUNK 1048576
 #define MISO_NN_MAX_CHUNKS 2048
@@ -812,6 +832,12 @@ int miso_nn_query(const miso_nn_plan_t* plan, void* workspace, const float* src,
                   int64_t* out_idx, int32_t* stats, void* stream);
 int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, float* out_d2,
                       int64_t* out_idx, void* stream);
+int miso_nn_knn(const miso_nn_plan_t* plan, void* workspace, const float* src, int64_t ld, int64_t n, int32_t k, float* out_d2,
+                int64_t* out_idx, int32_t* stats, void* stream);
+int miso_nn_knn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, int32_t k,
+                          float* out_d2, int64_t* out_idx, void* stream);
+int miso_nn_knn_normals(const miso_nn_plan_t* plan, void* workspace, const float* pts, int64_t ld, int64_t n, int32_t k,
+                        float* normals, int32_t* counts, void* stream);
 
 /* --- ICP on the nearest-neighbour index: the per-point work of Open3D's registration_icp, and normals -------------------
  * Users: grid_opt/utils/utils_registration.py (registration_icp), utils_scannet.align_mesh_to_ref, grid_opt/align/icp.py.
@@ -836,7 +862,8 @@ int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* sr
  *   miso_nn_normals  for every row of pts (n, 3) (row stride ld), over the targets of a built index within `radius`
  *       (d2 <= radius^2, d2 in float64): counts (n) int32 and normals (n, 3) fp32 contiguous, the unit eigenvector of the
  *       smallest eigenvalue of the neighbours' covariance (closed form; sign not fixed).  Fewer than three neighbours or
- *       a neighbourhood on a line gives (0, 0, 1), Open3D's fallback.  A radius search, not Open3D's default 30-NN. */
+ *       a neighbourhood on a line gives (0, 0, 1), Open3D's fallback.  A radius search; Open3D's default 30-NN search is
+ *       miso_nn_knn_normals. */
 #define MISO_ICP_SUMS 32
 #define MISO_ICP_MAX_BLOCKS 512
 #define MISO_ICP_POINT_TO_POINT 0

@@ -1086,6 +1086,33 @@ int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* sr
   return (int)launch_nn_all_pairs(tgt, ld_t, m, src, ld_s, n, out_d2, out_idx, (hipStream_t)stream);
 }
 
+// ---- exact k nearest neighbours on the index (knn.hip) -------------------------------------------------------------------
+static bool nn_k_ok(int32_t k) { return k >= 1 && k <= MISO_NN_KNN_MAX; }
+
+int miso_nn_knn(const miso_nn_plan_t* plan, void* workspace, const float* src, int64_t ld, int64_t n, int32_t k, float* out_d2,
+                int64_t* out_idx, int32_t* stats, void* stream) {
+  if (!nn_plan_ok(plan) || !nn_k_ok(k) || ld < 3 || n < 0 || n >= ((int64_t)1 << 31) || !stats) return MISO_E_BADARG;
+  if (n > 0 && (!src || !out_d2 || !out_idx)) return MISO_E_BADARG;
+  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  return (int)launch_nn_knn(*plan, workspace, src, ld, n, k, out_d2, out_idx, stats, (hipStream_t)stream);
+}
+
+int miso_nn_knn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, int32_t k,
+                          float* out_d2, int64_t* out_idx, void* stream) {
+  if (!nn_k_ok(k) || m < 0 || n < 0 || ld_t < 3 || ld_s < 3) return MISO_E_BADARG;
+  if (m >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_BADARG;
+  if ((m > 0 && !tgt) || (n > 0 && (!src || !out_d2 || !out_idx))) return MISO_E_BADARG;
+  return (int)launch_nn_knn_all_pairs(tgt, ld_t, m, src, ld_s, n, k, out_d2, out_idx, (hipStream_t)stream);
+}
+
+int miso_nn_knn_normals(const miso_nn_plan_t* plan, void* workspace, const float* pts, int64_t ld, int64_t n, int32_t k,
+                        float* normals, int32_t* counts, void* stream) {
+  if (!nn_plan_ok(plan) || !nn_k_ok(k) || ld < 3 || n < 0 || n >= ((int64_t)1 << 31)) return MISO_E_BADARG;
+  if (n > 0 && (!pts || !normals || !counts)) return MISO_E_BADARG;
+  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  return (int)launch_nn_knn_normals(*plan, workspace, pts, ld, n, k, normals, counts, (hipStream_t)stream);
+}
+
 // ---- ICP and normals on the index (icp.hip) ----------------------------------------------------------------------------------
 int miso_icp_transform(const float* src, int64_t ld, int64_t n, const float* pose, float* out, void* stream) {
   if (n < 0 || ld < 3 || !pose) return MISO_E_BADARG;

@@ -147,39 +147,7 @@ inline int icp_blocks(int64_t n) {
 }
 
 // ---- normals -----------------------------------------------------------------------------------------------------------
-// unit eigenvector of the smallest eigenvalue of the symmetric matrix {c00 c01 c02; . c11 c12; . . c22}; false: none
-__device__ __forceinline__ bool smallest_eigenvector(double c00, double c01, double c02, double c11, double c12, double c22,
-                                                     double v[3]) {
-  const double big = fmax(fmax(fmax(fabs(c00), fabs(c11)), fabs(c22)), fmax(fmax(fabs(c01), fabs(c02)), fabs(c12)));
-  if (!(big > 0.0) || !(big < __builtin_huge_val())) return false;
-  const double s = 1.0 / big;
-  c00 *= s; c01 *= s; c02 *= s; c11 *= s; c12 *= s; c22 *= s;
-  const double q = (c00 + c11 + c22) / 3.0;
-  const double b00 = c00 - q, b11 = c11 - q, b22 = c22 - q;
-  const double off = c01 * c01 + c02 * c02 + c12 * c12;
-  const double p = sqrt((b00 * b00 + b11 * b11 + b22 * b22 + 2.0 * off) / 6.0);
-  if (!(p > 0.0)) return false;                                       // a multiple of I
-  const double ip = 1.0 / p;
-  const double a00 = b00 * ip, a11 = b11 * ip, a22 = b22 * ip, a01 = c01 * ip, a02 = c02 * ip, a12 = c12 * ip;
-  const double det = a00 * (a11 * a22 - a12 * a12) - a01 * (a01 * a22 - a12 * a02) + a02 * (a01 * a12 - a11 * a02);
-  const double h = fmin(fmax(0.5 * det, -1.0), 1.0);
-  const double lam = q + 2.0 * p * cos(acos(h) / 3.0 + 2.0943951023931954923);      // the smallest root
-  const double r0[3] = {c00 - lam, c01, c02}, r1[3] = {c01, c11 - lam, c12}, r2[3] = {c02, c12, c22 - lam};
-  double best[3] = {0.0, 0.0, 0.0}, best2 = -1.0;
-#pragma unroll
-  for (int pair = 0; pair < 3; ++pair) {
-    const double* a = pair == 2 ? r1 : r0;
-    const double* b = pair == 0 ? r1 : r2;
-    const double x[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
-    const double n2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-    if (n2 > best2) { best2 = n2; best[0] = x[0]; best[1] = x[1]; best[2] = x[2]; }
-  }
-  if (!(best2 > 1e-24)) return false;
-  const double inv = 1.0 / sqrt(best2);
-  v[0] = best[0] * inv; v[1] = best[1] * inv; v[2] = best[2] * inv;
-  return true;
-}
-
+// (smallest_eigenvector / NormalSums / normal_from_sums: nn.hpp, shared with the k-nearest normals of knn.hip)
 __global__ __launch_bounds__(256) void nn_normals_kernel(NnK k, const int* __restrict__ table, const float4* __restrict__ rows,
                                                          const float* __restrict__ pts, int64_t ld, int64_t n, double radius,
                                                          float* __restrict__ normals, int32_t* __restrict__ counts) {
@@ -188,7 +156,8 @@ __global__ __launch_bounds__(256) void nn_normals_kernel(NnK k, const int* __res
   const float qf[3] = {pts[i * ld], pts[i * ld + 1], pts[i * ld + 2]};
   const double q[3] = {(double)qf[0], (double)qf[1], (double)qf[2]};
   const double r2 = radius * radius;
-  double cnt = 0.0, s[3] = {0.0, 0.0, 0.0}, ss[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  NormalSums acc;
+  acc.clear();
   if (k.n_tgt > 0) {
     int clo[3], chi[3];
     const float rf = (float)radius;
@@ -207,27 +176,14 @@ __global__ __launch_bounds__(256) void nn_normals_kernel(NnK k, const int* __res
           const float4 t = rows[j];
           const double d[3] = {(double)t.x - q[0], (double)t.y - q[1], (double)t.z - q[2]};
           const double d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
-          if (d2 <= r2) {
-            cnt += 1.0;
-            s[0] += d[0]; s[1] += d[1]; s[2] += d[2];
-            ss[0] += d[0] * d[0]; ss[1] += d[0] * d[1]; ss[2] += d[0] * d[2];
-            ss[3] += d[1] * d[1]; ss[4] += d[1] * d[2]; ss[5] += d[2] * d[2];
-          }
+          if (d2 <= r2) acc.add(d);
         }
       }
   }
-  double v[3] = {0.0, 0.0, 1.0};
-  if (cnt >= 3.0) {
-    const double inv = 1.0 / cnt;
-    const double m[3] = {s[0] * inv, s[1] * inv, s[2] * inv};
-    double e[3];
-    if (smallest_eigenvector(ss[0] * inv - m[0] * m[0], ss[1] * inv - m[0] * m[1], ss[2] * inv - m[0] * m[2],
-                             ss[3] * inv - m[1] * m[1], ss[4] * inv - m[1] * m[2], ss[5] * inv - m[2] * m[2], e)) {
-      v[0] = e[0]; v[1] = e[1]; v[2] = e[2];
-    }
-  }
+  double v[3];
+  normal_from_sums(acc, v);
   normals[i * 3] = (float)v[0]; normals[i * 3 + 1] = (float)v[1]; normals[i * 3 + 2] = (float)v[2];
-  counts[i] = (int32_t)cnt;
+  counts[i] = (int32_t)acc.cnt;
 }
 
 }  // namespace

@@ -163,6 +163,13 @@ hipError_t launch_nn_query(const miso_nn_plan_t& plan, void* workspace, const fl
                            int64_t* out_idx, int32_t* stats, hipStream_t s);
 hipError_t launch_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n,
                                float* out_d2, int64_t* out_idx, hipStream_t s);
+// knn.hip: the k nearest on the same index
+hipError_t launch_nn_knn(const miso_nn_plan_t& plan, void* workspace, const float* src, int64_t ld, int64_t n, int k, float* out_d2,
+                         int64_t* out_idx, int32_t* stats, hipStream_t s);
+hipError_t launch_nn_knn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, int k,
+                                   float* out_d2, int64_t* out_idx, hipStream_t s);
+hipError_t launch_nn_knn_normals(const miso_nn_plan_t& plan, void* workspace, const float* pts, int64_t ld, int64_t n, int k,
+                                 float* normals, int32_t* counts, hipStream_t s);
 
 // ---- icp.hip
 hipError_t launch_icp_transform(const float* pose, const float* src, int64_t ld, int64_t n, float* out, hipStream_t s);

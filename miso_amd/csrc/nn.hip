@@ -41,30 +41,12 @@ constexpr int NN_TILE = 1024;                                      // targets pe
 constexpr int NN_SEG_TILES = 8;                                    // the listed queries' all-pairs: at least 8 tiles a segment,
 constexpr int NN_SEGMENTS = 64;                                    // at most 64 segments (grid.y)
 
-struct Best {
-  float d2;
-  int idx;
-};
-
-__device__ __forceinline__ float nn_dist2(float ax, float ay, float az, float bx, float by, float bz) {
-  const float dx = ax - bx, dy = ay - by, dz = az - bz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
-
-// smallest (d2, idx); false for a NaN d2, and for d2 = +inf against the initial (+inf, -1)
-__device__ __forceinline__ void nn_take(Best& b, float d2, int idx) {
-  if (d2 < b.d2 || (d2 == b.d2 && idx < b.idx)) { b.d2 = d2; b.idx = idx; }
-}
+// (Best / nn_dist2 / nn_take / nn_finite3 / ring_finished: nn.hpp, shared with knn.hip)
 
 // (d2, idx) as one unsigned 64-bit key that orders like the pair: d2 >= +0 (floats then order like their bits), idx as
 // uint32 (-1 = the largest: no match).  The all-pairs kernel behind the rings merges its target segments with atomicMin.
 __device__ __forceinline__ unsigned long long nn_pack(const Best& b) {
   return ((unsigned long long)__float_as_uint(b.d2) << 32) | (unsigned long long)(uint32_t)b.idx;
-}
-
-__device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
-  const float inf = __builtin_huge_valf();
-  return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;       // false for NaN
 }
 
 // (nn_cell_axis / nn_cell_of: nn.hpp)
@@ -149,31 +131,6 @@ __device__ __forceinline__ void nn_scan_rows(const float4* __restrict__ rows, in
     const float4 t = rows[j];
     nn_take(b, nn_dist2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
   }
-}
-
-// After ring r the examined box is [c - r, c + r] (clamped to the grid).  A target outside it lies beyond a face of the box
-// that is not on the grid's edge, so in real arithmetic it is at least g away, g the smallest distance from the query to
-// such a face; with every face on the edge nothing is left.  In fp32 three things move that bound:
-//   * membership.  A target t is below the face of cell k when floor(fl(fl(t - lo) / cell)) < k, which allows
-//     t - lo < k cell (1 + 2.1 u), u = 2^-24: it may sit up to 2.1 u (k cell) beyond the plane lo + k cell.
-//   * the face.  fl(q - fl(lo + fl(k cell))) is off by at most u (k cell + |lo + k cell| + g).
-//   * the distance.  A computed d2 is within 5.1 u (relative) of the true one.
-// With A = the largest coordinate magnitude of the grid plus its largest extent (NnK.mag, from the host plan) the first two
-// are below u (4.1 A + g); the test takes 8 u (A + g) = 2^-21 (A + g) off g, which also covers the roundings of the test
-// itself, and 16 u = 2^-20 (relative) off its square.  The comparison is strict: a target left out has a computed d2
-// above `best`, so it loses whatever its index.
-__device__ __forceinline__ bool ring_finished(const NnK& k, const float q[3], const int c[3], int r, float best) {
-  const float inf = __builtin_huge_valf();
-  float g = inf;
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (c[a] - r > 0) g = fminf(g, q[a] - (k.lo[a] + (float)(c[a] - r) * k.cell));
-    if (c[a] + r < k.dims[a] - 1) g = fminf(g, (k.lo[a] + (float)(c[a] + r + 1) * k.cell) - q[a]);
-  }
-  if (g == inf) return true;                      // the box is the grid
-  const float gs = g - 0x1p-21f * (k.mag + g);
-  if (!(gs > 0.0f)) return false;
-  return best < (gs * gs) * (1.0f - 0x1p-20f);
 }
 
 __global__ __launch_bounds__(256) void nn_rings_kernel(NnK k, const int* __restrict__ table, const float4* __restrict__ rows,

@@ -1,5 +1,5 @@
-// The nearest-neighbour index as its kernels read it (nn.hip, and the normals kernel of icp.hip), and what capi.hip
-// calls: the plan itself is host logic and lives in capi.hip with the other argument checks.
+// The nearest-neighbour index as its kernels read it (nn.hip, knn.hip, and the normals kernel of icp.hip), and what
+// capi.hip calls: the plan itself is host logic and lives in capi.hip with the other argument checks.
 #pragma once
 #include "common.hpp"
 
@@ -26,6 +26,123 @@ __device__ __forceinline__ int nn_cell_of(const NnK& k, float x, float y, float 
   c[1] = nn_cell_axis(y, k.lo[1], k.cell, k.dims[1]);
   c[2] = nn_cell_axis(z, k.lo[2], k.cell, k.dims[2]);
   return (c[2] * k.dims[1] + c[1]) * k.dims[0] + c[0];
+}
+
+// ---- what the query kernels share (nn.hip, knn.hip) ----------------------------------------------------------------------
+// Every function here forms its result with one rounding per operation whatever the including file has set.
+struct Best {
+  float d2;
+  int idx;
+};
+
+__device__ __forceinline__ float nn_dist2(float ax, float ay, float az, float bx, float by, float bz) {
+#pragma clang fp contract(off)
+  const float dx = ax - bx, dy = ay - by, dz = az - bz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+// smallest (d2, idx); false for a NaN d2, and for d2 = +inf against the initial (+inf, -1)
+__device__ __forceinline__ void nn_take(Best& b, float d2, int idx) {
+  if (d2 < b.d2 || (d2 == b.d2 && idx < b.idx)) { b.d2 = d2; b.idx = idx; }
+}
+
+__device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
+  const float inf = __builtin_huge_valf();
+  return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;       // false for NaN
+}
+
+// After ring r the examined box is [c - r, c + r] (clamped to the grid).  A target outside it lies beyond a face of the box
+// that is not on the grid's edge, so in real arithmetic it is at least g away, g the smallest distance from the query to
+// such a face; with every face on the edge nothing is left.  In fp32 three things move that bound:
+//   * membership.  A target t is below the face of cell k when floor(fl(fl(t - lo) / cell)) < k, which allows
+//     t - lo < k cell (1 + 2.1 u), u = 2^-24: it may sit up to 2.1 u (k cell) beyond the plane lo + k cell.
+//   * the face.  fl(q - fl(lo + fl(k cell))) is off by at most u (k cell + |lo + k cell| + g).
+//   * the distance.  A computed d2 is within 5.1 u (relative) of the true one.
+// With A = the largest coordinate magnitude of the grid plus its largest extent (NnK.mag, from the host plan) the first two
+// are below u (4.1 A + g); the test takes 8 u (A + g) = 2^-21 (A + g) off g, which also covers the roundings of the test
+// itself, and 16 u = 2^-20 (relative) off its square.  The comparison is strict: a target left out has a computed d2
+// above `best`, so it loses whatever its index.
+__device__ __forceinline__ bool ring_finished(const NnK& k, const float q[3], const int c[3], int r, float best) {
+#pragma clang fp contract(off)
+  const float inf = __builtin_huge_valf();
+  float g = inf;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (c[a] - r > 0) g = fminf(g, q[a] - (k.lo[a] + (float)(c[a] - r) * k.cell));
+    if (c[a] + r < k.dims[a] - 1) g = fminf(g, (k.lo[a] + (float)(c[a] + r + 1) * k.cell) - q[a]);
+  }
+  if (g == inf) return true;                      // the box is the grid
+  const float gs = g - 0x1p-21f * (k.mag + g);
+  if (!(gs > 0.0f)) return false;
+  return best < (gs * gs) * (1.0f - 0x1p-20f);
+}
+
+// ---- normals from a neighbourhood's sums (icp.hip: radius; knn.hip: k nearest) -------------------------------------------
+// 1, d and d d^T of a neighbourhood, d = t - q in float64, added in the order add() is called
+struct NormalSums {
+  double cnt, s[3], ss[6];
+  __device__ __forceinline__ void clear() {
+    cnt = 0.0;
+    s[0] = s[1] = s[2] = 0.0;
+    ss[0] = ss[1] = ss[2] = ss[3] = ss[4] = ss[5] = 0.0;
+  }
+  __device__ __forceinline__ void add(const double d[3]) {
+#pragma clang fp contract(off)
+    cnt += 1.0;
+    s[0] += d[0]; s[1] += d[1]; s[2] += d[2];
+    ss[0] += d[0] * d[0]; ss[1] += d[0] * d[1]; ss[2] += d[0] * d[2];
+    ss[3] += d[1] * d[1]; ss[4] += d[1] * d[2]; ss[5] += d[2] * d[2];
+  }
+};
+
+// unit eigenvector of the smallest eigenvalue of the symmetric matrix {c00 c01 c02; . c11 c12; . . c22}; false: none
+__device__ __forceinline__ bool smallest_eigenvector(double c00, double c01, double c02, double c11, double c12, double c22,
+                                                     double v[3]) {
+#pragma clang fp contract(off)
+  const double big = fmax(fmax(fmax(fabs(c00), fabs(c11)), fabs(c22)), fmax(fmax(fabs(c01), fabs(c02)), fabs(c12)));
+  if (!(big > 0.0) || !(big < __builtin_huge_val())) return false;
+  const double s = 1.0 / big;
+  c00 *= s; c01 *= s; c02 *= s; c11 *= s; c12 *= s; c22 *= s;
+  const double q = (c00 + c11 + c22) / 3.0;
+  const double b00 = c00 - q, b11 = c11 - q, b22 = c22 - q;
+  const double off = c01 * c01 + c02 * c02 + c12 * c12;
+  const double p = sqrt((b00 * b00 + b11 * b11 + b22 * b22 + 2.0 * off) / 6.0);
+  if (!(p > 0.0)) return false;                                       // a multiple of I
+  const double ip = 1.0 / p;
+  const double a00 = b00 * ip, a11 = b11 * ip, a22 = b22 * ip, a01 = c01 * ip, a02 = c02 * ip, a12 = c12 * ip;
+  const double det = a00 * (a11 * a22 - a12 * a12) - a01 * (a01 * a22 - a12 * a02) + a02 * (a01 * a12 - a11 * a02);
+  const double h = fmin(fmax(0.5 * det, -1.0), 1.0);
+  const double lam = q + 2.0 * p * cos(acos(h) / 3.0 + 2.0943951023931954923);      // the smallest root
+  const double r0[3] = {c00 - lam, c01, c02}, r1[3] = {c01, c11 - lam, c12}, r2[3] = {c02, c12, c22 - lam};
+  double best[3] = {0.0, 0.0, 0.0}, best2 = -1.0;
+#pragma unroll
+  for (int pair = 0; pair < 3; ++pair) {
+    const double* a = pair == 2 ? r1 : r0;
+    const double* b = pair == 0 ? r1 : r2;
+    const double x[3] = {a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]};
+    const double n2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+    if (n2 > best2) { best2 = n2; best[0] = x[0]; best[1] = x[1]; best[2] = x[2]; }
+  }
+  if (!(best2 > 1e-24)) return false;
+  const double inv = 1.0 / sqrt(best2);
+  v[0] = best[0] * inv; v[1] = best[1] * inv; v[2] = best[2] * inv;
+  return true;
+}
+
+// the normal of the sums' covariance C = S_dd / n - (S_d / n)(S_d / n)^T; (0, 0, 1) for fewer than three neighbours and
+// for the degenerate cases of smallest_eigenvector
+__device__ __forceinline__ void normal_from_sums(const NormalSums& a, double v[3]) {
+#pragma clang fp contract(off)
+  v[0] = 0.0; v[1] = 0.0; v[2] = 1.0;
+  if (a.cnt >= 3.0) {
+    const double inv = 1.0 / a.cnt;
+    const double m[3] = {a.s[0] * inv, a.s[1] * inv, a.s[2] * inv};
+    double e[3];
+    if (smallest_eigenvector(a.ss[0] * inv - m[0] * m[0], a.ss[1] * inv - m[0] * m[1], a.ss[2] * inv - m[0] * m[2],
+                             a.ss[3] * inv - m[1] * m[1], a.ss[4] * inv - m[1] * m[2], a.ss[5] * inv - m[2] * m[2], e)) {
+      v[0] = e[0]; v[1] = e[1]; v[2] = e[2];
+    }
+  }
 }
 
 inline int64_t nn_a256(int64_t v) { return (v + 255) / 256 * 256; }

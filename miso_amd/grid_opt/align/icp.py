@@ -1,8 +1,8 @@
 """Pairwise submap alignment by ICP on the near-surface samples (reference: grid_opt/align/icp.py:14-118, an Open3D
 pipeline).  Here the clouds stay on the device: Open3D's voxel_down_sample is utils_geometry.voxel_centroid_down_sample,
-its estimate_normals is ops.NearestIndex.normals on the down-sampled target (a RADIUS search of NN_NORMAL_SPACINGS point
-spacings, not Open3D's default 30 nearest neighbours), registration_icp and get_information_matrix_from_point_clouds are
-utils_registration's (csrc/icp.hip).
+its estimate_normals is ops.NearestIndex.normals on the down-sampled target (by default a RADIUS search of
+NN_NORMAL_SPACINGS point spacings; ``normals_knn=30`` is Open3D's default 30 nearest neighbours, csrc/knn.hip),
+registration_icp and get_information_matrix_from_point_clouds are utils_registration's (csrc/icp.hip).
 
 The reference reads the batch keys 'submap_idxs' / 'coords_kf' / 'keyframe_idxs', which none of its current datasets
 write; this module reads what they write and what align/miso.py reads: 'sample_frame_ids' and 'coords_frame', the submap
@@ -48,11 +48,13 @@ def get_points_for_submap(grid_atlas: GridAtlas, dataset, submap_id: int, num_ba
 
 def align_submap_pair(grid_atlas: GridAtlas, dataset, src_id: int, dst_id: int, constraint_type='point_to_plane',
                       voxel_size=0.02, threshold_factor_coarse=15, threshold_factor_fine=1.5, num_iters=30, num_batches=10,
-                      update_grid_atlas=True, trunc_dist=1e-3, device=None):
+                      update_grid_atlas=True, trunc_dist=1e-3, device=None, normals_knn=None):
     """Reference :51-118, same defaults: coarse then fine ICP (both with the L2 loss, as upstream) of submap ``src_id``'s
     near-surface samples onto ``dst_id``'s, from the atlas' initial relative pose, and the information matrix of the
     result.  ``update_grid_atlas``: ``dst_id``'s pose correction is set so that its updated pose agrees with the result.
-    ``trunc_dist`` (get_points_for_submap's) and ``device`` (default: the first GPU) are additions.
+    ``trunc_dist`` (get_points_for_submap's) and ``device`` (default: the first GPU) are additions, and so is
+    ``normals_knn``: None takes the target normals from the radius search, an int from that many nearest neighbours
+    (30 is upstream's ``estimate_normals()``).
     -> (RegistrationResult with T_dst_src, information (6, 6) float64, {'cpu_time_sec', 'gpu_time_sec'})"""
     from miso_amd import ops
     from miso_amd.grid_opt.utils import utils_registration as reg
@@ -67,7 +69,7 @@ def align_submap_pair(grid_atlas: GridAtlas, dataset, src_id: int, dst_id: int, 
         clouds.append(utils_geometry.voxel_centroid_down_sample(pts, voxel_size).to(torch.float32).contiguous())
     src, dst = clouds
     index = ops.NearestIndex(dst)
-    normals = index.normals()[0] if constraint_type == 'point_to_plane' else None
+    normals = index.normals(knn=normals_knn)[0] if constraint_type == 'point_to_plane' else None
     R_world_src, t_world_src = grid_atlas.initial_submap_pose(src_id)
     R_world_dst, t_world_dst = grid_atlas.initial_submap_pose(dst_id)
     T_world_src = utils_geometry.pose_matrix(R_world_src, t_world_src)

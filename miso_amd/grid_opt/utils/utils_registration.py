@@ -107,6 +107,19 @@ def _evaluation(sums, n):
     return (count / n if n else 0.0), (float(np.sqrt(sums[_SUM_D2] / count)) if count > 0 else 0.0)
 
 
+def estimate_normals(points, knn=30, radius=None, index=None):
+    """Open3D's ``PointCloud.estimate_normals`` restated from its documented behaviour: for every point the unit
+    eigenvector of the smallest eigenvalue of the covariance of its neighbours among ``points`` -- by default its
+    ``knn`` = 30 nearest (KDTreeSearchParamKNN, the point itself being the first), with ``radius`` those within it
+    (KDTreeSearchParamRadius; ``knn`` is then not read, Open3D's hybrid search is not built).  Fewer than three neighbours,
+    or neighbours on a line, give (0, 0, 1).  Normals are NOT oriented (Open3D's are not either).  ``index``: an
+    ops.NearestIndex over ``points`` to reuse, else one is built.  -> (N, 3) fp32 on the device (ops.NearestIndex.normals)."""
+    index = ops.NearestIndex(points) if index is None else index
+    if tuple(index.tgt.shape) != tuple(points.shape):
+        raise ValueError("estimate_normals: index is not built on points")
+    return index.normals(radius=radius)[0] if radius is not None else index.normals(knn=int(knn))[0]
+
+
 def registration_icp(src, tgt_index, tgt=None, tgt_normals=None, max_dist=0.05, init=None, kind='point_to_plane',
                      loss=None, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, callback=None
                      ) -> RegistrationResult:

@@ -3,7 +3,8 @@ grid_opt/utils/utils_scannet.py:10-113).  ``create_scannet_dataset`` builds the 
 miso_amd.grid_opt.datasets.sdf_rgbd from the same files the reference reads (``<root>/scene<id>/scene<id>.txt``,
 ``frames/pose/*.pose.txt``, ``frames/depth/*.depth.pgm``).  ``align_mesh_to_ref`` (reference :115-156, an Open3D
 registration pipeline) is the second step of the demo's mesh grading: coarse and fine ICP of the reconstruction onto the
-ground truth, here on ops.NearestIndex and the kernels of csrc/icp.hip (utils_registration.registration_icp)."""
+ground truth, here on ops.NearestIndex and the kernels of csrc/icp.hip (utils_registration.registration_icp).
+utils_ncd.align_mesh_to_ref shares its two passes (``icp_coarse_then_fine``)."""
 import copy
 import logging
 from dataclasses import dataclass
@@ -103,31 +104,50 @@ def _sampled(mesh, count, seed, device, want_normals):
     return points.to(torch.float32).contiguous(), normals
 
 
+def icp_coarse_then_fine(src, tgt, normals, constraint_type, voxel_size, threshold_factor_coarse, threshold_factor_fine, num_iters,
+                         index=None):
+    """The two passes the reference's align_mesh_to_ref functions share (utils_scannet.py:140-151, utils_ncd.py:72-83): a
+    coarse ICP with the L2 loss at ``voxel_size * threshold_factor_coarse`` from the identity, then a fine one with
+    TukeyLoss(k=1e-2) at ``voxel_size * threshold_factor_fine`` from the coarse result, on one ops.NearestIndex over
+    ``tgt``.  -> the fine RegistrationResult"""
+    from miso_amd import ops
+    from miso_amd.grid_opt.utils import utils_registration as reg
+    index = ops.NearestIndex(tgt) if index is None else index
+    coarse = reg.registration_icp(src, index, tgt, normals, voxel_size * threshold_factor_coarse, np.eye(4),
+                                  kind=constraint_type, loss=None, max_iteration=num_iters)
+    fine = reg.registration_icp(src, index, tgt, normals, voxel_size * threshold_factor_fine, coarse.transformation,
+                                kind=constraint_type, loss=reg.TukeyLoss(k=1e-2), max_iteration=num_iters)
+    logger.debug(f"Finetuned ICP result: {fine}\n{fine.transformation}")
+    return fine
+
+
 def align_mesh_to_ref(est_mesh, ref_mesh, constraint_type='point_to_plane', voxel_size=0.02, threshold_factor_coarse=15,
-                      threshold_factor_fine=1.5, num_iters=100, num_points=1000000, seed=0):
+                      threshold_factor_fine=1.5, num_iters=100, num_points=1000000, seed=0, normals='faces'):
     """Reference :115-156, same defaults: ``num_points`` surface samples of each mesh (utils_eval.sample_surface, seeds
     ``seed`` and ``seed + 1``), a coarse ICP with the L2 loss at ``voxel_size * threshold_factor_coarse`` from the identity,
     then a fine one with TukeyLoss(k=1e-2) at ``voxel_size * threshold_factor_fine`` from the coarse result.  One
     ops.NearestIndex over the reference's samples serves both passes.  ``est_mesh`` / ``ref_mesh``: utils_sdf.TriangleMesh
     objects or PLY paths.
 
-    Differences from the reference, on purpose: the target normals of 'point_to_plane' are the FACE NORMALS of the sampled
-    triangles, which are exact, where the reference estimates them from the samples (``estimate_normals``); the samples
-    are not Open3D's; the input mesh is left alone and no viewer is opened.
+    ``normals``, the target normals of 'point_to_plane': 'faces' (the default) takes the FACE NORMALS of the sampled
+    triangles, which are exact; 'knn' estimates them from the reference's samples with the 30 nearest neighbours, as the
+    reference does (``estimate_normals()``, utils_registration.estimate_normals here).  Other differences from the
+    reference, on purpose: the samples are not Open3D's; the input mesh is left alone and no viewer is opened.
     -> (a copy of ``est_mesh`` moved by the fine result, that RegistrationResult; its ``transformation`` is T_ref_est)."""
     from miso_amd import ops
     from miso_amd.grid_opt.utils import utils_registration as reg
     if constraint_type not in ('point_to_plane', 'point_to_point'):
         raise ValueError(f"Unknown constraint type {constraint_type}")
+    if normals not in ('faces', 'knn'):
+        raise ValueError(f"Unknown normals {normals}")
     est, ref = _as_mesh(est_mesh), _as_mesh(ref_mesh)
     device = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
     plane = constraint_type == 'point_to_plane'
     src, _ = _sampled(est, num_points, seed, device, False)
-    tgt, normals = _sampled(ref, num_points, seed + 1, device, plane)
+    tgt, tgt_normals = _sampled(ref, num_points, seed + 1, device, plane and normals == 'faces')
     index = ops.NearestIndex(tgt)
-    coarse = reg.registration_icp(src, index, tgt, normals, voxel_size * threshold_factor_coarse, np.eye(4),
-                                  kind=constraint_type, loss=None, max_iteration=num_iters)
-    fine = reg.registration_icp(src, index, tgt, normals, voxel_size * threshold_factor_fine, coarse.transformation,
-                                kind=constraint_type, loss=reg.TukeyLoss(k=1e-2), max_iteration=num_iters)
-    logger.debug(f"Finetuned ICP result: {fine}\n{fine.transformation}")
+    if plane and normals == 'knn':
+        tgt_normals = reg.estimate_normals(tgt, index=index)
+    fine = icp_coarse_then_fine(src, tgt, tgt_normals, constraint_type, voxel_size, threshold_factor_coarse,
+                                threshold_factor_fine, num_iters, index)
     return copy.deepcopy(est).apply_transform(fine.transformation), fine

@@ -1033,6 +1033,7 @@ NN_CELL_SPACINGS = 2.0       # default cell = this many point spacings (DESIGN.m
 NN_MAX_RINGS = 4             # default number of shells around a query's cell before the all-pairs kernel takes it
 NN_ALL_PAIRS_BELOW = 1 << 22  # nearest(): N * M below this goes to the all-pairs kernel (the index costs ~8 more launches)
 NN_NORMAL_SPACINGS = 4.0     # NearestIndex.normals(radius=None): this many point spacings
+NN_KNN_MAX = _lib.NN_KNN_MAX  # the largest k of NearestIndex.knn / normals(knn=k)
 
 
 def _cloud(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -1065,8 +1066,8 @@ def nn_default_cell(lo, hi, m: int) -> float:
 
 
 class NearestIndex:
-    """A uniform cell list over ``tgt`` (M, 3) for exact 1-nearest-neighbour queries (miso_nn_plan / miso_nn_build,
-    csrc/nn.hip).  Building reads the targets' bounds back -- six floats, ONE device-to-host read per build -- to plan
+    """A uniform cell list over ``tgt`` (M, 3) for exact nearest-neighbour queries: the nearest (``query``, csrc/nn.hip), the
+    k nearest (``knn``, csrc/knn.hip) and normals from either neighbourhood (miso_nn_plan / miso_nn_build).  Building reads the targets' bounds back -- six floats, ONE device-to-host read per build -- to plan
     the grid on the host; queries read nothing back.  ``cell=None``: nn_default_cell; ``max_rings=None``: NN_MAX_RINGS.
     Rows with a non-finite coordinate are never a match and do not widen the bounds."""
 
@@ -1114,19 +1115,53 @@ class NearestIndex:
                                              _ptr(idx), _ptr(stats), _stream(src)), "miso_nn_query")
         return d2, idx, stats
 
-    def normals(self, points: Optional[torch.Tensor] = None, radius: Optional[float] = None):
+    def knn(self, src: torch.Tensor, k: int, out=None):
+        """The ``k`` nearest indexed targets of every row of ``src`` (miso_nn_knn, csrc/knn.hip; 1 <= k <= NN_KNN_MAX): the k
+        smallest (d2, index) pairs, ascending.  -> (d2 (N, k) fp32, idx (N, k) int64, stats (2,) int32 as ``query``'s), all
+        on the device; slots without a neighbour (fewer than k finite targets, a non-finite query) hold (+inf, -1).
+        Nothing is read back, so with ``out`` = (d2, idx, stats) the call replays inside a captured graph.  One query at
+        a time per index."""
+        src = _cloud(src, "src")
+        n, k = int(src.shape[0]), int(k)
+        if not 1 <= k <= NN_KNN_MAX:
+            raise ValueError(f"knn: k = {k} is outside 1 .. {NN_KNN_MAX}")
+        if out is None:
+            out = (torch.empty((n, k), device=src.device, dtype=torch.float32),
+                   torch.empty((n, k), device=src.device, dtype=torch.int64), torch.empty(2, device=src.device, dtype=torch.int32))
+        d2, idx, stats = out
+        assert d2.is_cuda and d2.dtype == torch.float32 and d2.is_contiguous() and tuple(d2.shape) == (n, k)
+        assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and tuple(idx.shape) == (n, k)
+        assert stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= 2
+        _lib.check(_lib.load().miso_nn_knn(C.byref(self.plan), _ptr(self.workspace), _ptr(src), _ld(src), n, k, _ptr(d2),
+                                           _ptr(idx), _ptr(stats), _stream(src)), "miso_nn_knn")
+        return d2, idx, stats
+
+    def normals(self, points: Optional[torch.Tensor] = None, radius: Optional[float] = None, knn: Optional[int] = None):
         """For every row of ``points`` (default: the indexed cloud itself) the normal of its neighbourhood among the
-        indexed targets: the unit eigenvector of the smallest eigenvalue of the covariance of the targets within
-        ``radius`` (miso_nn_normals, csrc/icp.hip).  -> (normals (N, 3) fp32, counts (N,) int32).  This is Open3D's RADIUS
-        search (KDTreeSearchParamRadius), not the 30-nearest-neighbour search estimate_normals() defaults to;
-        ``radius=None``: NN_NORMAL_SPACINGS point spacings (self.spacing, the estimate behind the default cell), about
-        fifty neighbours on a sampled surface.  Fewer than three neighbours, or neighbours on a line, give (0, 0, 1) as in
-        Open3D, and the count shows it.  The sign of a normal is not fixed (point-to-plane ICP does not read it)."""
+        indexed targets: the unit eigenvector of the smallest eigenvalue of the neighbours' covariance.
+        -> (normals (N, 3) fp32, counts (N,) int32).  The neighbourhood is either
+          * ``knn=k``: the k nearest targets (miso_nn_knn_normals, csrc/knn.hip), Open3D's KDTreeSearchParamKNN, which
+            estimate_normals() defaults to with k = 30; a point of the indexed cloud is its own first neighbour.  The sums
+            are taken in ascending (d2, index) order, so two builds of the index give the same bits; or
+          * the targets within ``radius`` (miso_nn_normals, csrc/icp.hip), Open3D's KDTreeSearchParamRadius.
+            ``radius=None`` and ``knn=None``: NN_NORMAL_SPACINGS point spacings (self.spacing, the estimate behind the
+            default cell), about fifty neighbours on a sampled surface.
+        Giving both raises.  Fewer than three neighbours, or neighbours on a line, give (0, 0, 1) as in Open3D, and the
+        count shows it.  The sign of a normal is not fixed (point-to-plane ICP does not read it)."""
+        if radius is not None and knn is not None:
+            raise ValueError("normals: give radius or knn, not both")
         pts = self.tgt if points is None else _cloud(points, "points")
         n = int(pts.shape[0])
-        radius = NN_NORMAL_SPACINGS * self.spacing if radius is None else float(radius)
         out = torch.empty((n, 3), device=pts.device, dtype=torch.float32)
         counts = torch.empty(n, device=pts.device, dtype=torch.int32)
+        if knn is not None:
+            k = int(knn)
+            if not 1 <= k <= NN_KNN_MAX:
+                raise ValueError(f"normals: knn = {k} is outside 1 .. {NN_KNN_MAX}")
+            _lib.check(_lib.load().miso_nn_knn_normals(C.byref(self.plan), _ptr(self.workspace), _ptr(pts), _ld(pts), n, k,
+                                                       _ptr(out), _ptr(counts), _stream(pts)), "miso_nn_knn_normals")
+            return out, counts
+        radius = NN_NORMAL_SPACINGS * self.spacing if radius is None else float(radius)
         _lib.check(_lib.load().miso_nn_normals(C.byref(self.plan), _ptr(self.workspace), _ptr(pts), _ld(pts), n, radius,
                                                _ptr(out), _ptr(counts), _stream(pts)), "miso_nn_normals")
         return out, counts
@@ -1152,6 +1187,31 @@ def nearest(src: torch.Tensor, tgt: torch.Tensor, cell: Optional[float] = None):
     if int(src.shape[0]) * int(tgt.shape[0]) < NN_ALL_PAIRS_BELOW:
         return nearest_all_pairs(src, tgt)
     d2, idx, _ = NearestIndex(tgt, cell=cell).query(src)
+    return d2, idx
+
+
+def knn_all_pairs(src: torch.Tensor, tgt: torch.Tensor, k: int):
+    """The all-pairs kernel for every query (miso_nn_knn_all_pairs): -> (d2 (N, k), idx (N, k)), the bits
+    NearestIndex.knn returns."""
+    src, tgt = _cloud(src, "src"), _cloud(tgt, "tgt")
+    n, m, k = int(src.shape[0]), int(tgt.shape[0]), int(k)
+    if not 1 <= k <= NN_KNN_MAX:
+        raise ValueError(f"knn_all_pairs: k = {k} is outside 1 .. {NN_KNN_MAX}")
+    d2 = torch.empty((n, k), device=src.device, dtype=torch.float32)
+    idx = torch.empty((n, k), device=src.device, dtype=torch.int64)
+    _lib.check(_lib.load().miso_nn_knn_all_pairs(_ptr(tgt), _ld(tgt), m, _ptr(src), _ld(src), n, k, _ptr(d2), _ptr(idx),
+                                                 _stream(src)), "miso_nn_knn_all_pairs")
+    return d2, idx
+
+
+def knn(src: torch.Tensor, tgt: torch.Tensor, k: int, cell: Optional[float] = None):
+    """For every row of ``src`` (N, 3) its ``k`` nearest rows of ``tgt`` (M, 3), pytorch3d's knn_points(K=k): the k smallest
+    (d2, index) pairs, ascending, d2 as ``nearest`` forms it.  -> (d2 (N, k) fp32, idx (N, k) int64) on the device, padded
+    with (+inf, -1).  The route is picked by N M as in ``nearest``; both give the same bits."""
+    _require_hip(src, tgt)
+    if int(src.shape[0]) * int(tgt.shape[0]) < NN_ALL_PAIRS_BELOW:
+        return knn_all_pairs(src, tgt, k)
+    d2, idx, _ = NearestIndex(tgt, cell=cell).knn(src, k)
     return d2, idx
 
 
