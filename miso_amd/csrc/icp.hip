@@ -24,7 +24,8 @@
 // calls on the same inputs return the same bits.  n == 0 launches the second kernel only, which writes zeros.
 //
 // Normals (miso_nn_normals).  A lane per query point q walks the cells of the index that the ball of `radius` around q
-// touches: per axis the cells of fl(q - rs) .. fl(q + rs), rs = radius + 2^-21 (|q| + radius), which covers the rounding of
+// touches, an x run of rows at a time (nn_visit_run, nn.hpp: the run visitor of the nearest-neighbour queries): per
+// axis the cells of fl(q - rs) .. fl(q + rs), rs = radius + 2^-21 (|q| + radius), which covers the rounding of
 // the two sums (the cell function itself is monotone, so a target within the radius along an axis never lies in a cell
 // outside that range).  For every target t of those cells, d = t - q in float64 and d2 = (d_x d_x + d_y d_y) + d_z d_z;
 // with d2 <= radius^2 it adds 1, d and d d^T to ten float64 accumulators.  C = S_dd / n - (S_d / n)(S_d / n)^T; the
@@ -167,17 +168,16 @@ __global__ __launch_bounds__(256) void nn_normals_kernel(NnK k, const int* __res
       clo[a] = nn_cell_axis(qf[a] - rs, k.lo[a], k.cell, k.dims[a]);
       chi[a] = nn_cell_axis(qf[a] + rs, k.lo[a], k.cell, k.dims[a]);
     }
-    const int n_rows = (int)k.n_tgt;
+    const auto add = [&](const float4& t, int) {
+      const double d[3] = {(double)t.x - q[0], (double)t.y - q[1], (double)t.z - q[2]};
+      const double d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+      if (d2 <= r2) acc.add(d);
+    };
+    // the box, z outer, y inner, one x run per (z, y): the order the sums are added in
     for (int z = clo[2]; z <= chi[2]; ++z)
       for (int y = clo[1]; y <= chi[1]; ++y) {
         const int row = (z * k.dims[1] + y) * k.dims[0];
-        const int e = min(table[row + chi[0] + 1], n_rows);            // (as nn_scan_rows: never outside the rows)
-        for (int j = max(table[row + clo[0]], 0); j < e; ++j) {
-          const float4 t = rows[j];
-          const double d[3] = {(double)t.x - q[0], (double)t.y - q[1], (double)t.z - q[2]};
-          const double d2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
-          if (d2 <= r2) acc.add(d);
-        }
+        nn_visit_run(table, rows, (int)k.n_tgt, row + clo[0], row + chi[0], add);
       }
   }
   double v[3];
@@ -222,11 +222,8 @@ hipError_t launch_icp_sums(const float* moved, const float* d2, const int64_t* i
 hipError_t launch_nn_normals(const miso_nn_plan_t& p, const void* ws, const float* pts, int64_t ld, int64_t n, double radius,
                              float* normals, int32_t* counts, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  const NnLayout l = nn_layout(p);
-  const char* w = reinterpret_cast<const char*>(ws);
-  const int* table = p.n_tgt > 0 ? reinterpret_cast<const int*>(w + l.table) : nullptr;
-  const float4* rows = p.n_tgt > 0 ? reinterpret_cast<const float4*>(w + l.rows) : nullptr;
-  nn_normals_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nn_k(p), table, rows, pts, ld, n, radius, normals, counts);
+  const auto v = nn_views(p, p.n_tgt > 0 ? ws : nullptr);
+  nn_normals_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(nn_k(p), v.table, v.rows, pts, ld, n, radius, normals, counts);
   return hipGetLastError();
 }
 

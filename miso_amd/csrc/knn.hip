@@ -3,7 +3,7 @@
 // arithmetic and the order are those of nn.hip:
 //     d2 = ((ax - bx)^2 + (ay - by)^2) + (az - bz)^2        fp32, one rounding per operation
 // and the answer of a query is the k smallest (d2, original target index) pairs in lexicographic order, listed ascending.
-// A NaN or +inf d2 is never a neighbour (both comparisons of knn_offer are false for it); a query with a non-finite
+// A NaN or +inf d2 is never a neighbour (both comparisons of KnnList::offer are false for it); a query with a non-finite
 // coordinate, and the slots beyond the number of finite targets, get (+inf, -1).  The k smallest pairs of a set do not
 // depend on the order in which the set is visited, so the answer depends neither on the visiting order, nor on the order
 // the build's atomics left inside a cell, nor on the kernel.
@@ -16,19 +16,19 @@
 //   payload  the original target index (neighbour lists), or the target's ROW in the index (normals: the epilogue reads
 //            the neighbours' coordinates from the rows, which hold the original index in .w; a tie on d2 reads it there).
 //
-// Rings (knn_rings_kernel), a lane per query, shells r = 0 .. max_rings as nn_rings_kernel walks them.  A query is
-// finished after ring r when its list holds k entries and ring_finished(k, q, c, r, worst kept d2) holds, or when every
-// face of the examined box is on the grid's edge (then with fewer than k entries: there are no more targets).  The
-// argument of ring_finished (nn.hpp) carries over with `best` = the worst kept d2: a target outside the box has a computed
-// d2 strictly above it, so it loses against every kept entry whatever its index.  Unfinished queries append themselves
-// to the chunk's list, one atomic per wavefront, and write nothing.
+// Rings (knn_rings_kernel), a lane per query: the walk of nn.hip's rings (nn_shell, nn_visit_shell_row; nn.hpp), with the
+// list as its accumulator.  A query is finished after ring r when its list holds k entries and ring_finished(k, q, c, r,
+// worst kept d2) holds, or when every face of the examined box is on the grid's edge (then with fewer than k entries:
+// there are no more targets).  The argument of ring_finished (nn.hpp) carries over with `best` = the worst kept d2: a
+// target outside the box has a computed d2 strictly above it, so it loses against every kept entry whatever its index.
+// Unfinished queries append themselves to the chunk's list (nn_defer) and write nothing.
 //
-// All pairs (knn_all_pairs_kernel).  LISTED: the queries the rings left, over the index's rows; each starts from an EMPTY
-// list (the scan meets every target, those the rings had taken too) and one block sees ALL targets, tile by tile: a
-// list of k entries has no 64-bit atomicMin to merge segments with, and one segment per block needs no second buffer and
-// is deterministic.  Blocks whose first slot is at or beyond the device-side count leave as a whole, before any barrier,
-// so the launch is sized for the worst case and the host reads nothing.  Else: every query over the caller's arrays, the
-// second independent route (miso_nn_knn_all_pairs).
+// All pairs (knn_all_pairs_kernel; queries and tiles as nn.hip's: nn_block_query, nn_stage_tile).  LISTED: the queries
+// the rings left, over the index's rows; each starts from an EMPTY list (the scan meets every target, those the rings
+// had taken too) and one block sees ALL targets, tile by tile: a list of k entries has no 64-bit atomicMin to merge
+// segments with, and one segment per block needs no second buffer and is deterministic.  Blocks whose first slot is at
+// or beyond the device-side count leave as a whole, before any barrier, so the launch is sized for the worst case and
+// the host reads nothing.  Else: every query over the caller's arrays, the second route (miso_nn_knn_all_pairs).
 //
 // Epilogue (knn_finish).  Lists: the lane writes its row of out_d2 / out_idx (n, k), padded with (+inf, -1).  Normals:
 // 1, d and d d^T, d = t - q in float64, are added in the list's order, ascending (d2, index): the order is a function of
@@ -78,11 +78,18 @@ struct KnnList {
     if (cnt < k) ++cnt;
     if (cnt == k) { wd = d[(k - 1) * KNN_LANES]; wi = original(p[(k - 1) * KNN_LANES]); }
   }
+  // target t, row `row` of the index (ROWPOS only), as a candidate of query q
+  __device__ __forceinline__ void take(float qx, float qy, float qz, const float4& t, int row) {
+    const int idx = __float_as_int(t.w);
+    offer(nn_dist2(qx, qy, qz, t.x, t.y, t.z), idx, ROWPOS ? row : idx);
+  }
+  // the stop test's `best`: the worst kept d2, and nothing is excluded while the list is short
+  __device__ __forceinline__ float bound() const { return cnt == k ? wd : __builtin_huge_valf(); }
 };
 
 // what a finished query writes: its row of the lists, or its normal and count
 template <bool NORMALS>
-__device__ __forceinline__ void knn_finish(const KnnList<NORMALS>& l, int64_t i, float qx, float qy, float qz,
+__device__ __forceinline__ void knn_finish(const KnnList<NORMALS>& l, int64_t i, const float qf[3],
                                            float* __restrict__ out_d2, int64_t* __restrict__ out_idx,
                                            float* __restrict__ normals, int32_t* __restrict__ counts) {
   if (!NORMALS) {
@@ -92,7 +99,7 @@ __device__ __forceinline__ void knn_finish(const KnnList<NORMALS>& l, int64_t i,
       out_idx[i * l.k + s] = has ? (int64_t)l.p[s * KNN_LANES] : (int64_t)-1;
     }
   } else {
-    const double q[3] = {(double)qx, (double)qy, (double)qz};
+    const double q[3] = {(double)qf[0], (double)qf[1], (double)qf[2]};
     NormalSums acc;
     acc.clear();
     for (int s = 0; s < l.cnt; ++s) {
@@ -108,17 +115,6 @@ __device__ __forceinline__ void knn_finish(const KnnList<NORMALS>& l, int64_t i,
 }
 
 // ---- rings -------------------------------------------------------------------------------------------------------------
-template <bool ROWPOS>
-__device__ __forceinline__ void knn_scan_rows(const float4* __restrict__ rows, int n_rows, int s, int e, float qx, float qy, float qz,
-                                              KnnList<ROWPOS>& l) {
-  e = min(e, n_rows);                            // (a table that no build wrote must not lead outside the rows)
-  for (int j = max(s, 0); j < e; ++j) {
-    const float4 t = rows[j];
-    const int idx = __float_as_int(t.w);
-    l.offer(nn_dist2(qx, qy, qz, t.x, t.y, t.z), idx, ROWPOS ? j : idx);
-  }
-}
-
 template <bool NORMALS>
 __global__ __launch_bounds__(KNN_LANES) void knn_rings_kernel(NnK k, int kk, const int* __restrict__ table, const float4* __restrict__ rows,
                                                               const float* __restrict__ src, int64_t ld, int64_t first, int count,
@@ -140,41 +136,15 @@ __global__ __launch_bounds__(KNN_LANES) void knn_rings_kernel(NnK k, int kk, con
       nn_cell_of(k, q[0], q[1], q[2], c);
       done = false;
       for (int r = 0; r <= k.max_rings && !done; ++r) {
-        const int xlo = max(c[0] - r, 0), xhi = min(c[0] + r, k.dims[0] - 1);
-        const int ylo = max(c[1] - r, 0), yhi = min(c[1] + r, k.dims[1] - 1);
-        const int zlo = max(c[2] - r, 0), zhi = min(c[2] + r, k.dims[2] - 1);
-        for (int z = zlo; z <= zhi; ++z)
-          for (int y = ylo; y <= yhi; ++y) {
-            const int row = (z * k.dims[1] + y) * k.dims[0];
-            if (abs(z - c[2]) == r || abs(y - c[1]) == r) {          // a whole x run of the shell: one run of rows
-              knn_scan_rows(rows, (int)k.n_tgt, table[row + xlo], table[row + xhi + 1], q[0], q[1], q[2], l);
-            } else {                                                  // (r > 0 here) the two end cells of the run
-              if (c[0] - r >= 0) knn_scan_rows(rows, (int)k.n_tgt, table[row + c[0] - r], table[row + c[0] - r + 1], q[0], q[1], q[2], l);
-              if (c[0] + r < k.dims[0]) knn_scan_rows(rows, (int)k.n_tgt, table[row + c[0] + r], table[row + c[0] + r + 1], q[0], q[1], q[2], l);
-            }
-          }
-        // a short list finishes only when the box is the grid (ring_finished is true then whatever `best`)
-        done = ring_finished(k, q, c, r, l.cnt == kk ? l.wd : __builtin_huge_valf());
+        const NnShell s = nn_shell(k, c, r);
+        for (int z = s.lo[2]; z <= s.hi[2]; ++z)
+          for (int y = s.lo[1]; y <= s.hi[1]; ++y) nn_visit_shell_row(k, table, rows, c, r, s, z, y, q, l);
+        done = ring_finished(k, q, c, r, l.bound());
       }
     }
-    if (done) knn_finish<NORMALS>(l, i, q[0], q[1], q[2], out_d2, out_idx, normals, counts);
+    if (done) knn_finish<NORMALS>(l, i, q, out_d2, out_idx, normals, counts);
   }
-  // one atomic per wavefront and counter
-  const uint64_t fin = __ballot(live && done), rest = __ballot(live && !done);
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == 0) {
-    if (fin && stats) atomicAdd(&stats[0], __popcll(fin));
-    if (rest) {
-      if (stats) atomicAdd(&stats[1], __popcll(rest));
-      base = atomicAdd(list_n, __popcll(rest));
-    }
-  }
-  base = __shfl(base, 0);
-  if (live && !done) {
-    const int at = base + __popcll(rest & ((1ull << lane) - 1));
-    if (at >= 0 && at < count) list[at] = li;
-  }
+  nn_defer<true>(live, done, li, count, list, list_n, stats);
 }
 
 // ---- all pairs ---------------------------------------------------------------------------------------------------------
@@ -191,43 +161,17 @@ __global__ __launch_bounds__(KNN_LANES) void knn_all_pairs_kernel(int kk, const 
   __shared__ float4 tile[KNN_TILE];
   __shared__ float list_d[MISO_NN_KNN_MAX * KNN_LANES];
   __shared__ int list_p[MISO_NN_KNN_MAX * KNN_LANES];
-  int64_t count = n;
-  if (LISTED) { const int c = *list_n; count = c < 0 ? 0 : (c > n ? n : c); }
-  if ((int64_t)blockIdx.x * KNN_LANES >= count) return;               // the whole block: no barrier is left waiting
-  const int64_t slot = (int64_t)blockIdx.x * KNN_LANES + threadIdx.x;
-  const bool live = slot < count;
-  int64_t i = 0;
-  if (live) {
-    i = slot;
-    if (LISTED) { const int li = list[slot]; i = li < 0 ? 0 : (li >= n ? n - 1 : li); }
-    i += first;
-  }
-  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  if (live) { qx = src[i * ld_s]; qy = src[i * ld_s + 1]; qz = src[i * ld_s + 2]; }
+  bool live; int64_t i; float q[3];
+  if (!nn_block_query<LISTED, KNN_LANES>(src, ld_s, first, n, list, list_n, live, i, q)) return;
   KnnList<NORMALS> l;
   l.open(list_d, list_p, rows, kk);                                   // empty: the scan meets every target once
   for (int64_t t0 = 0; t0 < m; t0 += KNN_TILE) {
     const int len = (int)(m - t0 < KNN_TILE ? m - t0 : KNN_TILE);
-    __syncthreads();
-    for (int j = threadIdx.x; j < len; j += KNN_LANES) {
-      if (LISTED) tile[j] = rows[t0 + j];
-      else tile[j] = make_float4(tgt[(t0 + j) * ld_t], tgt[(t0 + j) * ld_t + 1], tgt[(t0 + j) * ld_t + 2], __int_as_float((int)(t0 + j)));
-    }
-    __syncthreads();
+    nn_stage_tile<LISTED, KNN_LANES>(tile, len, rows, tgt, ld_t, t0);
     if (live)
-      for (int j = 0; j < len; ++j) {
-        const float4 t = tile[j];                                     // one address per wavefront: a broadcast
-        const int idx = __float_as_int(t.w);
-        l.offer(nn_dist2(qx, qy, qz, t.x, t.y, t.z), idx, NORMALS ? (int)(t0 + j) : idx);
-      }
+      for (int j = 0; j < len; ++j) l.take(q[0], q[1], q[2], tile[j], (int)(t0 + j));   // one address per wavefront: a broadcast
   }
-  if (live) knn_finish<NORMALS>(l, i, qx, qy, qz, out_d2, out_idx, normals, counts);
-}
-
-// n_tgt == 0: every slot is padding
-__global__ __launch_bounds__(256) void knn_fill_kernel(int64_t total, float* __restrict__ out_d2, int64_t* __restrict__ out_idx) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < total) { out_d2[i] = __builtin_huge_valf(); out_idx[i] = -1; }
+  if (live) knn_finish<NORMALS>(l, i, q, out_d2, out_idx, normals, counts);
 }
 
 __global__ __launch_bounds__(256) void knn_flat_normals_kernel(int64_t n, float* __restrict__ normals, int32_t* __restrict__ counts) {
@@ -235,33 +179,21 @@ __global__ __launch_bounds__(256) void knn_flat_normals_kernel(int64_t n, float*
   if (i < n) { normals[i * 3] = 0.0f; normals[i * 3 + 1] = 0.0f; normals[i * 3 + 2] = 1.0f; counts[i] = 0; }
 }
 
-__global__ void knn_set_stats_kernel(int* __restrict__ stats, int a, int b) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) { stats[0] = a; stats[1] = b; }
-}
-
 // the chunks of a query over the index: rings, then the all-pairs kernel for the queries they listed
 template <bool NORMALS>
 hipError_t knn_on_index(const miso_nn_plan_t& p, void* ws, const float* src, int64_t ld, int64_t n, int kk, float* out_d2,
                         int64_t* out_idx, float* normals, int32_t* counts, int32_t* stats, hipStream_t s) {
-  const NnLayout l = nn_layout(p);
-  char* w = reinterpret_cast<char*>(ws);
-  const int* table = reinterpret_cast<const int*>(w + l.table);
-  int* counters = reinterpret_cast<int*>(w + l.counters);
-  int* list = reinterpret_cast<int*>(w + l.list);
-  const float4* rows = reinterpret_cast<const float4*>(w + l.rows);
+  const auto v = nn_views(p, ws);
   const NnK k = nn_k(p);
-  const int chunks = (int)((n + MISO_NN_CHUNK - 1) / MISO_NN_CHUNK);
-  hipError_t e = launch_zero_words(counters, chunks, s);
+  const hipError_t e = launch_zero_words(v.counters, nn_chunks(n), s);
   if (e != hipSuccess) return e;
-  for (int c = 0; c < chunks; ++c) {
-    const int64_t first = (int64_t)c * MISO_NN_CHUNK;
-    const int count = (int)(n - first < MISO_NN_CHUNK ? n - first : MISO_NN_CHUNK);
+  nn_for_chunks(n, [&](int c, int64_t first, int count) {
     const unsigned g = (unsigned)((count + KNN_LANES - 1) / KNN_LANES);
-    knn_rings_kernel<NORMALS><<<g, KNN_LANES, 0, s>>>(k, kk, table, rows, src, ld, first, count, out_d2, out_idx, normals, counts, list,
-                                                      counters + c, stats);
-    knn_all_pairs_kernel<true, NORMALS><<<g, KNN_LANES, 0, s>>>(kk, rows, nullptr, 0, p.n_tgt, src, ld, first, (int64_t)count, list,
-                                                                counters + c, out_d2, out_idx, normals, counts);
-  }
+    knn_rings_kernel<NORMALS><<<g, KNN_LANES, 0, s>>>(k, kk, v.table, v.rows, src, ld, first, count, out_d2, out_idx, normals, counts,
+                                                      v.list, v.counters + c, stats);
+    knn_all_pairs_kernel<true, NORMALS><<<g, KNN_LANES, 0, s>>>(kk, v.rows, nullptr, 0, p.n_tgt, src, ld, first, (int64_t)count, v.list,
+                                                                v.counters + c, out_d2, out_idx, normals, counts);
+  });
   return hipGetLastError();
 }
 
@@ -270,9 +202,8 @@ hipError_t knn_on_index(const miso_nn_plan_t& p, void* ws, const float* src, int
 hipError_t launch_nn_knn(const miso_nn_plan_t& p, void* ws, const float* src, int64_t ld, int64_t n, int k, float* out_d2,
                          int64_t* out_idx, int32_t* stats, hipStream_t s) {
   if (p.n_tgt == 0) {
-    knn_set_stats_kernel<<<1, 64, 0, s>>>(stats, (int)n, 0);
-    if (n > 0) knn_fill_kernel<<<(unsigned)((n * k + 255) / 256), 256, 0, s>>>(n * k, out_d2, out_idx);
-    return hipGetLastError();
+    const hipError_t e = launch_nn_set_stats(stats, (int)n, 0, s);
+    return e != hipSuccess ? e : launch_nn_fill(n * k, out_d2, out_idx, s);
   }
   hipError_t e = launch_zero_words(stats, 2, s);
   if (e != hipSuccess || n == 0) return e;
@@ -283,11 +214,10 @@ hipError_t launch_nn_knn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, co
                                    float* out_d2, int64_t* out_idx, hipStream_t s) {
   if (n == 0) return hipSuccess;
   // (m == 0: no tile is loaded and every list stays empty)
-  for (int64_t first = 0; first < n; first += MISO_NN_CHUNK) {
-    const int64_t count = n - first < MISO_NN_CHUNK ? n - first : MISO_NN_CHUNK;
+  nn_for_chunks(n, [&](int, int64_t first, int count) {
     knn_all_pairs_kernel<false, false><<<(unsigned)((count + KNN_LANES - 1) / KNN_LANES), KNN_LANES, 0, s>>>(
-        k, nullptr, tgt, ld_t, m, src, ld_s, first, count, nullptr, nullptr, out_d2, out_idx, nullptr, nullptr);
-  }
+        k, nullptr, tgt, ld_t, m, src, ld_s, first, (int64_t)count, nullptr, nullptr, out_d2, out_idx, nullptr, nullptr);
+  });
   return hipGetLastError();
 }
 

@@ -16,12 +16,14 @@
 //   cell   c_a = int(clamp(floor((p_a - min_a) / cell), 0, dims_a - 1)), clamped as a float (fmaxf / fminf drop a NaN), so
 //          any input indexes inside the table; linear index (z dims_y + y) dims_x + x: the cells of an x run are one run
 //          of rows.
-// Query (miso_nn_query), a lane per query, chunks of NN_CHUNK queries:
-//   rings  shell r = 0, 1, .. max_rings of cells at Chebyshev distance r from the query's (clamped) cell, then the stop
-//          test (ring_finished).  Unfinished queries append themselves to the chunk's list (one atomic per wavefront).
-//   rest   blocks of 256 listed queries against the rows, staged through LDS in tiles, the rows split over grid.y and merged
-//          with a 64-bit atomicMin on the packed (d2, idx); a block whose first list slot is at or beyond the device
-//          counter leaves, so the launch is sized for the worst case and the host reads nothing.  Then the pairs are unpacked.
+// Query (miso_nn_query), a lane per query, chunks of NN_CHUNK queries (nn_for_chunks).  The walk, the deferral and the
+// staging are nn.hpp's, shared with knn.hip; what is this file's is the accumulator, Best::take:
+//   rings  shell r = 0, 1, .. max_rings around the query's (clamped) cell (nn_shell, nn_visit_shell_row), then the stop
+//          test (ring_finished).  Unfinished queries append themselves to the chunk's list (nn_defer).
+//   rest   blocks of 256 listed queries (nn_block_query) against the rows, staged through LDS in tiles (nn_stage_tile),
+//          the rows split over grid.y and merged with a 64-bit atomicMin on the packed (d2, idx); a block whose first
+//          list slot is at or beyond the device counter leaves, so the launch is sized for the worst case and the host
+//          reads nothing.  Then the pairs are unpacked.
 // miso_nn_all_pairs is the second kernel over the caller's arrays, every query, no index.
 #include "common.hpp"
 #include "launch.hpp"
@@ -41,15 +43,11 @@ constexpr int NN_TILE = 1024;                                      // targets pe
 constexpr int NN_SEG_TILES = 8;                                    // the listed queries' all-pairs: at least 8 tiles a segment,
 constexpr int NN_SEGMENTS = 64;                                    // at most 64 segments (grid.y)
 
-// (Best / nn_dist2 / nn_take / nn_finite3 / ring_finished: nn.hpp, shared with knn.hip)
-
 // (d2, idx) as one unsigned 64-bit key that orders like the pair: d2 >= +0 (floats then order like their bits), idx as
 // uint32 (-1 = the largest: no match).  The all-pairs kernel behind the rings merges its target segments with atomicMin.
 __device__ __forceinline__ unsigned long long nn_pack(const Best& b) {
   return ((unsigned long long)__float_as_uint(b.d2) << 32) | (unsigned long long)(uint32_t)b.idx;
 }
-
-// (nn_cell_axis / nn_cell_of: nn.hpp)
 
 // ---- build -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void nn_count_kernel(NnK k, const float* __restrict__ tgt, int64_t ld, int* __restrict__ table) {
@@ -124,15 +122,6 @@ __global__ __launch_bounds__(256) void nn_scatter_kernel(NnK k, const float* __r
 }
 
 // ---- query: rings ------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void nn_scan_rows(const float4* __restrict__ rows, int n_rows, int s, int e, float qx, float qy, float qz,
-                                             Best& b) {
-  e = min(e, n_rows);                            // (a table that no build wrote must not lead outside the rows)
-  for (int j = max(s, 0); j < e; ++j) {
-    const float4 t = rows[j];
-    nn_take(b, nn_dist2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
-  }
-}
-
 __global__ __launch_bounds__(256) void nn_rings_kernel(NnK k, const int* __restrict__ table, const float4* __restrict__ rows,
                                                        const float* __restrict__ src, int64_t ld, int64_t first, int count,
                                                        float* __restrict__ out_d2, int64_t* __restrict__ out_idx,
@@ -149,38 +138,16 @@ __global__ __launch_bounds__(256) void nn_rings_kernel(NnK k, const int* __restr
       nn_cell_of(k, q[0], q[1], q[2], c);
       done = false;
       for (int r = 0; r <= k.max_rings && !done; ++r) {
-        const int xlo = max(c[0] - r, 0), xhi = min(c[0] + r, k.dims[0] - 1);
-        const int ylo = max(c[1] - r, 0), yhi = min(c[1] + r, k.dims[1] - 1);
-        const int zlo = max(c[2] - r, 0), zhi = min(c[2] + r, k.dims[2] - 1);
-        for (int z = zlo; z <= zhi; ++z)
-          for (int y = ylo; y <= yhi; ++y) {
-            const int row = (z * k.dims[1] + y) * k.dims[0];
-            if (abs(z - c[2]) == r || abs(y - c[1]) == r) {          // a whole x run of the shell: one run of rows
-              nn_scan_rows(rows, (int)k.n_tgt, table[row + xlo], table[row + xhi + 1], q[0], q[1], q[2], b);
-            } else {                                                  // (r > 0 here) the two end cells of the run
-              if (c[0] - r >= 0) nn_scan_rows(rows, (int)k.n_tgt, table[row + c[0] - r], table[row + c[0] - r + 1], q[0], q[1], q[2], b);
-              if (c[0] + r < k.dims[0]) nn_scan_rows(rows, (int)k.n_tgt, table[row + c[0] + r], table[row + c[0] + r + 1], q[0], q[1], q[2], b);
-            }
-          }
+        const NnShell s = nn_shell(k, c, r);
+        for (int z = s.lo[2]; z <= s.hi[2]; ++z)
+          for (int y = s.lo[1]; y <= s.hi[1]; ++y) nn_visit_shell_row(k, table, rows, c, r, s, z, y, q, b);
         done = ring_finished(k, q, c, r, b.d2);
       }
     }
     if (done) { out_d2[i] = b.d2; out_idx[i] = (int64_t)b.idx; }
     else out_idx[i] = (int64_t)nn_pack(b);        // the best of the rings so far: the accumulator of the all-pairs blocks
   }
-  // one atomic per wavefront and counter
-  const uint64_t fin = __ballot(live && done), rest = __ballot(live && !done);
-  const int lane = threadIdx.x & 63;
-  int base = 0;
-  if (lane == 0) {
-    if (fin) atomicAdd(&stats[0], __popcll(fin));
-    if (rest) { atomicAdd(&stats[1], __popcll(rest)); base = atomicAdd(list_n, __popcll(rest)); }
-  }
-  base = __shfl(base, 0);
-  if (live && !done) {
-    const int at = base + __popcll(rest & ((1ull << lane) - 1));
-    if (at >= 0 && at < count) list[at] = li;
-  }
+  nn_defer<false>(live, done, li, count, list, list_n, stats);
 }
 
 // ---- all pairs ---------------------------------------------------------------------------------------------------------
@@ -197,33 +164,17 @@ __global__ __launch_bounds__(256) void nn_all_pairs_kernel(const float4* __restr
                                                            const int* __restrict__ list_n, float* __restrict__ out_d2,
                                                            int64_t* __restrict__ out_idx) {
   __shared__ float4 tile[NN_TILE];
-  int64_t count = n;
-  if (LISTED) { const int c = *list_n; count = c < 0 ? 0 : (c > n ? n : c); }
-  if ((int64_t)blockIdx.x * 256 >= count) return;                     // the whole block: no barrier is left waiting
-  const int64_t slot = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const bool live = slot < count;
-  int64_t i = 0;
-  if (live) {
-    i = slot;
-    if (LISTED) { const int li = list[slot]; i = li < 0 ? 0 : (li >= n ? n - 1 : li); }
-    i += first;
-  }
-  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  if (live) { qx = src[i * ld_s]; qy = src[i * ld_s + 1]; qz = src[i * ld_s + 2]; }
+  bool live; int64_t i; float q[3];
+  if (!nn_block_query<LISTED, 256>(src, ld_s, first, n, list, list_n, live, i, q)) return;
   Best b = {__builtin_huge_valf(), -1};
   const int64_t t_begin = (int64_t)blockIdx.y * seg_len, t_end = t_begin + seg_len < m ? t_begin + seg_len : m;
   for (int64_t t0 = t_begin; t0 < t_end; t0 += NN_TILE) {
     const int len = (int)(t_end - t0 < NN_TILE ? t_end - t0 : NN_TILE);
-    __syncthreads();
-    for (int j = threadIdx.x; j < len; j += 256) {
-      if (LISTED) tile[j] = rows[t0 + j];
-      else tile[j] = make_float4(tgt[(t0 + j) * ld_t], tgt[(t0 + j) * ld_t + 1], tgt[(t0 + j) * ld_t + 2], __int_as_float((int)(t0 + j)));
-    }
-    __syncthreads();
+    nn_stage_tile<LISTED, 256>(tile, len, rows, tgt, ld_t, t0);
 #pragma unroll 4
-    for (int j = 0; j < len; ++j) {
+    for (int j = 0; j < len; ++j) {                                   // (dead lanes too: the loop as it was measured)
       const float4 t = tile[j];                                       // one address per wavefront: a broadcast
-      nn_take(b, nn_dist2(qx, qy, qz, t.x, t.y, t.z), __float_as_int(t.w));
+      b.take(q[0], q[1], q[2], t, 0);
     }
   }
   if (!live) return;
@@ -237,83 +188,76 @@ __global__ __launch_bounds__(256) void nn_all_pairs_kernel(const float4* __restr
 // the merged pairs of the listed queries -> (d2, idx)
 __global__ __launch_bounds__(256) void nn_unpack_kernel(int64_t first, int n, const int* __restrict__ list, const int* __restrict__ list_n,
                                                         float* __restrict__ out_d2, int64_t* __restrict__ out_idx) {
-  const int c = *list_n, count = c < 0 ? 0 : (c > n ? n : c);
   const int slot = blockIdx.x * 256 + threadIdx.x;
-  if (slot >= count) return;
-  const int li = list[slot];
-  const int64_t i = first + (li < 0 ? 0 : (li >= n ? n - 1 : li));
+  if (slot >= nn_listed_count(list_n, n)) return;
+  const int64_t i = nn_listed_query(list, slot, first, n);
   const unsigned long long key = (unsigned long long)out_idx[i];
   out_d2[i] = __uint_as_float((uint32_t)(key >> 32));
   out_idx[i] = (int64_t)(int32_t)(uint32_t)key;
 }
 
-__global__ __launch_bounds__(256) void nn_fill_kernel(int64_t n, float* __restrict__ out_d2, int64_t* __restrict__ out_idx) {
+__global__ __launch_bounds__(256) void nn_fill_kernel(int64_t total, float* __restrict__ out_d2, int64_t* __restrict__ out_idx) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n) { out_d2[i] = __builtin_huge_valf(); out_idx[i] = -1; }
+  if (i < total) { out_d2[i] = __builtin_huge_valf(); out_idx[i] = -1; }
 }
 
 __global__ void nn_set_stats_kernel(int* __restrict__ stats, int a, int b) {
   if (threadIdx.x == 0 && blockIdx.x == 0) { stats[0] = a; stats[1] = b; }
 }
 
-// (NnLayout / nn_layout / nn_k: nn.hpp)
-
 }  // namespace
 
 int64_t nn_workspace_bytes(const miso_nn_plan_t& p) { return nn_layout(p).total; }
 
+hipError_t launch_nn_fill(int64_t total, float* out_d2, int64_t* out_idx, hipStream_t s) {
+  if (total > 0) nn_fill_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(total, out_d2, out_idx);
+  return hipGetLastError();
+}
+
+hipError_t launch_nn_set_stats(int32_t* stats, int a, int b, hipStream_t s) {
+  nn_set_stats_kernel<<<1, 64, 0, s>>>(stats, a, b);
+  return hipGetLastError();
+}
+
 hipError_t launch_nn_build(const miso_nn_plan_t& p, const float* tgt, int64_t ld, void* ws, hipStream_t s) {
   if (p.n_tgt == 0) return hipSuccess;
-  const NnLayout l = nn_layout(p);
-  char* w = reinterpret_cast<char*>(ws);
-  int* table = reinterpret_cast<int*>(w + l.table);
-  int* sums = reinterpret_cast<int*>(w + l.sums);
-  float4* rows = reinterpret_cast<float4*>(w + l.rows);
+  const auto v = nn_views(p, ws);
   const NnK k = nn_k(p);
   const int cells = (int)p.cells, nb = (cells + NN_SCAN_TILE - 1) / NN_SCAN_TILE;
   const unsigned g = (unsigned)((p.n_tgt + 255) / 256);
-  hipError_t e = launch_zero_words(table, cells + 1, s);
+  hipError_t e = launch_zero_words(v.table, cells + 1, s);
   if (e != hipSuccess) return e;
-  nn_count_kernel<<<g, 256, 0, s>>>(k, tgt, ld, table);
-  nn_scan_sums_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(table + 1, cells, sums);
-  nn_scan_blocks_kernel<<<1, NN_SCAN_THREADS, 0, s>>>(sums, nb);
-  nn_scan_apply_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(table + 1, cells, sums);
-  nn_scatter_kernel<<<g, 256, 0, s>>>(k, tgt, ld, table, rows);
+  nn_count_kernel<<<g, 256, 0, s>>>(k, tgt, ld, v.table);
+  nn_scan_sums_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(v.table + 1, cells, v.sums);
+  nn_scan_blocks_kernel<<<1, NN_SCAN_THREADS, 0, s>>>(v.sums, nb);
+  nn_scan_apply_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(v.table + 1, cells, v.sums);
+  nn_scatter_kernel<<<g, 256, 0, s>>>(k, tgt, ld, v.table, v.rows);
   return hipGetLastError();
 }
 
 hipError_t launch_nn_query(const miso_nn_plan_t& p, void* ws, const float* src, int64_t ld, int64_t n, float* out_d2,
                            int64_t* out_idx, int32_t* stats, hipStream_t s) {
   if (p.n_tgt == 0) {
-    nn_set_stats_kernel<<<1, 64, 0, s>>>(stats, (int)n, 0);
-    if (n > 0) nn_fill_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(n, out_d2, out_idx);
-    return hipGetLastError();
+    const hipError_t e = launch_nn_set_stats(stats, (int)n, 0, s);
+    return e != hipSuccess ? e : launch_nn_fill(n, out_d2, out_idx, s);
   }
   hipError_t e = launch_zero_words(stats, 2, s);
   if (e != hipSuccess || n == 0) return e;
-  const NnLayout l = nn_layout(p);
-  char* w = reinterpret_cast<char*>(ws);
-  const int* table = reinterpret_cast<const int*>(w + l.table);
-  int* counters = reinterpret_cast<int*>(w + l.counters);
-  int* list = reinterpret_cast<int*>(w + l.list);
-  const float4* rows = reinterpret_cast<const float4*>(w + l.rows);
+  const auto v = nn_views(p, ws);
   const NnK k = nn_k(p);
-  const int chunks = (int)((n + MISO_NN_CHUNK - 1) / MISO_NN_CHUNK);
   // the listed queries see the targets in up to NN_SEGMENTS segments of at least NN_SEG_TILES tiles
   const int64_t tiles = (p.n_tgt + NN_TILE - 1) / NN_TILE;
   const unsigned segs = (unsigned)(tiles / NN_SEG_TILES < 1 ? 1 : (tiles / NN_SEG_TILES > NN_SEGMENTS ? NN_SEGMENTS : tiles / NN_SEG_TILES));
   const int64_t seg_len = (tiles + segs - 1) / segs * NN_TILE;
-  e = launch_zero_words(counters, chunks, s);
+  e = launch_zero_words(v.counters, nn_chunks(n), s);
   if (e != hipSuccess) return e;
-  for (int c = 0; c < chunks; ++c) {
-    const int64_t first = (int64_t)c * MISO_NN_CHUNK;
-    const int count = (int)(n - first < MISO_NN_CHUNK ? n - first : MISO_NN_CHUNK);
+  nn_for_chunks(n, [&](int c, int64_t first, int count) {
     const unsigned g = (unsigned)((count + 255) / 256);
-    nn_rings_kernel<<<g, 256, 0, s>>>(k, table, rows, src, ld, first, count, out_d2, out_idx, list, counters + c, stats);
-    nn_all_pairs_kernel<true><<<dim3(g, segs), 256, 0, s>>>(rows, nullptr, 0, p.n_tgt, seg_len, src, ld, first, (int64_t)count, list,
-                                                            counters + c, out_d2, out_idx);
-    nn_unpack_kernel<<<g, 256, 0, s>>>(first, count, list, counters + c, out_d2, out_idx);
-  }
+    nn_rings_kernel<<<g, 256, 0, s>>>(k, v.table, v.rows, src, ld, first, count, out_d2, out_idx, v.list, v.counters + c, stats);
+    nn_all_pairs_kernel<true><<<dim3(g, segs), 256, 0, s>>>(v.rows, nullptr, 0, p.n_tgt, seg_len, src, ld, first, (int64_t)count, v.list,
+                                                            v.counters + c, out_d2, out_idx);
+    nn_unpack_kernel<<<g, 256, 0, s>>>(first, count, v.list, v.counters + c, out_d2, out_idx);
+  });
   return hipGetLastError();
 }
 
@@ -321,11 +265,10 @@ hipError_t launch_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const 
                                float* out_d2, int64_t* out_idx, hipStream_t s) {
   if (n == 0) return hipSuccess;
   // (m == 0: no tile is loaded and every query keeps (+inf, -1))
-  for (int64_t first = 0; first < n; first += MISO_NN_CHUNK) {
-    const int64_t count = n - first < MISO_NN_CHUNK ? n - first : MISO_NN_CHUNK;
-    nn_all_pairs_kernel<false><<<(unsigned)((count + 255) / 256), 256, 0, s>>>(nullptr, tgt, ld_t, m, m, src, ld_s, first, count,
+  nn_for_chunks(n, [&](int, int64_t first, int count) {
+    nn_all_pairs_kernel<false><<<(unsigned)((count + 255) / 256), 256, 0, s>>>(nullptr, tgt, ld_t, m, m, src, ld_s, first, (int64_t)count,
                                                                                nullptr, nullptr, out_d2, out_idx);
-  }
+  });
   return hipGetLastError();
 }
 

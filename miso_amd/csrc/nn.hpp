@@ -28,23 +28,22 @@ __device__ __forceinline__ int nn_cell_of(const NnK& k, float x, float y, float 
   return (c[2] * k.dims[1] + c[1]) * k.dims[0] + c[0];
 }
 
-// ---- what the query kernels share (nn.hip, knn.hip) ----------------------------------------------------------------------
+// ---- what the query kernels share (nn.hip, knn.hip, the radius normals of icp.hip) ---------------------------------------
 // Every function here forms its result with one rounding per operation whatever the including file has set.
-struct Best {
-  float d2;
-  int idx;
-};
-
 __device__ __forceinline__ float nn_dist2(float ax, float ay, float az, float bx, float by, float bz) {
 #pragma clang fp contract(off)
   const float dx = ax - bx, dy = ay - by, dz = az - bz;
   return (dx * dx + dy * dy) + dz * dz;
 }
 
-// smallest (d2, idx); false for a NaN d2, and for d2 = +inf against the initial (+inf, -1)
-__device__ __forceinline__ void nn_take(Best& b, float d2, int idx) {
-  if (d2 < b.d2 || (d2 == b.d2 && idx < b.idx)) { b.d2 = d2; b.idx = idx; }
-}
+struct Best {
+  float d2; int idx;
+  // target t as a candidate of query q: the smallest (d2, idx); false for a NaN d2, and for +inf against the initial (+inf, -1)
+  __device__ __forceinline__ void take(float qx, float qy, float qz, const float4& t, int) {
+    const float n2 = nn_dist2(qx, qy, qz, t.x, t.y, t.z); const int ni = __float_as_int(t.w);
+    if (n2 < d2 || (n2 == d2 && ni < idx)) { d2 = n2; idx = ni; }
+  }
+};
 
 __device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
   const float inf = __builtin_huge_valf();
@@ -76,6 +75,111 @@ __device__ __forceinline__ bool ring_finished(const NnK& k, const float q[3], co
   if (!(gs > 0.0f)) return false;
   return best < (gs * gs) * (1.0f - 0x1p-20f);
 }
+
+// The cells first_cell .. last_cell of one x run are one run of rows: f(t, row) for each, ascending.  The run is clamped
+// to [0, n_rows), so that a table no build wrote (a plan lives in the caller's memory) never leads outside the rows.
+template <class F>
+__device__ __forceinline__ void nn_visit_run(const int* table, const float4* rows, int n_rows, int first_cell, int last_cell,
+                                             const F& f) {
+  const int s = table[first_cell], e = min(table[last_cell + 1], n_rows);
+  for (int j = max(s, 0); j < e; ++j) f(rows[j], j);
+}
+
+// Shell r of cell c, the cells at Chebyshev distance r clamped to the grid: per (y, z) of lo .. hi either the whole x run
+// or its two end cells (nn_visit_shell_row).  A rings kernel walks the shells r = 0 .. max_rings of a finite query's
+// cell and after each asks ring_finished with the largest d2 its accumulator still admits: +inf while that is not full
+// (a list shorter than k), which finishes only when the box is the grid.  The loops over r, z and y stay in the kernels,
+// and the query goes down as three scalars (profiles/nn_shared_walk.json holds the reasons).
+struct NnShell { int lo[3], hi[3]; };
+__device__ __forceinline__ NnShell nn_shell(const NnK& k, const int c[3], int r) {
+  return {{max(c[0] - r, 0), max(c[1] - r, 0), max(c[2] - r, 0)},
+          {min(c[0] + r, k.dims[0] - 1), min(c[1] + r, k.dims[1] - 1), min(c[2] + r, k.dims[2] - 1)}};
+}
+
+// a run of cells offered to an accumulator
+template <class A>
+__device__ __forceinline__ void nn_offer_run(const int* table, const float4* rows, int n_rows, int first_cell, int last_cell,
+                                             float qx, float qy, float qz, A& acc) {
+  nn_visit_run(table, rows, n_rows, first_cell, last_cell, [&](const float4& t, int row) { acc.take(qx, qy, qz, t, row); });
+}
+
+template <class A>
+__device__ __forceinline__ void nn_visit_shell_row(const NnK& k, const int* table, const float4* rows, const int c[3], int r,
+                                                   const NnShell& s, int z, int y, const float q[3], A& acc) {
+  const int row = (z * k.dims[1] + y) * k.dims[0];
+  if (abs(z - c[2]) == r || abs(y - c[1]) == r) {                    // a whole x run of the shell
+    nn_offer_run(table, rows, (int)k.n_tgt, row + s.lo[0], row + s.hi[0], q[0], q[1], q[2], acc);
+  } else {                                                            // (r > 0 here) the two end cells of the run
+    if (c[0] - r >= 0) nn_offer_run(table, rows, (int)k.n_tgt, row + c[0] - r, row + c[0] - r, q[0], q[1], q[2], acc);
+    if (c[0] + r < k.dims[0]) nn_offer_run(table, rows, (int)k.n_tgt, row + c[0] + r, row + c[0] + r, q[0], q[1], q[2], acc);
+  }
+}
+
+// What every lane of a rings block ends with: the chunk's unfinished queries append their position li to its list.  One
+// atomic per wavefront and counter (stats = {finished, listed}, null only where allowed); a slot is written inside [0, count).
+template <bool STATS_MAY_BE_NULL>
+__device__ __forceinline__ void nn_defer(bool live, bool done, int li, int count, int* __restrict__ list, int* __restrict__ list_n,
+                                         int* __restrict__ stats) {
+  const uint64_t fin = __ballot(live && done), rest = __ballot(live && !done);
+  const int lane = threadIdx.x & 63;
+  int base = 0;
+  if (lane == 0) {
+    if (fin && (!STATS_MAY_BE_NULL || stats)) atomicAdd(&stats[0], __popcll(fin));
+    if (rest) {
+      if (!STATS_MAY_BE_NULL || stats) atomicAdd(&stats[1], __popcll(rest));
+      base = atomicAdd(list_n, __popcll(rest));
+    }
+  }
+  base = __shfl(base, 0);
+  if (live && !done) {
+    const int at = base + __popcll(rest & ((1ull << lane) - 1));
+    if (at >= 0 && at < count) list[at] = li;
+  }
+}
+
+// The listed queries of a chunk of n, as the kernels behind the rings read them: both values live in the caller's
+// memory, so both are clamped.
+__device__ __forceinline__ int64_t nn_listed_count(const int* __restrict__ list_n, int64_t n) {
+  const int c = *list_n; return c < 0 ? 0 : (c > n ? n : c);
+}
+__device__ __forceinline__ int64_t nn_listed_query(const int* __restrict__ list, int64_t slot, int64_t first, int64_t n) {
+  const int li = list[slot]; return first + (li < 0 ? 0 : (li >= n ? n - 1 : li));
+}
+
+// The query of a lane of an all-pairs block of LANES: slot `blockIdx.x LANES + lane` of the chunk's list (LISTED), or
+// of its n queries.  false: the block has no query and leaves as a whole, before any barrier.
+template <bool LISTED, int LANES>
+__device__ __forceinline__ bool nn_block_query(const float* __restrict__ src, int64_t ld_s, int64_t first, int64_t n,
+                                               const int* __restrict__ list, const int* __restrict__ list_n, bool& live, int64_t& i,
+                                               float q[3]) {
+  const int64_t count = LISTED ? nn_listed_count(list_n, n) : n;
+  if ((int64_t)blockIdx.x * LANES >= count) return false;
+  const int64_t slot = (int64_t)blockIdx.x * LANES + threadIdx.x;
+  live = slot < count;
+  i = 0; q[0] = q[1] = q[2] = 0.0f;
+  if (live) {
+    i = LISTED ? nn_listed_query(list, slot, first, n) : first + slot;
+    q[0] = src[i * ld_s]; q[1] = src[i * ld_s + 1]; q[2] = src[i * ld_s + 2];
+  }
+  return true;
+}
+
+// tile[0 .. len) = targets t0 .. t0 + len, {x, y, z, original index bits}: the index's rows (LISTED), or built from the
+// caller's (m, 3) cloud with row stride ld_t.  The first barrier waits for the readers of the previous tile.
+template <bool LISTED, int LANES>
+__device__ __forceinline__ void nn_stage_tile(float4* tile, int len, const float4* __restrict__ rows, const float* __restrict__ tgt,
+                                              int64_t ld_t, int64_t t0) {
+  __syncthreads();
+  for (int j = threadIdx.x; j < len; j += LANES) {
+    if (LISTED) tile[j] = rows[t0 + j];
+    else tile[j] = make_float4(tgt[(t0 + j) * ld_t], tgt[(t0 + j) * ld_t + 1], tgt[(t0 + j) * ld_t + 2], __int_as_float((int)(t0 + j)));
+  }
+  __syncthreads();
+}
+
+// nn.hip: (+inf, -1) into `total` slots (no target: every slot is padding); stats = {a, b}
+hipError_t launch_nn_fill(int64_t total, float* out_d2, int64_t* out_idx, hipStream_t s);
+hipError_t launch_nn_set_stats(int32_t* stats, int a, int b, hipStream_t s);
 
 // ---- normals from a neighbourhood's sums (icp.hip: radius; knn.hip: k nearest) -------------------------------------------
 // 1, d and d d^T of a neighbourhood, d = t - q in float64, added in the order add() is called
@@ -162,6 +266,31 @@ inline NnLayout nn_layout(const miso_nn_plan_t& p) {
   l.rows = at;     at += nn_a256(p.n_tgt * 16);
   l.total = at;
   return l;
+}
+
+// the workspace as its kernels read and write it, const for a const workspace; all null without one (no target)
+template <class I, class R>
+struct NnViews { I *table, *sums, *counters, *list; R* rows; };
+template <class I, class R, class B>
+inline NnViews<I, R> nn_views_of(const miso_nn_plan_t& p, B* w) {
+  if (!w) return {};
+  const NnLayout l = nn_layout(p);
+  return {reinterpret_cast<I*>(w + l.table), reinterpret_cast<I*>(w + l.sums), reinterpret_cast<I*>(w + l.counters),
+          reinterpret_cast<I*>(w + l.list), reinterpret_cast<R*>(w + l.rows)};
+}
+inline auto nn_views(const miso_nn_plan_t& p, void* ws) { return nn_views_of<int, float4>(p, static_cast<char*>(ws)); }
+inline auto nn_views(const miso_nn_plan_t& p, const void* ws) {
+  return nn_views_of<const int, const float4>(p, static_cast<const char*>(ws));
+}
+
+// the chunks of n queries, in order: f(chunk, first, count)
+inline int nn_chunks(int64_t n) { return (int)((n + MISO_NN_CHUNK - 1) / MISO_NN_CHUNK); }
+template <class F>
+inline void nn_for_chunks(int64_t n, const F& f) {
+  for (int c = 0, chunks = nn_chunks(n); c < chunks; ++c) {
+    const int64_t first = (int64_t)c * MISO_NN_CHUNK;
+    f(c, first, (int)(n - first < MISO_NN_CHUNK ? n - first : MISO_NN_CHUNK));
+  }
 }
 
 inline NnK nn_k(const miso_nn_plan_t& p) {

@@ -1050,6 +1050,32 @@ def _ld(t: torch.Tensor) -> int:
     return t.stride(0) if t.shape[0] > 1 else 3
 
 
+def _knn_k(k, what: str) -> int:
+    k = int(k)
+    if not 1 <= k <= NN_KNN_MAX:
+        raise ValueError(f"{what} = {k} is outside 1 .. {NN_KNN_MAX}")
+    return k
+
+
+def _nn_out(out, shape, device, exact_shape: bool):
+    """``out`` = (d2, idx, stats) of a query over the index, allocated when None: d2 fp32 and idx int64 of ``shape`` (with
+    ``exact_shape``; else at least that many elements), stats (2,) int32"""
+    if out is None:
+        out = (torch.empty(shape, device=device, dtype=torch.float32), torch.empty(shape, device=device, dtype=torch.int64),
+               torch.empty(2, device=device, dtype=torch.int32))
+    d2, idx, stats = out
+    for t, dtype in ((d2, torch.float32), (idx, torch.int64)):
+        assert t.is_cuda and t.dtype == dtype and t.is_contiguous()
+        assert (tuple(t.shape) == tuple(shape)) if exact_shape else (t.numel() >= shape[0])
+    assert stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= 2
+    return d2, idx, stats
+
+
+def _nn_small(src: torch.Tensor, tgt: torch.Tensor) -> bool:
+    """small problems take the all-pairs route (NN_ALL_PAIRS_BELOW is read at call time)"""
+    return int(src.shape[0]) * int(tgt.shape[0]) < NN_ALL_PAIRS_BELOW
+
+
 def nn_default_cell(lo, hi, m: int) -> float:
     """The cell of NearestIndex(cell=None): NN_CELL_SPACINGS point spacings, the spacing that of ``m`` points spread over
     the surface of their bounding box (a sampled mesh fills surfaces, not the volume); a flat or linear cloud falls back
@@ -1104,13 +1130,7 @@ class NearestIndex:
         (+inf, -1) for a query without a match.  One query at a time per index: the workspace holds the query's list."""
         src = _cloud(src, "src")
         n = int(src.shape[0])
-        if out is None:
-            out = (torch.empty(n, device=src.device, dtype=torch.float32), torch.empty(n, device=src.device, dtype=torch.int64),
-                   torch.empty(2, device=src.device, dtype=torch.int32))
-        d2, idx, stats = out
-        assert d2.is_cuda and d2.dtype == torch.float32 and d2.is_contiguous() and d2.numel() >= n
-        assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and idx.numel() >= n
-        assert stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= 2
+        d2, idx, stats = _nn_out(out, (n,), src.device, exact_shape=False)
         _lib.check(_lib.load().miso_nn_query(C.byref(self.plan), _ptr(self.workspace), _ptr(src), _ld(src), n, _ptr(d2),
                                              _ptr(idx), _ptr(stats), _stream(src)), "miso_nn_query")
         return d2, idx, stats
@@ -1122,16 +1142,8 @@ class NearestIndex:
         Nothing is read back, so with ``out`` = (d2, idx, stats) the call replays inside a captured graph.  One query at
         a time per index."""
         src = _cloud(src, "src")
-        n, k = int(src.shape[0]), int(k)
-        if not 1 <= k <= NN_KNN_MAX:
-            raise ValueError(f"knn: k = {k} is outside 1 .. {NN_KNN_MAX}")
-        if out is None:
-            out = (torch.empty((n, k), device=src.device, dtype=torch.float32),
-                   torch.empty((n, k), device=src.device, dtype=torch.int64), torch.empty(2, device=src.device, dtype=torch.int32))
-        d2, idx, stats = out
-        assert d2.is_cuda and d2.dtype == torch.float32 and d2.is_contiguous() and tuple(d2.shape) == (n, k)
-        assert idx.is_cuda and idx.dtype == torch.int64 and idx.is_contiguous() and tuple(idx.shape) == (n, k)
-        assert stats.is_cuda and stats.dtype == torch.int32 and stats.is_contiguous() and stats.numel() >= 2
+        n, k = int(src.shape[0]), _knn_k(k, "knn: k")
+        d2, idx, stats = _nn_out(out, (n, k), src.device, exact_shape=True)
         _lib.check(_lib.load().miso_nn_knn(C.byref(self.plan), _ptr(self.workspace), _ptr(src), _ld(src), n, k, _ptr(d2),
                                            _ptr(idx), _ptr(stats), _stream(src)), "miso_nn_knn")
         return d2, idx, stats
@@ -1155,9 +1167,7 @@ class NearestIndex:
         out = torch.empty((n, 3), device=pts.device, dtype=torch.float32)
         counts = torch.empty(n, device=pts.device, dtype=torch.int32)
         if knn is not None:
-            k = int(knn)
-            if not 1 <= k <= NN_KNN_MAX:
-                raise ValueError(f"normals: knn = {k} is outside 1 .. {NN_KNN_MAX}")
+            k = _knn_k(knn, "normals: knn")
             _lib.check(_lib.load().miso_nn_knn_normals(C.byref(self.plan), _ptr(self.workspace), _ptr(pts), _ld(pts), n, k,
                                                        _ptr(out), _ptr(counts), _stream(pts)), "miso_nn_knn_normals")
             return out, counts
@@ -1184,7 +1194,7 @@ def nearest(src: torch.Tensor, tgt: torch.Tensor, cell: Optional[float] = None):
     the device; (+inf, -1) where there is no match.  Small problems (N M < NN_ALL_PAIRS_BELOW) take the all-pairs kernel,
     the rest a NearestIndex: the same bits either way."""
     _require_hip(src, tgt)
-    if int(src.shape[0]) * int(tgt.shape[0]) < NN_ALL_PAIRS_BELOW:
+    if _nn_small(src, tgt):
         return nearest_all_pairs(src, tgt)
     d2, idx, _ = NearestIndex(tgt, cell=cell).query(src)
     return d2, idx
@@ -1194,9 +1204,7 @@ def knn_all_pairs(src: torch.Tensor, tgt: torch.Tensor, k: int):
     """The all-pairs kernel for every query (miso_nn_knn_all_pairs): -> (d2 (N, k), idx (N, k)), the bits
     NearestIndex.knn returns."""
     src, tgt = _cloud(src, "src"), _cloud(tgt, "tgt")
-    n, m, k = int(src.shape[0]), int(tgt.shape[0]), int(k)
-    if not 1 <= k <= NN_KNN_MAX:
-        raise ValueError(f"knn_all_pairs: k = {k} is outside 1 .. {NN_KNN_MAX}")
+    n, m, k = int(src.shape[0]), int(tgt.shape[0]), _knn_k(k, "knn_all_pairs: k")
     d2 = torch.empty((n, k), device=src.device, dtype=torch.float32)
     idx = torch.empty((n, k), device=src.device, dtype=torch.int64)
     _lib.check(_lib.load().miso_nn_knn_all_pairs(_ptr(tgt), _ld(tgt), m, _ptr(src), _ld(src), n, k, _ptr(d2), _ptr(idx),
@@ -1209,7 +1217,7 @@ def knn(src: torch.Tensor, tgt: torch.Tensor, k: int, cell: Optional[float] = No
     (d2, index) pairs, ascending, d2 as ``nearest`` forms it.  -> (d2 (N, k) fp32, idx (N, k) int64) on the device, padded
     with (+inf, -1).  The route is picked by N M as in ``nearest``; both give the same bits."""
     _require_hip(src, tgt)
-    if int(src.shape[0]) * int(tgt.shape[0]) < NN_ALL_PAIRS_BELOW:
+    if _nn_small(src, tgt):
         return knn_all_pairs(src, tgt, k)
     d2, idx, _ = NearestIndex(tgt, cell=cell).knn(src, k)
     return d2, idx
