@@ -63,6 +63,9 @@
  *                     Open3D's registration_icp and estimate_normals as utils_scannet.align_mesh_to_ref
  *                     (grid_opt/utils/utils_scannet.py:115-156) and align_submap_pair (grid_opt/align/icp.py:51-118)
  *                     call them: the per-point work of an iteration; the loop and the solve are host code.
+ *   miso_mesh_plan / miso_mesh_count / miso_mesh_build / miso_mesh_cast_rays / miso_mesh_cast_rays_all
+ *                     Open3D's RaycastingScene.cast_rays as PosedSdf3D.sample_frames calls it
+ *                     (grid_opt/datasets/sdf_3d.py:209-312): the first hit of every ray on a triangle mesh.
  *
  * This file is also the ONLY statement of the ABI for Python: miso_amd/_lib.py reads its structs, integer constants and
  * prototypes at import and refuses what it cannot read.  Keep the declarations in the style used below: block comments,
@@ -877,6 +880,59 @@ int miso_icp_sums(const float* moved, const float* d2, const int64_t* idx, int64
                   double tukey_k, const double* origin, void* workspace, double* out, void* stream);
 int miso_nn_normals(const miso_nn_plan_t* plan, const void* workspace, const float* pts, int64_t ld, int64_t n,
                     double radius, float* normals, int32_t* counts, void* stream);
+
+/* --- ray casting against a triangle mesh (csrc/mesh.hip) -----------------------------------------------------------------------
+ * What Open3D's RaycastingScene.cast_rays gives the reference's PosedSdf3D (grid_opt/datasets/sdf_3d.py:209-312): for every
+ * ray o + t d the first triangle it meets.  One intersection: Moller-Trumbore in fp32, two-sided, one rounding per
+ * operation (csrc/mesh.hpp: RayBest::take); a hit iff det != 0, u >= 0, v >= 0, u + v <= 1 and t_min <= t <= t_max, a NaN
+ * failing every comparison; t in units of |d| (directions are not normalised).  Every route keeps the smallest
+ * (t, triangle index) pair, compared lexicographically, and a miss is (+inf, -1): the same bits from the grid route and from
+ * the all-triangles route, from run to run and from build to build.  A triangle with a vertex index outside [0, n_vert), a
+ * non-finite coordinate or a zero fp32 cross product (v1 - v0) x (v2 - v0) is never hit.
+ *   miso_mesh_plan  host only.  bound_min / bound_max: three host floats each, the box of the vertices of the triangles
+ *       that can be hit; cell > 0; dims[a] = floor((max - min) / cell) + 1, and while dims_x dims_y dims_z >
+ *       MISO_MESH_MAX_CELLS the cell is doubled: plan.cell is the one used.  coord_mag as miso_nn_plan's; widen =
+ *       2^-17 coord_mag, the rounding slack by which the lists widen every triangle and the query widens the box.
+ *       n_tri == 0 is a valid plan.  MISO_E_BADARG / MISO_E_TOOLARGE as miso_nn_plan.
+ *   miso_mesh_workspace_bytes  the device workspace of a plan (16-byte aligned): the offset table (cells + 1 int32), scan
+ *       scratch and the triangles as three 16-byte rows each; 0 for a plan the library did not write.
+ *   miso_mesh_count  verts (n_vert, 3) fp32 with row stride ld_v >= 3, tris (n_tri, 3) int64 with row stride ld_t >= 3 ->
+ *       the rows and the scanned per-cell counts in `workspace`, and entries[0] (int64 on the device, 16 bytes) = the
+ *       total number of list entries.  The caller reads entries[0] back -- the one host read of a build -- and either
+ *       allocates `lists` (that many int32) or, above MISO_MESH_MAX_ENTRIES (512 MB of lists), plans again with twice
+ *       the cell.
+ *   miso_mesh_build  fills `lists` (capacity int32; an entry beyond it is dropped) from the workspace miso_mesh_count
+ *       left: once per count.
+ *   miso_mesh_cast_rays  origins / dirs (n, 3) with row strides >= 3, n < 2^31 -> out_t (n) fp32, out_tri (n) int64.
+ *       stats: NULL, or 3 int64 on the device = {cells visited, triangles offered, rays answered from all rows (a ray
+ *       the walk's rounding argument does not cover: a non-finite or far origin, |o_a| > 4 coord_mag)}.  No host read, no
+ *       allocation: the call replays inside a captured graph.
+ *   miso_mesh_cast_rays_all  the all-triangles kernel over the caller's arrays, no index (n_tri < 2^31).
+ *   All return MISO_E_BADARG before any launch for a NULL pointer with work to do, a stride < 3, negative sizes, a
+ *       workspace that is NULL or not 16-byte aligned with n_tri > 0, and a plan the library did not write. */
+#define MISO_MESH_MAX_CELLS 16777216
+#define MISO_MESH_MAX_ENTRIES 134217728
+typedef struct {
+  float bound_min[3];
+  float cell;
+  float coord_mag;
+  float widen;
+  int32_t dims[3];
+  int32_t reserved;
+  int64_t n_tri;
+  int64_t cells;
+} miso_mesh_plan_t;
+int miso_mesh_plan(const float* bound_min, const float* bound_max, float cell, int64_t n_tri, miso_mesh_plan_t* plan);
+int64_t miso_mesh_workspace_bytes(const miso_mesh_plan_t* plan);
+int miso_mesh_count(const miso_mesh_plan_t* plan, const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris,
+                    int64_t ld_t, void* workspace, int64_t* entries, void* stream);
+int miso_mesh_build(const miso_mesh_plan_t* plan, void* workspace, int32_t* lists, int64_t capacity, void* stream);
+int miso_mesh_cast_rays(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                        const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min,
+                        float t_max, float* out_t, int64_t* out_tri, int64_t* stats, void* stream);
+int miso_mesh_cast_rays_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t,
+                            int64_t n_tri, const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n,
+                            float t_min, float t_max, float* out_t, int64_t* out_tri, void* stream);
 
 /* --- fused atlas query: GridAtlas.query_feature / GridAtlas.forward in one launch (round 6) ---------------------------
  * Replaces the per-submap loop of grid_opt/models/grid_atlas.py:374-399 (for each active submap: transfrom_points_from,

@@ -1146,6 +1146,71 @@ int miso_nn_normals(const miso_nn_plan_t* plan, const void* workspace, const flo
   return (int)launch_nn_normals(*plan, workspace, pts, ld, n, radius, normals, counts, (hipStream_t)stream);
 }
 
+// ---- ray casting against a triangle mesh (mesh.hip) ---------------------------------------------------------------------------
+int miso_mesh_plan(const float* bound_min, const float* bound_max, float cell, int64_t n_tri, miso_mesh_plan_t* plan) {
+  if (!plan || n_tri < 0) return MISO_E_BADARG;
+  if (n_tri >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  // the grid is the nearest-neighbour index's: the same dims, doubling and coord_mag (MISO_MESH_MAX_CELLS == MISO_NN_MAX_CELLS)
+  static_assert(MISO_MESH_MAX_CELLS == MISO_NN_MAX_CELLS, "one grid plan");
+  miso_nn_plan_t g;
+  const int rc = miso_nn_plan(bound_min, bound_max, cell, n_tri, 0, &g);
+  if (rc != MISO_OK) return rc;
+  memset(plan, 0, sizeof(*plan));
+  for (int a = 0; a < 3; ++a) { plan->bound_min[a] = g.bound_min[a]; plan->dims[a] = g.dims[a]; }
+  plan->cell = g.cell; plan->coord_mag = g.coord_mag; plan->widen = 0x1p-17f * g.coord_mag;
+  plan->n_tri = n_tri; plan->cells = g.cells;
+  return MISO_OK;
+}
+
+// a plan as miso_mesh_plan writes it (the struct is the caller's memory: the kernels index by it)
+static bool mesh_plan_ok(const miso_mesh_plan_t* p) {
+  if (!p || p->n_tri < 0 || p->n_tri >= ((int64_t)1 << 31)) return false;
+  if (p->dims[0] < 1 || p->dims[1] < 1 || p->dims[2] < 1 || p->cells < 1 || p->cells > MISO_MESH_MAX_CELLS) return false;
+  if ((int64_t)p->dims[0] * p->dims[1] > MISO_MESH_MAX_CELLS || (int64_t)p->dims[0] * p->dims[1] * p->dims[2] != p->cells) return false;
+  return p->cell > 0.0f && p->cell < __builtin_huge_valf() && p->coord_mag >= 0.0f && p->coord_mag < __builtin_huge_valf() &&
+         p->widen >= 0.0f && p->widen <= p->coord_mag;
+}
+
+int64_t miso_mesh_workspace_bytes(const miso_mesh_plan_t* plan) {
+  return mesh_plan_ok(plan) ? mesh_workspace_bytes(*plan) : 0;
+}
+
+int miso_mesh_count(const miso_mesh_plan_t* plan, const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris,
+                    int64_t ld_t, void* workspace, int64_t* entries, void* stream) {
+  if (!mesh_plan_ok(plan) || ld_v < 3 || ld_t < 3 || n_vert < 0 || !entries || ((uintptr_t)entries & 7u)) return MISO_E_BADARG;
+  if (plan->n_tri > 0 && (!tris || (n_vert > 0 && !verts) || !workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  return (int)launch_mesh_count(*plan, verts, ld_v, n_vert, tris, ld_t, workspace, entries, (hipStream_t)stream);
+}
+
+int miso_mesh_build(const miso_mesh_plan_t* plan, void* workspace, int32_t* lists, int64_t capacity, void* stream) {
+  if (!mesh_plan_ok(plan) || capacity < 0) return MISO_E_BADARG;
+  if (capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
+  if (plan->n_tri == 0) return MISO_OK;
+  if (!workspace || ((uintptr_t)workspace & 15u) || (capacity > 0 && !lists)) return MISO_E_BADARG;
+  return (int)launch_mesh_build(*plan, workspace, lists, capacity, (hipStream_t)stream);
+}
+
+int miso_mesh_cast_rays(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                        const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min,
+                        float t_max, float* out_t, int64_t* out_tri, int64_t* stats, void* stream) {
+  if (!mesh_plan_ok(plan) || ld_o < 3 || ld_d < 3 || n < 0 || capacity < 0 || ((uintptr_t)stats & 7u)) return MISO_E_BADARG;
+  if (n >= ((int64_t)1 << 31) || capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
+  if (n > 0 && (!origins || !dirs || !out_t || !out_tri)) return MISO_E_BADARG;
+  if (plan->n_tri > 0 && (!workspace || ((uintptr_t)workspace & 15u) || (capacity > 0 && !lists))) return MISO_E_BADARG;
+  return (int)launch_mesh_cast_rays(*plan, workspace, lists, capacity, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_t, out_tri,
+                                    stats, (hipStream_t)stream);
+}
+
+int miso_mesh_cast_rays_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t,
+                            int64_t n_tri, const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n,
+                            float t_min, float t_max, float* out_t, int64_t* out_tri, void* stream) {
+  if (n_vert < 0 || n_tri < 0 || n < 0 || ld_v < 3 || ld_t < 3 || ld_o < 3 || ld_d < 3) return MISO_E_BADARG;
+  if (n_tri >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if ((n_tri > 0 && (!tris || (n_vert > 0 && !verts))) || (n > 0 && (!origins || !dirs || !out_t || !out_tri))) return MISO_E_BADARG;
+  return (int)launch_mesh_cast_rays_all(verts, ld_v, n_vert, tris, ld_t, n_tri, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_t,
+                                        out_tri, (hipStream_t)stream);
+}
+
 // ---- fused atlas query (atlas.hip) ------------------------------------------------------------------------------------
 int64_t miso_atlas_plan_bytes(int32_t n_submaps) {
   return n_submaps < 1 ? 0 : (int64_t)n_submaps * (int64_t)sizeof(GridK);

@@ -180,4 +180,16 @@ hipError_t launch_icp_sums(const float* moved, const float* d2, const int64_t* i
 hipError_t launch_nn_normals(const miso_nn_plan_t& plan, const void* workspace, const float* pts, int64_t ld, int64_t n,
                              double radius, float* normals, int32_t* counts, hipStream_t s);
 
+// ---- mesh.hip
+int64_t mesh_workspace_bytes(const miso_mesh_plan_t& plan);
+hipError_t launch_mesh_count(const miso_mesh_plan_t& plan, const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris,
+                             int64_t ld_t, void* workspace, int64_t* entries, hipStream_t s);
+hipError_t launch_mesh_build(const miso_mesh_plan_t& plan, void* workspace, int32_t* lists, int64_t capacity, hipStream_t s);
+hipError_t launch_mesh_cast_rays(const miso_mesh_plan_t& plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                                 const float* org, int64_t ld_o, const float* dir, int64_t ld_d, int64_t n, float t_min, float t_max,
+                                 float* out_t, int64_t* out_tri, int64_t* stats, hipStream_t s);
+hipError_t launch_mesh_cast_rays_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t,
+                                     int64_t n_tri, const float* org, int64_t ld_o, const float* dir, int64_t ld_d, int64_t n,
+                                     float t_min, float t_max, float* out_t, int64_t* out_tri, hipStream_t s);
+
 }  // namespace miso

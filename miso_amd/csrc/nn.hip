@@ -219,18 +219,26 @@ hipError_t launch_nn_set_stats(int32_t* stats, int a, int b, hipStream_t s) {
   return hipGetLastError();
 }
 
+// counts[0 .. n) -> their exclusive prefix sums, in place (n <= MISO_NN_MAX_CELLS; sums: 1024 ints of scratch)
+hipError_t launch_nn_scan(int* counts, int n, int* sums, hipStream_t s) {
+  const int nb = (n + NN_SCAN_TILE - 1) / NN_SCAN_TILE;
+  nn_scan_sums_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(counts, n, sums);
+  nn_scan_blocks_kernel<<<1, NN_SCAN_THREADS, 0, s>>>(sums, nb);
+  nn_scan_apply_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(counts, n, sums);
+  return hipGetLastError();
+}
+
 hipError_t launch_nn_build(const miso_nn_plan_t& p, const float* tgt, int64_t ld, void* ws, hipStream_t s) {
   if (p.n_tgt == 0) return hipSuccess;
   const auto v = nn_views(p, ws);
   const NnK k = nn_k(p);
-  const int cells = (int)p.cells, nb = (cells + NN_SCAN_TILE - 1) / NN_SCAN_TILE;
+  const int cells = (int)p.cells;
   const unsigned g = (unsigned)((p.n_tgt + 255) / 256);
   hipError_t e = launch_zero_words(v.table, cells + 1, s);
   if (e != hipSuccess) return e;
   nn_count_kernel<<<g, 256, 0, s>>>(k, tgt, ld, v.table);
-  nn_scan_sums_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(v.table + 1, cells, v.sums);
-  nn_scan_blocks_kernel<<<1, NN_SCAN_THREADS, 0, s>>>(v.sums, nb);
-  nn_scan_apply_kernel<<<nb, NN_SCAN_THREADS, 0, s>>>(v.table + 1, cells, v.sums);
+  e = launch_nn_scan(v.table + 1, cells, v.sums, s);
+  if (e != hipSuccess) return e;
   nn_scatter_kernel<<<g, 256, 0, s>>>(k, tgt, ld, v.table, v.rows);
   return hipGetLastError();
 }

@@ -180,6 +180,8 @@ __device__ __forceinline__ void nn_stage_tile(float4* tile, int len, const float
 // nn.hip: (+inf, -1) into `total` slots (no target: every slot is padding); stats = {a, b}
 hipError_t launch_nn_fill(int64_t total, float* out_d2, int64_t* out_idx, hipStream_t s);
 hipError_t launch_nn_set_stats(int32_t* stats, int a, int b, hipStream_t s);
+// nn.hip: the exclusive scan of the build, in place over counts[0 .. n), n <= MISO_NN_MAX_CELLS (mesh.hip's build too)
+hipError_t launch_nn_scan(int* counts, int n, int* sums, hipStream_t s);
 
 // ---- normals from a neighbourhood's sums (icp.hip: radius; knn.hip: k nearest) -------------------------------------------
 // 1, d and d d^T of a neighbourhood, d = t - q in float64, added in the order add() is called

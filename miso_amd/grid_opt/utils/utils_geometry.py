@@ -240,3 +240,53 @@ def write_kitti_format_poses(filename: str, poses_np: np.ndarray, direct_use_fil
     """(N,4,4) -> one row-major 3x4 line per pose, np.savetxt's default format (reference :415-424)."""
     np.savetxt(fname=filename if direct_use_filename else f"{filename}_kitti.txt",
                X=poses_np[:, :3, :].reshape(poses_np.shape[0], -1))
+
+
+def _cross3(a, b):
+    """a x b per component as a b - c d: two products and one difference, each rounded once (torch.cross may fuse)"""
+    return torch.stack((a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                        a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]), dim=-1)
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def cast_rays_torch(origins, dirs, vertices, triangles, t_min=0.0, t_max=float('inf'), chunk=4096):
+    """First hit of every ray origins[i] + t dirs[i] among the triangles, as chunked torch ops on any device: the formula
+    of the HIP kernels (csrc/mesh.hpp, two-sided Moller-Trumbore; a hit iff det != 0, u >= 0, v >= 0, u + v <= 1 and
+    t_min <= t <= t_max; the smallest (t, triangle index) pair; t in units of |dirs[i]|) in the dtype of ``origins``.
+    -> (t (N,), tri (N,) int64), (+inf, -1) for a miss.  A triangle with an index out of range, a non-finite vertex or a
+    zero cross product (v1 - v0) x (v2 - v0) is never hit.  ``chunk`` rays at a time against all triangles."""
+    dt, dev = origins.dtype, origins.device
+    n, nt, nv = int(origins.shape[0]), int(triangles.shape[0]), int(vertices.shape[0])
+    out_t = torch.full((n,), float('inf'), dtype=dt, device=dev)
+    out_i = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    if n == 0 or nt == 0 or nv == 0:
+        return out_t, out_i
+    triangles = triangles.to(device=dev, dtype=torch.int64)
+    vertices = vertices.to(device=dev, dtype=dt)
+    ok = ((triangles >= 0) & (triangles < nv)).all(dim=1)
+    v = vertices[triangles.clamp(0, nv - 1)]
+    v0, e1, e2 = v[:, 0], v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
+    nrm = _cross3(e1, e2)
+    ok &= torch.isfinite(v).all(dim=2).all(dim=1) & torch.isfinite(nrm).all(dim=1) & (nrm != 0).any(dim=1)
+    big = torch.iinfo(torch.int64).max
+    index = torch.arange(nt, device=dev)
+    for a in range(0, n, max(int(chunk), 1)):
+        o, d = origins[a:a + chunk, None, :], dirs[a:a + chunk, None, :].to(dt)
+        p = _cross3(d, e2[None])
+        det = _dot3(e1[None], p)
+        inv = 1.0 / det
+        s = o - v0[None]
+        u = _dot3(s, p) * inv
+        q = _cross3(s, e1[None])
+        w = _dot3(d, q) * inv
+        t = _dot3(e2[None], q) * inv
+        hit = ok[None] & (det != 0) & (u >= 0) & (w >= 0) & (u + w <= 1) & (t >= t_min) & (t <= t_max)
+        t = torch.where(hit, t, torch.full_like(t, float('inf')))
+        best = t.amin(dim=1)
+        first = torch.where(hit & (t == best[:, None]), index[None], big).amin(dim=1)
+        out_t[a:a + chunk] = best
+        out_i[a:a + chunk] = torch.where(first == big, torch.full_like(first, -1), first)
+    return out_t, out_i

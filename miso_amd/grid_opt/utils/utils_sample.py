@@ -3,6 +3,8 @@
 The per-iteration work of the reference's ``get_batch_data`` / ``stratified_sample`` / ``sample_along_rays``
 (:142-302) lives in the HIP kernel behind ``miso_amd.ops.sample_rays``; what stays here is set-up that runs once
 per dataset (ray directions, back-projection, normals) and the pixel draw."""
+import math
+
 import torch
 
 
@@ -64,3 +66,27 @@ def sample_pixels(n_rays, n_frames, h, w, device):
     indices_w = torch.randint(0, w, (total,), device=device)
     indices_b = torch.arange(n_frames, device=device).repeat_interleave(n_rays)
     return indices_b, indices_h, indices_w
+
+
+def pinhole_rays_lookat(fov_deg, center, eye, up, width_px, height_px, device=None):
+    """(H W, 6) rays [origin, direction] of a pinhole camera at ``eye`` looking at ``center``, row-major over the pixels:
+    what the reference asks of Open3D's RaycastingScene.create_rays_pinhole (grid_opt/datasets/sdf_3d.py:226-233).
+    Focal length f = 0.5 W / tan(fov / 2) in pixels (``fov_deg`` is the horizontal field of view), principal point
+    (W / 2, H / 2), and the ray of pixel (row r, column c) goes through its centre: in the camera frame its direction
+    is ((c + 0.5 - W / 2) / f, (r + 0.5 - H / 2) / f, 1), NOT normalised (the hit parameter is then the z-depth).  The camera
+    axes are Open3D's look-at: z = center - eye, x = up x z, y = z x x, each of unit length.
+    Open3D's own half-pixel convention (whether its rays pass through pixel centres or corners) could not be checked
+    here -- Open3D is not installed -- so a depth image may be shifted by half a pixel against one Open3D renders."""
+    as_t = lambda v: torch.as_tensor(v, dtype=torch.float32, device=device).reshape(3)        # noqa: E731
+    center, eye, up = as_t(center), as_t(eye), as_t(up)
+    W, H = int(width_px), int(height_px)
+    z = center - eye
+    z = z / z.norm()
+    x = torch.linalg.cross(up, z)
+    x = x / x.norm()
+    y = torch.linalg.cross(z, x)
+    f = 0.5 * W / math.tan(0.5 * math.radians(float(fov_deg)))
+    cols = (torch.arange(W, device=eye.device, dtype=torch.float32) + 0.5 - 0.5 * W) / f
+    rows = (torch.arange(H, device=eye.device, dtype=torch.float32) + 0.5 - 0.5 * H) / f
+    dirs = cols[None, :, None] * x + rows[:, None, None] * y + z              # (H, W, 3)
+    return torch.cat([eye.expand(H * W, 3), dirs.reshape(-1, 3)], dim=1)

@@ -1224,6 +1224,181 @@ def knn(src: torch.Tensor, tgt: torch.Tensor, k: int, cell: Optional[float] = No
 
 
 # --------------------------------------------------------------------------- #
+# ray casting against a triangle mesh (Open3D's RaycastingScene.cast_rays; csrc/mesh.hip)
+# --------------------------------------------------------------------------- #
+MESH_CELL_EDGES = 2.0         # default cell = this many triangle edges: the fastest cast of {0.5, 1, 2, 4, 8} at 10^4, 10^5
+                              # and 10^6 triangles (profiles/cast_rays.json: cell_sweep)
+MESH_MAX_ENTRIES = _lib.MESH_MAX_ENTRIES    # list entries of one index (512 MB); above it the cell is doubled
+# cast_rays(): a mesh of fewer triangles than this goes to the all-triangles kernel.  Measured (profiles/cast_rays.json,
+# route_threshold): with 256 .. 65 536 rays the all-triangles kernel takes 0.05 ms + 0.2 us per triangle whatever the ray
+# count (a lane per ray: up to 256 blocks run side by side), building an index and walking it 0.43 .. 0.58 ms; they cross
+# near 2 000 triangles (1 024: 0.24 against 0.44 ms; 8 192: 1.7 against 0.56 ms).
+MESH_ALL_BELOW = 2048
+
+
+def _tri_index(t: torch.Tensor) -> torch.Tensor:
+    """(T, 3) int64 vertex indices on the device, a row-strided view read in place"""
+    if not t.is_cuda:
+        raise RuntimeError(f"miso_amd ops run on the HIP device only (no CPU fallback); got a tensor on {t.device}")
+    assert t.ndim == 2 and t.shape[1] == 3 and t.dtype == torch.int64, "triangles is a (T, 3) int64 tensor"
+    if t.shape[0] <= 1 or t.stride(1) != 1 or t.stride(0) < 3:
+        t = t.contiguous()
+    return t
+
+
+def _ray_out(out, n: int, device):
+    if out is None:
+        out = (torch.empty(n, device=device, dtype=torch.float32), torch.empty(n, device=device, dtype=torch.int64))
+    t, tri = out
+    for x, dtype in ((t, torch.float32), (tri, torch.int64)):
+        assert x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() >= n
+    return t, tri
+
+
+def mesh_default_cell(lo, hi, n_tri: int) -> float:
+    """The cell of MeshIndex(cell=None): MESH_CELL_EDGES triangle edges, the edge that of ``n_tri`` triangles tiling the
+    surface of their bounding box (nn_default_cell's estimate with triangles for points)."""
+    return nn_default_cell(lo, hi, n_tri) / NN_CELL_SPACINGS * MESH_CELL_EDGES
+
+
+def mesh_plan_fit(lo, hi, cell: float, n_tri: int, count, max_entries: Optional[int] = None):
+    """miso_mesh_plan, then ``count(plan)`` -> (list entries, workspace); while the lists would exceed ``max_entries``
+    (default MESH_MAX_ENTRIES, read at call time) the cell is doubled and both run again.  -> (plan, entries, workspace);
+    plan.cell is the cell used.  n_tri == 0: the empty plan, nothing counted."""
+    lib = _lib.load()
+    cap = MESH_MAX_ENTRIES if max_entries is None else int(max_entries)
+    while True:
+        plan = _lib.MeshPlan()
+        _lib.check(lib.miso_mesh_plan((C.c_float * 3)(*lo), (C.c_float * 3)(*hi), float(cell), int(n_tri), C.byref(plan)),
+                   "miso_mesh_plan")
+        if not n_tri:
+            return plan, 0, None
+        entries, workspace = count(plan)
+        if entries <= cap:
+            return plan, entries, workspace
+        cell = 2.0 * float(plan.cell)
+
+
+def _hittable_bounds(vertices: torch.Tensor, triangles: torch.Tensor):
+    """min and max (six values, one tensor) over the vertices of the triangles the kernels can hit: vertex indices in
+    range, finite coordinates and a non-zero fp32 cross product, formed as csrc/mesh.hpp forms it (a product of two
+    floats is exact in float64, so .double() products rounded to float are the kernel's)."""
+    inf = float("inf")
+    nv = int(vertices.shape[0])
+    ok = ((triangles >= 0) & (triangles < nv)).all(dim=1)
+    v = vertices[triangles.clamp(0, max(nv - 1, 0))] if nv else vertices.new_zeros((triangles.shape[0], 3, 3))
+    ok &= torch.isfinite(v).all(dim=2).all(dim=1)
+    e1, e2 = (v[:, 1] - v[:, 0]).double(), (v[:, 2] - v[:, 0]).double()
+    prod = lambda a, b: (a * b).float()           # noqa: E731
+    n = torch.stack([prod(e1[:, 1], e2[:, 2]) - prod(e1[:, 2], e2[:, 1]), prod(e1[:, 2], e2[:, 0]) - prod(e1[:, 0], e2[:, 2]),
+                     prod(e1[:, 0], e2[:, 1]) - prod(e1[:, 1], e2[:, 0])], dim=1)
+    ok &= torch.isfinite(n).all(dim=1) & (n != 0).any(dim=1)
+    m = ok[:, None, None].expand_as(v)
+    return torch.cat([torch.where(m, v, inf).amin(dim=(0, 1)), torch.where(m, v, -inf).amax(dim=(0, 1))])
+
+
+class MeshIndex:
+    """A uniform grid over the triangles of a mesh for first-hit ray queries (miso_mesh_plan / count / build / cast_rays,
+    csrc/mesh.hip).  ``vertices`` (V, 3) fp32 and ``triangles`` (T, 3) int64 on the device, strided views read in place.
+    Building reads back the bounds (six floats) and, after the count, the number of list entries -- the host needs both to
+    size the grid and the lists; queries read nothing back.  ``cell=None``: mesh_default_cell.  While the lists would
+    exceed MESH_MAX_ENTRIES the cell is doubled (one more count and read each time); ``stats()`` names the cell used.
+    A triangle with a non-finite vertex, an index out of range or zero area is never hit and does not enter the bounds."""
+
+    def __init__(self, vertices: torch.Tensor, triangles: torch.Tensor, cell: Optional[float] = None):
+        vertices, triangles = _cloud(vertices, "vertices"), _tri_index(triangles)
+        self.vertices, self.triangles = vertices, triangles
+        self.n_vert, self.n_tri = int(vertices.shape[0]), int(triangles.shape[0])
+        lib = _lib.load()
+        lo, hi = [0.0] * 3, [0.0] * 3
+        n_plan = self.n_tri
+        if self.n_tri:
+            b = _hittable_bounds(vertices, triangles).tolist()                      # a host read
+            if all(abs(v) < float("inf") for v in b):
+                lo, hi = b[:3], b[3:]
+            else:
+                n_plan = 0                                                          # nothing can be hit: the empty index
+        self.bound_min, self.bound_max = tuple(lo), tuple(hi)
+        cell = float(mesh_default_cell(lo, hi, self.n_tri) if cell is None else cell)
+        dev = vertices.device
+
+        def count(plan):
+            workspace = torch.empty(int(lib.miso_mesh_workspace_bytes(C.byref(plan))), device=dev, dtype=torch.uint8)
+            total = torch.empty(2, device=dev, dtype=torch.int64)
+            _lib.check(lib.miso_mesh_count(C.byref(plan), _ptr(vertices), _ld(vertices), self.n_vert, _ptr(triangles),
+                                           _ld(triangles), _ptr(workspace), _ptr(total), _stream(vertices)), "miso_mesh_count")
+            return int(total[0].item()), workspace                                  # the host read of the build
+
+        self.plan, self.entries, self.workspace = mesh_plan_fit(lo, hi, cell, n_plan, count)
+        self.lists = None
+        if n_plan:
+            self.lists = torch.empty(max(self.entries, 1), device=dev, dtype=torch.int32)
+            _lib.check(lib.miso_mesh_build(C.byref(self.plan), _ptr(self.workspace), _ptr(self.lists), self.entries,
+                                           _stream(vertices)), "miso_mesh_build")
+        self.cell = float(self.plan.cell)
+        self.dims = tuple(int(d) for d in self.plan.dims)
+
+    def cast_rays(self, origins: torch.Tensor, dirs: torch.Tensor, t_min: float = 0.0, t_max: float = float("inf"), out=None,
+                  stats: Optional[torch.Tensor] = None):
+        """-> (t (N,) fp32, tri (N,) int64) on the device: the first hit of every ray origins[i] + t dirs[i] with
+        t_min <= t <= t_max, t in units of |dirs[i]| (directions are not normalised); (+inf, -1) for a miss.  Nothing is
+        read back, so with ``out`` = (t, tri) the call replays inside a captured graph.  ``stats``: (3,) int64 on the
+        device, filled with {cells visited, triangles offered, rays answered from all rows}."""
+        origins, dirs = _cloud(origins, "origins"), _cloud(dirs, "dirs")
+        n = int(origins.shape[0])
+        assert int(dirs.shape[0]) == n, "one direction per origin"
+        t, tri = _ray_out(out, n, origins.device)
+        if stats is not None:
+            assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 3
+        _lib.check(_lib.load().miso_mesh_cast_rays(C.byref(self.plan), _ptr(self.workspace), _ptr(self.lists), self.entries,
+                                                   _ptr(origins), _ld(origins), _ptr(dirs), _ld(dirs), n, float(t_min),
+                                                   float(t_max), _ptr(t), _ptr(tri), _ptr(stats), _stream(origins)),
+                   "miso_mesh_cast_rays")
+        return t, tri
+
+    def triangle_normals(self) -> torch.Tensor:
+        """(T, 3) unit face normals (v1 - v0) x (v2 - v0) from the winding; zero for a triangle that has none."""
+        nv = self.n_vert
+        if not self.n_tri or not nv:
+            return self.vertices.new_zeros((self.n_tri, 3))
+        v = self.vertices[self.triangles.clamp(0, nv - 1)]
+        n = torch.cross(v[:, 1] - v[:, 0], v[:, 2] - v[:, 0], dim=1)
+        length = n.norm(dim=1, keepdim=True)
+        ok = torch.isfinite(length) & (length > 0)
+        return torch.where(ok, n / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(n))
+
+    def stats(self) -> dict:
+        """the grid as built: cells, dims, list entries (and per triangle), the cell used, the slack w of the lists"""
+        return {"cells": int(self.plan.cells), "dims": self.dims, "entries": self.entries, "cell": self.cell,
+                "entries_per_triangle": self.entries / max(self.n_tri, 1), "widen": float(self.plan.widen)}
+
+
+def cast_rays_all(origins: torch.Tensor, dirs: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor,
+                  t_min: float = 0.0, t_max: float = float("inf"), out=None):
+    """The all-triangles kernel for every ray (miso_mesh_cast_rays_all): -> (t, tri), the bits MeshIndex.cast_rays returns."""
+    origins, dirs = _cloud(origins, "origins"), _cloud(dirs, "dirs")
+    vertices, triangles = _cloud(vertices, "vertices"), _tri_index(triangles)
+    n = int(origins.shape[0])
+    assert int(dirs.shape[0]) == n, "one direction per origin"
+    t, tri = _ray_out(out, n, origins.device)
+    _lib.check(_lib.load().miso_mesh_cast_rays_all(_ptr(vertices), _ld(vertices), int(vertices.shape[0]), _ptr(triangles),
+                                                   _ld(triangles), int(triangles.shape[0]), _ptr(origins), _ld(origins),
+                                                   _ptr(dirs), _ld(dirs), n, float(t_min), float(t_max), _ptr(t), _ptr(tri),
+                                                   _stream(origins)), "miso_mesh_cast_rays_all")
+    return t, tri
+
+
+def cast_rays(origins: torch.Tensor, dirs: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor,
+              t_min: float = 0.0, t_max: float = float("inf"), cell: Optional[float] = None):
+    """First hit of every ray among the triangles: -> (t (N,) fp32, tri (N,) int64), (+inf, -1) for a miss.  Small meshes
+    (T < MESH_ALL_BELOW, read at call time) take the all-triangles kernel, the rest a MeshIndex: the same bits."""
+    _require_hip(origins, dirs, vertices)
+    if int(triangles.shape[0]) < MESH_ALL_BELOW:
+        return cast_rays_all(origins, dirs, vertices, triangles, t_min, t_max)
+    return MeshIndex(vertices, triangles, cell=cell).cast_rays(origins, dirs, t_min, t_max)
+
+
+# --------------------------------------------------------------------------- #
 # ICP: the per-point work of Open3D's registration_icp (csrc/icp.hip)
 # --------------------------------------------------------------------------- #
 ICP_KINDS = {"point_to_point": _lib.ICP_POINT_TO_POINT, "point_to_plane": _lib.ICP_POINT_TO_PLANE}
