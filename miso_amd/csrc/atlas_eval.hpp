@@ -107,10 +107,8 @@ __device__ __forceinline__ float atlas_eval(const AtlasK& a, const AtlasDecoder<
       for (int l = 0; l < L; ++l) {
         if ((g.ignore_mask >> l) & 1u) continue;      // (zeros: utils.py:160-163; the atlas queries never set it)
         const LevelK lv = g.lv[l];
-        Axis ax = axis_coord(xl[0], g.bmin[0], g.bmax[0], lv.X, g.flags);
-        Axis ay = axis_coord(xl[1], g.bmin[1], g.bmax[1], lv.Y, g.flags);
-        Axis az = axis_coord(xl[2], g.bmin[2], g.bmax[2], lv.Z, g.flags);
-        Cell c = make_cell(ax, ay, az, lv);
+        Axis ax[3];
+        const Cell c = level_cell(g, lv, xl[0], xl[1], xl[2], ax);
         float fl[C];
         gather_level<C, true>(lv, c, fl);
 #pragma unroll
@@ -147,9 +145,10 @@ __device__ __forceinline__ bool atlas_to_submap(const AtlasK& a, const float* ps
 
 // The first half of atlas_eval for a caller that runs the decoder itself (atlas_sdf_bwd_kernel keeps the ReLU signs):
 // the masked mean over the submaps at one world point per lane, operation for operation the loop of atlas_eval above.
-// (A second copy on purpose: atlas_eval's own body stays as it is, so that the forward and trace kernels keep their code.)  mean[] receives the mean feature row (zeros past F), den the number of
-// submaps the lane is inside (1 where it is inside none: the divisor of the mean); returns whether any lane of the
-// wavefront is inside any submap (wave-uniform).
+// A second copy on purpose.  atlas_eval = atlas_mean + decode was built and measured: atlas_sdf_kernel<8,3,32,1,exact>
+// went 128 -> 130 VGPRs and ten atlas_trace_kernel instantiations took 1 - 4 more; apart, every kernel keeps its counts.
+// mean[] receives the mean feature row (zeros past F), den the number of submaps the lane is inside (1 where it is
+// inside none: the divisor of the mean); returns whether any lane of the wavefront is inside any submap (wave-uniform).
 template <int C, int L, int NF>
 __device__ __forceinline__ bool atlas_mean(const AtlasK& a, bool valid, float wx, float wy, float wz, float (&mean)[NF],
                                            float& den) {
@@ -171,10 +170,8 @@ __device__ __forceinline__ bool atlas_mean(const AtlasK& a, bool valid, float wx
       for (int l = 0; l < L; ++l) {
         if ((g.ignore_mask >> l) & 1u) continue;      // (zeros: utils.py:160-163; the atlas queries never set it)
         const LevelK lv = g.lv[l];
-        Axis ax = axis_coord(xl[0], g.bmin[0], g.bmax[0], lv.X, g.flags);
-        Axis ay = axis_coord(xl[1], g.bmin[1], g.bmax[1], lv.Y, g.flags);
-        Axis az = axis_coord(xl[2], g.bmin[2], g.bmax[2], lv.Z, g.flags);
-        Cell c = make_cell(ax, ay, az, lv);
+        Axis ax[3];
+        const Cell c = level_cell(g, lv, xl[0], xl[1], xl[2], ax);
         float fl[C];
         gather_level<C, true>(lv, c, fl);
 #pragma unroll

@@ -82,16 +82,6 @@ struct TraceK {
   float* grad;               // (N,3) central differences at points, or nullptr
 };
 
-__device__ __forceinline__ void load_point(const GridK& g, const float* __restrict__ x, int64_t p, float& px,
-                                           float& py, float& pz) {
-  if (g.xstride == 4) {
-    const float4 v = reinterpret_cast<const float4*>(x)[p];
-    px = v.x; py = v.y; pz = v.z;
-  } else {
-    px = x[p * 3 + 0]; py = x[p * 3 + 1]; pz = x[p * 3 + 2];
-  }
-}
-
 // miso_sorted_t.tiles_per_axis: a plain count (1..16: cubic binning) or MISO_TILES_XYZ(tx, ty, tz), 1..32 per axis
 inline bool tiles_xyz(int32_t code, int T[3]) {
   if (code >= 1 && code <= 16) { T[0] = T[1] = T[2] = code; return true; }
@@ -112,104 +102,6 @@ struct WgradOutK {
   float* w[MISO_MAX_LINEAR];
   float* b[MISO_MAX_LINEAR];
 };
-
-// Per-axis sample position.  Mirrors the reference op by op (no FMA
-// contraction) so coordinates are bit-identical to the PyTorch path:
-//   utils.normalize_coordinates (grid_opt/utils/utils.py:49):
-//       xn = 2 * (x - bmin) / (bmax - bmin) - 1
-//   ATen grid_sampler_unnormalize (align_corners=False): ix = ((xn + 1) * size - 1) / 2
-// `mult` is d(ix)/d(x) as autograd forms it.
-struct Axis {
-  float pos;   // continuous index ix
-  float mult;  // d ix / d x  (0 where border padding clipped the coordinate)
-};
-
-// (Without OCML_BASIC_ROUNDED_OPERATIONS HIP's __fadd_rn / __fsub_rn / __fmul_rn are plain operators, so the compiler may
-// contract them: (xn + 1) * size - 1 below is one v_fma_f32, a single rounding.  The same holds in axis_from_norm.)
-__device__ __forceinline__ Axis axis_coord(float x, float bmin, float bmax, int size, uint32_t flags) {
-  float xn = x;
-  float m = 1.0f;
-  if (!(flags & MISO_F_COORDS_NORMALIZED)) {
-    float len = __fsub_rn(bmax, bmin);
-    xn = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, __fsub_rn(x, bmin)), len), 1.0f);
-    m = __fdiv_rn(2.0f, len);
-  }
-  float fs = (float)size;
-  float ix;
-  if (flags & MISO_F_ALIGN_CORNERS) {
-    ix = __fmul_rn(__fmul_rn(__fadd_rn(xn, 1.0f), 0.5f), (float)(size - 1));   // x / 2 == x * 0.5 exactly
-    m *= 0.5f * (float)(size - 1);
-  } else {
-    ix = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(xn, 1.0f), fs), 1.0f), 0.5f);   // (an IEEE divide is ~10 instructions)
-    m *= 0.5f * fs;
-  }
-  if (flags & MISO_F_PAD_BORDER) {
-    float hi = (float)(size - 1);
-    if (ix <= 0.0f) { ix = 0.0f; m = 0.0f; }
-    else if (ix >= hi) { ix = hi; m = 0.0f; }
-  }
-  Axis a; a.pos = ix; a.mult = m;
-  return a;
-}
-
-// The two halves of axis_coord, for a kernel that evaluates several levels at one point: the normalised coordinate and
-// the factor 2 / len do not depend on the level (same operations, same order, same bits -- formed once instead of per level:
-// two IEEE divisions per axis and level otherwise).
-__device__ __forceinline__ void axis_norm(float x, float bmin, float bmax, uint32_t flags, float& xn, float& m) {
-  xn = x; m = 1.0f;
-  if (!(flags & MISO_F_COORDS_NORMALIZED)) {
-    const float len = __fsub_rn(bmax, bmin);
-    xn = __fsub_rn(__fdiv_rn(__fmul_rn(2.0f, __fsub_rn(x, bmin)), len), 1.0f);
-    m = __fdiv_rn(2.0f, len);
-  }
-}
-__device__ __forceinline__ Axis axis_from_norm(float xn, float m, int size, uint32_t flags) {
-  const float fs = (float)size;
-  float ix;
-  if (flags & MISO_F_ALIGN_CORNERS) {
-    ix = __fmul_rn(__fmul_rn(__fadd_rn(xn, 1.0f), 0.5f), (float)(size - 1));
-    m *= 0.5f * (float)(size - 1);
-  } else {
-    ix = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(xn, 1.0f), fs), 1.0f), 0.5f);
-    m *= 0.5f * fs;
-  }
-  if (flags & MISO_F_PAD_BORDER) {
-    const float hi = (float)(size - 1);
-    if (ix <= 0.0f) { ix = 0.0f; m = 0.0f; }
-    else if (ix >= hi) { ix = hi; m = 0.0f; }
-  }
-  Axis a; a.pos = ix; a.mult = m;
-  return a;
-}
-
-// Trilinear cell: base corner, the two 1-D weights per axis (ATen forms them
-// as (i0+1-ix) and (ix-i0), gridsample_cuda.cu:335-342) and in-range flags.
-struct Cell {
-  int i0, j0, k0;
-  float wx[2], wy[2], wz[2];
-  bool inx[2], iny[2], inz[2];
-};
-
-__device__ __forceinline__ void axis_cell(float pos, int size, int& i0, float w[2], bool in[2]) {
-  float f = floorf(pos);
-  // clamp before the int conversion so far-away points cannot overflow
-  f = fminf(fmaxf(f, -2.0f), (float)size + 1.0f);
-  i0 = (int)f;
-  if (pos != pos) { i0 = -2; }  // NaN coordinate: every corner out of range
-  w[0] = __fsub_rn(f + 1.0f, pos);
-  w[1] = __fsub_rn(pos, f);
-  in[0] = (i0 >= 0) && (i0 < size);
-  in[1] = (i0 + 1 >= 0) && (i0 + 1 < size);
-}
-
-__device__ __forceinline__ Cell make_cell(const Axis& ax, const Axis& ay, const Axis& az,
-                                          const LevelK& lv) {
-  Cell c;
-  axis_cell(ax.pos, lv.X, c.i0, c.wx, c.inx);
-  axis_cell(ay.pos, lv.Y, c.j0, c.wy, c.iny);
-  axis_cell(az.pos, lv.Z, c.k0, c.wz, c.inz);
-  return c;
-}
 
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) {
   // hardware fp32 add at L2 (global_atomic_add_f32, no return value)
@@ -363,3 +255,5 @@ struct LossInK {
 };
 
 }  // namespace miso
+
+#include "trilinear.hpp"      // the sampler (load_point, Axis, Cell, level_cell, corner table, lerp tree): needs the structs above

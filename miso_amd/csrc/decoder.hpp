@@ -62,10 +62,9 @@ __device__ __forceinline__ void gather_level(const LevelK& lv, const Cell& c, fl
   for (int q = 0; q < C; ++q) f[q] = 0.0f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-    bool in = c.inx[dx] && c.iny[dy] && c.inz[dz];
-    float w = in ? (c.wx[dx] * c.wy[dy]) * c.wz[dz] : 0.0f;
-    int off = in ? (c.k0 + dz) * lv.sZ + (c.j0 + dy) * lv.sY + (c.i0 + dx) * lv.sX : 0;
+    const bool in = corner_in(c, k);
+    const float w = corner_weight<0>(c, k, in).w;
+    int off = in ? corner_offset(c, lv, k) : 0;      // (the weight before the offset: sdf_train_kernel's registers)
 #ifdef MISO_ABL_UNIFORM_GATHER      // dev ablation (wrong results): every lane reads lane 0's rows -- perfectly coalesced gathers
     off = __builtin_amdgcn_readfirstlane(off);
 #endif

@@ -31,19 +31,12 @@ __global__ __launch_bounds__(256) void encode_fwd_kernel(GridK g, const float* _
       for (int c = 0; c < lv.C; ++c) o[lv.foff + c] = 0.0f;
       continue;
     }
-    Axis ax = axis_coord(px, g.bmin[0], g.bmax[0], lv.X, g.flags);
-    Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
-    Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
-    Cell c = make_cell(ax, ay, az, lv);
+    Axis a[3];
+    const Cell c = level_cell(g, lv, px, py, pz, a);
     int off[8];
     float w[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-      bool in = c.inx[dx] && c.iny[dy] && c.inz[dz];
-      w[k] = in ? (c.wx[dx] * c.wy[dy]) * c.wz[dz] : 0.0f;
-      off[k] = in ? (c.k0 + dz) * lv.sZ + (c.j0 + dy) * lv.sY + (c.i0 + dx) * lv.sX : 0;
-    }
+    for (int k = 0; k < 8; ++k) w[k] = corner_weight<0>(c, k, corner(c, lv, k, off[k])).w;
     if (VEC4) {
       for (int ch = 0; ch < lv.C; ch += 4) {
         float4 v[8];
@@ -88,24 +81,16 @@ __global__ __launch_bounds__(256) void encode_bwd_kernel(GridK g, const float* _
   for (int l = 0; l < g.n_levels; ++l) {
     const LevelK& lv = g.lv[l];
     if ((g.ignore_mask >> l) & 1u) continue;
-    Axis ax = axis_coord(px, g.bmin[0], g.bmax[0], lv.X, g.flags);
-    Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
-    Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
-    Cell c = make_cell(ax, ay, az, lv);
+    Axis a[3];
+    const Cell c = level_cell(g, lv, px, py, pz, a);
     int off[8];
     float w[8], dwx[8], dwy[8], dwz[8];
     bool inb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-      bool in = c.inx[dx] && c.iny[dy] && c.inz[dz];
-      inb[k] = in;
-      float sx = dx ? 1.f : -1.f, sy = dy ? 1.f : -1.f, sz = dz ? 1.f : -1.f;
-      w[k] = in ? (c.wx[dx] * c.wy[dy]) * c.wz[dz] : 0.0f;
-      dwx[k] = in ? sx * c.wy[dy] * c.wz[dz] : 0.0f;
-      dwy[k] = in ? sy * c.wx[dx] * c.wz[dz] : 0.0f;
-      dwz[k] = in ? sz * c.wx[dx] * c.wy[dy] : 0.0f;
-      off[k] = in ? (c.k0 + dz) * lv.sZ + (c.j0 + dy) * lv.sY + (c.i0 + dx) * lv.sX : 0;
+      inb[k] = corner(c, lv, k, off[k]);
+      const CornerW cw = corner_weight<1>(c, k, inb[k]);
+      w[k] = cw.w; dwx[k] = cw.dx; dwy[k] = cw.dy; dwz[k] = cw.dz;
     }
     float ax_ = 0.f, ay_ = 0.f, az_ = 0.f;
     if (VEC4) {
@@ -149,7 +134,7 @@ __global__ __launch_bounds__(256) void encode_bwd_kernel(GridK g, const float* _
         }
       }
     }
-    gpx += ax_ * (g.gscale[0] * ax.mult); gpy += ay_ * (g.gscale[1] * ay.mult); gpz += az_ * (g.gscale[2] * az.mult);
+    gpx += ax_ * (g.gscale[0] * a[0].mult); gpy += ay_ * (g.gscale[1] * a[1].mult); gpz += az_ * (g.gscale[2] * a[2].mult);
   }
   if (gx) { gx[po * 3 + 0] = gpx; gx[po * 3 + 1] = gpy; gx[po * 3 + 2] = gpz; }
 }
@@ -170,18 +155,14 @@ __global__ __launch_bounds__(256) void encode_bwd_x_kernel(GridK g, const float*
   for (int l = 0; l < g.n_levels; ++l) {
     const LevelK& lv = g.lv[l];
     if ((g.ignore_mask >> l) & 1u) continue;
-    Axis ax = axis_coord(px, g.bmin[0], g.bmax[0], lv.X, g.flags);
-    Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
-    Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
-    Cell c = make_cell(ax, ay, az, lv);
+    Axis a[3];
+    const Cell c = level_cell(g, lv, px, py, pz, a);
     float d[8];
     int off[8];
     bool inb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-      inb[k] = c.inx[dx] && c.iny[dy] && c.inz[dz];
-      off[k] = inb[k] ? (c.k0 + dz) * lv.sZ + (c.j0 + dy) * lv.sY + (c.i0 + dx) * lv.sX : 0;
+      inb[k] = corner(c, lv, k, off[k]);
       d[k] = 0.0f;
     }
     for (int ch = 0; ch < lv.C; ch += 4) {
@@ -194,15 +175,10 @@ __global__ __launch_bounds__(256) void encode_bwd_x_kernel(GridK g, const float*
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) d[k] = inb[k] ? d[k] : 0.0f;
-    const float tx = c.wx[1], ty = c.wy[1], tz = c.wz[1];
-    const float d00 = d[1] - d[0], d10 = d[3] - d[2], d01 = d[5] - d[4], d11 = d[7] - d[6];
-    const float a00 = d[0] + tx * d00, a10 = d[2] + tx * d10, a01 = d[4] + tx * d01, a11 = d[6] + tx * d11;
-    const float e0 = a10 - a00, e1 = a11 - a01;
-    const float b0 = a00 + ty * e0, b1 = a01 + ty * e1;
-    const float gx0 = d00 + ty * (d10 - d00), gx1 = d01 + ty * (d11 - d01);
-    gpx += (gx0 + tz * (gx1 - gx0)) * (g.gscale[0] * ax.mult);
-    gpy += (e0 + tz * (e1 - e0)) * (g.gscale[1] * ay.mult);
-    gpz += (b1 - b0) * (g.gscale[2] * az.mult);
+    const Lerp3 t = lerp_tree<false>(d, c.wx[1], c.wy[1], c.wz[1]);
+    gpx += t.fx * (g.gscale[0] * a[0].mult);
+    gpy += t.fy * (g.gscale[1] * a[1].mult);
+    gpz += t.fz * (g.gscale[2] * a[2].mult);
   }
   gx[po * 3 + 0] = gpx; gx[po * 3 + 1] = gpy; gx[po * 3 + 2] = gpz;
 }
@@ -239,35 +215,24 @@ __global__ __launch_bounds__(256) void encode_bwd2_kernel(GridK g, const float* 
       for (int c = 0; c < lv.C; ++c) ggout[lv.foff + c] = 0.0f;
       continue;
     }
-    Axis ax = axis_coord(px, g.bmin[0], g.bmax[0], lv.X, g.flags);
-    Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
-    Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
-    Cell c = make_cell(ax, ay, az, lv);
+    Axis a[3];
+    const Cell c = level_cell(g, lv, px, py, pz, a);
     // g.gscale restores d xn / d x when the points were pre-normalised (sorted batches)
-    const float mx = g.gscale[0] * ax.mult, my = g.gscale[1] * ay.mult, mz = g.gscale[2] * az.mult;
+    const float mx = g.gscale[0] * a[0].mult, my = g.gscale[1] * a[1].mult, mz = g.gscale[2] * a[2].mult;
     float dxi = ex * mx, dyi = ey * my, dzi = ez * mz;
     int off[8];
     float w[8], dwx[8], dwy[8], dwz[8], gwd[8], cx[8], cy[8], cz[8];
     bool inb[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-      bool in = c.inx[dx] && c.iny[dy] && c.inz[dz];
-      inb[k] = in;
-      float sx = dx ? 1.f : -1.f, sy = dy ? 1.f : -1.f, sz = dz ? 1.f : -1.f;
-      float m = in ? 1.0f : 0.0f;
-      w[k] = m * (c.wx[dx] * c.wy[dy]) * c.wz[dz];
-      dwx[k] = m * sx * c.wy[dy] * c.wz[dz];
-      dwy[k] = m * sy * c.wx[dx] * c.wz[dz];
-      dwz[k] = m * sz * c.wx[dx] * c.wy[dy];
-      float dwxy = m * sx * sy * c.wz[dz];
-      float dwxz = m * sx * sz * c.wy[dy];
-      float dwyz = m * sy * sz * c.wx[dx];
+      inb[k] = corner_in(c, k);
+      const CornerW cw = corner_weight<2>(c, k, inb[k]);
+      w[k] = cw.w; dwx[k] = cw.dx; dwy[k] = cw.dy; dwz[k] = cw.dz;
       gwd[k] = dxi * dwx[k] + dyi * dwy[k] + dzi * dwz[k];
-      cx[k] = dyi * dwxy + dzi * dwxz;   // multiplies G in gx_x
-      cy[k] = dxi * dwxy + dzi * dwyz;
-      cz[k] = dxi * dwxz + dyi * dwyz;
-      off[k] = in ? (c.k0 + dz) * lv.sZ + (c.j0 + dy) * lv.sY + (c.i0 + dx) * lv.sX : 0;
+      cx[k] = dyi * cw.dxy + dzi * cw.dxz;   // multiplies G in gx_x
+      cy[k] = dxi * cw.dxy + dzi * cw.dyz;
+      cz[k] = dxi * cw.dxz + dyi * cw.dyz;
+      off[k] = inb[k] ? corner_offset(c, lv, k) : 0;      // (behind the weights: before them, gx_z lost its last bits to another contraction)
     }
     float ax_ = 0.f, ay_ = 0.f, az_ = 0.f;
     if (VEC4) {
@@ -324,36 +289,11 @@ __global__ __launch_bounds__(256) void encode_bwd2_kernel(GridK g, const float* 
 
 // The same second backward for the case the binned path produces (channels-last levels, no grid scatter from here: the
 // pull forms that gradient): value, first and mixed second derivatives of the trilinear interpolant by a lerp tree on
-// the zero-padded corner values instead of eight arrays of corner weights.  The weight form above keeps 64 weight
+// the zero-padded corner values (lerp_tree, trilinear.hpp) instead of eight arrays of corner weights.  The weight form above keeps 64 weight
 // registers per level next to 64 gathered corner values (252 VGPRs: two wavefronts per SIMD on a kernel bound by the
 // latency of its gathers).
 //   ggF[c] = f(ggG_c) + d . grad f(G_c)
 //   gx_a   = mult_a * sum_c gF[c] * ( d_a f(ggG_c) + sum_{b != a} d_b d_ab f(G_c) )          (d_aa f = 0)
-struct Lerp3 {
-  float f, fx, fy, fz, fxy, fxz, fyz;
-};
-template <bool SECOND>
-__device__ __forceinline__ Lerp3 lerp_tree(const float v[8], float tx, float ty, float tz) {
-  Lerp3 r;
-  const float d00 = v[1] - v[0], d10 = v[3] - v[2], d01 = v[5] - v[4], d11 = v[7] - v[6];       // d/dx on the (y,z) edges
-  const float a00 = v[0] + tx * d00, a10 = v[2] + tx * d10, a01 = v[4] + tx * d01, a11 = v[6] + tx * d11;
-  const float e0 = a10 - a00, e1 = a11 - a01;                                                     // d/dy at z = 0, 1
-  const float b0 = a00 + ty * e0, b1 = a01 + ty * e1;
-  r.f = b0 + tz * (b1 - b0);
-  r.fz = b1 - b0;
-  r.fy = e0 + tz * (e1 - e0);
-  const float gx0 = d00 + ty * (d10 - d00), gx1 = d01 + ty * (d11 - d01);
-  r.fx = gx0 + tz * (gx1 - gx0);
-  if (SECOND) {
-    r.fyz = e1 - e0;
-    r.fxy = (d10 - d00) + tz * ((d11 - d01) - (d10 - d00));
-    r.fxz = (d01 - d00) + ty * ((d11 - d10) - (d01 - d00));
-  } else {
-    r.fyz = r.fxy = r.fxz = 0.0f;
-  }
-  return r;
-}
-
 template <bool HAS_GG>
 __global__ __launch_bounds__(256) void encode_bwd2_lean_kernel(GridK g, const float* __restrict__ x, int64_t n,
                                                               const float* __restrict__ gf, int64_t ld,
@@ -376,20 +316,14 @@ __global__ __launch_bounds__(256) void encode_bwd2_lean_kernel(GridK g, const fl
       for (int c = 0; c < lv.C; ++c) ggout[lv.foff + c] = 0.0f;
       continue;
     }
-    Axis ax = axis_coord(px, g.bmin[0], g.bmax[0], lv.X, g.flags);
-    Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
-    Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
-    Cell c = make_cell(ax, ay, az, lv);
-    const float mx = g.gscale[0] * ax.mult, my = g.gscale[1] * ay.mult, mz = g.gscale[2] * az.mult;
+    Axis a[3];
+    const Cell c = level_cell(g, lv, px, py, pz, a);
+    const float mx = g.gscale[0] * a[0].mult, my = g.gscale[1] * a[1].mult, mz = g.gscale[2] * a[2].mult;
     const float dxi = ex * mx, dyi = ey * my, dzi = ez * mz;
     int off[8];
     bool inb[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-      inb[k] = c.inx[dx] && c.iny[dy] && c.inz[dz];
-      off[k] = inb[k] ? (c.k0 + dz) * lv.sZ + (c.j0 + dy) * lv.sY + (c.i0 + dx) * lv.sX : 0;
-    }
+    for (int k = 0; k < 8; ++k) inb[k] = corner(c, lv, k, off[k]);
     const float tx = c.wx[1], ty = c.wy[1], tz = c.wz[1];
     const bool gg_here = HAS_GG && lv.gg != nullptr;
     float ax_ = 0.f, ay_ = 0.f, az_ = 0.f;

@@ -75,7 +75,7 @@ __device__ __forceinline__ int floor_div(int a, int b) {   // b > 0
   return (a % b != 0 && a < 0) ? q - 1 : q;
 }
 
-// continuous index from the normalised coordinate, op for op as common.hpp:axis_coord
+// continuous index from the normalised coordinate, op for op as trilinear.hpp:axis_coord
 __device__ __forceinline__ void cell_of(float xn, int size, int& i0, float& frac) {
   float pos = __fmul_rn(__fsub_rn(__fmul_rn(__fadd_rn(xn, 1.0f), (float)size), 1.0f), 0.5f);  // == /2 exactly
   float f = fminf(fmaxf(floorf(pos), -2.0f), (float)size + 1.0f);

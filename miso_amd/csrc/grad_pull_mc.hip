@@ -655,7 +655,7 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
         auto stage_w = [&]() {
           // per axis the sample's position relative to the sub-brick's first vertex, t; the weight of slot o is the hat
           // function max(0, 1 - |t - o|): (1 - frac) at the base corner, frac at the next one, 0 elsewhere (the null
-          // entry is 1e30 away from everything).  pos op for op as common.hpp:axis_coord.
+          // entry is 1e30 away from everything).  pos op for op as trilinear.hpp:axis_coord.
           const float4 c4 = cand[nslot];
           const int d = rcode >> 7;
           const int4 r0 = *reinterpret_cast<const int4*>(lvl + d * MC_LVL);          // X Y Z foff

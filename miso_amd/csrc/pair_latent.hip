@@ -204,26 +204,18 @@ __device__ __forceinline__ void pair_latent_body(const GridK& g, const float* __
         // through a reference every field was fetched where it is used, a dependent scalar round trip each: 0.651 ->
         // 0.632 ms per cfg-4 level-1 iteration)
         const LevelK lv = g.lv[l];
-        Axis ax = axis_from_norm(xn[0], mn[0], lv.X, g.flags);
-        Axis ay = axis_from_norm(xn[1], mn[1], lv.Y, g.flags);
-        Axis az = axis_from_norm(xn[2], mn[2], lv.Z, g.flags);
-        Cell c = make_cell(ax, ay, az, lv);
-        const bool ign = (g.ignore_mask >> l) & 1u;
+        Axis ax[3];
+        Cell c = level_cell_from_norm(xn, mn, g.flags, lv, ax);
+        if ((g.ignore_mask >> l) & 1u) c.inx[0] = c.inx[1] = false;      // an ignored level: every corner out of range
         // Corner values with zeros outside the grid (padding_mode = zeros), then the trilinear value and its three
-        // derivatives by a lerp tree along x, y, z -- the same polynomial as sum_k v_k w_k with w = (wx wy) wz and its
+        // derivatives by lerp_tree (trilinear.hpp) along x, y, z -- the same polynomial as sum_k v_k w_k with w = (wx wy) wz and its
         // derivative weights, without 32 weight registers per level live next to the 32 corner values: the kernel is
         // bound by the latency of its gathers and ran at two wavefronts per SIMD (225 VGPRs) with the weight form.
         int off[8];
         bool inb8[8];
-        // (the base corner's offset once, the others by additions: a 32-bit integer multiply is a quarter-rate instruction,
-        // and three per corner were 24 of them per level and vertex)
-        const int off0 = c.k0 * lv.sZ + c.j0 * lv.sY + c.i0 * lv.sX;
+        // (corner<true>: the base corner's offset once, the others by additions -- the measured form of this kernel)
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-          const int dx = kk & 1, dy = (kk >> 1) & 1, dz = kk >> 2;
-          inb8[kk] = c.inx[dx] && c.iny[dy] && c.inz[dz] && !ign;
-          off[kk] = inb8[kk] ? off0 + (dz ? lv.sZ : 0) + (dy ? lv.sY : 0) + (dx ? lv.sX : 0) : 0;
-        }
+        for (int kk = 0; kk < 8; ++kk) inb8[kk] = corner<true>(c, lv, kk, off[kk]);
         const float fx = c.wx[1], fy = c.wy[1], fz = c.wz[1];      // weight of the upper corner along each axis
         float ax_ = 0.f, ay_ = 0.f, az_ = 0.f;
         for (int ch = 0; ch < lv.C; ch += (VEC4 ? 4 : 1)) {
@@ -243,26 +235,18 @@ __device__ __forceinline__ void pair_latent_body(const GridK& g, const float* __
           }
 #pragma unroll
           for (int e = 0; e < (VEC4 ? 4 : 1); ++e) {
-            // along x: value and d/dx on the four (y,z) edges
-            const float d00 = v[1][e] - v[0][e], d10 = v[3][e] - v[2][e], d01 = v[5][e] - v[4][e], d11 = v[7][e] - v[6][e];
-            const float a00 = v[0][e] + fx * d00, a10 = v[2][e] + fx * d10, a01 = v[4][e] + fx * d01, a11 = v[6][e] + fx * d11;
-            // along y
-            const float e0 = a10 - a00, e1 = a11 - a01;
-            const float b0 = a00 + fy * e0, b1 = a01 + fy * e1;
-            const float gx0 = d00 + fy * (d10 - d00), gx1 = d01 + fy * (d11 - d01);
-            // along z
-            const float fto = b0 + fz * (b1 - b0);
-            const float gxs = gx0 + fz * (gx1 - gx0), gys = e0 + fz * (e1 - e0), gzs = b1 - b0;
-            const float r = fs[lv.foff + ch + e] - fto;
+            const float ve[8] = {v[0][e], v[1][e], v[2][e], v[3][e], v[4][e], v[5][e], v[6][e], v[7][e]};
+            const Lerp3 t = lerp_tree<false>(ve, fx, fy, fz);
+            const float r = fs[lv.foff + ch + e] - t.f;
             ss += r * r;
             if (pass == 1) {
               // d term / d f_to: L2 -> -2 r ; L1 -> -r / |r|
               const float gf = (k.loss_type == 2) ? -2.0f * r : -r * inv_norm;
-              ax_ += gf * gxs; ay_ += gf * gys; az_ += gf * gzs;
+              ax_ += gf * t.fx; ay_ += gf * t.fy; az_ += gf * t.fz;
             }
           }
         }
-        if (pass == 1) { gq[0] += ax_ * ax.mult; gq[1] += ay_ * ay.mult; gq[2] += az_ * az.mult; }
+        if (pass == 1) { gq[0] += ax_ * ax[0].mult; gq[1] += ay_ * ax[1].mult; gq[2] += az_ * ax[2].mult; }
       }
       if (k.loss_type == 1) {
         const float nrm = sqrtf(ss);

@@ -178,10 +178,8 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) MISO_FUSED_KERNEL_ATTR void sdf_
         // (sizes, bound) would be hoisted out of the chunk loop into VGPRs and stay live across the
         // MFMA chain; laundering the integers keeps the conversions inside the loop.
         asm volatile("" : "+s"(lv.X), "+s"(lv.Y), "+s"(lv.Z));
-        Axis ax = axis_coord(px, bmn[0], bmx[0], lv.X, g.flags);
-        Axis ay = axis_coord(py, bmn[1], bmx[1], lv.Y, g.flags);
-        Axis az = axis_coord(pz, bmn[2], bmx[2], lv.Z, g.flags);
-        Cell c = make_cell(ax, ay, az, lv);
+        Axis a[3];
+        const Cell c = level_cell(bmn, bmx, g.flags, lv, px, py, pz, a);
         gather_level<C>(lv, c, &f[l * C]);
       }
     }
@@ -320,10 +318,8 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
 #pragma unroll
         for (int l = 0; l < L; ++l) {
           const LevelK& lv = g.lv[l];
-          Axis ax = axis_coord(px, g.bmin[0], g.bmax[0], lv.X, g.flags);
-          Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
-          Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
-          Cell c = make_cell(ax, ay, az, lv);
+          Axis a[3];
+          const Cell c = level_cell(g, lv, px, py, pz, a);
           write_cell_record(rec + (lane * L + l) * REC, c, lv, valid);
         }
       }
@@ -355,19 +351,16 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
           // arguments would be spilled to scratch).
           LevelK lv = g.lv[(C == 8) ? gi : 2 * gi];
           if (C == 4 && 2 * gi + 1 < L && hi) lv = g.lv[(2 * gi + 1 < L) ? 2 * gi + 1 : 0];
-          Axis ax = axis_coord(px, g.bmin[0], g.bmax[0], lv.X, g.flags);
-          Axis ay = axis_coord(py, g.bmin[1], g.bmax[1], lv.Y, g.flags);
-          Axis az = axis_coord(pz, g.bmin[2], g.bmax[2], lv.Z, g.flags);
-          Cell c = make_cell(ax, ay, az, lv);
+          Axis a[3];
+          const Cell c = level_cell(g, lv, px, py, pz, a);
           const float v0 = df[t][4 * gi + 0], v1 = df[t][4 * gi + 1], v2 = df[t][4 * gi + 2],
                       v3 = df[t][4 * gi + 3];
           float sx_ = 0.f, sy_ = 0.f, sz_ = 0.f;
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-            bool in = c.inx[dx] && c.iny[dy] && c.inz[dz];
-            if (!in) continue;
-            int off = (c.k0 + dz) * lv.sZ + (c.j0 + dy) * lv.sY + (c.i0 + dx) * lv.sX + choff;
+            if (!corner_in(c, k)) continue;
+            int off = corner_offset(c, lv, k) + choff;
             float4 gv = *reinterpret_cast<const float4*>(lv.data + off);
             float dot = gv.x * v0 + gv.y * v1 + gv.z * v2 + gv.w * v3;
             float sx = dx ? 1.f : -1.f, sy = dy ? 1.f : -1.f, sz = dz ? 1.f : -1.f;
@@ -375,9 +368,9 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
             sy_ += dot * sy * c.wx[dx] * c.wz[dz];
             sz_ += dot * sz * c.wx[dx] * c.wy[dy];
           }
-          gacc[t][0] += sx_ * (g.gscale[0] * ax.mult);
-          gacc[t][1] += sy_ * (g.gscale[1] * ay.mult);
-          gacc[t][2] += sz_ * (g.gscale[2] * az.mult);
+          gacc[t][0] += sx_ * (g.gscale[0] * a[0].mult);
+          gacc[t][1] += sy_ * (g.gscale[1] * a[1].mult);
+          gacc[t][2] += sz_ * (g.gscale[2] * a[2].mult);
         }
       }
 #pragma unroll

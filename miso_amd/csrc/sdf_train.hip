@@ -56,10 +56,8 @@ _Pragma("unroll") \
         LevelK lv = g.lv[l]; \
         if ((g.ignore_mask >> l) & 1u) continue; \
         asm volatile("" : "+s"(lv.X), "+s"(lv.Y), "+s"(lv.Z)); \
-        Axis ax = axis_coord(px, bmn[0], bmx[0], lv.X, g.flags); \
-        Axis ay = axis_coord(py, bmn[1], bmx[1], lv.Y, g.flags); \
-        Axis az = axis_coord(pz, bmn[2], bmx[2], lv.Z, g.flags); \
-        Cell c = make_cell(ax, ay, az, lv); \
+        Axis a[3]; \
+        const Cell c = level_cell(bmn, bmx, g.flags, lv, px, py, pz, a); \
       MISO_TRAIN_GATHER_LEVEL(lv, c, &f[l * C]); \
         if (SCAT && ((scatter_mask >> l) & 1u)) { \
           write_cell_record((RECW_) + (row_l * L + l) * REC, c, lv, true); \

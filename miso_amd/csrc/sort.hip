@@ -197,7 +197,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(GridK g, con
         xs[(int64_t)pos[u] * 3 + 2] = v[u][2];
       }
       if (xn) {
-        // normalised coordinates exactly as common.hpp:axis_coord forms them, one float4 per
+        // normalised coordinates exactly as trilinear.hpp:axis_coord forms them, one float4 per
         // point: the sorted kernels read these and never repeat the division
         float w[3];
 #pragma unroll

@@ -20,7 +20,7 @@
 namespace miso {
 
 // c + a b as the two tensor ops it restates: the product rounded, then the sum.  (HIP's __fmul_rn / __fadd_rn are plain
-// operators that the compiler may contract into one v_fma_f32 -- see axis_coord in common.hpp; the pragma is what
+// operators that the compiler may contract into one v_fma_f32 -- see axis_from_norm in trilinear.hpp; the pragma is what
 // keeps them apart.)
 __device__ __forceinline__ float add_product(float c, float a, float b) {
 #pragma clang fp contract(off)
