@@ -66,6 +66,9 @@
  *   miso_mesh_plan / miso_mesh_count / miso_mesh_build / miso_mesh_cast_rays / miso_mesh_cast_rays_all
  *                     Open3D's RaycastingScene.cast_rays as PosedSdf3D.sample_frames calls it
  *                     (grid_opt/datasets/sdf_3d.py:209-312): the first hit of every ray on a triangle mesh.
+ *   miso_mesh_closest / miso_mesh_closest_all / miso_mesh_count_hits / miso_mesh_count_hits_all
+ *                     pysdf's signed distance to a mesh as Sdf3D and PosedSdf3D call it (grid_opt/datasets/sdf_3d.py:54,
+ *                     :84, :193-199, :252): the closest triangle of a point, and the crossings of a ray for the sign.
  *
  * This file is also the ONLY statement of the ABI for Python: miso_amd/_lib.py reads its structs, integer constants and
  * prototypes at import and refuses what it cannot read.  Keep the declarations in the style used below: block comments,
@@ -933,6 +936,45 @@ int miso_mesh_cast_rays(const miso_mesh_plan_t* plan, const void* workspace, con
 int miso_mesh_cast_rays_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t,
                             int64_t n_tri, const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n,
                             float t_min, float t_max, float* out_t, int64_t* out_tri, void* stream);
+
+/* --- closest triangle and crossing counts on the mesh index (csrc/mesh_sdf.hip) ------------------------------------------------
+ * What pysdf gives the reference's Sdf3D and PosedSdf3D (grid_opt/datasets/sdf_3d.py:17-155, 193-199): the distance from a
+ * point to the mesh, and -- for the sign -- how many triangles a ray crosses.  One closest point: the region-classified form
+ * (vertex, edge, interior) in fp32, one rounding per operation (csrc/mesh.hpp: TriBest::take), over the triangle
+ * (v0, v0 + e1, v0 + e2) of the index's rows.  Every route keeps the smallest (d2, triangle index) pair, compared
+ * lexicographically, with that winner's barycentrics (v, w) of e1 and e2: closest point = v0 + v e1 + w e2.  Without a
+ * triangle, for a non-finite query, and against triangles that are never hit the answer is (+inf, -1, 0, 0).  The same bits
+ * from the index and from the all-triangles route.
+ *   miso_mesh_closest  pts (n, 3) with row stride ld_p >= 3, n < 2^31 -> out_d2 (n) fp32 squared distance, out_tri (n) int64,
+ *       out_vw NULL or (n, 2) fp32, 8-byte aligned.  (plan, workspace, lists, capacity): an index as miso_mesh_build left it.
+ *       The far set (plan_far, workspace_far, lists_far, capacity_far) is a second index of the SAME vertices and triangles
+ *       with a coarser cell (MISO_MESH_FAR_FACTOR times the first's is what ops.py builds), or four zeros: a query not
+ *       finished after MISO_MESH_FAR_RINGS shells of the first index starts again on the second, which bounds the work of
+ *       a query far from every surface.  plan_far->reserved > 0 replaces MISO_MESH_FAR_RINGS for that call (sweeps).
+ *       stats: NULL, or 5 int64 on the device = {cells of the first index visited, cells of the far index visited,
+ *       triangles offered, queries that went to the far index, queries answered from all rows (finite, |q_a| >
+ *       4 coord_mag: outside the stop test's rounding argument)}.  No host read, no allocation: replays in a captured graph.
+ *   miso_mesh_closest_all  the all-triangles kernel over the caller's arrays, no index.
+ *   miso_mesh_count_hits  for every ray the NUMBER of triangles that pass miso_mesh_cast_rays' hit test (det != 0, u >= 0,
+ *       v >= 0, u + v <= 1, t_min <= t <= t_max) -> out_count (n) int32.  The walk of miso_mesh_cast_rays without its early
+ *       stop; a triangle listed in several cells counts once, in the cell whose half-open stretch of the ray holds its t.
+ *       A ray through an edge shared by two triangles counts both (u + v <= 1 is inclusive on both).
+ *   miso_mesh_count_hits_all  the same count from the all-triangles kernel.
+ *   MISO_E_BADARG as the calls above, and for a far set that is given in part or indexes another number of triangles. */
+#define MISO_MESH_FAR_FACTOR 4
+#define MISO_MESH_FAR_RINGS 3
+int miso_mesh_closest(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                      const miso_mesh_plan_t* plan_far, const void* workspace_far, const int32_t* lists_far, int64_t capacity_far,
+                      const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri, float* out_vw, int64_t* stats,
+                      void* stream);
+int miso_mesh_closest_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri,
+                          const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri, float* out_vw, void* stream);
+int miso_mesh_count_hits(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                         const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min, float t_max,
+                         int32_t* out_count, void* stream);
+int miso_mesh_count_hits_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri,
+                             const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min,
+                             float t_max, int32_t* out_count, void* stream);
 
 /* --- fused atlas query: GridAtlas.query_feature / GridAtlas.forward in one launch (round 6) ---------------------------
  * Replaces the per-submap loop of grid_opt/models/grid_atlas.py:374-399 (for each active submap: transfrom_points_from,

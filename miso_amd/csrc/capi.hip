@@ -1211,6 +1211,57 @@ int miso_mesh_cast_rays_all(const float* verts, int64_t ld_v, int64_t n_vert, co
                                         out_tri, (hipStream_t)stream);
 }
 
+// ---- closest triangle and crossing counts on the mesh index (mesh_sdf.hip) ----------------------------------------------------
+// an index as miso_mesh_build left it, ready to be read
+static bool mesh_index_ok(const miso_mesh_plan_t* p, const void* workspace, const int32_t* lists, int64_t capacity) {
+  if (!mesh_plan_ok(p) || capacity < 0) return false;
+  return p->n_tri == 0 || (workspace && !((uintptr_t)workspace & 15u) && (capacity == 0 || lists));
+}
+
+int miso_mesh_closest(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                      const miso_mesh_plan_t* plan_far, const void* workspace_far, const int32_t* lists_far, int64_t capacity_far,
+                      const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri, float* out_vw, int64_t* stats,
+                      void* stream) {
+  if (!mesh_index_ok(plan, workspace, lists, capacity) || ld_p < 3 || n < 0 || ((uintptr_t)stats & 7u) || ((uintptr_t)out_vw & 7u))
+    return MISO_E_BADARG;
+  // the far set is one more index of the SAME triangles (the kernel reads the rows of the first), or absent as a whole
+  if (plan_far ? (!mesh_index_ok(plan_far, workspace_far, lists_far, capacity_far) || plan_far->n_tri != plan->n_tri || plan_far->reserved < 0)
+               : (workspace_far || lists_far || capacity_far != 0))
+    return MISO_E_BADARG;
+  if (n >= ((int64_t)1 << 31) || capacity > MISO_MESH_MAX_ENTRIES || capacity_far > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
+  if (n > 0 && (!pts || !out_d2 || !out_tri)) return MISO_E_BADARG;
+  return (int)launch_mesh_closest(*plan, workspace, lists, capacity, plan_far, workspace_far, lists_far, capacity_far, pts, ld_p, n,
+                                  out_d2, out_tri, out_vw, stats, (hipStream_t)stream);
+}
+
+int miso_mesh_closest_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri,
+                          const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri, float* out_vw, void* stream) {
+  if (n_vert < 0 || n_tri < 0 || n < 0 || ld_v < 3 || ld_t < 3 || ld_p < 3 || ((uintptr_t)out_vw & 7u)) return MISO_E_BADARG;
+  if (n_tri >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if ((n_tri > 0 && (!tris || (n_vert > 0 && !verts))) || (n > 0 && (!pts || !out_d2 || !out_tri))) return MISO_E_BADARG;
+  return (int)launch_mesh_closest_all(verts, ld_v, n_vert, tris, ld_t, n_tri, pts, ld_p, n, out_d2, out_tri, out_vw, (hipStream_t)stream);
+}
+
+int miso_mesh_count_hits(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                         const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min, float t_max,
+                         int32_t* out_count, void* stream) {
+  if (!mesh_index_ok(plan, workspace, lists, capacity) || ld_o < 3 || ld_d < 3 || n < 0) return MISO_E_BADARG;
+  if (n >= ((int64_t)1 << 31) || capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
+  if (n > 0 && (!origins || !dirs || !out_count)) return MISO_E_BADARG;
+  return (int)launch_mesh_count_hits(*plan, workspace, lists, capacity, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_count,
+                                     (hipStream_t)stream);
+}
+
+int miso_mesh_count_hits_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri,
+                             const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min,
+                             float t_max, int32_t* out_count, void* stream) {
+  if (n_vert < 0 || n_tri < 0 || n < 0 || ld_v < 3 || ld_t < 3 || ld_o < 3 || ld_d < 3) return MISO_E_BADARG;
+  if (n_tri >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if ((n_tri > 0 && (!tris || (n_vert > 0 && !verts))) || (n > 0 && (!origins || !dirs || !out_count))) return MISO_E_BADARG;
+  return (int)launch_mesh_count_hits_all(verts, ld_v, n_vert, tris, ld_t, n_tri, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_count,
+                                         (hipStream_t)stream);
+}
+
 // ---- fused atlas query (atlas.hip) ------------------------------------------------------------------------------------
 int64_t miso_atlas_plan_bytes(int32_t n_submaps) {
   return n_submaps < 1 ? 0 : (int64_t)n_submaps * (int64_t)sizeof(GridK);

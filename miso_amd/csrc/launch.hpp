@@ -192,4 +192,19 @@ hipError_t launch_mesh_cast_rays_all(const float* verts, int64_t ld_v, int64_t n
                                      int64_t n_tri, const float* org, int64_t ld_o, const float* dir, int64_t ld_d, int64_t n,
                                      float t_min, float t_max, float* out_t, int64_t* out_tri, hipStream_t s);
 
+// ---- mesh_sdf.hip (plan_far: null = the fine index only)
+hipError_t launch_mesh_closest(const miso_mesh_plan_t& plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                               const miso_mesh_plan_t* plan_far, const void* workspace_far, const int32_t* lists_far,
+                               int64_t capacity_far, const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri,
+                               float* out_vw, int64_t* stats, hipStream_t s);
+hipError_t launch_mesh_closest_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri,
+                                   const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri, float* out_vw,
+                                   hipStream_t s);
+hipError_t launch_mesh_count_hits(const miso_mesh_plan_t& plan, const void* workspace, const int32_t* lists, int64_t capacity,
+                                  const float* org, int64_t ld_o, const float* dir, int64_t ld_d, int64_t n, float t_min, float t_max,
+                                  int32_t* out_count, hipStream_t s);
+hipError_t launch_mesh_count_hits_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t,
+                                      int64_t n_tri, const float* org, int64_t ld_o, const float* dir, int64_t ld_d, int64_t n,
+                                      float t_min, float t_max, int32_t* out_count, hipStream_t s);
+
 }  // namespace miso

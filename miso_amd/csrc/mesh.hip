@@ -12,7 +12,8 @@
 //          the rounding of n) of the triangle's plane: a plane-slab test, conservative.
 //          A wavefront per triangle, its lanes striding over the box: a triangle with two million box cells keeps 64
 //          lanes busy and no lane waits for another's loop.
-// Query (miso_mesh_cast_rays), a lane per ray: clip to the widened box, walk the cells by a 3-D DDA whose boundaries
+// Query (miso_mesh_cast_rays), a lane per ray, the walk itself being mesh.hpp's mesh_walk_ray (mesh_sdf.hip counts
+// crossings with it): clip to the widened box, walk the cells by a 3-D DDA whose boundaries
 // are recomputed from the cell index at every step (no accumulated increment), offer every listed triangle of a cell
 // wherever on the ray its hit lies, stop when best.t < the parameter at which the ray leaves the cell.  The rounding
 // slack sits in the lists (w), not in the stop test: section 4.15 shows why that is enough for origins within 4 coord_mag
@@ -27,8 +28,6 @@
 
 namespace miso {
 namespace {
-
-constexpr int MESH_TILE = 512;                                      // triangles per LDS tile of the all-triangles kernel (24 KB)
 
 __global__ __launch_bounds__(256) void mesh_rows_kernel(const float* __restrict__ verts, int64_t ld_v, int64_t n_vert,
                                                         const int64_t* __restrict__ tris, int64_t ld_t, int n_tri,
@@ -81,11 +80,6 @@ __global__ __launch_bounds__(256) void mesh_bin_kernel(MeshK k, const float4* __
   }
 }
 
-__device__ __forceinline__ MeshTri mesh_load(const float4* __restrict__ rows, int tri) {
-  const float4* r = rows + 3 * (int64_t)tri;
-  return mesh_unpack(r[0], r[1], r[2]);
-}
-
 // stats (STATS): {cells visited, triangles offered, rays answered from all rows}
 template <bool STATS>
 __global__ __launch_bounds__(256) void mesh_cast_rays_kernel(MeshK k, const int* __restrict__ table, const int* __restrict__ lists,
@@ -95,62 +89,17 @@ __global__ __launch_bounds__(256) void mesh_cast_rays_kernel(MeshK k, const int*
                                                              int64_t* __restrict__ out_tri, unsigned long long* __restrict__ stats) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float inf = __builtin_huge_valf();
   const float o[3] = {org[i * ld_o], org[i * ld_o + 1], org[i * ld_o + 2]};
   const float d[3] = {dir[i * ld_d], dir[i * ld_d + 1], dir[i * ld_d + 2]};
-  RayBest b = {inf, -1};
+  RayBest b = {__builtin_huge_valf(), -1};
   unsigned visited = 0, offered = 0;
-  bool walk = nn_finite3(o[0], o[1], o[2]) && nn_finite3(d[0], d[1], d[2]), miss = false;
-  float inv[3], t0 = t_min, t1 = t_max;
-  int step[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float lo = k.lo[a] - k.widen, hi = (k.lo[a] + (float)k.dims[a] * k.cell) + k.widen;
-    if (!(fabsf(o[a]) <= 4.0f * k.mag)) walk = false;
-    inv[a] = 0.0f; step[a] = 0;
-    if (d[a] == 0.0f) {
-      if (o[a] < lo || o[a] > hi) miss = true;
-    } else {
-      inv[a] = __fdiv_rn(1.0f, d[a]);
-      if (!(fabsf(inv[a]) < inf)) walk = false;
-      step[a] = d[a] > 0.0f ? 1 : -1;
-      const float ta = (lo - o[a]) * inv[a], tb = (hi - o[a]) * inv[a];
-      t0 = fmaxf(t0, fminf(ta, tb)); t1 = fminf(t1, fmaxf(ta, tb));
-    }
-  }
-  if ((step[0] | step[1] | step[2]) == 0) miss = true;             // a zero direction: det == 0 for every triangle
-  if (!(fabsf(t0) < inf) || t1 != t1) walk = false;
-  if (!walk) {
-    for (int t = 0; t < k.n_tri; ++t) b.take(o, d, t_min, t_max, mesh_load(rows, t), t);
-    if (STATS) { offered = (unsigned)k.n_tri; atomicAdd(&stats[2], 1ull); }
-  } else if (!miss && t0 <= t1) {
-    int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) c[a] = nn_cell_axis(o[a] + t0 * d[a], k.lo[a], k.cell, k.dims[a]);
-    const int cap = (int)(k.capacity < 0x7fffffff ? k.capacity : 0x7fffffff);
-    const int max_steps = k.dims[0] + k.dims[1] + k.dims[2] + 3;
-    for (int it = 0; it < max_steps; ++it) {
-      const int cell = (c[2] * k.dims[1] + c[1]) * k.dims[0] + c[0];
-      const int s = table[cell], e = min(table[cell + 1], cap);     // clamped: a table no build wrote stays inside the lists
-      for (int j = max(s, 0); j < e; ++j) {
-        const int tri = lists[j];
-        if ((unsigned)tri < (unsigned)k.n_tri) b.take(o, d, t_min, t_max, mesh_load(rows, tri), tri);
-      }
-      if (STATS) { ++visited; offered += (unsigned)max(e - max(s, 0), 0); }
-      // where the ray leaves the cell: per axis the plane ahead, from the cell index (monotone in it, no running sum)
-      float tm[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-        tm[a] = step[a] == 0 ? inf : ((k.lo[a] + (float)(c[a] + (step[a] > 0 ? 1 : 0)) * k.cell) - o[a]) * inv[a];
-      const float t_out = fminf(tm[0], fminf(tm[1], tm[2]));
-      if (b.t < t_out || t_out > t1 || !(t_out < inf)) break;
-      const int a = tm[0] == t_out ? 0 : (tm[1] == t_out ? 1 : 2);
-      c[a] += step[a];
-      if (c[a] < 0 || c[a] >= k.dims[a]) break;
-    }
-  }
+  bool all_rows;
+  mesh_walk_ray<STATS>(k, table, lists, rows, o, d, t_min, t_max, b, visited, offered, all_rows);
   out_t[i] = b.t; out_tri[i] = (int64_t)b.tri;
-  if (STATS) { atomicAdd(&stats[0], (unsigned long long)visited); atomicAdd(&stats[1], (unsigned long long)offered); }
+  if (STATS) {
+    atomicAdd(&stats[0], (unsigned long long)visited); atomicAdd(&stats[1], (unsigned long long)offered);
+    if (all_rows) atomicAdd(&stats[2], 1ull);
+  }
 }
 
 __global__ __launch_bounds__(256) void mesh_cast_rays_all_kernel(const float* __restrict__ verts, int64_t ld_v, int64_t n_vert,
@@ -167,14 +116,7 @@ __global__ __launch_bounds__(256) void mesh_cast_rays_all_kernel(const float* __
     for (int a = 0; a < 3; ++a) { o[a] = org[i * ld_o + a]; d[a] = dir[i * ld_d + a]; }
   }
   RayBest b = {__builtin_huge_valf(), -1};
-  for (int t0 = 0; t0 < n_tri; t0 += MESH_TILE) {
-    const int len = n_tri - t0 < MESH_TILE ? n_tri - t0 : MESH_TILE;
-    __syncthreads();                                                // the readers of the previous tile
-    for (int j = threadIdx.x; j < len; j += 256) mesh_make_row(verts, ld_v, n_vert, tris, ld_t, (int64_t)t0 + j, tile + 3 * j);
-    __syncthreads();
-    for (int j = 0; j < len; ++j)                                   // one address per wavefront: a broadcast
-      b.take(o, d, t_min, t_max, mesh_unpack(tile[3 * j], tile[3 * j + 1], tile[3 * j + 2]), t0 + j);
-  }
+  mesh_for_tiles(tile, verts, ld_v, n_vert, tris, ld_t, n_tri, [&](const MeshTri& m, int t) { b.take(o, d, t_min, t_max, m, t); });
   if (live) { out_t[i] = b.t; out_tri[i] = (int64_t)b.tri; }
 }
 

@@ -61,16 +61,23 @@ __device__ __forceinline__ bool nn_finite3(float x, float y, float z) {
 // are below u (4.1 A + g); the test takes 8 u (A + g) = 2^-21 (A + g) off g, which also covers the roundings of the test
 // itself, and 16 u = 2^-20 (relative) off its square.  The comparison is strict: a target left out has a computed d2
 // above `best`, so it loses whatever its index.
-__device__ __forceinline__ bool ring_finished(const NnK& k, const float q[3], const int c[3], int r, float best) {
+// g of the text above for any grid struct with lo, cell and dims (NnK; mesh.hpp's MeshK): +inf when the box is the grid
+template <class K>
+__device__ __forceinline__ float ring_gap(const K& k, const float q[3], const int c[3], int r) {
 #pragma clang fp contract(off)
-  const float inf = __builtin_huge_valf();
-  float g = inf;
+  float g = __builtin_huge_valf();
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     if (c[a] - r > 0) g = fminf(g, q[a] - (k.lo[a] + (float)(c[a] - r) * k.cell));
     if (c[a] + r < k.dims[a] - 1) g = fminf(g, (k.lo[a] + (float)(c[a] + r + 1) * k.cell) - q[a]);
   }
-  if (g == inf) return true;                      // the box is the grid
+  return g;
+}
+
+__device__ __forceinline__ bool ring_finished(const NnK& k, const float q[3], const int c[3], int r, float best) {
+#pragma clang fp contract(off)
+  const float g = ring_gap(k, q, c, r);
+  if (g == __builtin_huge_valf()) return true;    // the box is the grid
   const float gs = g - 0x1p-21f * (k.mag + g);
   if (!(gs > 0.0f)) return false;
   return best < (gs * gs) * (1.0f - 0x1p-20f);
@@ -91,7 +98,8 @@ __device__ __forceinline__ void nn_visit_run(const int* table, const float4* row
 // (a list shorter than k), which finishes only when the box is the grid.  The loops over r, z and y stay in the kernels,
 // and the query goes down as three scalars (profiles/nn_shared_walk.json holds the reasons).
 struct NnShell { int lo[3], hi[3]; };
-__device__ __forceinline__ NnShell nn_shell(const NnK& k, const int c[3], int r) {
+template <class K>
+__device__ __forceinline__ NnShell nn_shell(const K& k, const int c[3], int r) {
   return {{max(c[0] - r, 0), max(c[1] - r, 0), max(c[2] - r, 0)},
           {min(c[0] + r, k.dims[0] - 1), min(c[1] + r, k.dims[1] - 1), min(c[2] + r, k.dims[2] - 1)}};
 }

@@ -1,19 +1,22 @@
-"""SDF samples from simulated camera views of a mesh (reference: grid_opt/datasets/sdf_3d.py:157-383, :449-495).
+"""SDF samples of a mesh (reference: grid_opt/datasets/sdf_3d.py): ``Sdf3D`` / ``BatchedSdf3D`` (:17-155, :417-447), samples
+everywhere in the volume labelled with the mesh's signed distance, and ``PosedSdf3D`` / ``BatchPosedSdf3D`` (:157-383,
+:449-495), samples along the rays of simulated camera views.
 
-``PosedSdf3D`` places ``num_frames`` pin-hole cameras (90 degrees, 640 x 480) in a mesh, casts one ray per pixel and
-labels samples along the rays; the reference does the casting with Open3D's RaycastingScene and the labelling with pysdf.
-Here the rays of a frame go through ONE cast -- ``ops.MeshIndex.cast_rays`` (csrc/mesh.hip) on a HIP device,
-``utils_geometry.cast_rays_torch`` on the CPU -- and parts I-III of ``sample_frames`` run on that device.  The random
-draws come from numpy's global generator on the host, in the reference's order, and are then moved: the CPU and the
-device route draw the same numbers from the same seed.
+The reference gets the signed distance from pysdf and the ray casts from Open3D's RaycastingScene.  Here both come from
+the mesh index: ``utils_sdf.MeshSdf`` (``ops.MeshIndex.closest`` / ``contains``, csrc/mesh_sdf.hip, on a HIP device;
+``utils_geometry.closest_on_mesh_torch`` / ``count_crossings_torch`` on the CPU) is the pysdf-shaped callable, positive
+inside, and the rays of a frame go through ONE cast (``ops.MeshIndex.cast_rays`` / ``utils_geometry.cast_rays_torch``).
+The random draws come from numpy's global generator on the host, in the reference's order, and are then moved: the CPU
+and the device route draw the same numbers from the same seed.  (``Sdf3D``'s surface samples come from
+``utils_eval.sample_points_from_mesh``, seeded from that generator: not trimesh's stream.)
 
-pysdf (signed distance to the mesh) is not restated; it enters the reference twice:
-  * cameras are placed where sdf > 0.3 (:193-199).  Give ``sdf_fn`` (points (N, 3) numpy -> (N,) distances, positive
-    outside, pysdf's call) and that loop runs; give ``frame_poses`` = (R (F, 3, 3), t (F, 3, 1)) and they are used; with
-    neither the constructor raises.
-  * hit points are labelled sdf_fn(point) (:252).  Without ``sdf_fn`` they are labelled 0 and valid: they lie on the
-    surface up to the cast's rounding, which is what pysdf returns there up to its own.
-``Sdf3D`` / ``BatchedSdf3D`` sample pysdf everywhere in the volume and are not built."""
+``PosedSdf3D`` meets the signed distance twice:
+  * cameras are placed where sdf > 0.3 (:193-199).  ``sdf_fn='mesh'`` runs that loop against the dataset's own mesh; a
+    callable ``sdf_fn`` (points (N, 3) numpy -> (N,) distances, positive inside, pysdf's call) against the caller's;
+    ``frame_poses`` = (R (F, 3, 3), t (F, 3, 1)) are used as given; with none of the three the constructor raises.
+  * hit points are labelled sdf_fn(point) (:252): with 'mesh' on the device, no host round trip.  Without ``sdf_fn`` they
+    are labelled 0 and valid: they lie on the surface up to the cast's rounding.
+``visualize_open3d`` is left out, as elsewhere."""
 import logging
 import os
 
@@ -22,14 +25,113 @@ import torch
 from torch.utils.data import Dataset
 
 from miso_amd.grid_opt.utils import utils_geometry, utils_sample
-from miso_amd.grid_opt.utils.utils_sdf import TriangleMesh, read_ply
+from miso_amd.grid_opt.utils.utils_sdf import MeshSdf, TriangleMesh, read_ply
 
 logger = logging.getLogger(__name__)
 
 
+class Sdf3D(Dataset):
+    """Samples with the true signed distance everywhere: on the surface, in free space and inside (reference :17-155).
+    The reference's arguments, and ``device`` of the samples and batches.  Of ``total_samples`` (a multiple of 8) the first
+    half lies on the surface and is labelled 0 without a query, three eighths are surface samples moved by a Gaussian of
+    ``surface_stddev``, one eighth is uniform in the bound; the SDF is MeshSdf's, positive inside, not negated, as there.
+    ``trunc_dist``: a sample is valid while |sdf| < trunc_dist, and beyond it only the sign is kept (sdf_sign = +-1)."""
+
+    def __init__(self, meshfile, batch_size=2 ** 16, total_samples=2 ** 20, normalize=False, surface_stddev=0.1, bound_buffer=0.5,
+                 trunc_dist=None, *, device='cuda:0'):
+        super().__init__()
+        self.meshfile = meshfile
+        mesh = meshfile if isinstance(meshfile, TriangleMesh) else read_ply(os.fspath(meshfile))
+        v = np.asarray(mesh.vertices, dtype=np.float64)
+        self.normalize = normalize
+        if normalize:                                           # into [-1, 1]: centre of the box, 0.95 of its diagonal
+            vmin, vmax = v.min(axis=0), v.max(axis=0)
+            self.v_scale = 2.0 / np.sqrt(np.sum((vmax - vmin) ** 2)) * 0.95
+            mesh = TriangleMesh((v - (vmin + vmax)[None, :] / 2.0) * self.v_scale, mesh.triangles)
+            self.bound = np.array([[-1.0, 1.0]] * 3)
+            self.surface_stddev = 0.01
+        else:
+            self.bound = np.stack([v.min(axis=0) - bound_buffer, v.max(axis=0) + bound_buffer], axis=1)     # (3, 2)
+            self.surface_stddev = surface_stddev
+        self.mesh = mesh
+        if not _is_watertight(mesh.triangles):
+            logger.warning("the mesh is not closed (some edge is not shared by exactly two triangles): the sign of its "
+                           "distance is a crossing parity and may be wrong")
+        self.device = torch.device(device)
+        self.sdf_fn = MeshSdf(mesh.vertices, mesh.triangles, device=self.device)
+        self.total_samples, self.batch_size, self.trunc_dist = total_samples, batch_size, trunc_dist
+        assert self.total_samples % 8 == 0, "total_samples must be divisible by 8."
+        self.resample()
+
+    def __len__(self):
+        return self.total_samples // self.batch_size + 1
+
+    def _sample_uniformly(self, k):
+        return np.stack([np.random.uniform(self.bound[a, 0], self.bound[a, 1], k) for a in range(3)], axis=1)
+
+    def resample(self):
+        from miso_amd.grid_opt.utils import utils_eval
+        n, half = self.total_samples, self.total_samples // 2
+        surface = utils_eval.sample_points_from_mesh(self.mesh, n * 7 // 8, voxel_down_sample_res=0.0,
+                                                     seed=int(np.random.randint(0, 2 ** 31 - 1)))
+        surface[half:] += self.surface_stddev * np.random.randn(n * 3 // 8, 3)
+        points = np.concatenate([surface, self._sample_uniformly(n // 8)], axis=0).astype(np.float32)
+        self.coords = torch.from_numpy(points).to(self.device)
+        sdfs = torch.zeros((n, 1), dtype=torch.float32, device=self.device)
+        sdfs[half:, 0] = self.sdf_fn.on_device(self.coords[half:])
+        finite = sdfs.abs() < 1e10                              # (a mesh without a triangle answers +inf)
+        valid, signs = finite, torch.zeros_like(sdfs)
+        if self.trunc_dist is not None:
+            assert self.trunc_dist > 0
+            valid = sdfs.abs() < self.trunc_dist
+            signs = torch.where(finite & (sdfs > self.trunc_dist), 1.0, 0.0) - torch.where(finite & (sdfs < -self.trunc_dist), 1.0, 0.0)
+        self.sdfs, self.sdf_valid, self.sdf_signs = sdfs, valid.float(), signs.float()
+
+    def __getitem__(self, idx):
+        pick = torch.from_numpy(np.random.choice(self.total_samples, size=self.batch_size)).to(self.device)
+        return {'coords': self.coords[pick]}, {'sdf': self.sdfs[pick], 'sdf_valid': self.sdf_valid[pick],
+                                               'sdf_sign': self.sdf_signs[pick]}
+
+    def get_inflated_bound(self):
+        assert not self.normalize
+        return self.bound
+
+
+def _is_watertight(triangles) -> bool:
+    """every undirected edge belongs to exactly two triangles"""
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    if not len(t):
+        return False
+    edges = np.sort(np.concatenate([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]]), axis=1)
+    return bool((np.unique(edges, axis=0, return_counts=True)[1] == 2).all())
+
+
+class BatchedSdf3D(Dataset):
+    """A collection of Sdf3D datasets, one per mesh (reference :417-447); a batch comes from one of them at random and
+    carries its ``dataset_index``."""
+
+    def __init__(self, filelist, batch_size=2 ** 16, total_samples=2 ** 20, normalize=False, surface_stddev=0.1, trunc_dist=None,
+                 *, device='cuda:0'):
+        super().__init__()
+        self.num_datasets = len(filelist)
+        self.datasets = [Sdf3D(meshfile, batch_size=batch_size, total_samples=total_samples, normalize=normalize,
+                               surface_stddev=surface_stddev, trunc_dist=trunc_dist, device=device) for meshfile in filelist]
+        self.len = sum(len(d) for d in self.datasets)
+
+    def __len__(self):
+        return self.len
+
+    def __getitem__(self, idx):
+        dataset_index = np.random.choice(self.num_datasets, size=1)[0]
+        dataset = self.datasets[dataset_index]
+        input_dict, gt_dict = dataset[np.random.choice(len(dataset), size=1)[0]]
+        input_dict['dataset_index'] = torch.tensor(dataset_index).long()
+        return input_dict, gt_dict
+
+
 class PosedSdf3D(Dataset):
     """A SDF dataset obtained by simulating random camera views (reference :157-383).  The reference's arguments, and:
-    ``device`` of the frames and batches; ``frame_poses`` / ``sdf_fn`` (module docstring); ``meshfile`` may be a
+    ``device`` of the frames and batches; ``frame_poses`` / ``sdf_fn`` (module docstring: 'mesh', a callable or None); ``meshfile`` may be a
     TriangleMesh; ``fov_deg`` / ``width_px`` / ``height_px`` of the simulated camera (the reference hard-wires 90, 640, 480)."""
 
     def __init__(self, meshfile, frame_batchsize=2 ** 14, frame_samples=2 ** 14, num_frames=64, near_surface_n=2,
@@ -44,9 +146,13 @@ class PosedSdf3D(Dataset):
         self.near_surface_std, self.near_surface_n = near_surface_std, near_surface_n
         self.free_space_n, self.trunc_dist = free_space_n, trunc_dist
         self.frame_std_rad, self.frame_std_meter, self.distance_std = frame_std_rad, frame_std_meter, distance_std
-        self.sdf_fn = sdf_fn
         self.frame_samples, self.frame_batchsize = frame_samples, frame_batchsize
         self.device = torch.device(device)
+        if isinstance(sdf_fn, str):
+            if sdf_fn != 'mesh':
+                raise ValueError(f"sdf_fn = {sdf_fn!r}: 'mesh' (the dataset's own mesh), a callable, or None")
+            sdf_fn = MeshSdf(self.mesh.vertices, self.mesh.triangles, device=self.device)
+        self.sdf_fn = sdf_fn
         self.fov_deg, self.width_px, self.height_px = float(fov_deg), int(width_px), int(height_px)
         if frame_poses is not None:
             R, t = frame_poses
@@ -67,8 +173,9 @@ class PosedSdf3D(Dataset):
             self.t_world_frame_gt = torch.from_numpy(t_gt).float()
         else:
             raise ValueError("PosedSdf3D places its cameras where the mesh's signed distance exceeds 0.3, and the signed "
-                             "distance to a mesh (pysdf in the reference) is not built here: give frame_poses=(R, t), or "
-                             "sdf_fn, a callable returning the mesh signed distance of (N, 3) points")
+                             "distance to a mesh (pysdf in the reference) is not built here unless asked for: give "
+                             "sdf_fn='mesh', frame_poses=(R, t), or sdf_fn, a callable returning the mesh signed distance "
+                             "of (N, 3) points")
         self.R_world_frame_gt = self.R_world_frame_gt.to(self.device)
         self.t_world_frame_gt = self.t_world_frame_gt.to(self.device)
         self.sample_frames()
@@ -83,7 +190,8 @@ class PosedSdf3D(Dataset):
         tris = torch.as_tensor(np.asarray(self.mesh.triangles), dtype=torch.int64, device=self.device)
         if self.device.type == 'cuda':
             from miso_amd import ops
-            index = ops.MeshIndex(verts, tris)
+            own = isinstance(self.sdf_fn, MeshSdf) and isinstance(self.sdf_fn.mesh, ops.MeshIndex)
+            index = self.sdf_fn.mesh if own else ops.MeshIndex(verts, tris)       # sdf_fn='mesh': one index for both
             return lambda rays: index.cast_rays(rays[:, :3], rays[:, 3:])[0]
         chunk = max(1, min(4096, (1 << 22) // max(int(tris.shape[0]), 1)))
         return lambda rays: utils_geometry.cast_rays_torch(rays[:, :3], rays[:, 3:], verts, tris, chunk=chunk)[0]
@@ -109,7 +217,10 @@ class PosedSdf3D(Dataset):
             n_keep = min(self.frame_samples, n_hit)
             keep = hit[torch.from_numpy(np.random.permutation(n_hit)[:n_keep]).to(self.device)]
             points_gt = rays[keep, :3] + rays[keep, 3:] * t_hit[keep, None]
-            if self.sdf_fn is not None:
+            if isinstance(self.sdf_fn, MeshSdf):                # labelled where the points are
+                sdfs = self.sdf_fn.on_device(points_gt.contiguous()).reshape(-1, 1)
+                sdfs_valid = (sdfs.abs() < 1e10).float()
+            elif self.sdf_fn is not None:
                 sdfs = self._draw(np.asarray(self.sdf_fn(points_gt.cpu().numpy()), dtype=np.float32).reshape(-1, 1))
                 sdfs_valid = (sdfs.abs() < 1e10).float()
             else:                                               # on the surface: 0 and valid (module docstring)
@@ -194,7 +305,7 @@ class PosedSdf3D(Dataset):
 
 class BatchPosedSdf3D(Dataset):
     """A collection of PosedSdf3D datasets, one per mesh (reference :449-495).  ``frame_poses`` / ``sdf_fn``: one entry per
-    mesh, or None."""
+    mesh, or None; ``sdf_fn='mesh'``: every dataset's own mesh."""
 
     def __init__(self, filelist, frame_batchsize=2 ** 14, frame_samples=2 ** 14, num_frames=64, near_surface_n=2,
                  near_surface_std=0.05, free_space_n=1, trunc_dist=0.15, frame_std_rad=0.0, frame_std_meter=0.0,
@@ -209,7 +320,7 @@ class BatchPosedSdf3D(Dataset):
                                  trunc_dist=trunc_dist, frame_std_rad=frame_std_rad, frame_std_meter=frame_std_meter,
                                  distance_std=distance_std, device=device,
                                  frame_poses=None if frame_poses is None else frame_poses[i],
-                                 sdf_fn=None if sdf_fn is None else sdf_fn[i], **camera)
+                                 sdf_fn=sdf_fn if sdf_fn is None or isinstance(sdf_fn, str) else sdf_fn[i], **camera)
             self.len += len(dataset)
             self.datasets.append(dataset)
         self.getitem_count = 0

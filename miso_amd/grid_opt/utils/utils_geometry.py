@@ -290,3 +290,91 @@ def cast_rays_torch(origins, dirs, vertices, triangles, t_min=0.0, t_max=float('
         out_t[a:a + chunk] = best
         out_i[a:a + chunk] = torch.where(first == big, torch.full_like(first, -1), first)
     return out_t, out_i
+
+
+def _hittable_rows(vertices, triangles, dt, dev):
+    """v0, e1, e2 (T, 3) of the triangles and which of them can be hit (the rule of cast_rays_torch)"""
+    nv = int(vertices.shape[0])
+    triangles = triangles.to(device=dev, dtype=torch.int64)
+    vertices = vertices.to(device=dev, dtype=dt)
+    ok = ((triangles >= 0) & (triangles < nv)).all(dim=1)
+    v = vertices[triangles.clamp(0, nv - 1)]
+    v0, e1, e2 = v[:, 0], v[:, 1] - v[:, 0], v[:, 2] - v[:, 0]
+    nrm = _cross3(e1, e2)
+    ok &= torch.isfinite(v).all(dim=2).all(dim=1) & torch.isfinite(nrm).all(dim=1) & (nrm != 0).any(dim=1)
+    return v0, e1, e2, ok
+
+
+def closest_on_mesh_torch(points, vertices, triangles, chunk=1024):
+    """The closest triangle of every point as chunked torch ops on any device: the formula of the HIP kernels
+    (csrc/mesh.hpp: TriBest::take -- the region-classified closest point of a triangle: three vertex regions, three edge
+    regions, interior -- and the smallest (d2, triangle index) pair) in the dtype of ``points``.
+    -> (d2 (N,) squared distance, tri (N,) int64, vw (N, 2): the closest point is v0 + v (v1 - v0) + w (v2 - v0));
+    (+inf, -1, (0, 0)) without a triangle.  A triangle that cast_rays_torch never hits is never the answer, nor is anything
+    for a non-finite point.  ``chunk`` points at a time against all triangles."""
+    dt, dev = points.dtype, points.device
+    n, nt, nv = int(points.shape[0]), int(triangles.shape[0]), int(vertices.shape[0])
+    out_d = torch.full((n,), float('inf'), dtype=dt, device=dev)
+    out_i = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    out_vw = torch.zeros((n, 2), dtype=dt, device=dev)
+    if n == 0 or nt == 0 or nv == 0:
+        return out_d, out_i, out_vw
+    v0, e1, e2, ok = _hittable_rows(vertices, triangles, dt, dev)
+    a1, a2 = e1[None], e2[None]
+    big = torch.iinfo(torch.int64).max
+    index = torch.arange(nt, device=dev)
+    zero, one = torch.zeros((), dtype=dt, device=dev), torch.ones((), dtype=dt, device=dev)
+    inf = torch.full((), float('inf'), dtype=dt, device=dev)
+    for a in range(0, n, max(int(chunk), 1)):
+        ap = points[a:a + chunk, None, :] - v0[None]
+        bp, cp = ap - a1, ap - a2
+        d1, d2, d3, d4, d5, d6 = _dot3(a1, ap), _dot3(a2, ap), _dot3(a1, bp), _dot3(a2, bp), _dot3(a1, cp), _dot3(a2, cp)
+        vc, vb, va = d1 * d4 - d3 * d2, d5 * d2 - d1 * d6, d3 * d6 - d5 * d4
+        den = 1.0 / ((va + vb) + vc)
+        # the interior, then the six regions from the last to the first, so that the first that holds decides
+        v = torch.fmin(torch.fmax(vb * den, zero), one)
+        w = torch.fmin(torch.fmax(vc * den, zero), one - v)
+        w_bc = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+        for cond, rv, rw in (((va <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0), one - w_bc, w_bc),
+                             ((vb <= 0) & (d2 >= 0) & (d6 <= 0), zero, d2 / (d2 - d6)),
+                             ((d6 >= 0) & (d5 <= d6), zero, one),
+                             ((vc <= 0) & (d1 >= 0) & (d3 <= 0), d1 / (d1 - d3), zero),
+                             ((d3 >= 0) & (d4 <= d3), one, zero),
+                             ((d1 <= 0) & (d2 <= 0), zero, zero)):
+            v, w = torch.where(cond, rv, v), torch.where(cond, rw, w)
+        r = ap - (v[..., None] * a1 + w[..., None] * a2)
+        n2 = (r[..., 0] * r[..., 0] + r[..., 1] * r[..., 1]) + r[..., 2] * r[..., 2]
+        n2 = torch.where(ok[None] & ~torch.isnan(n2), n2, inf)
+        best = n2.amin(dim=1)
+        first = torch.where((n2 == best[:, None]) & (n2 < inf), index[None], big).amin(dim=1)
+        won = first != big
+        pick = torch.where(won, first, torch.zeros_like(first))[:, None]
+        out_d[a:a + chunk] = best
+        out_i[a:a + chunk] = torch.where(won, first, torch.full_like(first, -1))
+        out_vw[a:a + chunk, 0] = torch.where(won, v.gather(1, pick)[:, 0], zero)
+        out_vw[a:a + chunk, 1] = torch.where(won, w.gather(1, pick)[:, 0], zero)
+    return out_d, out_i, out_vw
+
+
+def count_crossings_torch(origins, dirs, vertices, triangles, t_min=0.0, t_max=float('inf'), chunk=4096):
+    """How many triangles every ray origins[i] + t dirs[i] crosses with t_min <= t <= t_max, by cast_rays_torch's hit test,
+    as chunked torch ops on any device -> (N,) int32.  A ray through an edge two triangles share counts both."""
+    dt, dev = origins.dtype, origins.device
+    n, nt, nv = int(origins.shape[0]), int(triangles.shape[0]), int(vertices.shape[0])
+    out = torch.zeros((n,), dtype=torch.int32, device=dev)
+    if n == 0 or nt == 0 or nv == 0:
+        return out
+    v0, e1, e2, ok = _hittable_rows(vertices, triangles, dt, dev)
+    for a in range(0, n, max(int(chunk), 1)):
+        o, d = origins[a:a + chunk, None, :], dirs[a:a + chunk, None, :].to(dt)
+        p = _cross3(d, e2[None])
+        det = _dot3(e1[None], p)
+        inv = 1.0 / det
+        s = o - v0[None]
+        u = _dot3(s, p) * inv
+        q = _cross3(s, e1[None])
+        w = _dot3(d, q) * inv
+        t = _dot3(e2[None], q) * inv
+        hit = ok[None] & (det != 0) & (u >= 0) & (w >= 0) & (u + w <= 1) & (t >= t_min) & (t <= t_max)
+        out[a:a + chunk] = hit.sum(dim=1).to(torch.int32)
+    return out

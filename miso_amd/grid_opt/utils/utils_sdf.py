@@ -369,6 +369,65 @@ def mesh_cast_rays(mesh, origins, dirs, t_min=0.0, t_max=float('inf')):
     return t, tri, normals_of
 
 
+def _mesh_inside_and_distance(mesh, points):
+    """-> (distance (N,) >= 0, inside (N,) bool) of ``points`` (N, 3) fp32 against ``mesh``, by the route of their device:
+    an ops.MeshIndex or a HIP tensor goes to MeshIndex.closest / contains (csrc/mesh_sdf.hip), a CPU tensor to
+    utils_geometry.closest_on_mesh_torch / count_crossings_torch with the same three parity directions."""
+    from miso_amd import ops
+    from miso_amd.grid_opt.utils import utils_geometry
+    if not isinstance(mesh, ops.MeshIndex) and points.is_cuda:
+        mesh = ops.MeshIndex(*_mesh_arrays(mesh, points.device))
+    if isinstance(mesh, ops.MeshIndex):
+        return mesh.closest(points)[0].sqrt(), mesh.contains(points)
+    verts, tris = _mesh_arrays(mesh, points.device)
+    n = int(points.shape[0])
+    chunk = max(1, min(4096, (1 << 21) // max(int(tris.shape[0]), 1)))
+    d = utils_geometry.closest_on_mesh_torch(points, verts, tris, chunk=chunk)[0].sqrt()
+    dirs = torch.tensor(ops.MESH_PARITY_DIRS, dtype=points.dtype, device=points.device)
+    odd = utils_geometry.count_crossings_torch(points.repeat(3, 1), dirs.repeat_interleave(n, dim=0), verts, tris,
+                                               chunk=chunk).view(3, n) & 1
+    return d, odd.sum(dim=0) >= 2
+
+
+def mesh_signed_distance(mesh, points, inside_positive=True):
+    """Signed distance from ``points`` (N, 3) fp32 to ``mesh`` -- an ops.MeshIndex, or a TriangleMesh / PLY path -- routed
+    by the points' device like mesh_cast_rays.  The magnitude is the distance to the closest triangle; the sign comes from
+    crossing parity (the vote of ops.MESH_PARITY_DIRS), which means inside only for a closed surface.  -> (N,) fp32,
+    positive inside with ``inside_positive`` (pysdf's convention: MeshSdf); +inf where the mesh has no triangle."""
+    d, inside = _mesh_inside_and_distance(mesh, points)
+    return torch.where((inside == bool(inside_positive)) | ~torch.isfinite(d), d, -d)      # THE sign, here and nowhere else
+
+
+class MeshSdf:
+    """The pysdf-shaped callable the reference builds with ``pysdf.SDF(vertices, faces)``: ``f(points) -> (N,) float32``,
+    numpy in, numpy out, and ``f.contains(points) -> (N,) bool``.
+    Sign: **positive inside**, negative outside.  pysdf cannot be installed beside this project, so the convention rests
+    on its documentation ("SDF is > 0 inside and < 0 outside") and on how the reference uses it: PosedSdf3D accepts a
+    camera position where ``sdf_fn(p) > 0.3``, i.e. at least 0.3 m inside the room shell (grid_opt/datasets/sdf_3d.py:193-199).
+    The sign is set in one line, mesh_signed_distance's.  ``device``: where the queries run (default: the HIP device when
+    there is one, else the CPU); on a HIP device the index is built once and kept."""
+
+    def __init__(self, vertices, faces, device=None):
+        self.device = torch.device(device if device is not None else ('cuda:0' if torch.cuda.is_available() else 'cpu'))
+        self.mesh = TriangleMesh(vertices, faces)
+        if self.device.type == 'cuda':
+            from miso_amd import ops
+            self.mesh = ops.MeshIndex(*_mesh_arrays(self.mesh, self.device))
+
+    def _points(self, points):
+        return torch.as_tensor(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)).to(self.device)
+
+    def on_device(self, points):
+        """``points`` (N, 3) fp32 tensor on self.device -> (N,) fp32 tensor there: no host round trip"""
+        return mesh_signed_distance(self.mesh, points, inside_positive=True)
+
+    def __call__(self, points):
+        return self.on_device(self._points(points)).cpu().numpy().astype(np.float32)
+
+    def contains(self, points):
+        return _mesh_inside_and_distance(self.mesh, self._points(points))[1].cpu().numpy()
+
+
 _TILE_ORDERS = {}
 
 

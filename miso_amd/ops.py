@@ -1234,6 +1234,16 @@ MESH_MAX_ENTRIES = _lib.MESH_MAX_ENTRIES    # list entries of one index (512 MB)
 # count (a lane per ray: up to 256 blocks run side by side), building an index and walking it 0.43 .. 0.58 ms; they cross
 # near 2 000 triangles (1 024: 0.24 against 0.44 ms; 8 192: 1.7 against 0.56 ms).
 MESH_ALL_BELOW = 2048
+# closest(): the coarse index has MESH_FAR_FACTOR times the cell, and a query goes there after MESH_FAR_RINGS unfinished
+# shells of the first (both the library's constants: include/miso_hip.h; DESIGN.md section 4.16 holds the sweep).
+MESH_FAR_FACTOR = _lib.MESH_FAR_FACTOR
+MESH_FAR_RINGS = _lib.MESH_FAR_RINGS
+# contains(): three fixed unit directions, generic: every component is at least 0.11 in magnitude (no ray runs in an
+# axis-aligned plane), the magnitudes of a direction's components differ by at least 0.14 (none runs in a face-diagonal
+# plane of an axis-aligned mesh), and no two directions are closer than 65 degrees to parallel.  They are Pythagorean
+# quadruples over their length -- (2, 3, 6) / 7, (-9, 6, 2) / 11, (-4, -8, 1) / 9 -- so they are unit vectors up to the
+# rounding of the quotients.
+MESH_PARITY_DIRS = ((2.0 / 7.0, 3.0 / 7.0, 6.0 / 7.0), (-9.0 / 11.0, 6.0 / 11.0, 2.0 / 11.0), (-4.0 / 9.0, -8.0 / 9.0, 1.0 / 9.0))
 
 
 def _tri_index(t: torch.Tensor) -> torch.Tensor:
@@ -1253,6 +1263,24 @@ def _ray_out(out, n: int, device):
     for x, dtype in ((t, torch.float32), (tri, torch.int64)):
         assert x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() >= n
     return t, tri
+
+
+def _closest_out(out, n: int, device, want_vw: bool):
+    """(d2, tri, vw or None) of a closest() call, allocated when ``out`` is None"""
+    if out is None:
+        out = (torch.empty(n, device=device, dtype=torch.float32), torch.empty(n, device=device, dtype=torch.int64)) + \
+            ((torch.empty((n, 2), device=device, dtype=torch.float32),) if want_vw else ())
+    assert len(out) == (3 if want_vw else 2), "out = (d2, tri, vw) with want_vw, else (d2, tri)"
+    for x, dtype, m in zip(out, (torch.float32, torch.int64, torch.float32), (n, n, 2 * n)):
+        assert x.is_cuda and x.dtype == dtype and x.is_contiguous() and x.numel() >= m
+    return out[0], out[1], (out[2] if want_vw else None)
+
+
+def _count_out(out, n: int, device):
+    if out is None:
+        out = torch.empty(n, device=device, dtype=torch.int32)
+    assert out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() >= n
+    return out
 
 
 def mesh_default_cell(lo, hi, n_tri: int) -> float:
@@ -1299,7 +1327,8 @@ def _hittable_bounds(vertices: torch.Tensor, triangles: torch.Tensor):
 
 class MeshIndex:
     """A uniform grid over the triangles of a mesh for first-hit ray queries (miso_mesh_plan / count / build / cast_rays,
-    csrc/mesh.hip).  ``vertices`` (V, 3) fp32 and ``triangles`` (T, 3) int64 on the device, strided views read in place.
+    csrc/mesh.hip) and for distance queries (closest, count_crossings, contains, signed_distance: csrc/mesh_sdf.hip).
+    ``vertices`` (V, 3) fp32 and ``triangles`` (T, 3) int64 on the device, strided views read in place.
     Building reads back the bounds (six floats) and, after the count, the number of list entries -- the host needs both to
     size the grid and the lists; queries read nothing back.  ``cell=None``: mesh_default_cell.  While the lists would
     exceed MESH_MAX_ENTRIES the cell is doubled (one more count and read each time); ``stats()`` names the cell used.
@@ -1309,7 +1338,6 @@ class MeshIndex:
         vertices, triangles = _cloud(vertices, "vertices"), _tri_index(triangles)
         self.vertices, self.triangles = vertices, triangles
         self.n_vert, self.n_tri = int(vertices.shape[0]), int(triangles.shape[0])
-        lib = _lib.load()
         lo, hi = [0.0] * 3, [0.0] * 3
         n_plan = self.n_tri
         if self.n_tri:
@@ -1320,6 +1348,15 @@ class MeshIndex:
                 n_plan = 0                                                          # nothing can be hit: the empty index
         self.bound_min, self.bound_max = tuple(lo), tuple(hi)
         cell = float(mesh_default_cell(lo, hi, self.n_tri) if cell is None else cell)
+        self._n_plan = n_plan
+        self.plan, self.entries, self.workspace, self.lists = self._build(cell)
+        self.far = None                          # (plan, entries, workspace, lists) of the coarse index: prepare_distance()
+        self.cell = float(self.plan.cell)
+        self.dims = tuple(int(d) for d in self.plan.dims)
+
+    def _build(self, cell: float):
+        """plan, count and build one index of the mesh at ``cell`` -> (plan, entries, workspace, lists)"""
+        lib, vertices, triangles = _lib.load(), self.vertices, self.triangles
         dev = vertices.device
 
         def count(plan):
@@ -1329,14 +1366,13 @@ class MeshIndex:
                                            _ld(triangles), _ptr(workspace), _ptr(total), _stream(vertices)), "miso_mesh_count")
             return int(total[0].item()), workspace                                  # the host read of the build
 
-        self.plan, self.entries, self.workspace = mesh_plan_fit(lo, hi, cell, n_plan, count)
-        self.lists = None
-        if n_plan:
-            self.lists = torch.empty(max(self.entries, 1), device=dev, dtype=torch.int32)
-            _lib.check(lib.miso_mesh_build(C.byref(self.plan), _ptr(self.workspace), _ptr(self.lists), self.entries,
-                                           _stream(vertices)), "miso_mesh_build")
-        self.cell = float(self.plan.cell)
-        self.dims = tuple(int(d) for d in self.plan.dims)
+        plan, entries, workspace = mesh_plan_fit(self.bound_min, self.bound_max, cell, self._n_plan, count)
+        lists = None
+        if self._n_plan:
+            lists = torch.empty(max(entries, 1), device=dev, dtype=torch.int32)
+            _lib.check(lib.miso_mesh_build(C.byref(plan), _ptr(workspace), _ptr(lists), entries, _stream(vertices)),
+                       "miso_mesh_build")
+        return plan, entries, workspace, lists
 
     def cast_rays(self, origins: torch.Tensor, dirs: torch.Tensor, t_min: float = 0.0, t_max: float = float("inf"), out=None,
                   stats: Optional[torch.Tensor] = None):
@@ -1356,6 +1392,70 @@ class MeshIndex:
                    "miso_mesh_cast_rays")
         return t, tri
 
+    def prepare_distance(self, factor: Optional[float] = None, rings: Optional[int] = None):
+        """Build the coarse index closest() falls back on far from every surface: the same mesh at ``factor`` (default
+        MESH_FAR_FACTOR) times this index's cell.  closest() builds it on first use; built here beforehand, closest()
+        reads nothing back and replays inside a captured graph.  ``rings``: the fine shells walked before a query starts
+        again on the coarse index (default MESH_FAR_RINGS, the library's).  Calling again rebuilds (sweeps)."""
+        if self._n_plan:
+            factor = float(MESH_FAR_FACTOR if factor is None else factor)
+            assert factor > 1.0, "the far index is coarser than the first"
+            self.far = self._build(self.cell * factor)
+            self.far[0].reserved = 0 if rings is None else int(rings)
+        return self
+
+    def closest(self, points: torch.Tensor, out=None, want_vw: bool = False, stats: Optional[torch.Tensor] = None,
+                far: bool = True):
+        """-> (d2 (N,) fp32, tri (N,) int64[, vw (N, 2) fp32]) on the device: the squared distance from every point to the
+        mesh, the triangle that holds the closest point (the lowest index among equals) and, with ``want_vw``, that
+        point's barycentrics: v0 + v (v1 - v0) + w (v2 - v0).  (+inf, -1, (0, 0)) without a triangle and for a non-finite
+        point.  ``out`` = (d2, tri[, vw]).  ``stats``: (5,) int64 on the device, filled with {cells of this index visited,
+        cells of the coarse index visited, triangles offered, queries that went coarse, queries answered from all rows}.
+        ``far=False``: this index's shells only (the same bits, for tests and sweeps)."""
+        points = _cloud(points, "points")
+        n = int(points.shape[0])
+        if far and self.far is None:
+            self.prepare_distance()
+        d2, tri, vw = _closest_out(out, n, points.device, want_vw)
+        if stats is not None:
+            assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() >= 5
+        f = self.far if far and self.far is not None else None
+        _lib.check(_lib.load().miso_mesh_closest(C.byref(self.plan), _ptr(self.workspace), _ptr(self.lists), self.entries,
+                                                 C.byref(f[0]) if f else None, _ptr(f[2] if f else None),
+                                                 _ptr(f[3] if f else None), f[1] if f else 0, _ptr(points), _ld(points), n,
+                                                 _ptr(d2), _ptr(tri), _ptr(vw), _ptr(stats), _stream(points)), "miso_mesh_closest")
+        return (d2, tri, vw) if want_vw else (d2, tri)
+
+    def count_crossings(self, origins: torch.Tensor, dirs: torch.Tensor, t_min: float = 0.0, t_max: float = float("inf"),
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """-> (N,) int32 on the device: how many triangles the ray origins[i] + t dirs[i] crosses with t_min <= t <= t_max,
+        by cast_rays' hit test.  A ray through an edge two triangles share counts both, one through a vertex every
+        triangle of its fan: contains() votes over three rays for that reason."""
+        origins, dirs = _cloud(origins, "origins"), _cloud(dirs, "dirs")
+        n = int(origins.shape[0])
+        assert int(dirs.shape[0]) == n, "one direction per origin"
+        out = _count_out(out, n, origins.device)
+        _lib.check(_lib.load().miso_mesh_count_hits(C.byref(self.plan), _ptr(self.workspace), _ptr(self.lists), self.entries,
+                                                    _ptr(origins), _ld(origins), _ptr(dirs), _ld(dirs), n, float(t_min),
+                                                    float(t_max), _ptr(out), _stream(origins)), "miso_mesh_count_hits")
+        return out
+
+    def contains(self, points: torch.Tensor) -> torch.Tensor:
+        """-> (N,) bool: inside the closed surface by crossing parity, the vote of MESH_PARITY_DIRS (at least two of the
+        three rays cross an odd number of triangles).  A non-finite point is outside."""
+        points = _cloud(points, "points")
+        n = int(points.shape[0])
+        dirs = torch.tensor(MESH_PARITY_DIRS, device=points.device, dtype=torch.float32)
+        odd = self.count_crossings(points.repeat(3, 1), dirs.repeat_interleave(n, dim=0)).view(3, n) & 1
+        return odd.sum(dim=0) >= 2
+
+    def signed_distance(self, points: torch.Tensor, inside_positive: bool = True) -> torch.Tensor:
+        """-> (N,) fp32: sqrt(closest d2) with the sign of contains(): positive inside with ``inside_positive`` (pysdf's
+        convention, the reference's), else negative inside.  +inf where there is no triangle."""
+        d = self.closest(points)[0].sqrt()
+        inside = self.contains(points)
+        return torch.where(inside == bool(inside_positive), d, -d) if self._n_plan else d
+
     def triangle_normals(self) -> torch.Tensor:
         """(T, 3) unit face normals (v1 - v0) x (v2 - v0) from the winding; zero for a triangle that has none."""
         nv = self.n_vert
@@ -1371,6 +1471,42 @@ class MeshIndex:
         """the grid as built: cells, dims, list entries (and per triangle), the cell used, the slack w of the lists"""
         return {"cells": int(self.plan.cells), "dims": self.dims, "entries": self.entries, "cell": self.cell,
                 "entries_per_triangle": self.entries / max(self.n_tri, 1), "widen": float(self.plan.widen)}
+
+
+def closest_all(points: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, out=None, want_vw: bool = False):
+    """The all-triangles kernel for every point (miso_mesh_closest_all): -> (d2, tri[, vw]), the bits MeshIndex.closest returns."""
+    points, vertices, triangles = _cloud(points, "points"), _cloud(vertices, "vertices"), _tri_index(triangles)
+    n = int(points.shape[0])
+    d2, tri, vw = _closest_out(out, n, points.device, want_vw)
+    _lib.check(_lib.load().miso_mesh_closest_all(_ptr(vertices), _ld(vertices), int(vertices.shape[0]), _ptr(triangles),
+                                                 _ld(triangles), int(triangles.shape[0]), _ptr(points), _ld(points), n, _ptr(d2),
+                                                 _ptr(tri), _ptr(vw), _stream(points)), "miso_mesh_closest_all")
+    return (d2, tri, vw) if want_vw else (d2, tri)
+
+
+def closest(points: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor, cell: Optional[float] = None,
+            want_vw: bool = False):
+    """Closest triangle of every point: -> (d2 (N,) fp32, tri (N,) int64[, vw]).  Small meshes (T < MESH_ALL_BELOW, read at
+    call time) take the all-triangles kernel, the rest a MeshIndex: the same bits."""
+    _require_hip(points, vertices)
+    if int(triangles.shape[0]) < MESH_ALL_BELOW:
+        return closest_all(points, vertices, triangles, want_vw=want_vw)
+    return MeshIndex(vertices, triangles, cell=cell).closest(points, want_vw=want_vw)
+
+
+def count_crossings_all(origins: torch.Tensor, dirs: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor,
+                        t_min: float = 0.0, t_max: float = float("inf"), out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The all-triangles count for every ray (miso_mesh_count_hits_all): the values MeshIndex.count_crossings returns."""
+    origins, dirs = _cloud(origins, "origins"), _cloud(dirs, "dirs")
+    vertices, triangles = _cloud(vertices, "vertices"), _tri_index(triangles)
+    n = int(origins.shape[0])
+    assert int(dirs.shape[0]) == n, "one direction per origin"
+    out = _count_out(out, n, origins.device)
+    _lib.check(_lib.load().miso_mesh_count_hits_all(_ptr(vertices), _ld(vertices), int(vertices.shape[0]), _ptr(triangles),
+                                                    _ld(triangles), int(triangles.shape[0]), _ptr(origins), _ld(origins),
+                                                    _ptr(dirs), _ld(dirs), n, float(t_min), float(t_max), _ptr(out),
+                                                    _stream(origins)), "miso_mesh_count_hits_all")
+    return out
 
 
 def cast_rays_all(origins: torch.Tensor, dirs: torch.Tensor, vertices: torch.Tensor, triangles: torch.Tensor,
