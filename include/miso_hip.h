@@ -353,7 +353,7 @@ int miso_grad_pull_dx(const miso_grid_t* grid, const miso_sorted_t* sorted, int6
  * flags) keep the atomic scatter. */
 /* Levels (bit l) whose gradient miso_sdf_bwd_sorted forms by the matrix-core push instead of the pull (grad_pull.hip:
  * per run of tile-sorted samples a (samples x 25)^T (samples x 5 C) product on v_mfma_f32_32x32x2_f32, added to the
- * zero-filled level with atomics): a batch that averages >= 100 samples per tile ($MISO_DENSE_MIN), 4 or 8 channels,
+ * zero-filled level with atomics): a batch that averages >= 100 samples per tile (a constant of the library), 4 or 8 channels,
  * and every tile's samples within 5 vertices per axis (a tile owns <= 3).  n = batch size.  Informational: the entry
  * point decides by itself. */
 uint32_t miso_sdf_bwd_push_levels(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n);

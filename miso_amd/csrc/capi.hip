@@ -24,8 +24,6 @@ int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) 
   out->flags = in->flags & ~(MISO_F_GRAD_OVERWRITE | MISO_F_GRAD_SDF_SORTED | MISO_F_GRAD_ZEROED);   // host-side flags
   for (int a = 0; a < 3; ++a) { out->bmin[a] = in->bound_min[a]; out->bmax[a] = in->bound_max[a]; out->gscale[a] = 1.0f; }
   out->xstride = 3;
-  static const uint32_t tune = [] { const char* e = getenv("MISO_TUNE"); return e ? (uint32_t)atoi(e) : 0u; }();
-  out->tune = tune;
   bool v4 = true;
   int foff = 0;
   for (int l = 0; l < in->n_levels; ++l) {

@@ -59,7 +59,7 @@ __device__ __forceinline__ void write_cell_record(int* r, const Cell& c, const L
 // of its 16 dwords carry data.  So the scatter runs "row-major": the 2*C consecutive lanes of a group cover the x-pair
 // (i0, i0+1) x C channels = one contiguous run of 2*C floats, and one atomic instruction serves 64/(2C) (point, row)
 // pairs; four (dy, dz) atomics per lane and level, the cell of every (point, level) broadcast from its record rec[point][l].
-// TOUCH: mark the Adam chunks written to (touch_chunk).  no_atomics: dev ablation (MISO_DEBUG_BWD & 1).
+// TOUCH: mark the Adam chunks written to (touch_chunk).  no_atomics: sdf_bwd_kernel's retained dev bit, always false.
 // MISO_ABL_NO_SCATTER (dev ablation, a define of the build): was the training kernel's alone; here it takes the atomics
 // out of every kernel that scatters, sdf_bwd_kernel and atlas_sdf_bwd_kernel included.
 // Grid: GridK where the grid is the kernel's own argument -- by value, so that its level table is still read from the

@@ -6,9 +6,8 @@
 namespace miso {
 
 PullKnobs pull_knobs() {
-  static const int dense_min = [] { const char* e = getenv("MISO_DENSE_MIN"); return e ? atoi(e) : 100; }();
-  const char *mc = getenv("MISO_PULL_MC"), *dbg = getenv("MISO_DEBUG_PULL");
-  return PullKnobs{mc && atoi(mc) == 0, getenv("MISO_PULL_NO_SPLIT") != nullptr, dense_min, dbg ? atoi(dbg) : 0};
+  const char* mc = getenv("MISO_PULL_MC");
+  return PullKnobs{mc && atoi(mc) == 0, getenv("MISO_PULL_NO_SPLIT") != nullptr};
 }
 
 // A tile's brick of the level is at most PULL_BMAX^3 vertices, and the kernels' tile arithmetic stays within an int.
@@ -37,7 +36,7 @@ static bool push_fits(const LevelK& lv, int T) {
 GradPlan plan_grad(const GridK& g, const GradAsk& a, const PullKnobs& k) {
   GradPlan p = {};
   p.valid = tiles_xyz(a.tiles, p.T);
-  p.n = a.n; p.ld = a.ld; p.debug = k.debug;
+  p.n = a.n; p.ld = a.ld;
   const bool cubic = tiles_cubic16(a.tiles);      // the vector kernels and the push: cubic binnings of <= 16 tiles only
   uint32_t have = 0;                              // levels with a gradient buffer
   for (int l = 0; l < g.n_levels; ++l)
@@ -76,13 +75,13 @@ GradPlan plan_grad(const GridK& g, const GradAsk& a, const PullKnobs& k) {
     }
   }
 
-  // ---- push: coarse levels under a crowd -- an average of dense_min samples per tile, or MISO_F_CROWDED: the caller
+  // ---- push: coarse levels under a crowd -- an average of PULL_DENSE_MIN samples per tile, or MISO_F_CROWDED: the caller
   // knows the batch piles up on a few tiles (ray samples: a 54 000-sample batch of the synthetic RGB-D demo put 112 us of
   // pull + drain launches on the 40 x 20 x 40 level, the push 46 us); a uniform batch below the threshold is better off
   // pulled (cfg-2: 107 -> 180 us).  (A finer binning: the matrix-core pull takes crowded levels as they come.)
   const bool crowded = (g.flags & MISO_F_CROWDED) != 0 && a.n >= 4096;
-  if (a.caller != GRAD_PULL && cubic && k.dense_min > 0 && a.n < (1ll << 31) &&
-      (crowded || a.n >= (int64_t)k.dense_min * p.T[0] * p.T[0] * p.T[0]))
+  if (a.caller != GRAD_PULL && cubic && a.n < (1ll << 31) &&
+      (crowded || a.n >= (int64_t)PULL_DENSE_MIN * p.T[0] * p.T[0] * p.T[0]))
     for (int l = 0; l < g.n_levels; ++l)
       if (((p.owned >> l) & 1u) && push_fits(g.lv[l], p.T[0])) p.push |= 1u << l;
 

@@ -16,13 +16,12 @@ enum PullForm {
   PULL_INVALID     // a per-axis binning the matrix-core kernel does not take (MISO_PULL_MC=0, gg_x): hipErrorInvalidValue
 };
 
-// Environment knobs.  MISO_PULL_MC, MISO_PULL_NO_SPLIT and MISO_DEBUG_PULL are read at every call (tests and the ablation
-// tools toggle them within a process); MISO_DENSE_MIN once.
+// Environment knobs, read at every call: the tests toggle them within a process to reach kernels that other inputs
+// reach too.
 struct PullKnobs {
   bool mc_off, no_split;      // MISO_PULL_MC=0: vector kernels only; MISO_PULL_NO_SPLIT: heavy tiles are not cut
-  int dense_min;              // samples per tile, on average, from which coarse levels are pushed (100)
-  int debug;                  // dev ablation bits handed to the kernels (PullK::debug, McK::debug)
 };
+constexpr int PULL_DENSE_MIN = 100;      // samples per tile, on average, from which coarse levels are pushed
 PullKnobs pull_knobs();
 
 struct GradAsk {
@@ -48,7 +47,7 @@ struct GradPlan {
   PullForm form;              // what serves owned & ~push
   bool drain;                 // PULL_WAVE / PULL_BLOCK: the launch that works off the slice queue follows,
   int qcap;                   // ... and the queue's item capacity
-  int overwrite, debug;       // PullK's, McK's
+  int overwrite;              // PullK's, McK's
   int64_t n, ld;              // GradAsk's
   int nl, lev[PULL_MAXL];     // the pulled levels, and per level and axis:
   int bdiv[PULL_MAXL][3];     // size / T where T divides the size, else 0

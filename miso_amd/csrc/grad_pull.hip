@@ -943,7 +943,7 @@ __global__ __launch_bounds__(64 * PUSH_WAVES) void grad_push_mfma_kernel(GridK g
       wave_sync_lds();
       // ---- 32 x 32 x 2 products: lanes 0-31 feed sample 2 s, lanes 32-63 sample 2 s + 1 --------------------------
       // (in groups of four steps: rows past `cnt` are staged as zeros, so running over them adds nothing)
-      const int nstep = (pk.debug & 128) ? 0 : (cnt + 1) >> 1;
+      const int nstep = (cnt + 1) >> 1;
       for (int st0 = 0; st0 < nstep; st0 += 4) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -970,7 +970,7 @@ __global__ __launch_bounds__(64 * PUSH_WAVES) void grad_push_mfma_kernel(GridK g
         const int row = 8 * (r >> 2) + 4 * half + (r & 3);
         const int vx = r0[0] + row % 5, vy = r0[1] + row / 5;
         const float v = acc[nb][r];
-        if (col_ok && row < 25 && v != 0.0f && vx >= 0 && vx < lv.X && vy >= 0 && vy < lv.Y && !(pk.debug & 64)) {
+        if (col_ok && row < 25 && v != 0.0f && vx >= 0 && vx < lv.X && vy >= 0 && vy < lv.Y) {
           float* dst = colp + (int64_t)vy * lv.sY + (int64_t)vx * lv.sX;
           atomic_add_f32(dst, v);
           touch_chunk(lv, (int64_t)(dst - lv.grad));
@@ -998,7 +998,7 @@ static PullK pull_args(const GradPlan& p, const PullBatch& b) {
   PullK pk;
   memset(&pk, 0, sizeof(pk));
   pk.T = p.T[0]; pk.tile_off = b.tile_off; pk.xn = reinterpret_cast<const float4*>(b.xn); pk.dfeat = b.dfeat;
-  pk.ld = p.ld; pk.perm = b.perm; pk.debug = p.debug;
+  pk.ld = p.ld; pk.perm = b.perm; pk.debug = 0;
   return pk;
 }
 

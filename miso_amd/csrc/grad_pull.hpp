@@ -45,7 +45,9 @@ struct PullK {
   int overwrite;         // 1: grad = sum (no zero-fill needed), 0: grad += sum
   int bdiv[PULL_MAXL][3];   // size / T per pulled level and axis where T divides the size, else 0
   float inv_size[PULL_MAXL][3];
-  int debug;             // ablation (MISO_DEBUG_PULL, dev only): 1 no pull loop, 2 no groups, 4 no sweep
+  int debug;             // always 0: the ablation bits of grad_pull_kernel / grad_pull_block_kernel (1 no pull loop, 2 no groups,
+                         // 4 no sweep, 8 16 32 256 block kernel), whose branches stay: without them the kernels took other
+                         // registers and the block kernel measured ~0.5 us slower
   int32_t* queue;        // slice queue (see PULL_WORK0) or nullptr: tiles are never split
   int qcap;              // item capacity
   int drain;             // 0: one wavefront per tile, slice 0 + queueing; 1: process the queued slices

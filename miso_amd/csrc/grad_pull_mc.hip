@@ -28,7 +28,6 @@
 //       straddles a boundary leaves partial tiles in LDS that the wavefront where it starts sums and stores.
 // Used when no pulled level has fewer than 2/3 as many vertices as tiles on an axis (the sweep then stays within 7 tile
 // rows per axis); everything else -- second-order weights (MODE 1), grids coarser than the binning -- keeps grad_pull.hip.
-#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -68,14 +67,8 @@ struct McK {
   int nl;                    // pulled levels
   int overwrite;             // 1: grad = sum, 0: grad += sum
   unsigned int drow_bytes;   // bytes of the d-feat rows: n * ld * 4 (< 2^31: row offsets are 32-bit buffer offsets)
-  int debug;                 // dev ablation (MISO_DEBUG_PULL): 8 no multiply phase, 16 nothing after the sweep, 64 / 128 half the
-                             // workgroups.  (Bits 1 2 4 -- no MFMAs / staging loads / stores -- sat inside the multiply loop
-                             // and are gone: the branch around the loads alone made the compiler wait for them at every
-                             // later join)
   int cand_cap, pool_cap;    // table entries / pool pairs in use: MC_CAND / MC_POOL (tests: MISO_MC_SMALL shrinks them so that the
                              // epoch and pool-overflow paths run on ordinary batches)
-  int prof_wave;             // dev: the wavefront that stamps (MISO_MC_PROF=1+wave)
-  unsigned long long* prof;  // dev (MISO_MC_PROF): clocks per phase, or nullptr
   McLv lv[MC_MAXL];
 };
 
@@ -88,7 +81,8 @@ template <int C, int NLV> struct McLds {
   static constexpr int O_POOL = O_CAND + (MC_CAND + 1) * 4;          // uint32[MC_POOL]: table slot | sub-brick code << 16
   static constexpr int O_CNT = O_POOL + MC_POOL;                     // int[MC_ITEMS]: pairs per sub-brick
   static constexpr int O_CUR = O_CNT + MC_ITEMS;                     // int[MC_ITEMS]: fill cursors (absolute)
-  static constexpr int O_MISC = O_CUR + MC_ITEMS;                    // 96 ints
+  static constexpr int O_MISC = O_CUR + MC_ITEMS;                    // 96 ints (M_*; the last 32 were the profiler's and are
+                                                                     // unused: every offset behind them stays where it was measured)
   static constexpr int O_LVL = O_MISC + 96;                          // MC_MAXL block-geometry records of MC_LVL words
   static constexpr int O_LVG = O_LVL + MC_MAXL * MC_LVL;             // MC_MAXL records of 8 words: grad, strides, touched
   static constexpr int O_GEO = O_LVG + MC_MAXL * 8;                  // the block's catchment box and tile-row bounds (G_*)
@@ -103,8 +97,7 @@ template <int C, int NLV> struct McLds {
   static_assert(WORDS * 4 <= 80 * 1024, "two workgroups per CU");
 };
 // O_MISC slots
-constexpr int M_NSURV = 0, M_FULL = 1, M_MORE = 2, M_PTOT = 3, M_A = 8, M_B = 16, M_CONT = 24, M_EMPTY = 32, M_BOUND = 40,
-              M_PROF = 64;
+constexpr int M_NSURV = 0, M_FULL = 1, M_MORE = 2, M_PTOT = 3, M_A = 8, M_B = 16, M_CONT = 24, M_EMPTY = 32, M_BOUND = 40;
 // a share's cost: 2 per group of four pairs + MC_FLUSH per sub-brick that ends in it (storing a tile costs ~2.5 groups)
 // O_GEO slots
 constexpr int G_ULO = 0, G_UHI = 4, G_NROWS = 8, G_RS = 16, G_RE = 80;
@@ -125,14 +118,6 @@ __device__ __forceinline__ McLevel mc_level(const int* lvl, int d) {
   m.E[0] = r2.x; m.E[1] = r2.y; m.E[2] = r2.z;
   return m;
 }
-
-// dev: wavefront 0 adds the clocks since the previous stamp to prof[phase] (MISO_MC_PROF; see the launcher)
-#define MC_STAMP(PH)                                                                              \
-  if (pk.prof && wave == pk.prof_wave) {                                                          \
-    const unsigned long long now_ = __builtin_readcyclecounter();                                 \
-    if (lane == 0) misc[M_PROF + (PH)] += (int)(now_ - t_prev);                                       \
-    t_prev = now_;                                                                                \
-  }
 
 template <int C, int NLV>
 __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) {
@@ -180,13 +165,6 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
       *reinterpret_cast<unsigned char**>(lvg + d * 8 + 6) = lv.touched;
     }
   }
-  {
-    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);      // (workgroup i runs on XCD i % 8)
-    if ((pk.debug & 64) && ((lin >> 3) & 1)) return;       // dev: half the workgroups of every XCD, alternating
-    if ((pk.debug & 128) && lin >= (int)(gridDim.x * gridDim.y * gridDim.z) / 2) return;      // dev: the first half only
-  }      // dev: half the workgroups (one per CU): latency- or throughput-bound?
-  if (pk.prof && threadIdx.x < 16) misc[M_PROF + threadIdx.x] = 0;
-  unsigned long long t_prev = pk.prof ? __builtin_readcyclecounter() : 0ull;
   {
     // ---- per-block geometry -> LDS records (computed by the first threads, read back where needed) ----------------
     // level d, axis a: the block owns vertices [v0, v0 + E) = the bricks of its two tiles; points that touch them lie in
@@ -287,7 +265,6 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
         rs_v = geo[G_RS + lane]; re_v = geo[G_RE + lane];
         p_cur = (r_cur < nrows) ? __builtin_amdgcn_readlane(rs_v, min(r_cur, 63)) : 0;
       }
-      MC_STAMP(0)
       // ---- (1) sweep ------------------------------------------------------------------------------------------------
       while (r_cur < nrows) {
         const int p_end = __builtin_amdgcn_readlane(re_v, r_cur);
@@ -342,11 +319,9 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
         p_cur += 64 * done;
         if (done < nstep) break;
       }
-      MC_STAMP(1)
       if (r_cur < nrows && lane == 0) misc[M_MORE] = 1;
       __syncthreads();
-      MC_STAMP(2)
-      const int ncand = (pk.debug & 16) ? 0 : min(__builtin_amdgcn_readfirstlane(misc[M_NSURV]), pk.cand_cap);
+      const int ncand = min(__builtin_amdgcn_readfirstlane(misc[M_NSURV]), pk.cand_cap);
       const bool more = __builtin_amdgcn_readfirstlane(misc[M_MORE]) != 0;
 
       // ---- (2) + (3): route and multiply the table, in one range unless the pool overflows --------------------------
@@ -410,9 +385,7 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
             }
           }
         }
-        MC_STAMP(3)
         __syncthreads();
-        MC_STAMP(4)
         // (2b) offsets: every sub-brick's list padded to a multiple of four pairs
         if (wave == 0) {
           int c8[8], tot = 0, nz = 0;
@@ -449,7 +422,6 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
           if (lane == 63) misc[M_PTOT] = ptot_;
         }
         __syncthreads();
-        MC_STAMP(5)
         const int ptot = __builtin_amdgcn_readfirstlane(misc[M_PTOT]);
         if (ptot > pk.pool_cap) {      // a crowd on few sub-bricks: half the range at a time
           hi = lo + max(1, (hi - lo) >> 1);
@@ -516,7 +488,6 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
             }
           }
         }
-        MC_STAMP(6)
         // the first range also zero-fills the sub-bricks nothing touches (the gradient buffer is not cleared): wavefront w
         // looks at codes 16 w .. 16 w + 15 of every level
         if (first && pk.overwrite) {
@@ -552,12 +523,10 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
             }
           }
         }
-        MC_STAMP(7)
         __syncthreads();
-        MC_STAMP(8)
 
         // ---- (3) multiply: this wavefront's share of the pool ------------------------------------------------------
-        const int G = (pk.debug & 8) ? 0 : ptot >> 2;
+        const int G = ptot >> 2;
         const int g_begin = min(G, __builtin_amdgcn_readfirstlane(misc[M_BOUND + wave])),
                   g_end = min(G, __builtin_amdgcn_readfirstlane(misc[M_BOUND + wave + 1]));
         int first_code = -1, last_code = -1;
@@ -706,7 +675,6 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
           const int ng = min(16, g_end - g0);
 #pragma unroll
           for (int o = 0; o < 8 + ZS; ++o) stg[o * MC_CS + wr_p] = rw[o];
-          MC_STAMP(9)
 #pragma unroll
           for (int c = 0; c < C; ++c) stg[(8 + ZS + c) * MC_CS + wr_p] = rd[c];
           const int codev = rcode;
@@ -715,7 +683,6 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
           const int prevc = __shfl_up(codev, 4);
           const unsigned long long chg = __ballot((lane & 3) == 0 && codev != (lane < 4 ? cur_code : prevc));
           wave_sync_lds();
-          MC_STAMP(12)
           const bool has_next = g0 + 16 < g_end;
           // two duos of operands live at a time (ping-pong); the scheduling barriers keep the compiler from hoisting
           // every read to the top (registers)
@@ -745,18 +712,14 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
           __builtin_amdgcn_sched_barrier(0);
           MC_DUO(6, x0, y0, z0, d0)
           __builtin_amdgcn_sched_barrier(0);
-          MC_STAMP(13)
           if (has_next) stage_w();
           __builtin_amdgcn_sched_barrier(0);
-          MC_STAMP(14)
           MC_DUO(7, x1, y1, z1, d1)
-          MC_STAMP(15)
           wave_sync_lds();
         }
 #undef MC_DREAD
 #undef MC_GROUP
 #undef MC_DUO
-        MC_STAMP(9)
         // the share's last sub-brick
         int a_code = -1, b_code = -1, cont = 0;
         if (cur_code >= 0) {
@@ -772,7 +735,6 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
           misc[M_EMPTY + wave] = (g_begin >= g_end) ? 1 : 0;
         }
         __syncthreads();
-        MC_STAMP(10)
         if (b_code >= 0) {   // a sub-brick that starts here and runs on: sum the pieces in wavefront order
           f32x4 tot = acc;
           for (int v = wave + 1; v < MC_WAVES; ++v) {
@@ -792,14 +754,10 @@ __global__ __launch_bounds__(64 * MC_WAVES, 4) void grad_pull_mc_kernel(McK pk) 
           for (int i = threadIdx.x; i < MC_POOL; i += NT) pool[i] = 0xFFFFFFFFu;
         }
         __syncthreads();
-        MC_STAMP(11)
       }
       if (!more) break;
     }
   }
-  __syncthreads();
-  if (pk.prof && threadIdx.x < 16)
-    atomicAdd(&pk.prof[((blockIdx.x + blockIdx.y * 5 + blockIdx.z * 11) & 63) * 16 + threadIdx.x], (unsigned long long)misc[M_PROF + threadIdx.x]);
 }
 
 // PULL_MC of a plan (grad_plan.hpp: first-order rows below 2 GB, every pulled level at least 2/3 as fine as the binning)
@@ -823,15 +781,6 @@ hipError_t launch_grad_pull_mc(const GridK& g, const GradPlan& p, const PullBatc
   const bool small = getenv("MISO_MC_SMALL") != nullptr;      // tests: epochs and halved ranges on ordinary batches
   pk.cand_cap = small ? 192 : MC_CAND;
   pk.pool_cap = small ? 640 : MC_POOL;
-  pk.debug = p.debug;
-  // dev: MISO_MC_PROF=1 prints the clocks wavefront 0 of every workgroup spent per phase, averaged, every 64 launches
-  static unsigned long long* prof = [] {
-    unsigned long long* p = nullptr;
-    if (getenv("MISO_MC_PROF") && hipMalloc(&p, 1024 * sizeof(unsigned long long)) == hipSuccess) (void)hipMemset(p, 0, 1024 * 8);
-    return p;
-  }();
-  pk.prof = prof;
-  pk.prof_wave = prof ? atoi(getenv("MISO_MC_PROF")) - 1 : 0;
   void (*k)(McK) = nullptr;
   size_t words = 0;
 #define PICK(c, n)                                                      \
@@ -846,24 +795,6 @@ hipError_t launch_grad_pull_mc(const GridK& g, const GradPlan& p, const PullBatc
   hipError_t e = allow_dynamic_lds((const void*)k, lds);
   if (e != hipSuccess) return e;
   k<<<dim3((unsigned)pk.nb[0], (unsigned)pk.nb[1], (unsigned)pk.nb[2]), 64 * MC_WAVES, lds, s>>>(pk);
-  if (prof) {
-    static int calls = 0;
-    if (++calls % 64 == 0) {
-      static unsigned long long h[1024];
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpy(h, prof, sizeof(h), hipMemcpyDeviceToHost);
-      (void)hipMemset(prof, 0, sizeof(h));
-      static const char* nm[16] = {"setup", "sweep", "barrier", "count", "barrier", "prefix+b", "fill", "zero", "barrier",
-                                   "m:write-w", "tail+b", "combine+b", "m:write-d+sync", "m:duo0-6+loads", "m:weights", "m:duo7"};
-      fprintf(stderr, "[mc prof] clocks per workgroup:");
-      for (int i = 0; i < 16; ++i) {
-        double t = 0.0;
-        for (int b = 0; b < 64; ++b) t += (double)h[b * 16 + i];
-        fprintf(stderr, " %s %.0f", nm[i], t / (64.0 * pk.nb[0] * pk.nb[1] * pk.nb[2]));
-      }
-      fprintf(stderr, "\n");
-    }
-  }
   return hipGetLastError();
 }
 

@@ -622,8 +622,7 @@ hipError_t launch_pair_batch(const AlignPairK* plan_dev, int n_pairs, int64_t ma
     const unsigned lat = (unsigned)((max_gate_rows + GATE_ROWS - 1) / GATE_ROWS);
     if (lat > gate_blocks) gate_blocks = lat;
   }
-  static const bool split = getenv("MISO_PAIR_STAGE_SPLIT") != nullptr;      // dev / tests: the two launches of rounds 2-3
-  if (gate_blocks && (max_n <= 0 || split))
+  if (gate_blocks && max_n <= 0)
     overlap_count_batch_kernel<<<dim3(gate_blocks, (unsigned)n_pairs), 256, 0, s>>>(plan_dev, pose_all, cnt_all, stopped);
   if (max_n > 0) {
     unsigned blocks = (unsigned)((max_n + 2047) / 2048);
@@ -631,11 +630,10 @@ hipError_t launch_pair_batch(const AlignPairK* plan_dev, int n_pairs, int64_t ma
     // most 2048 per pair: a workgroup's fixed part -- poses, the 23-value reduction, 23 atomics -- is paid per
     // workgroup, and with 2048 of them for each of cfg-4's 28 pairs it was a fifth of the level-1 pair stage
     // (1.15 -> 0.89 ms per iteration at 256 per pair)
-    static const int cap_all = [] { const char* e = getenv("MISO_PAIR_WGS"); return e ? atoi(e) : 7168; }();      // dev: scan
-    unsigned cap = (unsigned)(cap_all / n_pairs);
+    unsigned cap = 7168u / (unsigned)n_pairs;
     cap = cap < 128u ? 128u : (cap > 2048u ? 2048u : cap);
     if (blocks > cap) blocks = cap;
-    if (gate_blocks && !split) {
+    if (gate_blocks) {
       const dim3 grid(blocks + gate_blocks, (unsigned)n_pairs);
       if (vec4) pair_stage_kernel<true><<<grid, 256, 0, s>>>(plan_dev, pose_all, loss_type, out_all, cnt_all, stopped, blocks, order);
       else pair_stage_kernel<false><<<grid, 256, 0, s>>>(plan_dev, pose_all, loss_type, out_all, cnt_all, stopped, blocks, order);

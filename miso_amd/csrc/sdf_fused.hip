@@ -108,7 +108,7 @@ __global__ void mlp_pack_kernel(MlpK m, int F, int H, int NH, float* __restrict_
 
 // ---------------------------------------------------------------------------
 template <int C, int L, int H, int NH, bool SPLIT>
-__global__ __launch_bounds__(256, MISO_FWD_OCC) MISO_FUSED_KERNEL_ATTR void sdf_fwd_kernel(GridK g, const float* __restrict__ packed,
+__global__ __launch_bounds__(256, MISO_FWD_OCC) void sdf_fwd_kernel(GridK g, const float* __restrict__ packed,
                                                         const float* __restrict__ x, int64_t n,
                                                         float* __restrict__ sdf,
                                                         uint32_t* __restrict__ mask,
@@ -164,8 +164,8 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) MISO_FUSED_KERNEL_ATTR void sdf_
     float f[2 * KS0];
 #pragma unroll
     for (int i = 0; i < 2 * KS0; ++i) f[i] = 0.0f;
-    memory_phase(true, g.tune);
-    if (valid && !(g.tune & 2u)) {
+    memory_phase(true);
+    if (valid) {
       float px, py, pz;
       load_point(g, x, p, px, py, pz);
       float bmn[3] = {g.bmin[0], g.bmin[1], g.bmin[2]}, bmx[3] = {g.bmax[0], g.bmax[1], g.bmax[2]};
@@ -183,14 +183,7 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) MISO_FUSED_KERNEL_ATTR void sdf_
         gather_level<C>(lv, c, &f[l * C]);
       }
     }
-    memory_phase(false, g.tune);
-    if (g.tune & 4u) {   // dev ablation: gather only
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < 2 * KS0; ++i) sum += f[i];
-      if (valid) sdf[perm ? (int64_t)perm[p] : p] = sum;
-      continue;
-    }
+    memory_phase(false);
     uint32_t mw[MW];
     float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
     if constexpr (SPLIT) {
@@ -238,8 +231,9 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) MISO_FUSED_KERNEL_ATTR void sdf_
 // gradients and/or grad_x.  Lane (hi, l&31) holds, for tile t, point 32t+(l&31):
 //   C == 8: channels 4hi..4hi+3 of level j>>2      (registers j = 4*level + c)
 //   C == 4: channels 0..3 of level 2*(j>>2) + hi   (registers j = 4*g + c)
+constexpr int BWD_GSDF_SORTED = 16, BWD_LEAN = 32;      // sdf_bwd_kernel's `debug` bits in use
 template <int C, int L, int H, int NH, bool WANT_GRID, bool WANT_X, bool SPLIT>
-__global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(GridK g, const float* __restrict__ packed,
+__global__ __launch_bounds__(256, 2) void sdf_bwd_kernel(GridK g, const float* __restrict__ packed,
                                                         const float* __restrict__ x, int64_t n,
                                                         const float* __restrict__ gsdf,
                                                         const uint32_t* __restrict__ mask,
@@ -250,8 +244,9 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
   // perm != nullptr: x and mask are in tile-sorted order, gsdf / gx in the caller's.
   // dfeat_out != nullptr: rows of d(feats) (N,F, sorted order) are written out and the levels in
   // defer_mask are NOT scattered here: grad_pull_kernel (grad_pull.hip) forms their gradient owner-computes.
-  // debug: ablation switches (MISO_DEBUG_BWD, dev only): 1 = no atomics, 8 = no scatter; bit 16 (set by the
-  // launcher for MISO_F_GRAD_SDF_SORTED): gsdf is already in the binned order.
+  // debug: BWD_GSDF_SORTED and BWD_LEAN, set by the launcher.  Bits 1 (no atomics) and 8 (no scatter) were ablation
+  // switches and are never set; their branches, and g.tune (always 0), stay so that the kernel compiles to the code it
+  // had: without them the coordinate gradient of <4, 2, 32, 1, true, true> came out wrong now and then.
   constexpr int F = C * L, RT = H / 32;
   constexpr int MW = (NH + 1) * RT;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -269,7 +264,7 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
   constexpr int FP = dfeat_pitch(F), REC = CELL_REC;      // the tile and the cell records: dfeat_tile.hpp
   constexpr int WAVE_LDS = 64 * FP + 64 * L * REC;
-  // debug bit 32 (set by the launcher when nothing is scattered from here): only the d-feat tile is
+  // BWD_LEAN (debug bit 32, set by the launcher when nothing is scattered from here): only the d-feat tile is
   // allocated per wave -- 50 KB per workgroup instead of 74, i.e. three workgroups per CU
   float* wave_lds = smem + ((nb + H + 3) / 4) * 4 + wave * ((debug & 32) ? 64 * FP : WAVE_LDS);
   const int64_t nchunks = (n + 63) / 64;
@@ -287,7 +282,7 @@ __global__ __launch_bounds__(256, 2) MISO_FUSED_KERNEL_ATTR void sdf_bwd_kernel(
     float ds[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
-      ds[t] = (pt[t] < n) ? gsdf[(perm && !(debug & 16)) ? (int64_t)perm[pt[t]] : pt[t]] : 0.0f;   // 16: gsdf is binned
+      ds[t] = (pt[t] < n) ? gsdf[(perm && !(debug & 16)) ? (int64_t)perm[pt[t]] : pt[t]] : 0.0f;   // 16 = BWD_GSDF_SORTED
     uint32_t mw[MW];
     {
       const uint32_t* mi = mask + (chunk * 64 + lane) * MW;
@@ -426,10 +421,7 @@ static hipError_t launch_bwd_t(FusedShape<C, L, H, NH>, const GridK& g, const fl
   unsigned blocks = (unsigned)((nchunks + 3) / 4);
   const unsigned use_cap = lean ? 768u : 512u;
   if (blocks > use_cap) blocks = use_cap;
-  int debug = 0;
-  if (const char* d = getenv("MISO_DEBUG_BWD")) debug = atoi(d) & ~(16 | 32);
-  if (gsdf_sorted) debug |= 16;
-  if (lean) debug |= 32;
+  const int debug = (gsdf_sorted ? BWD_GSDF_SORTED : 0) | (lean ? BWD_LEAN : 0);
   void (*k)(GridK, const float*, const float*, int64_t, const float*, const uint32_t*, float*, const int*, int,
             float*, uint32_t) =
       split ? ((want_grid && gx) ? sdf_bwd_kernel<C, L, H, NH, true, true, true>

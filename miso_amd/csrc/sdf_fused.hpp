@@ -17,17 +17,22 @@ namespace miso {
 // address arithmetic slip in between the co-resident wave's matrix instructions instead of queueing
 // behind them.  Measured: forward over unsorted points 80 -> 66 us; sorted 46 -> 45 us.  (Fixed
 // per-slot priorities and start delays were tried first: no effect.)
-__device__ __forceinline__ void memory_phase(bool on, uint32_t tune, bool first = false) {
-  if (tune & 16u) return;   // dev ablation
+__device__ __forceinline__ void memory_phase(bool on) {
   if (on) __builtin_amdgcn_s_setprio(3);
-  else if ((tune & 64u) && first) __builtin_amdgcn_s_setprio(2);      // dev: the SIMD's first wavefront computes ahead of its second
+  else __builtin_amdgcn_s_setprio(0);
+}
+// sdf_bwd_kernel's form, with the ablation bits of rounds 2-6 (tune is always 0 now): kept so that the kernel compiles to
+// the code it had -- without them its coordinate gradient came out wrong now and then
+__device__ __forceinline__ void memory_phase(bool on, uint32_t tune, bool first = false) {
+  if (tune & 16u) return;
+  if (on) __builtin_amdgcn_s_setprio(3);
+  else if ((tune & 64u) && first) __builtin_amdgcn_s_setprio(2);
   else __builtin_amdgcn_s_setprio(0);
 }
 
 #ifndef MISO_FWD_OCC
 #define MISO_FWD_OCC 2
 #endif
-#define MISO_FUSED_KERNEL_ATTR
 
 // Chunk schedule of the persistent waves.  Plain batches: chunk = global wave id,
 // grid-strided.  Tile-sorted batches (perm != nullptr): the chunk range is cut into 8

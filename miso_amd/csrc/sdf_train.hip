@@ -45,7 +45,7 @@ namespace miso {
     if (gvalid_) glin_ = lin.aux[gpo_]; \
 _Pragma("unroll") \
     for (int i = 0; i < 2 * KS0; ++i) f[i] = 0.0f; \
-    memory_phase(true, g.tune); \
+    memory_phase(true); \
     if (gvalid_) { \
       float px, py, pz; \
       load_point(g, x, gp_, px, py, pz); \
@@ -67,21 +67,21 @@ _Pragma("unroll") \
 _Pragma("unroll") \
       for (int l = 0; l < L; ++l) (RECW_)[(row_l * L + l) * REC + CELL_REC_FLAGS] = 0; \
     } \
-    memory_phase(false, g.tune, wave < NW / 2); \
+    memory_phase(false); \
     P_O_ = gp_; PO_O_ = gpo_; VALID_O_ = gvalid_; LIN_O_ = glin_; \
   }
 template <int C, int L, int H, int NH, bool SCAT, int NW = 4, bool HALF = false, bool SPLIT = false>
-__global__ __launch_bounds__(64 * NW, 2) MISO_FUSED_KERNEL_ATTR void sdf_train_kernel(GridK g, const float* __restrict__ packed,
+__global__ __launch_bounds__(64 * NW, 2) void sdf_train_kernel(GridK g, const float* __restrict__ packed,
                                                           const float* __restrict__ x, int64_t n,
                                                           float* __restrict__ sdf, const int* __restrict__ perm,
                                                           LossInK lin, float* __restrict__ dfeat_out,
-                                                          uint32_t defer_mask) {
+                                                          uint32_t defer_mask, bool rotate_records) {
   constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2, KS1 = H / 2;
   constexpr int MW = (NH + 1) * RT;
   constexpr int FP = dfeat_pitch(F), REC = CELL_REC;      // the d-feat tile and (SCAT) the cell records: dfeat_tile.hpp
-  // SCAT: the cell records are double-buffered when the launcher found room for a second block (MISO_TUNE_ROTATE) -- the
-  // next chunk's gathers are then issued in FRONT of this chunk's atomics, see the loop
-  const bool rotate = SCAT && C * L <= MISO_ROTATE_MAX_F && (g.tune & MISO_TUNE_ROTATE) != 0;
+  // SCAT: the cell records are double-buffered when the launcher found room for a second block (rotate_records,
+  // TrainPlan::rotate) -- the next chunk's gathers are then issued in FRONT of this chunk's atomics, see the loop
+  const bool rotate = SCAT && C * L <= MISO_ROTATE_MAX_F && rotate_records;
   const int WAVE_LDS = 64 * FP + (SCAT ? (rotate ? 2 : 1) * 64 * L * REC : 0);
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const PackLayout pl(F, H, NH);
@@ -124,11 +124,6 @@ __global__ __launch_bounds__(64 * NW, 2) MISO_FUSED_KERNEL_ATTR void sdf_train_k
   float inv_n = lin.inv_n;
   if (lin.n_live) { const int live = *lin.n_live; inv_n = 1.0f / (float)(live > 1 ? live : 1); }
   ChunkSched sched(nchunks, wave, NW, true);
-  // dev (MISO_TUNE bits 8..15): the second wavefront of every SIMD starts k x 1024 clocks late
-  if ((g.tune >> 8) & 255u) {
-    if (wave >= NW / 2)
-      for (uint32_t i = 0; i < ((g.tune >> 8) & 255u); ++i) __builtin_amdgcn_s_sleep(16);
-  }
   const int row_l = HALF ? (lane & 31) : lane;      // this lane's row of the wavefront's LDS tile / records
   float f[2 * KS0];
   // Rotated (scattering, room for two record blocks): chunk k+1's gathers are requested between chunk k's decoder
@@ -335,7 +330,7 @@ __global__ __launch_bounds__(64 * NW, 2) MISO_FUSED_KERNEL_ATTR void sdf_train_k
         }
     }
     // ---- d-feat rows: accumulator layout -> LDS tile -> 64 contiguous rows of the (N, F) buffer, 16-B stores --------
-    memory_phase(true, g.tune);
+    memory_phase(true);
     dfeat_to_tile<F, HALF ? 1 : 2>(df, dF, lane & 31, hi);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -345,7 +340,7 @@ __global__ __launch_bounds__(64 * NW, 2) MISO_FUSED_KERNEL_ATTR void sdf_train_k
     if (SCAT) scatter_tile<C, L, true, GridK>(g, scatter_mask, dF, rec_cur, PTS, lane);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();      // the next chunk overwrites the tile (and the records)
-    memory_phase(false, g.tune, wave < NW / 2);
+    memory_phase(false);
     if (rotate) { int* t_ = rec_cur; rec_cur = rec_nxt; rec_nxt = t_; }
   }
   // loss sums: as sdf_fwd_kernel (every block stores its pair into its own slot, the slots nobody owns are cleared)
@@ -368,14 +363,6 @@ __global__ __launch_bounds__(64 * NW, 2) MISO_FUSED_KERNEL_ATTR void sdf_train_k
 // ---------------------------------------------------------------------------
 // host side: the launch is planned in one place (plan_train) and made in one place (launch_train_t)
 // ---------------------------------------------------------------------------
-// development A/B switches of the launch, each on unless its variable is set
-struct TrainToggles {
-  bool rotate = true;        // MISO_TRAIN_NO_ROTATE: never a second block of cell records
-  bool nw8 = true;           // MISO_TRAIN_NW4: four wavefronts where nothing is scattered
-  bool scat_nw8 = true;      // MISO_TRAIN_SCAT_NW4: four wavefronts where narrow rows are scattered
-  bool half = true;          // MISO_TRAIN_NO_HALF: 64-point trips for small unbinned batches too
-};
-
 // what the planner looks at beside the decoder shape
 struct TrainCase {
   bool split;           // bf16x3 decoder (the exact fp32 pack is the smaller one)
@@ -390,12 +377,12 @@ struct TrainCase {
 struct TrainPlan {
   int wavefronts;       // per workgroup: 8 (one workgroup per CU) or 4 (two)
   bool half;            // 32-point trips
-  bool rotate;          // two blocks of cell records per wavefront, MISO_TUNE_ROTATE
+  bool rotate;          // two blocks of cell records per wavefront (the kernel's rotate_records)
   unsigned blocks;      // workgroups
   size_t lds_bytes;     // the pack, then per wavefront a d-feat tile [64][FP] and, scattering, its cell records [64][L][8]
 };
 
-static TrainPlan plan_train(int C, int L, int H, int NH, const TrainCase& c, const TrainToggles& t) {
+static TrainPlan plan_train(int C, int L, int H, int NH, const TrainCase& c) {
   const PackLayout pl(C * L, H, NH);
   const int F = C * L, FP = dfeat_pitch(F), tile = 64 * FP, records = 64 * L * CELL_REC;
   const int pack = c.split ? pl.total_all - pl.s_w0 + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
@@ -411,19 +398,19 @@ static TrainPlan plan_train(int C, int L, int H, int NH, const TrainCase& c, con
   // Nothing scattered from the kernel (the mapping step): ONE workgroup of eight wavefronts per CU instead of two of
   // four -- the same two wavefronts per SIMD, half the copies of the 48 KB pack out of L2 at the start of the launch,
   // one barrier per CU (cfg-2: 72.9 -> 72.0 us, A/B in one process).
-  if (!c.scat) return t.nw8 ? TrainPlan{8, false, false, blocks8, bytes(8, 0)} : TrainPlan{4, false, false, blocks4, bytes(4, 0)};
+  if (!c.scat) return {8, false, false, blocks8, bytes(8, 0)};
   // Scattering: with room for a second block of cell records the kernel rotates its loop (feature rows up to
   // MISO_ROTATE_MAX_F floats).  Narrow rows of a binned batch (cfg-3's C = 4, L = 2): eight wavefronts and their two
   // record blocks each fit beside the pack, and the four-wavefront form is ONE workgroup per CU there (the bf16x3 pack
   // is 67 KB) -- one wavefront per SIMD.  Wide rows keep four wavefronts: their cell records would not fit beside eight
   // d-feat tiles.
-  const bool may_rotate = t.rotate && F <= MISO_ROTATE_MAX_F;
-  if (may_rotate && t.scat_nw8 && c.binned && fits(bytes(8, 2))) return {8, false, true, blocks8, bytes(8, 2)};
+  const bool may_rotate = F <= MISO_ROTATE_MAX_F;
+  if (may_rotate && c.binned && fits(bytes(8, 2))) return {8, false, true, blocks8, bytes(8, 2)};
   const bool rotate = may_rotate && fits(bytes(4, 2));
   const size_t lds = bytes(4, rotate ? 2 : 1);
   // an unbinned batch of at most one 64-point chunk per SIMD (<= 65 536 samples): 32-point trips -- the batch is latency, not
   // throughput, and half the matrix chain per wavefront on twice the wavefronts is what shortens it
-  if (!c.perm && !c.deferred && nchunks <= 1024 && t.half && !c.full_trips)
+  if (!c.perm && !c.deferred && nchunks <= 1024 && !c.full_trips)
     return {4, true, rotate, at_most(((c.n + 31) / 32 + 3) / 4, MISO_LOSS_SLOTS), lds};
   return {4, false, rotate, blocks4, lds};
 }
@@ -432,15 +419,14 @@ template <int C, int L, int H, int NH>
 static hipError_t launch_train_t(FusedShape<C, L, H, NH>, const GridK& g, const float* packed, const float* x, int64_t n,
                                  float* sdf, const int* perm, const LossInK& lin, float* dfeat_out, uint32_t defer_mask,
                                  bool scat, hipStream_t s) {
-  static const TrainToggles env = {getenv("MISO_TRAIN_NO_ROTATE") == nullptr, getenv("MISO_TRAIN_NW4") == nullptr,
-                                   getenv("MISO_TRAIN_SCAT_NW4") == nullptr, getenv("MISO_TRAIN_NO_HALF") == nullptr};
   const bool split = use_split(g.flags & MISO_F_EXACT_F32);
   const TrainCase c = {split, scat, perm != nullptr, perm || (g.flags & MISO_F_INDEX_IN_XN), dfeat_out != nullptr,
                        (g.flags & MISO_F_FULL_TRIPS) != 0, n};
-  const TrainPlan p = plan_train(C, L, H, NH, c, env);
-  // sdf_train_kernel<C, L, H, NH, SCAT, NW, HALF, SPLIT>
-  void (*k)(GridK, const float*, const float*, int64_t, float*, const int*, LossInK, float*, uint32_t) = nullptr;
-  if (p.wavefronts == 8 && !scat) {
+  const TrainPlan p = plan_train(C, L, H, NH, c);
+  // sdf_train_kernel<C, L, H, NH, SCAT, NW, HALF, SPLIT>: the plan is eight wavefronts exactly where nothing is
+  // scattered, or narrow rows are; four, in whole or half trips, for every other scattering launch
+  void (*k)(GridK, const float*, const float*, int64_t, float*, const int*, LossInK, float*, uint32_t, bool) = nullptr;
+  if (!scat) {
     k = split ? sdf_train_kernel<C, L, H, NH, false, 8, false, true> : sdf_train_kernel<C, L, H, NH, false, 8, false, false>;
   } else if (p.wavefronts == 8) {
     if constexpr (C * L <= MISO_ROTATE_MAX_F)      // (the plan names this form for such rows only)
@@ -448,15 +434,12 @@ static hipError_t launch_train_t(FusedShape<C, L, H, NH>, const GridK& g, const 
   } else if (p.half) {
     k = split ? sdf_train_kernel<C, L, H, NH, true, 4, true, true> : sdf_train_kernel<C, L, H, NH, true, 4, true, false>;
   } else {
-    k = split ? (scat ? sdf_train_kernel<C, L, H, NH, true, 4, false, true> : sdf_train_kernel<C, L, H, NH, false, 4, false, true>)
-              : (scat ? sdf_train_kernel<C, L, H, NH, true, 4, false, false> : sdf_train_kernel<C, L, H, NH, false, 4, false, false>);
+    k = split ? sdf_train_kernel<C, L, H, NH, true, 4, false, true> : sdf_train_kernel<C, L, H, NH, true, 4, false, false>;
   }
   if (!k) return hipErrorInvalidValue;
-  GridK gr = g;
-  gr.tune = p.rotate ? g.tune | MISO_TUNE_ROTATE : g.tune & ~MISO_TUNE_ROTATE;
   hipError_t e = allow_lds((const void*)k, p.lds_bytes);
   if (e != hipSuccess) return e;
-  k<<<p.blocks, 64 * p.wavefronts, p.lds_bytes, s>>>(gr, packed, x, n, sdf, perm, lin, dfeat_out, defer_mask);
+  k<<<p.blocks, 64 * p.wavefronts, p.lds_bytes, s>>>(g, packed, x, n, sdf, perm, lin, dfeat_out, defer_mask, p.rotate);
   return hipGetLastError();
 }
 
@@ -468,7 +451,7 @@ int64_t sdf_train_lds_bytes(int C, int L, int H, int NH, bool scat) {
   for (int split = 0; split < 2; ++split)
     for (int binned = 0; binned < 2; ++binned) {
       const TrainCase c = {split != 0, scat, binned != 0, binned != 0, binned != 0, false, (int64_t)1 << 20};
-      const size_t lds = plan_train(C, L, H, NH, c, TrainToggles()).lds_bytes;
+      const size_t lds = plan_train(C, L, H, NH, c).lds_bytes;
       if (lds > most) most = lds;
     }
   return most <= MISO_LDS_LIMIT ? (int64_t)most : 0;

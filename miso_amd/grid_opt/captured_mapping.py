@@ -3,7 +3,6 @@ request followed by the usual optimizer.step() -- and the fast plan with the opt
 either of them decides by is written once here; Trainer.train_step (trainer.py) only calls in."""
 import dataclasses
 import logging
-import os
 import weakref
 
 import torch
@@ -14,9 +13,6 @@ from miso_amd.step import MappingStep
 from .loss import MisoLossMapping, MisoLossMappingBase
 
 logger = logging.getLogger(__name__)
-
-_GUARD_COPY = os.environ.get('MISO_GUARD_COPY') is not None      # dev: the guard through a copy on the stream
-
 
 def plain_mapping_loss(lf):
     """The loss is the plain mapping loss: nobody overrode MisoLossMappingBase.compute."""
@@ -304,7 +300,7 @@ class _FastMappingPlan:
             # no copy kernel on the launch stream (4 us per step)
             total, step.total = step.total, torch.empty_like(step.total)
         # guards resolved while making room: those steps were skipped on the device, whose counter never moved
-        self.dev.count -= opt.note_guarded_step(total, self.states, host=None if _GUARD_COPY else step.host_total)
+        self.dev.count -= opt.note_guarded_step(total, self.states, host=step.host_total)
         return total
 
 

@@ -522,10 +522,9 @@ class GridAtlas(BaseNet):
         cfg-4 level 1, FETCH_SIZE calibrated by tools/ubench/fetch_calib.hip); in brick order a wavefront's 512 vertices are
         one 8^3 block whose 9^3 destination corners it fetches once, and a step's 64 vertices one 4^3 cube with a tight box
         for the reach test (miso_align_src_boxes)."""
-        import os
         Z, Y, X = (int(d) for d in dims)
         idx = torch.nonzero(keep.view(-1), as_tuple=False).view(-1)
-        if os.environ.get("MISO_ALIGN_ORDER", "brick") != "brick" or idx.numel() == 0:
+        if idx.numel() == 0:
             return idx
         i, j, k = idx % X, (idx // X) % Y, idx // (X * Y)
         nbx, nby = (X + 7) // 8, (Y + 7) // 8

@@ -18,9 +18,10 @@ from .modules import MLPNet
 logger = logging.getLogger(__name__)
 
 # A decoder with trainable weights keeps the fused forward and backward: GridNet.forward hands ops.sdf_fused the pack and
-# the weight gradients come from the HIP weight-gradient kernel (csrc/decoder_wgrad.hip).  MISO_NO_FUSED_WGRAD=1 (read
-# once, here) restores the op-by-op route for such a decoder: query_feature + utils.grid_decode, torch's own autograd.
-_FUSED_WGRAD = os.environ.get("MISO_NO_FUSED_WGRAD", "0") in ("", "0")
+# the weight gradients come from the HIP weight-gradient kernel (csrc/decoder_wgrad.hip).  _FUSED_WGRAD = False (tests
+# and tools set it, as their reference) restores the op-by-op route for such a decoder: query_feature +
+# utils.grid_decode, torch's own autograd.
+_FUSED_WGRAD = True
 
 
 class GridNet(BaseNet):

@@ -485,7 +485,7 @@ class SortedBatch:
     # from 76 to 47 us, and the backward goes from 240 us (atomic scatter + 15 us zero-fill) to
     # 157 us (MFMA pass + owner-computes pull, no zero-fill).  Below ~64 K points the tiles hold
     # too few points for the sweep to pay.  None = never automatic.
-    AUTO_MIN_POINTS = int(os.environ.get("MISO_SORT_MIN_POINTS", 65536)) or None
+    AUTO_MIN_POINTS = 65536
 
     def __init__(self, n: int, device, tiles=TILES, keep_metric: bool = False, need_perm: bool = True):
         """tiles: tiles per axis -- a count (1..16) or per-axis counts (tx, ty, tz) of 1..32 (MISO_TILES_XYZ).
@@ -789,7 +789,7 @@ def grad_pull_raw(features, meta, sorted_batch: SortedBatch, dfeat, grads, overw
     return grads
 
 
-_BWD2_TORCH = os.environ.get("MISO_BWD2_TORCH", "0") not in ("", "0")
+_BWD2_TORCH = False
 
 # torch.autograd.grad(sdf, x, create_graph=True) asks for the coordinate gradient only, but a custom Function's backward
 # cannot see which of its inputs the caller listed (ctx.needs_input_grad is fixed at forward time: every grid that
@@ -894,8 +894,8 @@ class _SdfFused(torch.autograd.Function):
         need_f = tuple(ctx.needs_input_grad[3:])
         if torch.is_grad_enabled():
             # create_graph=True (eikonal / smoothness terms, loss_isdf.py:367-377): the first backward as a Function whose
-            # own backward is the second-order encode (_SdfFusedBackward).  MISO_BWD2_TORCH=1 (dev A/B): the graph rebuilt
-            # from encode + torch.nn.functional.linear, as rounds 1-5 did
+            # own backward is the second-order encode (_SdfFusedBackward).  _BWD2_TORCH (tests and tools set it, as their
+            # reference): the graph rebuilt from encode + torch.nn.functional.linear, as rounds 1-5 did
             if _BWD2_TORCH:
                 with torch.enable_grad():
                     out = _mlp_torch(encode(x, features, ctx.meta), ctx.pack.weights, ctx.pack.biases)
@@ -940,7 +940,7 @@ class _SdfFusedTrainable(torch.autograd.Function):
         need_p = tuple(ctx.needs_input_grad[4 + n_feat:])
         n_w = len(pack.weights)
         if torch.is_grad_enabled():
-            # create_graph=True: the graph rebuilt from encode + torch.nn.functional.linear (the MISO_BWD2_TORCH branch of
+            # create_graph=True: the graph rebuilt from encode + torch.nn.functional.linear (the _BWD2_TORCH branch of
             # _SdfFused.backward, with the weights and biases among the wanted) -- the double backward of the weight path
             # is not built in HIP
             if _ONLY_X:
@@ -2238,7 +2238,7 @@ class AlignPlan:
     def __init__(self, R0, t0, pairs, *, loss_type="L2", align_weight=3000.0, overlap_thresh=1e-2, lr=1e-2,
                  betas=(0.9, 0.999), eps=1e-8, reg_weight=0.0, reg_thresh_rad=1.0, reg_thresh_m=1.0,
                  rel_change_thresh=0.0, ring_iters=0, save_poses=False, cull=None):
-        """cull (default on; MISO_ALIGN_CULL=0 switches it off): one box per run of 64 source vertices
+        """cull (default on, None included): one box per run of 64 source vertices
         (miso_align_src_boxes, built once per source list) lets the residual kernel skip runs that cannot reach the
         destination bound at the current poses without reading them -- same sums, fewer bytes."""
         _require_hip(R0, t0)
@@ -2256,8 +2256,7 @@ class AlignPlan:
         cfg.rel_change_thresh = float(rel_change_thresh)
         cfg.lr, cfg.beta1, cfg.beta2, cfg.eps = float(lr), float(betas[0]), float(betas[1]), float(eps)
         self._keep = []
-        if cull is None:
-            cull = os.environ.get("MISO_ALIGN_CULL", "1") != "0"
+        cull = cull is None or bool(cull)
         boxes_of = {}                                 # one table per source list (a submap is the source of up to S-1 pairs)
         descs = (_lib.AlignPair * max(P, 1))()
         for i, pr in enumerate(pairs):

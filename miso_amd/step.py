@@ -242,7 +242,7 @@ class MappingStep:
             rows = [(p, g, st[0], st[1], st[2], self.sorted is None or bool((self._adam_clears >> l) & 1), tch)
                     for l, (p, g, st, tch) in enumerate(zip(self.features, self.grads, self.adam_state, self.touched))
                     if g is not None]
-            one = 2 <= len(rows) <= ops._lib.ADAM_MAX_TENSORS and os.environ.get("MISO_ADAM_PER_LEVEL") is None
+            one = 2 <= len(rows) <= ops._lib.ADAM_MAX_TENSORS
             self._adam_key, self._adam_rows, self._adam_multi = key, rows, ops.adam_tensors(rows) if one else False
         return self._adam_multi, self._adam_rows
 
@@ -268,8 +268,7 @@ class MappingStep:
         """Whether the binned step runs as sort -> sdf_train_kernel -> pull (decided once: the grids do not change)."""
         ok = self._fused_train_ok
         if ok is None:
-            ok = self._fused_train_ok = (os.environ.get("MISO_NO_FUSED_TRAIN") is None      # dev: the two-launch form
-                                         and ops.sdf_train_supported(self.features, self.meta, self.grads, self.pack))
+            ok = self._fused_train_ok = ops.sdf_train_supported(self.features, self.meta, self.grads, self.pack)
         return ok
 
     @property

@@ -398,3 +398,41 @@ def test_train_kernel_lds_fits_for_every_fused_shape():
     assert ops.sdf_train_supported(feats, meta, [feats[0], None, None]) and not ops.sdf_train_supported(feats, meta, [None] * 3)
     ncdhw = [torch.zeros(1, 8, 4, 4, 4)] * 3          # channel stride != 1: no fused kernel takes the layout
     assert not ops.sdf_train_supported(ncdhw, meta, [ncdhw[0], None, None])
+
+
+def _environment_reads():
+    """-> (names, sites, literal): the variables the library reads -- getenv("NAME") in miso_amd/csrc, os.environ in the
+    package's Python -- with the number of read sites and of those whose name is a string literal."""
+    import glob
+    names, sites, literal = set(), 0, 0
+    csrc = os.path.join(ROOT, "miso_amd", "csrc")
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.hpp"))):
+        code = re.sub(r"//[^\n]*", "", open(path).read())
+        sites += len(re.findall(r"\bgetenv\s*\(", code))
+        found = re.findall(r"\bgetenv\s*\(\s*\"([A-Za-z0-9_]+)\"\s*\)", code)
+        literal += len(found)
+        names.update(found)
+    # (every source of the library is a .hip or a .hpp; Python reads go through `os.`: importing the names is refused)
+    for path in sorted(glob.glob(os.path.join(ROOT, "miso_amd", "**", "*.py"), recursive=True)):
+        code = open(path).read()
+        assert not re.search(r"from\s+os\s+import[^\n]*\b(environ|getenv|putenv)\b", code), path
+        sites += len(re.findall(r"\bos\s*\.\s*(?:environ|getenv|putenv)\b", code))
+        found = re.findall(r"\bos\.environ(?:\.get|\.setdefault|\.pop)?\s*[\(\[]\s*[\"']([A-Za-z0-9_]+)[\"']", code)
+        literal += len(found)
+        names.update(found)
+    return names, sites, literal
+
+
+def test_readme_lists_every_environment_variable_the_library_reads():
+    """The table under "Environment variables" in README.md is closed: it names exactly the variables that miso_amd/csrc
+    reads through getenv and the Python package through os.environ, and every such read names its variable literally,
+    so that none can be added without a row that says what it is for."""
+    names, sites, literal = _environment_reads()
+    assert sites == literal, "an environment read whose variable is not a string literal"
+    assert names >= {"MISO_HIP_LIB", "MISO_EXACT_F32", "MISO_PULL_MC"}      # (the scan still finds what is known to be there)
+    readme = open(os.path.join(ROOT, "README.md")).read()
+    section = readme.split("### Environment variables", 1)[1].split("\n#", 1)[0]
+    rows = [ln.split("|")[1] for ln in section.splitlines() if ln.startswith("| `")]
+    listed = [n for cell in rows for n in re.findall(r"`([A-Za-z0-9_]+)`", cell)]
+    assert len(listed) == len(set(listed)), "a variable is listed twice"
+    assert set(listed) == names, (sorted(names - set(listed)), sorted(set(listed) - names))

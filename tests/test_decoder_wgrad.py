@@ -276,7 +276,7 @@ def test_autograd_end_to_end(monkeypatch):
     sdf_f, got_f = _backward(net, x, True)
     assert calls, "a trainable decoder did not take the fused route"
     sdf_t, got_t = _backward(net, x, False)
-    assert len(calls) == 1, "MISO_NO_FUSED_WGRAD did not restore the torch route"
+    assert len(calls) == 1, "_FUSED_WGRAD = False did not restore the torch route"
     assert not torch.equal(sdf_f, sdf_t), "both routes returned the same bits: is the switch connected?"
     assert (sdf_f - sdf_t).abs().max().item() <= 1e-5
     o = Oracle64(x, [f.detach().cpu() for f in feats], net.bound.detach().cpu(), [w.detach().cpu() for w in ws],

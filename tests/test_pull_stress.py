@@ -227,7 +227,7 @@ def test_heavy_tiles_are_cut_and_summed_exactly(shape, monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("seed,C", [(0, 4), (1, 4), (2, 4), (3, 8)])
 def test_dense_wave_scatter_matches_pull_and_atomics(seed, C, monkeypatch):
-    """the matrix-core push of coarse levels under a crowd (the knob MISO_DENSE_MIN is read once by the
+    """the matrix-core push of coarse levels under a crowd (the threshold is a constant of the
     library, so the crowd is real): a batch that averages >= 100 points per tile on a two-level ScanNet-like grid
     pushes both levels; the gradients equal the unsorted atomic path's to fp32 summation-order tolerance."""
     from miso_amd import ops

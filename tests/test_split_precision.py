@@ -144,7 +144,7 @@ def test_exact_fp32_form_still_passes_its_parity_checks():
 def test_fused_double_backward_equals_the_torch_linear_chain(n):
     """create_graph=True through the fused decoder (round 6: ops._SdfFusedBackward -- the first backward keeps its d-feat
     rows, the second-order encode differentiates them) against the graph rebuilt from encode + torch.nn.functional.linear
-    (rounds 1-5, MISO_BWD2_TORCH), on an eikonal + |sdf| loss (grid_opt/loss_isdf.py:96-152,367-377): loss, and the
+    (rounds 1-5, ops._BWD2_TORCH), on an eikonal + |sdf| loss (grid_opt/loss_isdf.py:96-152,367-377): loss, and the
     gradient of every level.  n = 70 000 takes the binned forward (its sign bits are in tile order: the first backward
     then runs in that order too, _SdfFusedBackward._rows); ReLU-tie points carry no weight."""
     from miso_amd import ops

@@ -1,5 +1,5 @@
 """A training step with a TRAINABLE decoder: the fused route (one-kernel forward, one-kernel backward, HIP weight gradients:
-csrc/decoder_wgrad.hip) against the op-by-op route such a decoder took before (MISO_NO_FUSED_WGRAD=1: query_feature +
+csrc/decoder_wgrad.hip) against the op-by-op route such a decoder took before (grid_net._FUSED_WGRAD = False: query_feature +
 utils.grid_decode under torch autograd), and the frozen-decoder step for context.
 
 Step = GridNet.forward + L1 loss + backward + DenseAdam over the grids and the decoder, 262 144 uniform points, at

@@ -1,6 +1,6 @@
 """dev / bench extra: one eikonal step through the fused decoder at cfg-2 -- sdf = fused(x), g = d sdf / d x with
 create_graph=True, loss = mean (|g| - 1)^2 + mean |sdf|, backward to the grids (grid_opt/loss_isdf.py:96-152,367-377).
-MISO_BWD2_TORCH=1: the double backward rebuilt from encode + torch.nn.functional.linear (rounds 1-5)."""
+--torch-chain: the double backward rebuilt from encode + torch.nn.functional.linear (rounds 1-5)."""
 import os
 import sys
 
@@ -48,5 +48,6 @@ def timed(iters=10):
 
 
 if __name__ == "__main__":
+    ops._BWD2_TORCH = "--torch-chain" in sys.argv[1:]
     print("eikonal step through the fused decoder, 262144 points (%s): %.1f us" %
           ("torch linear chain" if ops._BWD2_TORCH else "fused double backward", timed()))

@@ -8,6 +8,13 @@ second set: one point per every second cell of the coarse level, so that no vert
 depends on the order of the atomics (and a single wavefront, so the pose sums of the atlas backward have one order).
 pair_latent: 193 vertices are one workgroup (launch_pair_latent: 2048 per workgroup), one fp64 atomic per sum.
 
+The binned calls (the sort, the binned forward / backward / training step, the pull in each of its forms, the push, the
+batched pair stage) run three times on the same inputs: an output whose three runs agree bit for bit is recorded by its
+digest, one whose runs differ -- sums ordered by LDS or float atomics -- as "not reproducible run to run", which is then
+what both commits must say.  The sort leaves the order inside a tile to its atomics, so the binned batch is put into a
+canonical order first (every tile's points by their original index) and is in the list itself: equal lists mean that
+both commits worked on the same binned batch.
+
     python tools/sampler_digest.py [--out digests.json]"""
 import argparse
 import hashlib
@@ -156,6 +163,96 @@ def pair(tag, feats, meta, x):
             put(f"{tag}/pair_latent.{loss}.g{i}", t.grad)
 
 
+def repeatable(name, fn, runs=3):
+    """fn() -> [(label, tensor)]: the digest of every tensor whose `runs` runs agree, else that they do not"""
+    seen = {}
+    for _ in range(runs):
+        for label, t in fn():
+            torch.cuda.synchronize()
+            seen.setdefault(label, set()).add(hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest())
+    for label, digests in seen.items():
+        OUT[f"{name}/{label}"] = digests.pop() if len(digests) == 1 else "not reproducible run to run"
+
+
+def binned(tag, C, pack, tiles):
+    """8192 points (a uniform cloud and a clump: the push's crowd of >= 100 per tile at 4 tiles per axis) on 8^3, 16^3
+    and 32^3 vertices, binned at `tiles` per axis: 4 -- even bricks, the block kernel -- or 5 -- the wavefront kernel."""
+    n, sizes = 8192, (8, 16, 32)
+    feats = [rnd(70 + l, 1, C, s, s, s).mul_(0.1).to(DEV).contiguous(memory_format=torch.channels_last_3d)
+             for l, s in enumerate(sizes)]
+    meta = ops.GridMeta.from_bound(BOUND)
+    lo, hi = torch.tensor([b[0] for b in BOUND]), torch.tensor([b[1] for b in BOUND])
+    u = torch.rand(n, 3, generator=torch.Generator().manual_seed(71))
+    u[n // 2:] = 0.4 + 0.1 * u[n // 2:]
+    x = (lo + u * (hi - lo)).to(DEV)
+    sb = ops.SortedBatch(n, DEV, tiles=tiles)
+
+    def sort_canonical():
+        sb.sort(x, meta)
+        ends = sb.tile_offsets.long()[1:].contiguous()
+        tile = torch.searchsorted(ends, torch.arange(n, device=DEV), right=True)
+        order = torch.argsort(tile * n + sb.perm.long())
+        sb.xn_sorted.copy_(sb.xn_sorted[order])
+        sb.perm.copy_(sb.perm[order])
+        return [(k, getattr(sb, k)) for k in ("xn_sorted", "perm", "tile_offsets")]
+
+    repeatable(tag + "/sort", sort_canonical)
+    rows = rnd(72, n, 3 * C).to(DEV)
+    every = [True] * 3
+    for form, env in (("mc", {}), ("vector", {"MISO_PULL_MC": "0"}),
+                      ("vector_no_split", {"MISO_PULL_MC": "0", "MISO_PULL_NO_SPLIT": "1"})):
+        os.environ.update(env)
+        try:
+            repeatable(f"{tag}/pull/{form}", lambda: [(f"grad{l}", g) for l, g in enumerate(
+                ops.grad_pull_raw(feats, meta, sb, rows, [torch.empty_like(f) for f in feats]))])
+        finally:
+            for k in env:
+                os.environ.pop(k)
+    lin = torch.cat((rnd(73, n, 1) * 0.1, torch.ones(n, 3)), 1).to(DEV).contiguous()
+
+    def two_launches():
+        slots, mask = torch.zeros(_lib.LOSS_SLOTS, 2, device=DEV), ops.sdf_mask_buffer(pack, n, DEV)
+        gpred, sdf = torch.empty(n, device=DEV), torch.empty(n, 1, device=DEV)
+        ops.sdf_fwd_loss_raw(feats, meta, pack, sb, lin, mask, gpred, slots, sdf_out=sdf)
+        _, grads = ops.sdf_bwd_raw(x, feats, meta, pack, gpred, mask, False, every, sorted_batch=sb, overwrite=True,
+                                   gsdf_sorted=True)
+        return [("loss", slots), ("sdf", sdf), ("gsdf", gpred), ("mask", mask), ("rows", sb._ws[:n * 3 * C].clone())] + \
+               [(f"grad{l}", g) for l, g in enumerate(grads)]
+
+    def one_launch():
+        slots, sdf = torch.zeros(_lib.LOSS_SLOTS, 2, device=DEV), torch.empty(n, 1, device=DEV)
+        grads = [torch.empty_like(f) for f in feats]
+        ops.sdf_train_raw(feats, meta, pack, sb, lin, slots, grads, sdf_out=sdf)
+        return [("loss", slots), ("sdf", sdf), ("rows", sb._ws[:n * 3 * C].clone())] + [(f"grad{l}", g) for l, g in enumerate(grads)]
+
+    for exact in (False, True):
+        with ops.exact_fp32(exact):
+            form = "exact" if exact else "split"
+            repeatable(f"{tag}/fwd_loss+bwd/{form}", two_launches)
+            repeatable(f"{tag}/train/{form}", one_launch)
+
+
+def pair_stage(tag, C, gate):
+    """The batched pair stage (AlignPlan.iteration_a) of three submaps and their six pairs: 1500 source vertices per pair
+    are one workgroup; with gate points the launch is pair_stage_kernel, without them pair_latent_batch_kernel."""
+    feats, meta = features(C, True), ops.GridMeta.from_bound(BOUND)
+    lo, hi = torch.tensor([b[0] for b in BOUND]), torch.tensor([b[1] for b in BOUND])
+    coords = (lo + torch.rand(1500, 3, generator=torch.Generator().manual_seed(81)) * (hi - lo)).to(DEV)
+    fsrc = rnd(82, 1500, 2 * C).to(DEV)
+    R0 = torch.eye(3).repeat(3, 1, 1).to(DEV)
+    t0 = torch.tensor([[0.0, 0.0, 0.0], [0.3, -0.2, 0.1], [-0.4, 0.5, 0.2]]).reshape(3, 3, 1).to(DEV)
+    descr = [dict(src=a, dst=b, coords=coords, feats_src=fsrc, feats_dst=feats, meta_dst=meta,
+                  gate_pts=coords[:700].contiguous() if gate else None) for a in range(3) for b in range(3) if a != b]
+
+    def stage():
+        plan = ops.AlignPlan(R0, t0, descr, loss_type="L2")
+        plan.params[1, :3] = torch.tensor([0.02, -0.01, 0.03], device=DEV)
+        plan.iteration_a()
+        return [("pair_out", plan.pair_out.clone()), ("overlap_counts", plan.overlap_counts.clone())]
+
+    repeatable(f"{tag}/gate={gate}", stage)
+
+
 def run(tag, fn, *args):
     """a flag set or layout that an entry point refuses is recorded as such (the refusal has to stay the same too)"""
     try:
@@ -182,6 +279,12 @@ def main():
                     tag = f"{fname}/C{C}/{'exact' if exact else 'split'}"
                     run(tag, fused, feats, meta, pack, x, xs)
                     run(tag, atlas, C, meta, pack, x, xs)
+    for C in (4, 8):
+        pack = decoder(3 * C, 64)
+        for tiles in (4, 5):
+            run(f"binned/C{C}/tiles{tiles}", binned, C, pack, tiles)
+        for gate in (False, True):
+            run(f"pair_stage/C{C}", pair_stage, C, gate)
     for k in sorted(OUT):
         print(OUT[k], k)
     if a.out:
