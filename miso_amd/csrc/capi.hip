@@ -1,5 +1,21 @@
-// extern "C" entry points of libmiso_hip.so (see include/miso_hip.h).
-// Argument validation + conversion to kernel-side structs + dispatch.
+// extern "C" entry points of libmiso_hip.so (see include/miso_hip.h): each one is the named argument checks of its
+// family (the anonymous namespace below), the conversion to the kernel-side structs, then the launch -- nothing is
+// launched before every check has passed.  tests/golden/capi_refusals.json pins every refusal.
+//
+// Sibling differences, kept as found (a behaviour fix is its own change; the refusal table records each):
+//  * a count >= 2^31 is MISO_E_BADARG from miso_nn_knn, miso_nn_knn_all_pairs, miso_nn_knn_normals, miso_sort_points and
+//    miso_atlas_sdf_fwd's lattice; MISO_E_TOOLARGE from every other entry point.
+//  * mlp == NULL is MISO_E_BADARG from miso_sdf_bwd_rows, miso_sdf_wgrad and the three atlas calls; MISO_E_UNSUPPORTED
+//    from the other fused calls (and from miso_mlp_pack, which says UNSUPPORTED for packed == NULL too).
+//  * a loss type out of range is MISO_E_BADARG from the mapping-loss and alignment calls, MISO_E_UNSUPPORTED from
+//    miso_lm_normal_eq, miso_lm_track_step and miso_track_adam_step.
+//  * n == 0: miso_sdf_fwd_loss and miso_sdf_fwd_sorted_loss zero the loss slots without looking at grid, mlp or packed,
+//    miso_sdf_train* check them first; miso_atlas_sdf_bwd and miso_atlas_sphere_trace return before their per-point
+//    pointers are looked at, miso_atlas_sdf_fwd has no such return.
+//  * the tracker steps check grid shape, mlp and packed in the fused forward, BEHIND their first launch (the head).
+//  * miso_sdf_bwd_rows refuses the host-side gradient flags (OVERWRITE, SDF_SORTED, ZEROED); miso_sdf_bwd ignores them.
+//  * miso_adam_dense asks no alignment of its four arrays; miso_adam_touched asks 4-byte alignment of `active` even
+//    for numel == 0, miso_adam_step_dev and the multi-tensor calls only where `touched` is given.
 #include <stdlib.h>
 #include <string.h>
 
@@ -12,6 +28,17 @@
 using namespace miso;
 
 namespace {
+
+// ---- small predicates --------------------------------------------------------------------------------------------------
+inline bool fits32(int64_t n) { return n < ((int64_t)1 << 31); }            // a size the 32-bit index math holds
+inline bool fits_fp32_count(int64_t n) { return n < ((int64_t)1 << 24); }   // ... an fp32 counter holds exactly
+inline bool fits_voxel_key(int64_t n) { return n < ((int64_t)1 << 22); }    // ... the index field of the voxel sort key holds
+template <class... P> inline bool aligned(uintptr_t bytes, const P*... p) {   // NULL passes: optional pointers
+  return ((... | (uintptr_t)p) & (bytes - 1)) == 0;
+}
+template <class... P> inline bool all_set(const P*... p) { return (... && (p != nullptr)); }
+template <class... P> inline bool set_if(int64_t n, const P*... p) { return n <= 0 || all_set(p...); }   // non-NULL when n > 0
+inline bool mapping_loss_ok(int loss_type) { return loss_type == 1 || loss_type == 2; }                  // L1 | L2
 
 int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) {
   if (!in || in->n_levels < 1 || in->n_levels > MISO_MAX_LEVELS) return MISO_E_BADARG;
@@ -31,7 +58,7 @@ int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) 
     if (s.C < 1 || s.X < 1 || s.Y < 1 || s.Z < 1) return MISO_E_BADARG;
     if (need_data && !s.data) return MISO_E_BADARG;
     if (s.sC < 0 || s.sX < 0 || s.sY < 0 || s.sZ < 0) return MISO_E_BADARG;
-    if (level_span(s) >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+    if (!fits32(level_span(s))) return MISO_E_TOOLARGE;
     LevelK& d = out->lv[l];
     d.data = s.data; d.grad = s.grad; d.gg = nullptr;
     d.touched = s.grad ? s.grad_touched : nullptr;
@@ -40,7 +67,7 @@ int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) 
     d.foff = foff;
     foff += s.C;
     bool ok = (s.C % 4 == 0) && (s.sC == 1 || s.C == 1) && (s.sX % 4 == 0) && (s.sY % 4 == 0) &&
-              (s.sZ % 4 == 0) && (((uintptr_t)s.data & 15u) == 0) && (((uintptr_t)s.grad & 15u) == 0);
+              (s.sZ % 4 == 0) && aligned(16, s.data, s.grad);
     v4 = v4 && ok;
   }
   out->F = foff;
@@ -61,10 +88,131 @@ int fused_shape(const GridK& g, bool vec4, const miso_mlp_t* m, int* C, int* L, 
   return MISO_OK;
 }
 
+// ---- the fused call: grid + decoder as the fused kernels take them ----------------------------------------------------
+struct FusedCall { GridK g; bool vec4; int C, L, H, NH; };      // (C, L, H, NH): the kernel table's key
+// FUSED_ATLAS: `grid` is the atlas' shape grid -- the levels the kernels address are the plan's, which
+// miso_atlas_plan_build admitted as 16-byte addressable, so the shape's own vec4 is not asked; the key starts from the
+// one decoder the atlas kernels were first built for (H = 64, NH = 1)
+enum FusedKind { FUSED_GRID, FUSED_ATLAS };
+
+// the grid half: what a query for features only stops at (miso_atlas_sdf_fwd without sdf)
+int fused_grid(FusedCall* f, const miso_grid_t* grid, bool need_data) {
+  if (int rc = convert_grid(grid, &f->g, need_data, &f->vec4)) return rc;
+  f->C = f->g.lv[0].C; f->L = f->g.n_levels; f->H = 64; f->NH = 1;
+  return MISO_OK;
+}
+// the queries' form: no packed weights
+int fused_query(FusedCall* f, const miso_grid_t* grid, const miso_mlp_t* mlp, bool need_data, FusedKind kind = FUSED_GRID) {
+  if (int rc = fused_grid(f, grid, need_data)) return rc;
+  return fused_shape(f->g, kind == FUSED_ATLAS ? true : f->vec4, mlp, &f->C, &f->L, &f->H, &f->NH);
+}
+// the launching form: `packed` (miso_mlp_pack's output) is read with 16-byte loads
+int fused_call(FusedCall* f, const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, bool need_data,
+               FusedKind kind = FUSED_GRID) {
+  if (!packed || !aligned(16, packed)) return MISO_E_BADARG;
+  return fused_query(f, grid, mlp, need_data, kind);
+}
+
+// ---- the atlas call: plan, pose table and flags of the three atlas entry points -----------------------------------------
+int atlas_call(AtlasK* a, const void* plan, int32_t n_submaps, const float* poses, int64_t n, uint32_t flags) {
+  if (!plan || !poses || n_submaps < 1 || n < 0) return MISO_E_BADARG;
+  if (flags & ~(MISO_F_EXACT_F32 | MISO_F_ATLAS_NO_BOUND)) return MISO_E_BADARG;
+  memset(a, 0, sizeof(*a));
+  a->submaps = reinterpret_cast<const GridK*>(plan);
+  a->poses = poses; a->n_submaps = n_submaps; a->n = n;
+  a->no_bound = (flags & MISO_F_ATLAS_NO_BOUND) ? 1 : 0;
+  return MISO_OK;
+}
+
+// ---- clouds, ray pairs, the caller's mesh arrays, an index with its workspace ----------------------------------------------
+// a cloud p (n, 3) of row pitch ld, and what the call writes per point
+template <class... Out> int check_cloud(const float* p, int64_t ld, int64_t n, const Out*... out) {
+  if (ld < 3 || n < 0) return MISO_E_BADARG;
+  if (!fits32(n)) return MISO_E_TOOLARGE;
+  return set_if(n, p, out...) ? MISO_OK : MISO_E_BADARG;
+}
+// kept as found: the k-nearest calls say BADARG where their siblings say TOOLARGE
+inline int knn_code(int rc) { return rc == MISO_E_TOOLARGE ? MISO_E_BADARG : rc; }
+
+// n rays: origins and dirs (n, 3) of their row pitches, and what the call writes per ray
+template <class... Out> int check_rays(const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n,
+                                       const Out*... out) {
+  if (ld_o < 3 || ld_d < 3 || n < 0) return MISO_E_BADARG;
+  if (!fits32(n)) return MISO_E_TOOLARGE;
+  return set_if(n, origins, dirs, out...) ? MISO_OK : MISO_E_BADARG;
+}
+
+// a mesh in the caller's arrays: verts (n_vert, 3) fp32, tris (n_tri, 3) int64 (a mesh of triangles without a vertex is
+// one whose triangles are never hit)
+int check_mesh_arrays(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri) {
+  if (n_vert < 0 || n_tri < 0 || ld_v < 3 || ld_t < 3) return MISO_E_BADARG;
+  if (!fits32(n_tri)) return MISO_E_TOOLARGE;
+  return n_tri == 0 || (tris && (n_vert == 0 || verts)) ? MISO_OK : MISO_E_BADARG;
+}
+
+// an index over `indexed` targets or triangles has them in its workspace, which the kernels read with 16-byte loads
+inline bool index_ready(int64_t indexed, const void* workspace) {
+  return indexed == 0 || (workspace && aligned(16, workspace));
+}
+
+// the cell grid of a plan, as miso_nn_plan writes it for both kinds of index (MISO_MESH_MAX_CELLS == MISO_NN_MAX_CELLS)
+bool plan_grid_ok(const int32_t dims[3], int64_t cells, float cell, float coord_mag) {
+  if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || cells < 1 || cells > MISO_NN_MAX_CELLS) return false;
+  if ((int64_t)dims[0] * dims[1] > MISO_NN_MAX_CELLS || (int64_t)dims[0] * dims[1] * dims[2] != cells) return false;
+  return cell > 0.0f && cell < __builtin_huge_valf() && coord_mag >= 0.0f;
+}
+// a plan as miso_nn_plan / miso_mesh_plan writes it (the struct is the caller's memory: the kernels index by it)
+bool nn_plan_ok(const miso_nn_plan_t* p) {
+  if (!p || p->n_tgt < 0 || !fits32(p->n_tgt) || p->max_rings < 0 || p->max_rings > MISO_NN_MAX_RINGS) return false;
+  return plan_grid_ok(p->dims, p->cells, p->cell, p->coord_mag);
+}
+bool mesh_plan_ok(const miso_mesh_plan_t* p) {
+  if (!p || p->n_tri < 0 || !fits32(p->n_tri)) return false;
+  return plan_grid_ok(p->dims, p->cells, p->cell, p->coord_mag) && p->coord_mag < __builtin_huge_valf() &&
+         p->widen >= 0.0f && p->widen <= p->coord_mag;
+}
+// a mesh index as miso_mesh_build fills it, or left it: plan, workspace and the per-cell lists
+bool mesh_index_ok(const miso_mesh_plan_t* p, const void* workspace, const int32_t* lists, int64_t capacity) {
+  if (!mesh_plan_ok(p) || capacity < 0) return false;
+  return p->n_tri == 0 || (index_ready(p->n_tri, workspace) && (capacity == 0 || lists));
+}
+inline bool nn_k_ok(int32_t k) { return k >= 1 && k <= MISO_NN_KNN_MAX; }
+
+// ---- Adam: the pointers of one tensor --------------------------------------------------------------------------------------
+// the four arrays are read and written 16 bytes at a time; the flag bytes four at a time where `touched` drives the step
+bool adam_tensor_ok(const float* param, const float* grad, const float* exp_avg, const float* exp_avg_sq,
+                    const uint8_t* active, const uint8_t* touched, int64_t numel) {
+  if (numel < 0 || !set_if(numel, param, grad, exp_avg, exp_avg_sq, active)) return false;
+  if (!aligned(16, param, grad, exp_avg, exp_avg_sq)) return false;
+  return !touched || aligned(4, active, touched);
+}
+bool adam_tensors_ok(const miso_adam_tensor_t* tensors, int32_t n_tensors) {
+  if (!tensors || n_tensors < 1 || n_tensors > MISO_ADAM_MAX_TENSORS) return false;
+  for (int i = 0; i < n_tensors; ++i) {
+    const miso_adam_tensor_t& t = tensors[i];
+    if (!adam_tensor_ok(t.param, t.grad, t.exp_avg, t.exp_avg_sq, t.active, t.touched, t.numel)) return false;
+  }
+  return true;
+}
+
+// ---- tracker: miso_lm_track_t as both steps read it -------------------------------------------------------------------------
+// step_scratch: the one per-row buffer that differs between the steps (ones | grad_pred)
+bool lm_track_ok(const miso_lm_track_t* a, const float* step_scratch) {
+  if (a->n < 0 || !all_set(a->R_base, a->t_base, a->rot_correction, a->trans_correction, a->pose, a->sums, a->info)) return false;
+  if (!set_if(a->n, a->coords_frame, a->target, a->coords_world, a->sdf, a->grad, a->relu_mask, step_scratch)) return false;
+  return a->stride_target >= 0 && a->stride_valid >= 0 && a->stride_frame_ids >= 0;
+}
+// the steps want d sdf / d x only: a grid that carries a gradient buffer is refused
+bool has_grad_buffers(const miso_grid_t* grid) {
+  for (int l = 0; l < grid->n_levels && l < MISO_MAX_LEVELS; ++l)
+    if (grid->level[l].grad) return true;
+  return false;
+}
+
 // what a call asks of plan_grad (sorted == nullptr: an unbinned batch, nothing is pulled), the pointers its launch reads
 GradAsk grad_ask(GradCaller who, bool v4, const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, int64_t ld,
                  const void* workspace, bool ggx) {
-  GradAsk a = {who, v4, grid->flags, n, ld, ggx, workspace && ((uintptr_t)workspace & 15u) == 0, false, false, 0, 0};
+  GradAsk a = {who, v4, grid->flags, n, ld, ggx, workspace && aligned(16, workspace), false, false, 0, 0};
   if (!sorted) return a;
   a.sorted = true; a.xn = sorted->xn_sorted != nullptr; a.tiles = sorted->tiles_per_axis;
   a.queue_ints = sorted->pull_queue ? sorted->pull_queue_ints : 0;
@@ -87,6 +235,38 @@ LossInK loss_in(int loss_type, float w_sdf, float w_fs, float trunc, const float
   lin.n_live = n_live;
   return lin;
 }
+// an empty batch has a loss of zero: every slot is written, as by a launch
+hipError_t zero_loss_slots(float* loss_slots, hipStream_t stream) {
+  return launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, stream);
+}
+
+// perm_optional: the entry point can take the original index from xn_sorted[p].w (miso_sdf_train_sorted)
+int check_sorted(const miso_sorted_t* s, int64_t n, bool perm_optional = false) {
+  if (!s || !s->tile_offsets) return MISO_E_BADARG;
+  if (n > 0 && (!s->x_sorted && !s->xn_sorted)) return MISO_E_BADARG;   // an empty batch has no buffers
+  if (n > 0 && !s->perm && !(perm_optional && s->xn_sorted)) return MISO_E_BADARG;
+  if (!aligned(16, s->xn_sorted)) return MISO_E_BADARG;
+  { int t3_[3]; if (!tiles_xyz(s->tiles_per_axis, t3_)) return MISO_E_BADARG; }
+  return MISO_OK;
+}
+
+// Sorted batches: read the pre-normalised float4 points instead of the metric ones.
+const float* sorted_points(GridK* g, const miso_sorted_t* sorted) {
+  if (!sorted->xn_sorted) return sorted->x_sorted;
+  if (!(g->flags & MISO_F_COORDS_NORMALIZED)) {
+    for (int a = 0; a < 3; ++a) g->gscale[a] = 2.0f / (g->bmax[a] - g->bmin[a]);   // axis_coord's m
+    g->flags |= MISO_F_COORDS_NORMALIZED;
+  }
+  g->xstride = 4;
+  return sorted->xn_sorted;
+}
+
+int mc_check_dims(int32_t nx, int32_t ny, int32_t nz) {
+  if (nx < 1 || ny < 1 || nz < 1) return MISO_E_BADARG;
+  // cell ids are 32-bit; sample indices (and keys = 3 * index + axis) are 64-bit
+  if (!fits32((int64_t)nx * ny * nz)) return MISO_E_TOOLARGE;
+  return 0;
+}
 
 }  // namespace
 
@@ -106,23 +286,18 @@ const char* miso_error_string(int code) {
 
 int miso_encode_fwd(const miso_grid_t* grid, const float* x, int64_t n, float* feats, int64_t ld_out,
                     void* stream) {
-  if (n < 0 || (n > 0 && (!x || !feats))) return MISO_E_BADARG;
+  if (n < 0 || !set_if(n, x, feats)) return MISO_E_BADARG;
   GridK g; bool v4;
-  int rc = convert_grid(grid, &g, true, &v4);
-  if (rc) return rc;
+  if (int rc = convert_grid(grid, &g, true, &v4)) return rc;
   if (ld_out < g.F) return MISO_E_BADARG;
   return (int)launch_encode_fwd(g, v4, x, n, feats, ld_out, nullptr, (hipStream_t)stream);
 }
 
-static const float* sorted_points(GridK* g, const miso_sorted_t* sorted);
-static int check_sorted(const miso_sorted_t* s, int64_t n, bool perm_optional = false);
-
 static int encode_bwd_impl(const miso_grid_t* grid, const float* x, int64_t n, const float* grad_feats,
                            int64_t ld_g, float* grad_x, const miso_sorted_t* sorted, void* stream) {
-  if (n < 0 || (n > 0 && !grad_feats)) return MISO_E_BADARG;
+  if (n < 0 || !set_if(n, grad_feats)) return MISO_E_BADARG;
   GridK g; bool v4;
-  int rc = convert_grid(grid, &g, grad_x != nullptr, &v4);
-  if (rc) return rc;
+  if (int rc = convert_grid(grid, &g, grad_x != nullptr, &v4)) return rc;
   if (ld_g < g.F) return MISO_E_BADARG;
   const int* perm = nullptr;
   if (sorted) { x = sorted_points(&g, sorted); perm = sorted->perm; }
@@ -137,18 +312,16 @@ int miso_encode_bwd(const miso_grid_t* grid, const float* x, int64_t n, const fl
 
 int miso_encode_bwd_sorted(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n,
                            const float* grad_feats, int64_t ld_g, float* grad_x, void* stream) {
-  int rc = check_sorted(sorted, n);
-  if (rc) return rc;
+  if (int rc = check_sorted(sorted, n)) return rc;
   return encode_bwd_impl(grid, nullptr, n, grad_feats, ld_g, grad_x, sorted, stream);
 }
 
 static int encode_bwd2_impl(const miso_grid_t* grid, const miso_grid_t* gg_grid, const float* x, int64_t n,
                             const float* grad_feats, int64_t ld_g, const float* gg_x, float* gg_out,
                             int64_t ld_gg, float* g_x, const miso_sorted_t* sorted, void* stream) {
-  if (n < 0 || (n > 0 && (!grad_feats || !gg_out))) return MISO_E_BADARG;
+  if (n < 0 || !set_if(n, grad_feats, gg_out)) return MISO_E_BADARG;
   GridK g; bool v4;
-  int rc = convert_grid(grid, &g, true, &v4);
-  if (rc) return rc;
+  if (int rc = convert_grid(grid, &g, true, &v4)) return rc;
   if (ld_g < g.F || ld_gg < g.F) return MISO_E_BADARG;
   if (gg_grid) {
     if (gg_grid->n_levels != grid->n_levels) return MISO_E_BADARG;
@@ -159,7 +332,7 @@ static int encode_bwd2_impl(const miso_grid_t* grid, const miso_grid_t* gg_grid,
       if (a.C != b.C || a.X != b.X || a.Y != b.Y || a.Z != b.Z || a.sC != b.sC || a.sX != b.sX ||
           a.sY != b.sY || a.sZ != b.sZ)
         return MISO_E_BADARG;  // cotangent must share the layout of the grid
-      if (((uintptr_t)b.data & 15u) != 0) v4 = false;
+      if (!aligned(16, b.data)) v4 = false;
       g.lv[l].gg = b.data;
     }
   }
@@ -179,8 +352,7 @@ int miso_encode_bwd2(const miso_grid_t* grid, const miso_grid_t* gg_grid, const 
 int miso_encode_bwd2_sorted(const miso_grid_t* grid, const miso_grid_t* gg_grid, const miso_sorted_t* sorted,
                             int64_t n, const float* grad_feats, int64_t ld_g, const float* gg_x, float* gg_out,
                             int64_t ld_gg, float* g_x, void* stream) {
-  int rc = check_sorted(sorted, n);
-  if (rc) return rc;
+  if (int rc = check_sorted(sorted, n)) return rc;
   return encode_bwd2_impl(grid, gg_grid, nullptr, n, grad_feats, ld_g, gg_x, gg_out, ld_gg, g_x, sorted, stream);
 }
 
@@ -210,29 +382,14 @@ int miso_mlp_pack(const miso_mlp_t* mlp, float* packed, void* stream) {
 }
 
 int64_t miso_sdf_train_lds_bytes(const miso_grid_t* grid, const miso_mlp_t* mlp, int32_t scattering) {
-  GridK g; bool v4;
-  if (convert_grid(grid, &g, false, &v4)) return 0;
-  int C, L, H, NH;
-  if (fused_shape(g, v4, mlp, &C, &L, &H, &NH) != MISO_OK) return 0;
-  return sdf_train_lds_bytes(C, L, H, NH, scattering != 0);
+  FusedCall f;
+  if (fused_query(&f, grid, mlp, false)) return 0;
+  return sdf_train_lds_bytes(f.C, f.L, f.H, f.NH, scattering != 0);
 }
 
 int miso_sdf_supported(const miso_grid_t* grid, const miso_mlp_t* mlp) {
-  GridK g; bool v4;
-  if (convert_grid(grid, &g, false, &v4)) return 0;
-  int C, L, H, NH;
-  return fused_shape(g, v4, mlp, &C, &L, &H, &NH) == MISO_OK ? 1 : 0;
-}
-
-// Sorted batches: read the pre-normalised float4 points instead of the metric ones.
-static const float* sorted_points(GridK* g, const miso_sorted_t* sorted) {
-  if (!sorted->xn_sorted) return sorted->x_sorted;
-  if (!(g->flags & MISO_F_COORDS_NORMALIZED)) {
-    for (int a = 0; a < 3; ++a) g->gscale[a] = 2.0f / (g->bmax[a] - g->bmin[a]);   // axis_coord's m
-    g->flags |= MISO_F_COORDS_NORMALIZED;
-  }
-  g->xstride = 4;
-  return sorted->xn_sorted;
+  FusedCall f;
+  return fused_query(&f, grid, mlp, false) == MISO_OK ? 1 : 0;
 }
 
 static int sdf_fwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
@@ -241,36 +398,27 @@ static int sdf_fwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
   LossInK lin;
   memset(&lin, 0, sizeof(lin));
   if (loss) lin = *loss;
-  if (n < 0 || !packed || (n > 0 && !sdf && !loss)) return MISO_E_BADARG;
-  if (((uintptr_t)packed & 15u) != 0) return MISO_E_BADARG;
-  GridK g; bool v4;
-  int rc = convert_grid(grid, &g, true, &v4);
-  if (rc) return rc;
-  int C, L, H, NH;
-  rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
-  if (rc) return rc;
+  if (n < 0 || (n > 0 && !sdf && !loss)) return MISO_E_BADARG;
+  FusedCall f;
+  if (int rc = fused_call(&f, grid, mlp, packed, true)) return rc;
   const int* perm = nullptr;
-  if (sorted) { x = sorted_points(&g, sorted); perm = sorted->perm; }
+  if (sorted) { x = sorted_points(&f.g, sorted); perm = sorted->perm; }
   if (n > 0 && !x) return MISO_E_BADARG;
-  return (int)launch_sdf_fwd(C, L, H, NH, g, packed, x, n, sdf, relu_mask, perm, lin, (hipStream_t)stream);
+  return (int)launch_sdf_fwd(f.C, f.L, f.H, f.NH, f.g, packed, x, n, sdf, relu_mask, perm, lin, (hipStream_t)stream);
 }
 
 static int sdf_bwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
                         const float* x, int64_t n, const float* grad_sdf, const uint32_t* relu_mask,
                         float* grad_x, const miso_sorted_t* sorted, float* workspace, void* stream) {
-  if (n < 0 || !packed || (n > 0 && (!grad_sdf || !relu_mask))) return MISO_E_BADARG;
-  if (((uintptr_t)packed & 15u) != 0) return MISO_E_BADARG;
-  GridK g; bool v4;
-  int rc = convert_grid(grid, &g, grad_x != nullptr, &v4);
-  if (rc) return rc;
+  if (n < 0 || !set_if(n, grad_sdf, relu_mask)) return MISO_E_BADARG;
+  FusedCall f;
+  if (int rc = fused_call(&f, grid, mlp, packed, grad_x != nullptr)) return rc;
+  const GridK& g = f.g;
   GridK gp = g;                                   // sample positions as the kernels read them
   if (sorted) x = sorted_points(&gp, sorted);
   if (n > 0 && !x) return MISO_E_BADARG;
-  int C, L, H, NH;
-  rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
-  if (rc) return rc;
   // owned levels leave their d-feat rows in the workspace (a pushed level's go the same way); the rest is scattered
-  const GradPlan plan = plan_grad(g, grad_ask(GRAD_BWD, v4, grid, sorted, n, g.F, workspace, false), pull_knobs());
+  const GradPlan plan = plan_grad(g, grad_ask(GRAD_BWD, f.vec4, grid, sorted, n, g.F, workspace, false), pull_knobs());
   const bool want_grid = plan.want != 0;
   if (!want_grid && !grad_x) return MISO_OK;
   if (plan.refuse) return MISO_E_UNSUPPORTED;
@@ -279,10 +427,10 @@ static int sdf_bwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
   if (e != hipSuccess) return (int)e;
   if (n == 0 && !plan.owned) return MISO_OK;
   if (n > 0) {
-    rc = (int)launch_sdf_bwd(C, L, H, NH, gp, packed, x, n, grad_sdf, relu_mask, grad_x, want_grid,
-                             sorted ? sorted->perm : nullptr, plan.owned ? workspace : nullptr, plan.owned,
-                             sorted && (grid->flags & MISO_F_GRAD_SDF_SORTED), st);
-    if (rc) return rc;
+    e = launch_sdf_bwd(f.C, f.L, f.H, f.NH, gp, packed, x, n, grad_sdf, relu_mask, grad_x, want_grid,
+                       sorted ? sorted->perm : nullptr, plan.owned ? workspace : nullptr, plan.owned,
+                       sorted && (grid->flags & MISO_F_GRAD_SDF_SORTED), st);
+    if (e != hipSuccess) return (int)e;
   }
   if (!plan.owned) return MISO_OK;
   return (int)launch_grad_pull(g, plan, pull_batch(sorted, workspace, nullptr, nullptr), st);
@@ -306,29 +454,14 @@ int miso_sdf_bwd_rows(const miso_grid_t* grid, const miso_mlp_t* mlp, const floa
                       const float* grad_sdf, const uint32_t* relu_mask, float* grad_x, float* dfeat_rows, void* stream) {
   if (!grid || !mlp) return MISO_E_BADARG;
   if (!dfeat_rows) return sdf_bwd_impl(grid, mlp, packed, x, n, grad_sdf, relu_mask, grad_x, nullptr, nullptr, stream);
-  if (n < 0 || !packed || (n > 0 && (!grad_sdf || !relu_mask || !x))) return MISO_E_BADARG;
-  if ((((uintptr_t)packed) & 15u) != 0 || (((uintptr_t)dfeat_rows) & 15u) != 0) return MISO_E_BADARG;
+  if (n < 0 || !set_if(n, grad_sdf, relu_mask, x) || !aligned(16, dfeat_rows)) return MISO_E_BADARG;
   if (grid->flags & (MISO_F_GRAD_OVERWRITE | MISO_F_GRAD_SDF_SORTED | MISO_F_GRAD_ZEROED)) return MISO_E_BADARG;
-  GridK g; bool v4;
-  int rc = convert_grid(grid, &g, grad_x != nullptr, &v4);
-  if (rc) return rc;
-  int C, L, H, NH;
-  rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
-  if (rc) return rc;
+  FusedCall f;
+  if (int rc = fused_call(&f, grid, mlp, packed, grad_x != nullptr)) return rc;
   if (n == 0) return MISO_OK;
   // want_grid = true selects the kernel form that stages the d-feat tile; levels without a gradient buffer are not scattered
-  return (int)launch_sdf_bwd(C, L, H, NH, g, packed, x, n, grad_sdf, relu_mask, grad_x, true, nullptr, dfeat_rows, 0u, false,
-                             (hipStream_t)stream);
-}
-
-// perm_optional: the entry point can take the original index from xn_sorted[p].w (miso_sdf_train_sorted)
-static int check_sorted(const miso_sorted_t* s, int64_t n, bool perm_optional) {
-  if (!s || !s->tile_offsets) return MISO_E_BADARG;
-  if (n > 0 && (!s->x_sorted && !s->xn_sorted)) return MISO_E_BADARG;   // an empty batch has no buffers
-  if (n > 0 && !s->perm && !(perm_optional && s->xn_sorted)) return MISO_E_BADARG;
-  if (((uintptr_t)s->xn_sorted & 15u) != 0) return MISO_E_BADARG;
-  { int t3_[3]; if (!tiles_xyz(s->tiles_per_axis, t3_)) return MISO_E_BADARG; }
-  return MISO_OK;
+  return (int)launch_sdf_bwd(f.C, f.L, f.H, f.NH, f.g, packed, x, n, grad_sdf, relu_mask, grad_x, true, nullptr, dfeat_rows, 0u,
+                             false, (hipStream_t)stream);
 }
 
 int64_t miso_sort_workspace_bytes(int64_t n, int32_t tiles_per_axis) {
@@ -339,13 +472,12 @@ int64_t miso_sort_workspace_bytes(int64_t n, int32_t tiles_per_axis) {
 int miso_sort_points(const miso_grid_t* grid, const float* x, int64_t n, int32_t tiles_per_axis,
                      void* workspace, float* x_sorted, float* xn_sorted, int32_t* perm,
                      int32_t* tile_offsets, void* stream) {
-  { int t3_[3]; if (n < 0 || n >= ((int64_t)1 << 31) || !tiles_xyz(tiles_per_axis, t3_)) return MISO_E_BADARG; }
+  { int t3_[3]; if (n < 0 || !fits32(n) || !tiles_xyz(tiles_per_axis, t3_)) return MISO_E_BADARG; }
   if (!workspace || !tile_offsets || (n > 0 && (!x || (!x_sorted && !xn_sorted)))) return MISO_E_BADARG;
   if (n > 0 && !perm && !xn_sorted) return MISO_E_BADARG;      // without perm the index lives in xn_sorted[p].w only
-  if (((uintptr_t)xn_sorted & 15u) != 0) return MISO_E_BADARG;
+  if (!aligned(16, xn_sorted)) return MISO_E_BADARG;
   GridK g;
-  int rc = convert_grid(grid, &g, false, nullptr);
-  if (rc) return rc;
+  if (int rc = convert_grid(grid, &g, false, nullptr)) return rc;
   return (int)launch_sort(g, x, n, tiles_per_axis, workspace, x_sorted, xn_sorted, perm, tile_offsets,
                           (hipStream_t)stream);
 }
@@ -353,19 +485,16 @@ int miso_sort_points(const miso_grid_t* grid, const float* x, int64_t n, int32_t
 int miso_sdf_fwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
                         const miso_sorted_t* sorted, int64_t n, float* sdf, uint32_t* relu_mask,
                         void* stream) {
-  int rc = check_sorted(sorted, n);
-  if (rc) return rc;
+  if (int rc = check_sorted(sorted, n)) return rc;
   return sdf_fwd_impl(grid, mlp, packed, nullptr, n, sdf, relu_mask, sorted, stream);
 }
 
 int miso_encode_fwd_sorted(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, float* feats,
                            int64_t ld_out, void* stream) {
-  int rc = check_sorted(sorted, n);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && !feats)) return MISO_E_BADARG;
+  if (int rc = check_sorted(sorted, n)) return rc;
+  if (n < 0 || !set_if(n, feats)) return MISO_E_BADARG;
   GridK g; bool v4;
-  rc = convert_grid(grid, &g, true, &v4);
-  if (rc) return rc;
+  if (int rc = convert_grid(grid, &g, true, &v4)) return rc;
   if (ld_out < g.F) return MISO_E_BADARG;
   const float* x = sorted_points(&g, sorted);
   return (int)launch_encode_fwd(g, v4, x, n, feats, ld_out, sorted->perm, (hipStream_t)stream);
@@ -376,12 +505,10 @@ int miso_sdf_fwd_sorted_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, con
                              float weight_fs, float trunc_dist, const float* loss_inputs, float* sdf,
                              uint32_t* relu_mask, float* grad_sdf_sorted, float* loss_slots,
                              const int32_t* n_live, void* stream) {
-  int rc = check_sorted(sorted, n);
-  if (rc) return rc;
-  if ((loss_type != 1 && loss_type != 2) || !loss_slots || (n > 0 && (!loss_inputs || !grad_sdf_sorted)))
+  if (int rc = check_sorted(sorted, n)) return rc;
+  if (!mapping_loss_ok(loss_type) || !loss_slots || !set_if(n, loss_inputs, grad_sdf_sorted) || !aligned(16, loss_inputs))
     return MISO_E_BADARG;
-  if (((uintptr_t)loss_inputs & 15u) != 0) return MISO_E_BADARG;
-  if (n == 0) return (int)launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, (hipStream_t)stream);
+  if (n == 0) return (int)zero_loss_slots(loss_slots, (hipStream_t)stream);
   const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, grad_sdf_sorted, loss_slots, n, n_live);
   return sdf_fwd_impl(grid, mlp, packed, nullptr, n, sdf, relu_mask, sorted, stream, &lin);
 }
@@ -389,10 +516,9 @@ int miso_sdf_fwd_sorted_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, con
 int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
                       int loss_type, float weight_sdf, float weight_fs, float trunc_dist, const float* loss_inputs,
                       float* sdf, uint32_t* relu_mask, float* grad_sdf, float* loss_slots, void* stream) {
-  if ((loss_type != 1 && loss_type != 2) || !loss_slots || n < 0 || (n > 0 && (!x || !loss_inputs || !grad_sdf)))
+  if (!mapping_loss_ok(loss_type) || !loss_slots || n < 0 || !set_if(n, x, loss_inputs, grad_sdf) || !aligned(16, loss_inputs))
     return MISO_E_BADARG;
-  if (((uintptr_t)loss_inputs & 15u) != 0) return MISO_E_BADARG;
-  if (n == 0) return (int)launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, (hipStream_t)stream);
+  if (n == 0) return (int)zero_loss_slots(loss_slots, (hipStream_t)stream);
   const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, grad_sdf, loss_slots, n, nullptr);
   return sdf_fwd_impl(grid, mlp, packed, x, n, sdf, relu_mask, nullptr, stream, &lin);
 }
@@ -424,13 +550,10 @@ uint32_t miso_grad_pull_levels(const miso_grid_t* grid, int32_t tiles_per_axis) 
 
 static int grad_pull_impl(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, const float* dfeat,
                           int64_t ld_d, int32_t rows_in_caller_order, const float* gg_x, void* stream) {
-  int rc = check_sorted(sorted, n);
-  if (rc) return rc;
-  if (n < 0 || (n > 0 && (!sorted->xn_sorted || !dfeat)) || ((uintptr_t)dfeat & 15u) != 0 || (ld_d & 3) != 0)
-    return MISO_E_BADARG;
+  if (int rc = check_sorted(sorted, n)) return rc;
+  if (n < 0 || !set_if(n, sorted->xn_sorted, dfeat) || !aligned(16, dfeat) || (ld_d & 3) != 0) return MISO_E_BADARG;
   GridK g; bool v4;
-  rc = convert_grid(grid, &g, false, &v4);
-  if (rc) return rc;
+  if (int rc = convert_grid(grid, &g, false, &v4)) return rc;
   if (ld_d < g.F) return MISO_E_BADARG;
   const GradPlan plan = plan_grad(g, grad_ask(GRAD_PULL, v4, grid, sorted, n, ld_d, dfeat, gg_x != nullptr), pull_knobs());
   if (plan.refuse) return MISO_E_UNSUPPORTED;
@@ -460,18 +583,15 @@ int64_t miso_sdf_bwd_workspace_floats(const miso_grid_t* grid, int64_t n) {
 int miso_sdf_bwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
                         const miso_sorted_t* sorted, int64_t n, const float* grad_sdf,
                         const uint32_t* relu_mask, float* grad_x, float* workspace, void* stream) {
-  int rc = check_sorted(sorted, n);
-  if (rc) return rc;
+  if (int rc = check_sorted(sorted, n)) return rc;
   return sdf_bwd_impl(grid, mlp, packed, nullptr, n, grad_sdf, relu_mask, grad_x, sorted, workspace,
                       stream);
 }
 
 int64_t miso_sdf_wgrad_workspace_floats(const miso_grid_t* grid, const miso_mlp_t* mlp, int64_t n) {
-  GridK g; bool v4;
-  if (n < 0 || convert_grid(grid, &g, false, &v4)) return 0;
-  int C, L, H, NH;
-  if (fused_shape(g, v4, mlp, &C, &L, &H, &NH) != MISO_OK) return 0;
-  return sdf_wgrad_workspace_floats(C, L, H, NH, n);
+  FusedCall f;
+  if (n < 0 || fused_query(&f, grid, mlp, false)) return 0;
+  return sdf_wgrad_workspace_floats(f.C, f.L, f.H, f.NH, n);
 }
 
 // The decoder's weight and bias gradients (decoder_wgrad.hip): the sign bits and the point order are those of the forward
@@ -479,19 +599,12 @@ int64_t miso_sdf_wgrad_workspace_floats(const miso_grid_t* grid, const miso_mlp_
 int miso_sdf_wgrad(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
                    const float* grad_sdf, const uint32_t* relu_mask, const miso_sorted_t* sorted, uint32_t flags,
                    const miso_mlp_grad_t* grads, float* workspace, int64_t workspace_floats, void* stream) {
-  if (!grid || !mlp || !packed || !grads || n < 0 || (n > 0 && (!grad_sdf || !relu_mask))) return MISO_E_BADARG;
-  if (((uintptr_t)packed & 15u) != 0 || (flags & ~MISO_F_GRAD_SDF_SORTED)) return MISO_E_BADARG;
-  if ((flags & MISO_F_GRAD_SDF_SORTED) && !sorted) return MISO_E_BADARG;
-  if (sorted) {
-    int rc = check_sorted(sorted, n);
-    if (rc) return rc;
-  }
-  GridK g; bool v4;
-  int rc = convert_grid(grid, &g, n > 0, &v4);
-  if (rc) return rc;
-  int C, L, H, NH;
-  rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
-  if (rc) return rc;
+  if (!grid || !mlp || !grads || n < 0 || !set_if(n, grad_sdf, relu_mask)) return MISO_E_BADARG;
+  if ((flags & ~MISO_F_GRAD_SDF_SORTED) || ((flags & MISO_F_GRAD_SDF_SORTED) && !sorted)) return MISO_E_BADARG;
+  if (sorted)
+    if (int rc = check_sorted(sorted, n)) return rc;
+  FusedCall f;
+  if (int rc = fused_call(&f, grid, mlp, packed, n > 0)) return rc;
   WgradOutK out;
   memset(&out, 0, sizeof(out));
   for (int l = 0; l < mlp->n_linear; ++l) {
@@ -499,11 +612,11 @@ int miso_sdf_wgrad(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* 
     out.w[l] = grads->weight[l];
     out.b[l] = grads->bias[l];
   }
-  const int64_t need = sdf_wgrad_workspace_floats(C, L, H, NH, n);
-  if (need > 0 && (!workspace || workspace_floats < need || ((uintptr_t)workspace & 15u) != 0)) return MISO_E_BADARG;
-  if (sorted) x = sorted_points(&g, sorted);
+  const int64_t need = sdf_wgrad_workspace_floats(f.C, f.L, f.H, f.NH, n);
+  if (need > 0 && (!workspace || workspace_floats < need || !aligned(16, workspace))) return MISO_E_BADARG;
+  if (sorted) x = sorted_points(&f.g, sorted);
   if (n > 0 && !x) return MISO_E_BADARG;
-  return (int)launch_sdf_wgrad(C, L, H, NH, g, packed, x, n, grad_sdf, relu_mask, sorted ? sorted->perm : nullptr,
+  return (int)launch_sdf_wgrad(f.C, f.L, f.H, f.NH, f.g, packed, x, n, grad_sdf, relu_mask, sorted ? sorted->perm : nullptr,
                                (flags & MISO_F_GRAD_SDF_SORTED) != 0, out, workspace, (hipStream_t)stream);
 }
 
@@ -515,34 +628,30 @@ static int sdf_train_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const 
                           const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
                           float trunc_dist, const float* loss_inputs, float* sdf, float* loss_slots,
                           const int32_t* n_live, float* workspace, void* stream) {
-  if ((loss_type != 1 && loss_type != 2) || !loss_slots || !packed || n < 0 || (n > 0 && !loss_inputs))
-    return MISO_E_BADARG;
-  if ((((uintptr_t)loss_inputs | (uintptr_t)packed | (uintptr_t)workspace) & 15u) != 0) return MISO_E_BADARG;
+  if (!mapping_loss_ok(loss_type) || !loss_slots || n < 0 || !set_if(n, loss_inputs)) return MISO_E_BADARG;
+  if (!aligned(16, loss_inputs, workspace)) return MISO_E_BADARG;
   if (sorted && !sorted->xn_sorted && n > 0) return MISO_E_BADARG;
   if (!sorted && n > 0 && !x) return MISO_E_BADARG;
-  GridK g; bool v4;
-  int rc = convert_grid(grid, &g, true, &v4);
-  if (rc) return rc;
-  int C, L, H, NH;
-  rc = fused_shape(g, v4, mlp, &C, &L, &H, &NH);
-  if (rc) return rc;
+  FusedCall f;
+  if (int rc = fused_call(&f, grid, mlp, packed, true)) return rc;
+  const GridK& g = f.g;
   // owned levels are formed from the d-feat rows (pull or push); the rest is scattered from the kernel
-  const GradPlan plan = plan_grad(g, grad_ask(GRAD_TRAIN, v4, grid, sorted, n, g.F, workspace, false), pull_knobs());
+  const GradPlan plan = plan_grad(g, grad_ask(GRAD_TRAIN, f.vec4, grid, sorted, n, g.F, workspace, false), pull_knobs());
   if (!plan.want || plan.refuse) return MISO_E_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = zero_level_grads(g, plan.fill, st);
   if (e != hipSuccess) return (int)e;
   if (n == 0) {
-    e = launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, st);
+    e = zero_loss_slots(loss_slots, st);
     if (e != hipSuccess) return (int)e;
   } else {
     const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, nullptr, loss_slots, n, n_live);
     GridK gp = g;
     if (sorted) x = sorted_points(&gp, sorted);
     if (sorted && !sorted->perm) gp.flags |= MISO_F_INDEX_IN_XN;
-    rc = (int)launch_sdf_train(C, L, H, NH, gp, packed, x, n, sdf, sorted ? sorted->perm : nullptr, lin,
-                               plan.owned ? workspace : nullptr, plan.owned, plan.scatter != 0, st);
-    if (rc) return rc;
+    e = launch_sdf_train(f.C, f.L, f.H, f.NH, gp, packed, x, n, sdf, sorted ? sorted->perm : nullptr, lin,
+                         plan.owned ? workspace : nullptr, plan.owned, plan.scatter != 0, st);
+    if (e != hipSuccess) return (int)e;
   }
   if (!plan.owned) return MISO_OK;
   return (int)launch_grad_pull(g, plan, pull_batch(sorted, workspace, nullptr, nullptr), st);
@@ -552,8 +661,7 @@ int miso_sdf_train_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const 
                           const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
                           float trunc_dist, const float* loss_inputs, float* sdf, float* loss_slots,
                           const int32_t* n_live, float* workspace, void* stream) {
-  int rc = check_sorted(sorted, n, true);
-  if (rc) return rc;
+  if (int rc = check_sorted(sorted, n, true)) return rc;
   if (n > 0 && !workspace) return MISO_E_BADARG;
   return sdf_train_impl(grid, mlp, packed, nullptr, sorted, n, loss_type, weight_sdf, weight_fs, trunc_dist,
                         loss_inputs, sdf, loss_slots, n_live, workspace, stream);
@@ -569,12 +677,11 @@ int miso_sdf_train(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* 
 int miso_pair_latent(const miso_grid_t* dst_grid, const float* pose, const float* coords_src,
                      const float* feats_src, int64_t ld_feats, int64_t n, int loss_type, double* out,
                      void* stream) {
-  if (n < 0 || !pose || !out || (loss_type != 1 && loss_type != 2)) return MISO_E_BADARG;
-  if (reinterpret_cast<uintptr_t>(out) & 7u) return MISO_E_BADARG;      // fp64 atomics
-  if (n > 0 && (!coords_src || !feats_src)) return MISO_E_BADARG;
+  if (n < 0 || !pose || !out || !mapping_loss_ok(loss_type)) return MISO_E_BADARG;
+  if (!aligned(8, out)) return MISO_E_BADARG;      // fp64 atomics
+  if (!set_if(n, coords_src, feats_src)) return MISO_E_BADARG;
   GridK g; bool v4;
-  int rc = convert_grid(dst_grid, &g, true, &v4);
-  if (rc) return rc;
+  if (int rc = convert_grid(dst_grid, &g, true, &v4)) return rc;
   if (g.flags & (MISO_F_COORDS_NORMALIZED | MISO_F_ALIGN_CORNERS | MISO_F_PAD_BORDER)) return MISO_E_UNSUPPORTED;
   if (ld_feats < g.F) return MISO_E_BADARG;
   return (int)launch_pair_latent(g, v4, pose, coords_src, feats_src, ld_feats, n, loss_type, out,
@@ -583,13 +690,13 @@ int miso_pair_latent(const miso_grid_t* dst_grid, const float* pose, const float
 
 int miso_overlap_count(const float* pose, const float* coords_src, int64_t n, const float* bound_min,
                        const float* bound_max, float* count_out, void* stream) {
-  if (n < 0 || !pose || !bound_min || !bound_max || !count_out || (n > 0 && !coords_src)) return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 24)) return MISO_E_TOOLARGE;     // the fp32 count stays exact
+  if (n < 0 || !all_set(pose, bound_min, bound_max, count_out) || !set_if(n, coords_src)) return MISO_E_BADARG;
+  if (!fits_fp32_count(n)) return MISO_E_TOOLARGE;
   return (int)launch_overlap_count(pose, coords_src, n, bound_min, bound_max, count_out, (hipStream_t)stream);
 }
 
 int miso_align_src_boxes(const float* coords, int64_t n, float* boxes, void* stream) {
-  if (n < 0 || (n > 0 && (!coords || !boxes))) return MISO_E_BADARG;
+  if (n < 0 || !set_if(n, coords, boxes)) return MISO_E_BADARG;
   return (int)launch_src_boxes(coords, n, boxes, (hipStream_t)stream);
 }
 
@@ -607,13 +714,12 @@ int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, voi
     const miso_align_pair_t& in = pairs[p];
     if (in.src < 0 || in.src >= cfg->n_submaps || in.dst < 0 || in.dst >= cfg->n_submaps || in.src == in.dst)
       return MISO_E_BADARG;
-    if (in.n < 0 || in.gate_n < 0 || (in.n > 0 && (!in.coords_src || !in.feats_src))) return MISO_E_BADARG;
-    if (in.gate_n >= ((int64_t)1 << 24)) return MISO_E_TOOLARGE;     // the fp32 count stays exact
+    if (in.n < 0 || in.gate_n < 0 || !set_if(in.n, in.coords_src, in.feats_src)) return MISO_E_BADARG;
+    if (!fits_fp32_count(in.gate_n)) return MISO_E_TOOLARGE;
     AlignPairK& d = out[p];
     memset(&d, 0, sizeof(d));
     bool v4;
-    int rc = convert_grid(&in.dst_grid, &d.g, true, &v4);
-    if (rc) return rc;
+    if (int rc = convert_grid(&in.dst_grid, &d.g, true, &v4)) return rc;
     if (d.g.flags & (MISO_F_COORDS_NORMALIZED | MISO_F_ALIGN_CORNERS | MISO_F_PAD_BORDER)) return MISO_E_UNSUPPORTED;
     if (in.ld_feats < d.g.F) return MISO_E_BADARG;
     v4_all = v4_all && v4;
@@ -660,8 +766,7 @@ int64_t miso_align_state_layout(int32_t n_submaps, int32_t n_pairs, int32_t ring
 static int align_k(const miso_align_t* c, AlignK* k) {
   if (!c || c->n_submaps < 1 || c->n_submaps > 64 || c->n_pairs < 0 || c->ring_iters < 0) return MISO_E_BADARG;
   if (!c->R0 || !c->t0 || !c->state || (c->n_pairs > 0 && !c->plan)) return MISO_E_BADARG;
-  if (c->loss_type != 1 && c->loss_type != 2) return MISO_E_BADARG;
-  if (((uintptr_t)c->state & 15u) != 0) return MISO_E_BADARG;
+  if (!mapping_loss_ok(c->loss_type) || !aligned(16, c->state)) return MISO_E_BADARG;
   memset(k, 0, sizeof(*k));
   k->S = c->n_submaps; k->P = c->n_pairs; k->loss_type = c->loss_type; k->ring_iters = c->ring_iters;
   k->save_poses = c->save_poses;
@@ -675,24 +780,21 @@ static int align_k(const miso_align_t* c, AlignK* k) {
 
 int miso_align_iteration_a(const miso_align_t* cfg, void* stream) {
   AlignK k;
-  int rc = align_k(cfg, &k);
-  if (rc) return rc;
+  if (int rc = align_k(cfg, &k)) return rc;
   return (int)launch_align_a(k, cfg->max_n, cfg->max_gate_n, cfg->max_gate_rows, cfg->vec4 != 0, cfg->poses_ready != 0,
                              (hipStream_t)stream);
 }
 
 int miso_align_iteration_b(const miso_align_t* cfg, void* stream) {
   AlignK k;
-  int rc = align_k(cfg, &k);
-  if (rc) return rc;
+  if (int rc = align_k(cfg, &k)) return rc;
   return (int)launch_align_b(k, (hipStream_t)stream);
 }
 
 int miso_lm_normal_eq(const float* coords_frame, const float* R_frame, const float* grad_sdf_x,
                       const float* sdf, const float* target, int64_t n, int loss_type, float gm_scale,
                       float* out, void* stream) {
-  if (n < 0 || !out || !R_frame) return MISO_E_BADARG;
-  if (n > 0 && (!coords_frame || !grad_sdf_x || !sdf || !target)) return MISO_E_BADARG;
+  if (n < 0 || !out || !R_frame || !set_if(n, coords_frame, grad_sdf_x, sdf, target)) return MISO_E_BADARG;
   if (loss_type != 2 && loss_type != 3) return MISO_E_UNSUPPORTED;
   if (loss_type == 3 && !(gm_scale > 0.0f)) return MISO_E_BADARG;
   return (int)launch_lm_normal_eq(coords_frame, R_frame, grad_sdf_x, sdf, target, n, loss_type, gm_scale, out,
@@ -724,16 +826,12 @@ int miso_track_adam_step(const miso_grid_t* grid, const miso_mlp_t* mlp, const f
                          void* stream) {
   if (!t || !grid) return MISO_E_BADARG;
   const miso_lm_track_t* a = &t->s;
-  if (a->n < 0 || !a->R_base || !a->t_base || !a->rot_correction || !a->trans_correction || !a->pose || !a->sums ||
-      !a->info || !t->adam_table || t->adam_table_len < 1 || !t->state || t->ring_len < 0 || (t->ring_len > 0 && !t->loss_ring))
+  if (!lm_track_ok(a, t->grad_pred)) return MISO_E_BADARG;
+  if (!t->adam_table || t->adam_table_len < 1 || !t->state || t->ring_len < 0 || !set_if(t->ring_len, t->loss_ring))
     return MISO_E_BADARG;
-  if (a->n > 0 && (!a->coords_frame || !a->target || !a->coords_world || !a->sdf || !a->grad || !a->relu_mask || !t->grad_pred))
-    return MISO_E_BADARG;
-  if (a->stride_target < 0 || a->stride_valid < 0 || a->stride_frame_ids < 0) return MISO_E_BADARG;
   if (t->loss_type < 1 || t->loss_type > 3) return MISO_E_UNSUPPORTED;
   if (t->loss_type == 3 && !(t->gm_scale > 0.0f)) return MISO_E_BADARG;
-  for (int l = 0; l < grid->n_levels && l < MISO_MAX_LEVELS; ++l)
-    if (grid->level[l].grad) return MISO_E_BADARG;
+  if (has_grad_buffers(grid)) return MISO_E_BADARG;
   TrackAdamK k;
   memset(&k, 0, sizeof(k));
   lm_track_args(grid, a, &k.s);
@@ -742,44 +840,31 @@ int miso_track_adam_step(const miso_grid_t* grid, const miso_mlp_t* mlp, const f
   k.table = reinterpret_cast<const AdamScalars*>(t->adam_table); k.table_len = t->adam_table_len;
   k.state = t->state; k.ring = t->loss_ring; k.ring_len = t->ring_len;
   hipStream_t st = (hipStream_t)stream;
-  int rc = (int)launch_lm_track_head(k.s, st);
-  if (rc) return rc;
+  if (int rc = (int)launch_lm_track_head(k.s, st)) return rc;
   lm_track_use_clean(&k.s);
   if (a->n > 0) {
-    rc = sdf_fwd_impl(grid, mlp, packed, a->coords_world, a->n, a->sdf, a->relu_mask, nullptr, stream);
-    if (rc) return rc;
-    rc = (int)launch_track_loss(k, st);
-    if (rc) return rc;
-    rc = sdf_bwd_impl(grid, mlp, packed, a->coords_world, a->n, t->grad_pred, a->relu_mask, a->grad, nullptr, nullptr, stream);
-    if (rc) return rc;
+    if (int rc = sdf_fwd_impl(grid, mlp, packed, a->coords_world, a->n, a->sdf, a->relu_mask, nullptr, stream)) return rc;
+    if (int rc = (int)launch_track_loss(k, st)) return rc;
+    if (int rc = sdf_bwd_impl(grid, mlp, packed, a->coords_world, a->n, t->grad_pred, a->relu_mask, a->grad, nullptr, nullptr, stream))
+      return rc;
   }
   return (int)launch_track_tail(k, st);
 }
 
 int miso_lm_track_step(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const miso_lm_track_t* a,
                        void* stream) {
-  if (!a || a->n < 0 || !a->R_base || !a->t_base || !a->rot_correction || !a->trans_correction || !a->pose || !a->sums ||
-      !a->info)
-    return MISO_E_BADARG;
-  if (a->n > 0 && (!a->coords_frame || !a->target || !a->coords_world || !a->sdf || !a->grad || !a->ones || !a->relu_mask))
-    return MISO_E_BADARG;
-  if (a->stride_target < 0 || a->stride_valid < 0 || a->stride_frame_ids < 0) return MISO_E_BADARG;
+  if (!a || !lm_track_ok(a, a->ones)) return MISO_E_BADARG;
   if (a->loss_type != 2 && a->loss_type != 3) return MISO_E_UNSUPPORTED;
   if (a->loss_type == 3 && !(a->gm_scale > 0.0f)) return MISO_E_BADARG;
-  if (!grid) return MISO_E_BADARG;
-  for (int l = 0; l < grid->n_levels && l < MISO_MAX_LEVELS; ++l)
-    if (grid->level[l].grad) return MISO_E_BADARG;      // the step wants d sdf / d x only
+  if (!grid || has_grad_buffers(grid)) return MISO_E_BADARG;
   LmTrackK k;
   lm_track_args(grid, a, &k);
   hipStream_t st = (hipStream_t)stream;
-  int rc = (int)launch_lm_track_head(k, st);
-  if (rc) return rc;
+  if (int rc = (int)launch_lm_track_head(k, st)) return rc;
   lm_track_use_clean(&k);
   if (a->n > 0) {
-    rc = sdf_fwd_impl(grid, mlp, packed, a->coords_world, a->n, a->sdf, a->relu_mask, nullptr, stream);
-    if (rc) return rc;
-    rc = sdf_bwd_impl(grid, mlp, packed, a->coords_world, a->n, a->ones, a->relu_mask, a->grad, nullptr, nullptr, stream);
-    if (rc) return rc;
+    if (int rc = sdf_fwd_impl(grid, mlp, packed, a->coords_world, a->n, a->sdf, a->relu_mask, nullptr, stream)) return rc;
+    if (int rc = sdf_bwd_impl(grid, mlp, packed, a->coords_world, a->n, a->ones, a->relu_mask, a->grad, nullptr, nullptr, stream)) return rc;
   }
   return (int)launch_lm_track_tail(k, a->grad, a->sdf, a->loss_type, a->gm_scale, st);
 }
@@ -799,13 +884,13 @@ int miso_sample_rays(const miso_ray_frames_t* f, const miso_ray_sampling_t* c, i
   if (c->n_strat < 0 || c->n_surf < 0 || c->n_strat + c->n_surf < 1) return MISO_E_BADARG;
   if (c->n_strat > MISO_RAY_MAX_BINS) return MISO_E_UNSUPPORTED;
   const int64_t S = c->n_strat + c->n_surf;
-  if (n_rays * S >= (int64_t(1) << 31)) return MISO_E_TOOLARGE;
+  if (!fits32(n_rays * S)) return MISO_E_TOOLARGE;
   if (n_rays > 0) {
     if (!f->depth || !f->T_WC || !f->R_wk || !f->t_wk || f->n_frames < 1 || f->H < 1 || f->W < 1) return MISO_E_BADARG;
     if (!pix_h || !pix_w || !workspace || !coords_frame || !sample_frame_ids || !aux) return MISO_E_BADARG;
     if (!pix_b && c->rays_per_frame < 1) return MISO_E_BADARG;
     if ((c->n_strat > 0 && !u) || (c->n_surf > 1 && !g)) return MISO_E_BADARG;
-    if (reinterpret_cast<uintptr_t>(aux) & 15u) return MISO_E_BADARG;
+    if (!aligned(16, aux)) return MISO_E_BADARG;
   }
   float lin[MISO_RAY_MAX_BINS + 1];
   if (c->bin_edges) {
@@ -823,8 +908,7 @@ int miso_mapping_loss(int loss_type, float weight_sdf, float weight_fs, float tr
                       const float* pred, const float* target, const float* valid, const float* sign,
                       const float* weight, int64_t n, float* grad_pred, float* grad_pred_fs,
                       float* loss_out, void* stream) {
-  if (n < 0 || (loss_type != 1 && loss_type != 2) || !loss_out) return MISO_E_BADARG;
-  if (n > 0 && (!pred || !target || !grad_pred)) return MISO_E_BADARG;
+  if (n < 0 || !mapping_loss_ok(loss_type) || !loss_out || !set_if(n, pred, target, grad_pred)) return MISO_E_BADARG;
   return (int)launch_mapping_loss(loss_type, weight_sdf, weight_fs, trunc_dist, pred, target, valid,
                                   sign, weight, n, grad_pred, grad_pred_fs, loss_out, (hipStream_t)stream);
 }
@@ -832,8 +916,7 @@ int miso_mapping_loss(int loss_type, float weight_sdf, float weight_fs, float tr
 int miso_adam_dense(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t numel,
                     double lr, double beta1, double beta2, double eps, int32_t step, int zero_grad,
                     void* stream) {
-  if (numel < 0 || step < 1 || (numel > 0 && (!param || !grad || !exp_avg || !exp_avg_sq)))
-    return MISO_E_BADARG;
+  if (numel < 0 || step < 1 || !set_if(numel, param, grad, exp_avg, exp_avg_sq)) return MISO_E_BADARG;
   return (int)launch_adam(param, grad, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, step,
                           zero_grad, (hipStream_t)stream);
 }
@@ -841,10 +924,7 @@ int miso_adam_dense(float* param, float* grad, float* exp_avg, float* exp_avg_sq
 int miso_adam_active(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active, int64_t numel,
                      double lr, double beta1, double beta2, double eps, int32_t step, int zero_grad,
                      const float* guard, void* stream) {
-  if (numel < 0 || step < 1 || (numel > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !active)))
-    return MISO_E_BADARG;
-  if ((((uintptr_t)param) | ((uintptr_t)grad) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) & 15u)
-    return MISO_E_BADARG;
+  if (step < 1 || !adam_tensor_ok(param, grad, exp_avg, exp_avg_sq, active, nullptr, numel)) return MISO_E_BADARG;
   return (int)launch_adam_active(param, grad, exp_avg, exp_avg_sq, active, numel, lr, beta1, beta2, eps, step,
                                  zero_grad, guard, (hipStream_t)stream, nullptr, nullptr, 0);
 }
@@ -852,11 +932,8 @@ int miso_adam_active(float* param, float* grad, float* exp_avg, float* exp_avg_s
 int miso_adam_touched(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active, uint8_t* touched,
                       int64_t numel, double lr, double beta1, double beta2, double eps, int32_t step, int zero_grad,
                       const float* guard, void* stream) {
-  if (numel < 0 || step < 1 || (numel > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !active || !touched)))
-    return MISO_E_BADARG;
-  if ((((uintptr_t)param) | ((uintptr_t)grad) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) & 15u)
-    return MISO_E_BADARG;
-  if ((((uintptr_t)active) | ((uintptr_t)touched)) & 3u) return MISO_E_BADARG;      // read four flag bytes at a time
+  if (step < 1 || !adam_tensor_ok(param, grad, exp_avg, exp_avg_sq, active, touched, numel)) return MISO_E_BADARG;
+  if (!set_if(numel, touched) || !aligned(4, active, touched)) return MISO_E_BADARG;      // here the flags are not optional
   return (int)launch_adam_touched(param, grad, exp_avg, exp_avg_sq, active, touched, numel, lr, beta1, beta2, eps,
                                   step, zero_grad, guard, (hipStream_t)stream, nullptr, nullptr, 0);
 }
@@ -888,28 +965,13 @@ int miso_adam_bump(int32_t* step, const float* guard, void* stream) {
 int miso_adam_step_dev(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active, uint8_t* touched,
                        int64_t numel, const float* table, int32_t table_len, const int32_t* step, int zero_grad,
                        const float* guard, void* stream) {
-  if (numel < 0 || table_len < 1 || !table || !step ||
-      (numel > 0 && (!param || !grad || !exp_avg || !exp_avg_sq || !active)))
+  if (table_len < 1 || !table || !step || !adam_tensor_ok(param, grad, exp_avg, exp_avg_sq, active, touched, numel))
     return MISO_E_BADARG;
-  if ((((uintptr_t)param) | ((uintptr_t)grad) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq)) & 15u)
-    return MISO_E_BADARG;
-  if (touched && ((((uintptr_t)active) | ((uintptr_t)touched)) & 3u)) return MISO_E_BADARG;
   if (touched)
     return (int)launch_adam_touched(param, grad, exp_avg, exp_avg_sq, active, touched, numel, 1e-3, 0.9, 0.999, 1e-8, 1,
                                     zero_grad, guard, (hipStream_t)stream, table, step, table_len);
   return (int)launch_adam_active(param, grad, exp_avg, exp_avg_sq, active, numel, 1e-3, 0.9, 0.999, 1e-8, 1, zero_grad,
                                  guard, (hipStream_t)stream, table, step, table_len);
-}
-
-static int adam_tensors_ok(const miso_adam_tensor_t* tensors, int32_t n_tensors) {
-  if (!tensors || n_tensors < 1 || n_tensors > MISO_ADAM_MAX_TENSORS) return 0;
-  for (int i = 0; i < n_tensors; ++i) {
-    const miso_adam_tensor_t& t = tensors[i];
-    if (t.numel < 0 || (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || !t.active))) return 0;
-    if ((((uintptr_t)t.param) | ((uintptr_t)t.grad) | ((uintptr_t)t.exp_avg) | ((uintptr_t)t.exp_avg_sq)) & 15u) return 0;
-    if (t.touched && ((((uintptr_t)t.active) | ((uintptr_t)t.touched)) & 3u)) return 0;      // four flag bytes at a time
-  }
-  return 1;
 }
 
 int miso_adam_active_multi(const miso_adam_tensor_t* tensors, int32_t n_tensors, double lr, double beta1, double beta2,
@@ -934,32 +996,23 @@ int miso_mapping_batch(const float* R, const float* t, int32_t n_poses, const in
   if (col_strides)
     for (int i = 0; i < 4; ++i)
       if (col_strides[i] < 0) return MISO_E_BADARG;
-  if (n > 0 && (!frame_ids || !coords_frame || !target || !coords_world || !loss_rows)) return MISO_E_BADARG;
-  if (((uintptr_t)loss_rows & 15u) != 0) return MISO_E_BADARG;
+  if (!set_if(n, frame_ids, coords_frame, target, coords_world, loss_rows) || !aligned(16, loss_rows)) return MISO_E_BADARG;
   return (int)launch_mapping_batch(R, t, n_poses, table, table_len, frame_ids, coords_frame, target, valid, sign, weight,
                                    n, coords_world, loss_rows, col_strides, valid_is_bool, sanitize, (hipStream_t)stream);
 }
 
 int miso_mapping_loss_rows(int loss_type, float weight_sdf, float weight_fs, float trunc_dist, const float* pred,
                            const float* loss_rows, int64_t n, float* grad_pred, float* loss_out, void* stream) {
-  if ((loss_type != 1 && loss_type != 2) || n < 0 || !loss_out || (n > 0 && (!pred || !loss_rows || !grad_pred)))
+  if (!mapping_loss_ok(loss_type) || n < 0 || !loss_out || !set_if(n, pred, loss_rows, grad_pred) || !aligned(16, loss_rows))
     return MISO_E_BADARG;
-  if (((uintptr_t)loss_rows & 15u) != 0) return MISO_E_BADARG;
   return (int)launch_mapping_loss_rows(loss_type, weight_sdf, weight_fs, trunc_dist, pred, loss_rows, n, grad_pred,
                                        loss_out, (hipStream_t)stream);
 }
 
 int miso_rigid_by_index(const float* R, const float* t, const int64_t* idx, const float* x, int64_t n, int32_t n_poses,
                         int transpose, float* y, void* stream) {
-  if (n < 0 || n_poses < 1 || !R || (n > 0 && (!idx || !x || !y))) return MISO_E_BADARG;
+  if (n < 0 || n_poses < 1 || !R || !set_if(n, idx, x, y)) return MISO_E_BADARG;
   return (int)launch_rigid_by_index(R, t, idx, x, n, n_poses, transpose, y, (hipStream_t)stream);
-}
-
-static int mc_check_dims(int32_t nx, int32_t ny, int32_t nz) {
-  if (nx < 1 || ny < 1 || nz < 1) return MISO_E_BADARG;
-  // cell ids are 32-bit; sample indices (and keys = 3 * index + axis) are 64-bit
-  if ((int64_t)nx * ny * nz >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  return 0;
 }
 
 int64_t miso_mc_words(int32_t nx, int32_t ny, int32_t nz) {
@@ -972,14 +1025,14 @@ int miso_grid_pool_avg(const float* coords, const float* features, int64_t n, in
                        int32_t* counts, void* stream) {
   if (n < 0 || d < 1 || nx < 1 || ny < 1 || nz < 1 || !bound_min || !pooled || !counts || !(cell_size > 0.0f)) return MISO_E_BADARG;
   if (n > 0 && (!coords || !features || ld_features < d)) return MISO_E_BADARG;
-  if ((int64_t)nx * ny * nz * d >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (!fits32((int64_t)nx * ny * nz * d)) return MISO_E_TOOLARGE;
   return (int)launch_grid_pool_avg(coords, features, n, d, ld_features, bound_min, cell_size, nx, ny, nz, pooled, counts,
                                    (hipStream_t)stream);
 }
 
 // ---- voxel down-sampling (voxel.hip) -------------------------------------------------------------------------------------
 int64_t miso_voxel_down_workspace_bytes(int64_t capacity) {
-  if (capacity < 0 || capacity >= (int64_t(1) << 22)) return 0;
+  if (capacity < 0 || !fits_voxel_key(capacity)) return 0;
   return voxel_down_workspace_bytes(capacity);
 }
 
@@ -987,9 +1040,9 @@ int miso_voxel_down_sample(const float* points, int64_t ld, int64_t capacity, co
                            void* workspace, int64_t* out_idx, int32_t* out_count, void* stream) {
   if (capacity < 0 || ld < 3 || !out_count || !(voxel_size > 0.0f) || !(voxel_size < __builtin_huge_valf()))
     return MISO_E_BADARG;
-  if (capacity >= (int64_t(1) << 22)) return MISO_E_TOOLARGE;      // the index field of the sort key
+  if (!fits_voxel_key(capacity)) return MISO_E_TOOLARGE;
   if (capacity == 0) return (int)launch_zero_words(out_count, 1, (hipStream_t)stream);
-  if (!points || !workspace || !out_idx || ((uintptr_t)workspace & 7u)) return MISO_E_BADARG;
+  if (!all_set(points, workspace, out_idx) || !aligned(8, workspace)) return MISO_E_BADARG;
   return (int)launch_voxel_down_sample(points, ld, capacity, n_live, voxel_size, workspace, out_idx, out_count,
                                        (hipStream_t)stream);
 }
@@ -998,10 +1051,9 @@ int miso_voxel_select_rows(const float* src_coords, const int64_t* src_ids, cons
                            const int32_t* out_count, int64_t capacity, float* dst_coords, int64_t* dst_ids, float* dst_aux,
                            int32_t* live_rows, void* stream) {
   if (capacity < 0 || !out_count || !live_rows) return MISO_E_BADARG;
-  if (capacity >= (int64_t(1) << 22)) return MISO_E_TOOLARGE;
-  if (capacity > 0 && (!src_coords || !src_ids || !src_aux || !out_idx || !dst_coords || !dst_ids || !dst_aux))
-    return MISO_E_BADARG;
-  if ((((uintptr_t)src_aux) | ((uintptr_t)dst_aux)) & 15u) return MISO_E_BADARG;
+  if (!fits_voxel_key(capacity)) return MISO_E_TOOLARGE;
+  if (!set_if(capacity, src_coords, src_ids, src_aux, out_idx, dst_coords, dst_ids, dst_aux)) return MISO_E_BADARG;
+  if (!aligned(16, src_aux, dst_aux)) return MISO_E_BADARG;
   if (capacity > 0 && (src_coords == dst_coords || src_ids == dst_ids || src_aux == dst_aux)) return MISO_E_BADARG;
   return (int)launch_voxel_select_rows(src_coords, src_ids, src_aux, out_idx, out_count, capacity, dst_coords, dst_ids,
                                        dst_aux, live_rows, (hipStream_t)stream);
@@ -1013,7 +1065,7 @@ int miso_nn_plan(const float* bound_min, const float* bound_max, float cell, int
   const float inf = __builtin_huge_valf();
   if (!plan || !bound_min || !bound_max || n_tgt < 0 || max_rings < 0 || max_rings > MISO_NN_MAX_RINGS) return MISO_E_BADARG;
   if (!(cell > 0.0f) || !(cell < inf)) return MISO_E_BADARG;
-  if (n_tgt >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (!fits32(n_tgt)) return MISO_E_TOOLARGE;
   memset(plan, 0, sizeof(*plan));
   plan->n_tgt = n_tgt; plan->max_rings = max_rings; plan->cell = cell;
   plan->dims[0] = plan->dims[1] = plan->dims[2] = 1; plan->cells = 1;
@@ -1048,14 +1100,6 @@ int miso_nn_plan(const float* bound_min, const float* bound_max, float cell, int
   return MISO_OK;
 }
 
-// a plan as miso_nn_plan writes it (the struct is the caller's memory: the kernels index by it)
-static bool nn_plan_ok(const miso_nn_plan_t* p) {
-  if (!p || p->n_tgt < 0 || p->n_tgt >= ((int64_t)1 << 31) || p->max_rings < 0 || p->max_rings > MISO_NN_MAX_RINGS) return false;
-  if (p->dims[0] < 1 || p->dims[1] < 1 || p->dims[2] < 1 || p->cells < 1 || p->cells > MISO_NN_MAX_CELLS) return false;
-  if ((int64_t)p->dims[0] * p->dims[1] > MISO_NN_MAX_CELLS || (int64_t)p->dims[0] * p->dims[1] * p->dims[2] != p->cells) return false;
-  return p->cell > 0.0f && p->cell < __builtin_huge_valf() && p->coord_mag >= 0.0f;
-}
-
 int64_t miso_nn_workspace_bytes(const miso_nn_plan_t* plan) {
   return nn_plan_ok(plan) ? nn_workspace_bytes(*plan) : 0;
 }
@@ -1063,59 +1107,59 @@ int64_t miso_nn_workspace_bytes(const miso_nn_plan_t* plan) {
 int miso_nn_build(const miso_nn_plan_t* plan, const float* tgt, int64_t ld, void* workspace, void* stream) {
   if (!nn_plan_ok(plan) || ld < 3) return MISO_E_BADARG;
   if (plan->n_tgt == 0) return MISO_OK;
-  if (!tgt || !workspace || ((uintptr_t)workspace & 15u)) return MISO_E_BADARG;
+  if (!tgt || !index_ready(plan->n_tgt, workspace)) return MISO_E_BADARG;
   return (int)launch_nn_build(*plan, tgt, ld, workspace, (hipStream_t)stream);
 }
 
 int miso_nn_query(const miso_nn_plan_t* plan, void* workspace, const float* src, int64_t ld, int64_t n, float* out_d2,
                   int64_t* out_idx, int32_t* stats, void* stream) {
-  if (!nn_plan_ok(plan) || ld < 3 || n < 0 || !stats) return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  if (n > 0 && (!src || !out_d2 || !out_idx)) return MISO_E_BADARG;
-  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  if (!nn_plan_ok(plan) || !stats) return MISO_E_BADARG;
+  if (int rc = check_cloud(src, ld, n, out_d2, out_idx)) return rc;
+  if (!index_ready(plan->n_tgt, workspace)) return MISO_E_BADARG;
   return (int)launch_nn_query(*plan, workspace, src, ld, n, out_d2, out_idx, stats, (hipStream_t)stream);
+}
+
+// targets and queries both in the caller's arrays
+static int check_cloud_pair(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, float* out_d2,
+                            int64_t* out_idx) {
+  if (int rc = check_cloud(tgt, ld_t, m)) return rc;
+  return check_cloud(src, ld_s, n, out_d2, out_idx);
 }
 
 int miso_nn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, float* out_d2,
                       int64_t* out_idx, void* stream) {
-  if (m < 0 || n < 0 || ld_t < 3 || ld_s < 3) return MISO_E_BADARG;
-  if (m >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  if ((m > 0 && !tgt) || (n > 0 && (!src || !out_d2 || !out_idx))) return MISO_E_BADARG;
+  if (int rc = check_cloud_pair(tgt, ld_t, m, src, ld_s, n, out_d2, out_idx)) return rc;
   return (int)launch_nn_all_pairs(tgt, ld_t, m, src, ld_s, n, out_d2, out_idx, (hipStream_t)stream);
 }
 
 // ---- exact k nearest neighbours on the index (knn.hip) -------------------------------------------------------------------
-static bool nn_k_ok(int32_t k) { return k >= 1 && k <= MISO_NN_KNN_MAX; }
-
 int miso_nn_knn(const miso_nn_plan_t* plan, void* workspace, const float* src, int64_t ld, int64_t n, int32_t k, float* out_d2,
                 int64_t* out_idx, int32_t* stats, void* stream) {
-  if (!nn_plan_ok(plan) || !nn_k_ok(k) || ld < 3 || n < 0 || n >= ((int64_t)1 << 31) || !stats) return MISO_E_BADARG;
-  if (n > 0 && (!src || !out_d2 || !out_idx)) return MISO_E_BADARG;
-  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  if (!nn_plan_ok(plan) || !nn_k_ok(k) || !stats) return MISO_E_BADARG;
+  if (int rc = check_cloud(src, ld, n, out_d2, out_idx)) return knn_code(rc);
+  if (!index_ready(plan->n_tgt, workspace)) return MISO_E_BADARG;
   return (int)launch_nn_knn(*plan, workspace, src, ld, n, k, out_d2, out_idx, stats, (hipStream_t)stream);
 }
 
 int miso_nn_knn_all_pairs(const float* tgt, int64_t ld_t, int64_t m, const float* src, int64_t ld_s, int64_t n, int32_t k,
                           float* out_d2, int64_t* out_idx, void* stream) {
-  if (!nn_k_ok(k) || m < 0 || n < 0 || ld_t < 3 || ld_s < 3) return MISO_E_BADARG;
-  if (m >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_BADARG;
-  if ((m > 0 && !tgt) || (n > 0 && (!src || !out_d2 || !out_idx))) return MISO_E_BADARG;
+  if (!nn_k_ok(k)) return MISO_E_BADARG;
+  if (int rc = check_cloud_pair(tgt, ld_t, m, src, ld_s, n, out_d2, out_idx)) return knn_code(rc);
   return (int)launch_nn_knn_all_pairs(tgt, ld_t, m, src, ld_s, n, k, out_d2, out_idx, (hipStream_t)stream);
 }
 
 int miso_nn_knn_normals(const miso_nn_plan_t* plan, void* workspace, const float* pts, int64_t ld, int64_t n, int32_t k,
                         float* normals, int32_t* counts, void* stream) {
-  if (!nn_plan_ok(plan) || !nn_k_ok(k) || ld < 3 || n < 0 || n >= ((int64_t)1 << 31)) return MISO_E_BADARG;
-  if (n > 0 && (!pts || !normals || !counts)) return MISO_E_BADARG;
-  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  if (!nn_plan_ok(plan) || !nn_k_ok(k)) return MISO_E_BADARG;
+  if (int rc = check_cloud(pts, ld, n, normals, counts)) return knn_code(rc);
+  if (!index_ready(plan->n_tgt, workspace)) return MISO_E_BADARG;
   return (int)launch_nn_knn_normals(*plan, workspace, pts, ld, n, k, normals, counts, (hipStream_t)stream);
 }
 
 // ---- ICP and normals on the index (icp.hip) ----------------------------------------------------------------------------------
 int miso_icp_transform(const float* src, int64_t ld, int64_t n, const float* pose, float* out, void* stream) {
-  if (n < 0 || ld < 3 || !pose) return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  if (n > 0 && (!src || !out)) return MISO_E_BADARG;
+  if (!pose) return MISO_E_BADARG;
+  if (int rc = check_cloud(src, ld, n, out)) return rc;
   return (int)launch_icp_transform(pose, src, ld, n, out, (hipStream_t)stream);
 }
 
@@ -1124,8 +1168,8 @@ int64_t miso_icp_workspace_bytes(int64_t n) { return n < 0 ? 0 : icp_workspace_b
 int miso_icp_sums(const float* moved, const float* d2, const int64_t* idx, int64_t n, const float* tgt, int64_t ld_t,
                   int64_t m, const float* normals, int64_t ld_n, double max_dist, int32_t kind, int32_t loss,
                   double tukey_k, const double* origin, void* workspace, double* out, void* stream) {
-  if (n < 0 || m < 0 || ld_t < 3 || !workspace || !out || ((uintptr_t)workspace & 7u) || ((uintptr_t)out & 7u)) return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 31) || m >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (n < 0 || m < 0 || ld_t < 3 || !workspace || !out || !aligned(8, workspace, out)) return MISO_E_BADARG;
+  if (!fits32(n) || !fits32(m)) return MISO_E_TOOLARGE;
   if (kind != MISO_ICP_POINT_TO_POINT && kind != MISO_ICP_POINT_TO_PLANE) return MISO_E_BADARG;
   if (loss != MISO_ICP_LOSS_L2 && loss != MISO_ICP_LOSS_TUKEY) return MISO_E_BADARG;
   if (!(max_dist >= 0.0) || (loss == MISO_ICP_LOSS_TUKEY && !(tukey_k > 0.0))) return MISO_E_BADARG;
@@ -1137,17 +1181,16 @@ int miso_icp_sums(const float* moved, const float* d2, const int64_t* idx, int64
 
 int miso_nn_normals(const miso_nn_plan_t* plan, const void* workspace, const float* pts, int64_t ld, int64_t n,
                     double radius, float* normals, int32_t* counts, void* stream) {
-  if (!nn_plan_ok(plan) || ld < 3 || n < 0 || !(radius > 0.0) || !(radius < 1e30)) return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  if (n > 0 && (!pts || !normals || !counts)) return MISO_E_BADARG;
-  if (plan->n_tgt > 0 && (!workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  if (!nn_plan_ok(plan) || !(radius > 0.0) || !(radius < 1e30)) return MISO_E_BADARG;
+  if (int rc = check_cloud(pts, ld, n, normals, counts)) return rc;
+  if (!index_ready(plan->n_tgt, workspace)) return MISO_E_BADARG;
   return (int)launch_nn_normals(*plan, workspace, pts, ld, n, radius, normals, counts, (hipStream_t)stream);
 }
 
 // ---- ray casting against a triangle mesh (mesh.hip) ---------------------------------------------------------------------------
 int miso_mesh_plan(const float* bound_min, const float* bound_max, float cell, int64_t n_tri, miso_mesh_plan_t* plan) {
   if (!plan || n_tri < 0) return MISO_E_BADARG;
-  if (n_tri >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
+  if (!fits32(n_tri)) return MISO_E_TOOLARGE;
   // the grid is the nearest-neighbour index's: the same dims, doubling and coord_mag (MISO_MESH_MAX_CELLS == MISO_NN_MAX_CELLS)
   static_assert(MISO_MESH_MAX_CELLS == MISO_NN_MAX_CELLS, "one grid plan");
   miso_nn_plan_t g;
@@ -1160,41 +1203,31 @@ int miso_mesh_plan(const float* bound_min, const float* bound_max, float cell, i
   return MISO_OK;
 }
 
-// a plan as miso_mesh_plan writes it (the struct is the caller's memory: the kernels index by it)
-static bool mesh_plan_ok(const miso_mesh_plan_t* p) {
-  if (!p || p->n_tri < 0 || p->n_tri >= ((int64_t)1 << 31)) return false;
-  if (p->dims[0] < 1 || p->dims[1] < 1 || p->dims[2] < 1 || p->cells < 1 || p->cells > MISO_MESH_MAX_CELLS) return false;
-  if ((int64_t)p->dims[0] * p->dims[1] > MISO_MESH_MAX_CELLS || (int64_t)p->dims[0] * p->dims[1] * p->dims[2] != p->cells) return false;
-  return p->cell > 0.0f && p->cell < __builtin_huge_valf() && p->coord_mag >= 0.0f && p->coord_mag < __builtin_huge_valf() &&
-         p->widen >= 0.0f && p->widen <= p->coord_mag;
-}
-
 int64_t miso_mesh_workspace_bytes(const miso_mesh_plan_t* plan) {
   return mesh_plan_ok(plan) ? mesh_workspace_bytes(*plan) : 0;
 }
 
 int miso_mesh_count(const miso_mesh_plan_t* plan, const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris,
                     int64_t ld_t, void* workspace, int64_t* entries, void* stream) {
-  if (!mesh_plan_ok(plan) || ld_v < 3 || ld_t < 3 || n_vert < 0 || !entries || ((uintptr_t)entries & 7u)) return MISO_E_BADARG;
-  if (plan->n_tri > 0 && (!tris || (n_vert > 0 && !verts) || !workspace || ((uintptr_t)workspace & 15u))) return MISO_E_BADARG;
+  if (!mesh_plan_ok(plan) || !entries || !aligned(8, entries)) return MISO_E_BADARG;
+  if (int rc = check_mesh_arrays(verts, ld_v, n_vert, tris, ld_t, plan->n_tri)) return rc;
+  if (!index_ready(plan->n_tri, workspace)) return MISO_E_BADARG;
   return (int)launch_mesh_count(*plan, verts, ld_v, n_vert, tris, ld_t, workspace, entries, (hipStream_t)stream);
 }
 
 int miso_mesh_build(const miso_mesh_plan_t* plan, void* workspace, int32_t* lists, int64_t capacity, void* stream) {
-  if (!mesh_plan_ok(plan) || capacity < 0) return MISO_E_BADARG;
+  if (!mesh_index_ok(plan, workspace, lists, capacity)) return MISO_E_BADARG;
   if (capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
   if (plan->n_tri == 0) return MISO_OK;
-  if (!workspace || ((uintptr_t)workspace & 15u) || (capacity > 0 && !lists)) return MISO_E_BADARG;
   return (int)launch_mesh_build(*plan, workspace, lists, capacity, (hipStream_t)stream);
 }
 
 int miso_mesh_cast_rays(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
                         const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min,
                         float t_max, float* out_t, int64_t* out_tri, int64_t* stats, void* stream) {
-  if (!mesh_plan_ok(plan) || ld_o < 3 || ld_d < 3 || n < 0 || capacity < 0 || ((uintptr_t)stats & 7u)) return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 31) || capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
-  if (n > 0 && (!origins || !dirs || !out_t || !out_tri)) return MISO_E_BADARG;
-  if (plan->n_tri > 0 && (!workspace || ((uintptr_t)workspace & 15u) || (capacity > 0 && !lists))) return MISO_E_BADARG;
+  if (!mesh_index_ok(plan, workspace, lists, capacity) || !aligned(8, stats)) return MISO_E_BADARG;
+  if (capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
+  if (int rc = check_rays(origins, ld_o, dirs, ld_d, n, out_t, out_tri)) return rc;
   return (int)launch_mesh_cast_rays(*plan, workspace, lists, capacity, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_t, out_tri,
                                     stats, (hipStream_t)stream);
 }
@@ -1202,50 +1235,42 @@ int miso_mesh_cast_rays(const miso_mesh_plan_t* plan, const void* workspace, con
 int miso_mesh_cast_rays_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t,
                             int64_t n_tri, const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n,
                             float t_min, float t_max, float* out_t, int64_t* out_tri, void* stream) {
-  if (n_vert < 0 || n_tri < 0 || n < 0 || ld_v < 3 || ld_t < 3 || ld_o < 3 || ld_d < 3) return MISO_E_BADARG;
-  if (n_tri >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  if ((n_tri > 0 && (!tris || (n_vert > 0 && !verts))) || (n > 0 && (!origins || !dirs || !out_t || !out_tri))) return MISO_E_BADARG;
+  if (int rc = check_mesh_arrays(verts, ld_v, n_vert, tris, ld_t, n_tri)) return rc;
+  if (int rc = check_rays(origins, ld_o, dirs, ld_d, n, out_t, out_tri)) return rc;
   return (int)launch_mesh_cast_rays_all(verts, ld_v, n_vert, tris, ld_t, n_tri, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_t,
                                         out_tri, (hipStream_t)stream);
 }
 
 // ---- closest triangle and crossing counts on the mesh index (mesh_sdf.hip) ----------------------------------------------------
-// an index as miso_mesh_build left it, ready to be read
-static bool mesh_index_ok(const miso_mesh_plan_t* p, const void* workspace, const int32_t* lists, int64_t capacity) {
-  if (!mesh_plan_ok(p) || capacity < 0) return false;
-  return p->n_tri == 0 || (workspace && !((uintptr_t)workspace & 15u) && (capacity == 0 || lists));
-}
-
 int miso_mesh_closest(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
                       const miso_mesh_plan_t* plan_far, const void* workspace_far, const int32_t* lists_far, int64_t capacity_far,
                       const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri, float* out_vw, int64_t* stats,
                       void* stream) {
-  if (!mesh_index_ok(plan, workspace, lists, capacity) || ld_p < 3 || n < 0 || ((uintptr_t)stats & 7u) || ((uintptr_t)out_vw & 7u))
-    return MISO_E_BADARG;
+  if (!mesh_index_ok(plan, workspace, lists, capacity) || !aligned(8, stats, out_vw)) return MISO_E_BADARG;
   // the far set is one more index of the SAME triangles (the kernel reads the rows of the first), or absent as a whole
   if (plan_far ? (!mesh_index_ok(plan_far, workspace_far, lists_far, capacity_far) || plan_far->n_tri != plan->n_tri || plan_far->reserved < 0)
                : (workspace_far || lists_far || capacity_far != 0))
     return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 31) || capacity > MISO_MESH_MAX_ENTRIES || capacity_far > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
-  if (n > 0 && (!pts || !out_d2 || !out_tri)) return MISO_E_BADARG;
+  if (capacity > MISO_MESH_MAX_ENTRIES || capacity_far > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
+  if (int rc = check_cloud(pts, ld_p, n, out_d2, out_tri)) return rc;
   return (int)launch_mesh_closest(*plan, workspace, lists, capacity, plan_far, workspace_far, lists_far, capacity_far, pts, ld_p, n,
                                   out_d2, out_tri, out_vw, stats, (hipStream_t)stream);
 }
 
 int miso_mesh_closest_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri,
                           const float* pts, int64_t ld_p, int64_t n, float* out_d2, int64_t* out_tri, float* out_vw, void* stream) {
-  if (n_vert < 0 || n_tri < 0 || n < 0 || ld_v < 3 || ld_t < 3 || ld_p < 3 || ((uintptr_t)out_vw & 7u)) return MISO_E_BADARG;
-  if (n_tri >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  if ((n_tri > 0 && (!tris || (n_vert > 0 && !verts))) || (n > 0 && (!pts || !out_d2 || !out_tri))) return MISO_E_BADARG;
+  if (!aligned(8, out_vw)) return MISO_E_BADARG;
+  if (int rc = check_mesh_arrays(verts, ld_v, n_vert, tris, ld_t, n_tri)) return rc;
+  if (int rc = check_cloud(pts, ld_p, n, out_d2, out_tri)) return rc;
   return (int)launch_mesh_closest_all(verts, ld_v, n_vert, tris, ld_t, n_tri, pts, ld_p, n, out_d2, out_tri, out_vw, (hipStream_t)stream);
 }
 
 int miso_mesh_count_hits(const miso_mesh_plan_t* plan, const void* workspace, const int32_t* lists, int64_t capacity,
                          const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min, float t_max,
                          int32_t* out_count, void* stream) {
-  if (!mesh_index_ok(plan, workspace, lists, capacity) || ld_o < 3 || ld_d < 3 || n < 0) return MISO_E_BADARG;
-  if (n >= ((int64_t)1 << 31) || capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
-  if (n > 0 && (!origins || !dirs || !out_count)) return MISO_E_BADARG;
+  if (!mesh_index_ok(plan, workspace, lists, capacity)) return MISO_E_BADARG;
+  if (capacity > MISO_MESH_MAX_ENTRIES) return MISO_E_TOOLARGE;
+  if (int rc = check_rays(origins, ld_o, dirs, ld_d, n, out_count)) return rc;
   return (int)launch_mesh_count_hits(*plan, workspace, lists, capacity, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_count,
                                      (hipStream_t)stream);
 }
@@ -1253,9 +1278,8 @@ int miso_mesh_count_hits(const miso_mesh_plan_t* plan, const void* workspace, co
 int miso_mesh_count_hits_all(const float* verts, int64_t ld_v, int64_t n_vert, const int64_t* tris, int64_t ld_t, int64_t n_tri,
                              const float* origins, int64_t ld_o, const float* dirs, int64_t ld_d, int64_t n, float t_min,
                              float t_max, int32_t* out_count, void* stream) {
-  if (n_vert < 0 || n_tri < 0 || n < 0 || ld_v < 3 || ld_t < 3 || ld_o < 3 || ld_d < 3) return MISO_E_BADARG;
-  if (n_tri >= ((int64_t)1 << 31) || n >= ((int64_t)1 << 31)) return MISO_E_TOOLARGE;
-  if ((n_tri > 0 && (!tris || (n_vert > 0 && !verts))) || (n > 0 && (!origins || !dirs || !out_count))) return MISO_E_BADARG;
+  if (int rc = check_mesh_arrays(verts, ld_v, n_vert, tris, ld_t, n_tri)) return rc;
+  if (int rc = check_rays(origins, ld_o, dirs, ld_d, n, out_count)) return rc;
   return (int)launch_mesh_count_hits_all(verts, ld_v, n_vert, tris, ld_t, n_tri, origins, ld_o, dirs, ld_d, n, t_min, t_max, out_count,
                                          (hipStream_t)stream);
 }
@@ -1270,8 +1294,7 @@ int miso_atlas_plan_build(const miso_grid_t* grids, int32_t n_submaps, void* pla
   GridK* out = reinterpret_cast<GridK*>(plan_host);
   for (int s = 0; s < n_submaps; ++s) {
     bool v4;
-    int rc = convert_grid(&grids[s], &out[s], true, &v4);
-    if (rc) return rc;
+    if (int rc = convert_grid(&grids[s], &out[s], true, &v4)) return rc;
     if (!v4 || (out[s].flags & MISO_F_COORDS_NORMALIZED)) return MISO_E_UNSUPPORTED;
     if (out[s].n_levels != out[0].n_levels) return MISO_E_UNSUPPORTED;
     for (int l = 0; l < out[s].n_levels; ++l)
@@ -1286,35 +1309,29 @@ int miso_atlas_sdf_fwd(const void* plan, int32_t n_submaps, const miso_grid_t* s
                        const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n, const float* axis_x,
                        const float* axis_y, const float* axis_z, int32_t nx, int32_t ny, int32_t nz, float* sdf,
                        float* feats, int64_t ld_feats, uint32_t flags, void* stream) {
-  if (!plan || !poses || !shape || n_submaps < 1 || n < 0 || (!sdf && !feats)) return MISO_E_BADARG;
-  if (flags & ~(MISO_F_EXACT_F32 | MISO_F_ATLAS_NO_BOUND)) return MISO_E_BADARG;
-  GridK g; bool v4;
-  int rc = convert_grid(shape, &g, false, &v4);
-  if (rc) return rc;
-  int C = g.lv[0].C, L = g.n_levels, H = 64, NH = 1;
-  if (sdf) {
-    if (!mlp || !packed || (((uintptr_t)packed) & 15u)) return MISO_E_BADARG;
-    rc = fused_shape(g, true, mlp, &C, &L, &H, &NH);
-    if (rc) return rc;
-  } else {
-    for (int l = 0; l < L; ++l)
-      if (g.lv[l].C != C) return MISO_E_UNSUPPORTED;
-    if (!fused_shape_supported(C, L, H, NH)) return MISO_E_UNSUPPORTED;
-  }
-  if (feats && ld_feats < g.F) return MISO_E_BADARG;
   AtlasK a;
-  memset(&a, 0, sizeof(a));
-  a.submaps = reinterpret_cast<const GridK*>(plan);
-  a.poses = poses; a.n_submaps = n_submaps; a.n = n; a.sdf = sdf; a.feats = feats; a.ld = ld_feats;
-  a.no_bound = (flags & MISO_F_ATLAS_NO_BOUND) ? 1 : 0;
+  if (int rc = atlas_call(&a, plan, n_submaps, poses, n, flags)) return rc;
+  if (!shape || (!sdf && !feats)) return MISO_E_BADARG;
+  FusedCall f;
+  if (sdf) {
+    if (!mlp) return MISO_E_BADARG;
+    if (int rc = fused_call(&f, shape, mlp, packed, false, FUSED_ATLAS)) return rc;
+  } else {      // features only: no decoder is read, the shape is still one of the kernel table's
+    if (int rc = fused_grid(&f, shape, false)) return rc;
+    for (int l = 0; l < f.L; ++l)
+      if (f.g.lv[l].C != f.C) return MISO_E_UNSUPPORTED;
+    if (!fused_shape_supported(f.C, f.L, f.H, f.NH)) return MISO_E_UNSUPPORTED;
+  }
+  if (feats && ld_feats < f.g.F) return MISO_E_BADARG;
+  a.sdf = sdf; a.feats = feats; a.ld = ld_feats;
   if (x) {
     a.x = x;
   } else {
     if (!axis_x || !axis_y || !axis_z || nx < 1 || ny < 1 || nz < 1) return MISO_E_BADARG;
-    if ((int64_t)nx * ny * nz != n || n >= ((int64_t)1 << 31)) return MISO_E_BADARG;
+    if ((int64_t)nx * ny * nz != n || !fits32(n)) return MISO_E_BADARG;
     a.ax[0] = axis_x; a.ax[1] = axis_y; a.ax[2] = axis_z; a.dim[0] = nx; a.dim[1] = ny; a.dim[2] = nz;
   }
-  return (int)launch_atlas_sdf(C, L, H, NH, a, packed, (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
+  return (int)launch_atlas_sdf(f.C, f.L, f.H, f.NH, a, packed, (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
 }
 
 // ---- backward of the fused atlas query (atlas_bwd.hip) ------------------------------------------------------------------
@@ -1323,35 +1340,25 @@ int64_t miso_atlas_bwd_workspace_bytes(int64_t n, int32_t n_submaps) {
 }
 
 int miso_atlas_bwd_supported(const miso_grid_t* shape, const miso_mlp_t* mlp, int32_t n_submaps, int want_poses) {
-  GridK g; bool v4;
-  if (!shape || !mlp || convert_grid(shape, &g, false, &v4)) return 0;
-  if (g.flags & MISO_F_COORDS_NORMALIZED) return 0;
-  int C, L, H, NH;
-  if (fused_shape(g, true, mlp, &C, &L, &H, &NH)) return 0;
-  return atlas_bwd_covered(C, L, H, NH, n_submaps, want_poses != 0) ? 1 : 0;
+  FusedCall f;
+  if (!shape || !mlp || fused_query(&f, shape, mlp, false, FUSED_ATLAS)) return 0;
+  if (f.g.flags & MISO_F_COORDS_NORMALIZED) return 0;
+  return atlas_bwd_covered(f.C, f.L, f.H, f.NH, n_submaps, want_poses != 0) ? 1 : 0;
 }
 
 int miso_atlas_sdf_bwd(const void* plan, int32_t n_submaps, const miso_grid_t* shape, const float* poses,
                        const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n, const float* gsdf,
                        float* gx, float* gposes, void* workspace, uint32_t flags, void* stream) {
-  if (!plan || !poses || !shape || !mlp || !packed || n_submaps < 1 || n < 0) return MISO_E_BADARG;
-  if (flags & ~(MISO_F_EXACT_F32 | MISO_F_ATLAS_NO_BOUND)) return MISO_E_BADARG;
-  if (((uintptr_t)packed) & 15u) return MISO_E_BADARG;
-  GridK g; bool v4;
-  int rc = convert_grid(shape, &g, false, &v4);
-  if (rc) return rc;
-  int C = g.lv[0].C, L = g.n_levels, H = 64, NH = 1;
-  rc = fused_shape(g, true, mlp, &C, &L, &H, &NH);
-  if (rc) return rc;
-  if (!atlas_bwd_covered(C, L, H, NH, n_submaps, gposes != nullptr)) return MISO_E_UNSUPPORTED;
-  if (n == 0) return MISO_OK;
-  if (!x || !gsdf || (gposes && (!workspace || (((uintptr_t)workspace) & 3u)))) return MISO_E_BADARG;
   AtlasK a;
-  memset(&a, 0, sizeof(a));
-  a.submaps = reinterpret_cast<const GridK*>(plan);
-  a.poses = poses; a.n_submaps = n_submaps; a.n = n; a.x = x;
-  a.no_bound = (flags & MISO_F_ATLAS_NO_BOUND) ? 1 : 0;
-  return (int)launch_atlas_sdf_bwd(C, L, H, NH, a, packed, gsdf, gx, gposes, reinterpret_cast<float*>(workspace),
+  if (int rc = atlas_call(&a, plan, n_submaps, poses, n, flags)) return rc;
+  if (!shape || !mlp) return MISO_E_BADARG;
+  FusedCall f;
+  if (int rc = fused_call(&f, shape, mlp, packed, false, FUSED_ATLAS)) return rc;
+  if (!atlas_bwd_covered(f.C, f.L, f.H, f.NH, n_submaps, gposes != nullptr)) return MISO_E_UNSUPPORTED;
+  if (n == 0) return MISO_OK;
+  if (!x || !gsdf || (gposes && (!workspace || !aligned(4, workspace)))) return MISO_E_BADARG;
+  a.x = x;
+  return (int)launch_atlas_sdf_bwd(f.C, f.L, f.H, f.NH, a, packed, gsdf, gx, gposes, reinterpret_cast<float*>(workspace),
                                    (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
 }
 
@@ -1361,28 +1368,19 @@ int miso_atlas_sphere_trace(const void* plan, int32_t n_submaps, const miso_grid
                             int64_t n_rays, float min_dist, float max_dist, int32_t max_iters, float epsilon,
                             float fd_step, float* points, uint8_t* hit, float* sdf, int32_t* steps, float* grad,
                             uint32_t flags, void* stream) {
-  if (!plan || !poses || !shape || !mlp || !packed || !origins || !dirs || !points || !hit) return MISO_E_BADARG;
-  if (n_submaps < 1 || n_rays < 0 || max_iters < 1 || (grad && !(fd_step > 0.0f))) return MISO_E_BADARG;
-  if (flags & ~(MISO_F_EXACT_F32 | MISO_F_ATLAS_NO_BOUND)) return MISO_E_BADARG;
-  if (((uintptr_t)packed) & 15u) return MISO_E_BADARG;
-  GridK g; bool v4;
-  int rc = convert_grid(shape, &g, false, &v4);
-  if (rc) return rc;
-  int C = g.lv[0].C, L = g.n_levels, H = 64, NH = 1;
-  rc = fused_shape(g, true, mlp, &C, &L, &H, &NH);
-  if (rc) return rc;
-  if (n_rays == 0) return MISO_OK;
   AtlasK a;
-  memset(&a, 0, sizeof(a));
-  a.submaps = reinterpret_cast<const GridK*>(plan);
-  a.poses = poses; a.n_submaps = n_submaps; a.n = n_rays;
-  a.no_bound = (flags & MISO_F_ATLAS_NO_BOUND) ? 1 : 0;
+  if (int rc = atlas_call(&a, plan, n_submaps, poses, n_rays, flags)) return rc;
+  if (!shape || !mlp || !all_set(origins, dirs, points) || !hit) return MISO_E_BADARG;
+  if (max_iters < 1 || (grad && !(fd_step > 0.0f))) return MISO_E_BADARG;
+  FusedCall f;
+  if (int rc = fused_call(&f, shape, mlp, packed, false, FUSED_ATLAS)) return rc;
+  if (n_rays == 0) return MISO_OK;
   TraceK t;
   memset(&t, 0, sizeof(t));
   t.origins = origins; t.dirs = dirs; t.n = n_rays;
   t.min_dist = min_dist; t.max_dist = max_dist; t.epsilon = epsilon; t.fd_step = fd_step; t.max_iters = max_iters;
   t.points = points; t.hit = hit; t.sdf = sdf; t.steps = steps; t.grad = grad;
-  return (int)launch_atlas_trace(C, L, H, NH, a, t, packed, (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
+  return (int)launch_atlas_trace(f.C, f.L, f.H, f.NH, a, t, packed, (flags & MISO_F_EXACT_F32) != 0, (hipStream_t)stream);
 }
 
 int64_t miso_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
@@ -1393,7 +1391,7 @@ int64_t miso_mc_workspace_bytes(int32_t nx, int32_t ny, int32_t nz) {
 int miso_mc_classify(const float* vol, int32_t nx, int32_t ny, int32_t nz, float iso, void* workspace,
                      int32_t* counts, void* stream) {
   if (int rc = mc_check_dims(nx, ny, nz)) return rc;
-  if (!vol || !workspace || !counts || (((uintptr_t)workspace) & 7u)) return MISO_E_BADARG;
+  if (!all_set(vol, workspace, counts) || !aligned(8, workspace)) return MISO_E_BADARG;
   return (int)launch_mc_classify(vol, nx, ny, nz, iso, workspace, counts, (hipStream_t)stream);
 }
 
