@@ -38,7 +38,7 @@
  *   miso_mapping_loss miso_loss_regression + miso_loss_free_space and their gradient
  *                     w.r.t. the prediction, grid_opt/loss.py:594-635, :668-700, as
  *                     combined by MisoLossMappingBase.compute (loss.py:776-806).
- *   miso_adam_dense / miso_adam_active
+ *   miso_adam_dense / miso_adam_step
  *                     torch.optim.Adam.step on one dense tensor as used by
  *                     grid_opt/trainer.py:196-228 / :410-452.
  *   miso_rigid_by_index  the per-keyframe frame change of a sample batch (grid_opt/loss.py:763-774 around
@@ -131,7 +131,7 @@ typedef struct {
   int64_t sC, sZ, sY, sX;
   /* NULL, or one byte per MISO_ADAM_CHUNK (64) consecutive floats of the DENSE storage that starts at `grad`:
    * every kernel of this library that adds or stores a non-zero into grad[off] also sets grad_touched[off / 64]
-   * = 1 (nothing here ever clears a byte).  miso_adam_touched then steps a 0.6 G-byte level from its 2.3 M flag
+   * = 1 (nothing here ever clears a byte).  miso_adam_step then steps a 0.6 G-byte level from its 2.3 M flag
    * bytes instead of reading the whole gradient to find the few chunks a small batch wrote. */
   uint8_t* grad_touched;
 } miso_level_t;
@@ -302,7 +302,7 @@ int miso_sdf_train_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const 
                           const int32_t* n_live, float* workspace, void* stream);
 /* The same step for an unbinned (small) batch, x (N,3) and loss_inputs (N,4) in the caller's order: forward + mapping
  * loss + decoder backward + the atomic scatter of every level's gradient in ONE launch (what miso_sdf_fwd_loss +
- * miso_sdf_bwd do in two).  The gradients are ADDED to `grad` (clear them first, or let miso_adam_active(zero_grad)). */
+ * miso_sdf_bwd do in two).  The gradients are ADDED to `grad` (clear them first, or let miso_adam_step clear them: zero_grad). */
 int miso_sdf_train(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
                    int loss_type, float weight_sdf, float weight_fs, float trunc_dist, const float* loss_inputs,
                    float* sdf /* may be NULL */, float* loss_slots, void* stream);
@@ -643,78 +643,77 @@ int miso_sample_rays(const miso_ray_frames_t* frames, const miso_ray_sampling_t*
                      const float* g, void* workspace, float* coords_frame, int64_t* sample_frame_ids,
                      float* aux, float* pc_world, float* z_vals, int32_t* counts, void* stream);
 
-/* The same step without the work that changes nothing: an element whose gradient has been zero in
- * every step so far has exp_avg = exp_avg_sq = 0 and an update of exactly 0.  `active` holds one byte
- * per MISO_ADAM_CHUNK consecutive floats of the storage ((numel + CHUNK-1)/CHUNK bytes, zeroed by the
- * caller together with the moments): a chunk is stepped if any of its gradients is non-zero or if it
- * has been stepped before (then the byte is 1).  Bit-identical to miso_adam_dense; reads 4 B per
- * element plus 28 B per active element.  All four arrays must be 16-B aligned.  zero_grad clears the
- * gradient of the stepped chunks -- the others are zero already.
- * guard (device float, or NULL): the loss of the step.  If it is NaN the launch changes no parameter, moment or
- * flag (the reference's NaN guard, grid_opt/trainer.py:213-219: "Loss is nan! Skip backward step") and only
- * clears the gradients it was asked to clear -- the host can launch without reading the loss back first. */
+/* --- Adam that skips what cannot move: miso_adam_step and the four entries around it -------------------------------
+ * miso_adam_dense's step without the work that changes nothing: an element whose gradient has been zero in every step
+ * so far has exp_avg = exp_avg_sq = 0 and an update of exactly 0.  `active` holds one byte per MISO_ADAM_CHUNK
+ * consecutive floats of a tensor's storage ((numel + CHUNK-1)/CHUNK bytes, zeroed by the caller together with the
+ * moments): a chunk is stepped if it has been stepped before (then the byte is 1) or if this step's gradient reaches it.
+ * Results are bit-identical to miso_adam_dense.  Which chunks the gradient reaches is found in one of two ways, per
+ * tensor:
+ *   touched == NULL  by reading the gradient: 4 B per element plus 28 B per stepped element.
+ *   touched != NULL  from the flags the scatter kernels leave (miso_level_t.grad_touched): a chunk is stepped if
+ *                    active[c] or touched[c]; touched[c] is cleared.  2 B per chunk plus 28 B per stepped element.  Same
+ *                    results PROVIDED every writer of `grad` since the last step maintained the flags (the kernels of
+ *                    this library do; a caller that adds to the gradient by other means leaves `touched` NULL).  Both
+ *                    flag arrays must then be 4-byte aligned (four bytes are read as one word) and hold 0 / 1 only.
+ * zero_grad clears the gradient of the stepped chunks (of the touched ones in the second form) -- the others are zero
+ * already. */
 #define MISO_ADAM_CHUNK 64
-int miso_adam_active(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active,
-                     int64_t numel, double lr, double beta1, double beta2, double eps,
-                     int32_t step /* 1-based */, int zero_grad, const float* guard, void* stream);
-
-/* miso_adam_active driven by the flags the scatter kernels leave (miso_level_t.grad_touched) instead of by reading
- * the gradient: a chunk is stepped if active[c] or touched[c]; touched[c] is cleared.  Same arithmetic, same results
- * PROVIDED every writer of `grad` since the last call maintained the flags (the kernels of this library do; a caller
- * that adds to the gradient by other means must use miso_adam_active).  `active` and `touched` must be 4-byte aligned
- * (four flag bytes are read as one word) and hold the values 0 / 1 only.  Traffic: 2 B per chunk + 28 B per stepped
- * element.  zero_grad and guard as above (a NaN guard leaves parameters, moments and `active` alone, still clears
- * the flags and, if asked, the touched gradients). */
-int miso_adam_touched(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active,
-                      uint8_t* touched, int64_t numel, double lr, double beta1, double beta2, double eps,
-                      int32_t step /* 1-based */, int zero_grad, const float* guard, void* stream);
-
-/* Adam inside a captured HIP graph.  The bias corrections change every step but the arguments of a captured launch do
- * not, so a captured step reads them from the device: `table` (device, table_len rows of 6 floats) holds the step
- * scalars of steps 1..table_len exactly as miso_adam_active computes them on the host -- filled by
- * miso_adam_scalars_table (a HOST function writing a HOST buffer; upload it) -- and `step` (device int32) the 1-based
- * count of the step being taken.  Steps past the table use its last row (choose table_len so that beta^table_len
- * has left fp32: the rows no longer change).  miso_adam_bump, once per step and in front of the level launches:
- * step += 1 unless *guard is NaN (the reference's NaN guard skips optimizer.step(), grid_opt/trainer.py:213-219, so
- * the count must not move).  miso_adam_step_dev = miso_adam_active (touched == NULL) / miso_adam_touched with the
- * scalars of table[*step - 1]: bit-identical to the launch-by-launch step. */
-int miso_adam_scalars_table(double lr, double beta1, double beta2, double eps, int32_t first_step, int32_t count,
-                            float* host_out /* count x 6 */);
-int miso_adam_bump(int32_t* step, const float* guard /* or NULL */, void* stream);
-/* total[0] = sum of n_floats floats (the loss slots of miso_sdf_fwd_sorted_loss / miso_sdf_fwd_loss: 2 * MISO_LOSS_SLOTS,
- * i.e. both terms of the mapping loss) and, with step != NULL, miso_adam_bump(step, total) in the same launch. */
-int miso_loss_total_bump(const float* loss_slots, int32_t n_floats, float* total, int32_t* step /* or NULL */,
-                         void* stream);
-/* The same with the total ALSO handed to the host: slot s = step2[1] % ring_len of host_ring receives
- * host_ring[2 s] = total and then, behind a system-scope fence, ((int32_t*)host_ring)[2 s + 1] = step2[1] + 1 (the
- * 1-based number of this launch); step2[1] += 1.  step2: device int32[2] = {Adam step count, launches so far};
- * host_ring: PINNED HOST memory mapped into the device, 2 * ring_len words, zeroed once; ring_len a power of two.
- * The reference reads the loss on the host after every step to decide whether to skip it (grid_opt/trainer.py:213-219);
- * here the host polls the slot for its launch's number -- no copy and no event on the stream.  The launch counter
- * moves on NaN too, so a skipped step does not alias the next one's slot. */
-int miso_loss_total_bump_host(const float* loss_slots, int32_t n_floats, float* total, int32_t* step2,
-                              float* host_ring, int32_t ring_len, void* stream);
-int miso_adam_step_dev(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active,
-                       uint8_t* touched /* or NULL */, int64_t numel, const float* table, int32_t table_len,
-                       const int32_t* step, int zero_grad, const float* guard, void* stream);
-/* miso_adam_step_dev for up to MISO_ADAM_MAX_TENSORS tensors in ONE launch, each bit-identical to its
- * own call: the levels of a grid as one optimizer.step() (grid_opt/trainer.py:217), without a launch's ramp and tail per
- * level.  `tensors` is a HOST array (copied into the kernel arguments). */
 #define MISO_ADAM_MAX_TENSORS 8
 typedef struct {
   float* param; float* grad; float* exp_avg; float* exp_avg_sq;   /* DEVICE, 16-byte aligned, numel floats each */
-  uint8_t* active;                                                /* miso_adam_flag_bytes(numel) */
-  uint8_t* touched;                                               /* NULL: stepped by reading the gradient (miso_adam_active);
-                                                                     else the scatter kernels' flags, as miso_adam_touched */
+  uint8_t* active;                                                /* (numel + MISO_ADAM_CHUNK - 1) / MISO_ADAM_CHUNK bytes */
+  uint8_t* touched;                                               /* NULL: stepped by reading the gradient; else the
+                                                                     scatter kernels' flags, sized as `active` */
   int64_t numel;
   int32_t zero_grad;
   int32_t reserved;
 } miso_adam_tensor_t;
-int miso_adam_step_dev_multi(const miso_adam_tensor_t* tensors, int32_t n_tensors, const float* table, int32_t table_len,
-                             const int32_t* step, const float* guard, void* stream);
-/* the same for miso_adam_active (the step's scalars from the host: lr .. eps, the 1-based step) */
-int miso_adam_active_multi(const miso_adam_tensor_t* tensors, int32_t n_tensors, double lr, double beta1, double beta2,
-                           double eps, int32_t step, const float* guard, void* stream);
+
+/* Where a step's scalars come from.  Exactly one of two forms; anything else is MISO_E_BADARG.
+ *   host form    table == NULL, step >= 1: lr .. eps as doubles like torch's Python-side hyper-parameters, step the
+ *                1-based count of the step being taken.
+ *   device form  table != NULL, table_len >= 1, step_dev != NULL: Adam inside a captured HIP graph.  The bias
+ *                corrections change every step but the arguments of a captured launch do not, so the kernels read
+ *                table[*step_dev - 1]: `table` (device, table_len rows of 6 floats) holds the scalars of steps
+ *                1..table_len exactly as the host form computes them -- filled by miso_adam_scalars_table -- and
+ *                step_dev (device int32) the 1-based count, moved by miso_adam_bump / miso_loss_total_bump in front of
+ *                the step.  Steps past the table use its last row (choose table_len so that beta^table_len has left
+ *                fp32: the rows no longer change).  lr .. step are never read.  Bit-identical to the host form. */
+typedef struct {
+  double lr, beta1, beta2, eps; int32_t step;
+  const float* table; int32_t table_len;
+  const int32_t* step_dev;
+} miso_adam_when_t;
+
+/* One optimizer.step() (grid_opt/trainer.py:217) over 1..MISO_ADAM_MAX_TENSORS tensors in ONE launch, each
+ * bit-identical to a call of its own: the levels of a grid without a launch's ramp and tail per level.  `tensors` and
+ * `when` are HOST memory (copied into the kernel arguments).
+ * guard (device float, or NULL): the loss of the step.  If it is NaN the launch changes no parameter, moment or
+ * `active` byte (the reference's NaN guard, grid_opt/trainer.py:213-219: "Loss is nan! Skip backward step"); it still
+ * clears the `touched` flags and the gradients it was asked to clear -- the host can launch without reading the loss
+ * back first. */
+int miso_adam_step(const miso_adam_tensor_t* tensors, int32_t n_tensors, const miso_adam_when_t* when,
+                   const float* guard /* or NULL */, void* stream);
+
+/* The rows of miso_adam_when_t.table for steps first_step .. first_step + count - 1: a HOST function writing a HOST
+ * buffer (upload it). */
+int miso_adam_scalars_table(double lr, double beta1, double beta2, double eps, int32_t first_step, int32_t count,
+                            float* host_out /* count x 6 */);
+/* Once per step and in front of its miso_adam_step: step[0] += 1 unless *guard is NaN (the reference's NaN guard skips
+ * optimizer.step(), so the count must not move). */
+int miso_adam_bump(int32_t* step, const float* guard /* or NULL */, void* stream);
+/* total[0] = sum of n_floats floats (the loss slots of miso_sdf_fwd_sorted_loss / miso_sdf_fwd_loss: 2 * MISO_LOSS_SLOTS,
+ * i.e. both terms of the mapping loss) and, with step != NULL, miso_adam_bump(step, total) in the same launch.
+ * host_ring != NULL: the total is ALSO handed to the host.  `step` is then device int32[2] = {Adam step count, launches
+ * so far} and must be set; host_ring is PINNED HOST memory mapped into the device, 2 * ring_len words, zeroed once;
+ * ring_len a power of two.  Slot s = step[1] % ring_len receives host_ring[2 s] = total and then, behind a system-scope
+ * fence, ((int32_t*)host_ring)[2 s + 1] = step[1] + 1 (the 1-based number of this launch); step[1] += 1.  The
+ * reference reads the loss on the host after every step to decide whether to skip it (grid_opt/trainer.py:213-219); here
+ * the host polls the slot for its launch's number -- no copy and no event on the stream.  The launch counter moves on
+ * NaN too, so a skipped step does not alias the next one's slot.  host_ring == NULL: ring_len is not read. */
+int miso_loss_total_bump(const float* loss_slots, int32_t n_floats, float* total, int32_t* step /* or NULL */,
+                         float* host_ring /* or NULL */, int32_t ring_len, void* stream);
 
 /* --- per-keyframe rigid map of a sample batch ---------------------------------
  * y[i] = R[idx[i]] x[i] + t[idx[i]] (transpose = 0) or R[idx[i]]^T x[i] (+ t if given; transpose = 1: the cotangent

@@ -191,6 +191,8 @@ __global__ __launch_bounds__(256) void adam_active_kernel(float* __restrict__ p,
                                                          unsigned char* __restrict__ active, int64_t n,
                                                          AdamScalars a, const float* __restrict__ guard,
                                                          AdamDevK dev) {
+  // The four opening lines are written out in each of the three kernels: as a shared inlined helper they compile to
+  // 10 - 51 more scalar instructions per kernel (the by-value kernel arguments are copied, the scalar loads regrouped).
   if (dev.table) a = dev.table[min(max(dev.step[0], 1), dev.table_len) - 1];     // a captured step: see AdamDevK
   // guard (optional, device): the step's loss.  NaN => the reference skips backward and optimizer step
   // (grid_opt/trainer.py:213-219); here the launch leaves parameters, moments and flags alone (and still clears
@@ -201,7 +203,7 @@ __global__ __launch_bounds__(256) void adam_active_kernel(float* __restrict__ p,
   adam_active_body<ZERO>(p, g, m, v, active, n, a, skip, wave, nwaves);
 }
 
-// The same step driven by flags instead of by reading the gradient (miso_adam_touched): the scatter kernels set
+// The same step driven by flags instead of by reading the gradient (a tensor with `touched`): the scatter kernels set
 // touched[c] when they put a non-zero into chunk c (common.hpp:touch_chunk), so a chunk is stepped iff
 // active[c] | touched[c].  A sparse level is latency, not bytes -- the Newer College fine level has 2.3 M flag bytes of
 // which a batch sets a few per cent, all in the rows around the sensor:
@@ -330,8 +332,8 @@ __global__ __launch_bounds__(256) void adam_touched_kernel(float* __restrict__ p
   adam_touched_body<ZERO>(p, g, m, v, active, touched, n, a, skip, wave, nwaves);
 }
 
-// Several tensors in ONE launch (miso_adam_step_dev_multi), each stepped by its gradient or by its `touched` flags: the
-// levels of a grid differ by a factor of eight each, and as
+// Several tensors in ONE launch (miso_adam_step with 2..8 tensors), each stepped by its gradient or by its `touched`
+// flags: the levels of a grid differ by a factor of eight each, and as
 // launches of their own the two coarse ones of cfg-2 are 8.5 + 13.4 us of ramp and tail for 67 MB (the fine one: 74.5 us
 // for 469 MB).  Every wavefront walks the tensors in turn, the grid sized for the largest.
 struct AdamSegK {
@@ -395,23 +397,20 @@ void adam_scalars_table(double lr, double b1, double b2, double eps, int first_s
   }
 }
 
-hipError_t launch_adam_active(float* p, float* g, float* m, float* v, unsigned char* active, int64_t n, double lr,
-                              double b1, double b2, double eps, int step, int zero_grad, const float* guard,
-                              hipStream_t s, const float* table, const int32_t* step_dev, int table_len) {
-  if (n == 0) return hipSuccess;
-  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
-  const AdamDevK dev{reinterpret_cast<const AdamScalars*>(table), step_dev, table_len};
+// workgroups a tensor gets: four wavefronts of ADAM_UN slabs each where the gradient is read, of ADAM_SLOTS groups of
+// ADAM_GROUP slabs (one round of flag words) where `touched` drives the step
+static int64_t adam_blocks(int64_t n, bool touched) {
   const int64_t nslabs = (n + ADAM_SLAB - 1) / ADAM_SLAB;
-  int64_t blocks = (nslabs + 4 * ADAM_UN - 1) / (4 * ADAM_UN);
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (zero_grad) adam_active_kernel<true><<<(unsigned)blocks, 256, 0, s>>>(p, g, m, v, active, n, a, guard, dev);
-  else adam_active_kernel<false><<<(unsigned)blocks, 256, 0, s>>>(p, g, m, v, active, n, a, guard, dev);
-  return hipGetLastError();
+  const int64_t per_block = touched ? 4 * (int64_t)ADAM_SLOTS * ADAM_GROUP : 4 * ADAM_UN;
+  const int64_t blocks = (nslabs + per_block - 1) / per_block;
+  return blocks > 256 * 16 ? 256 * 16 : blocks;
 }
 
-hipError_t launch_adam_active_multi(const miso_adam_tensor_t* t, int count, double lr, double b1, double b2, double eps,
-                                    int step, const float* table, int table_len, const int32_t* step_dev,
-                                    const float* guard, hipStream_t s) {
+// One step of `count` tensors (miso_adam_step): one of them runs the kernel of its form, several run as the segments of
+// adam_active_multi_kernel, the grid sized for the largest.  when.table set: the kernels read the scalars there and the
+// by-value ones are not formed.
+hipError_t launch_adam_step(const miso_adam_tensor_t* t, int count, const miso_adam_when_t& when, const float* guard,
+                            hipStream_t s) {
   AdamMultiK k;
   memset(&k, 0, sizeof(k));
   int64_t most = 0;
@@ -421,54 +420,26 @@ hipError_t launch_adam_active_multi(const miso_adam_tensor_t* t, int count, doub
     sg.p = t[i].param; sg.g = t[i].grad; sg.m = t[i].exp_avg; sg.v = t[i].exp_avg_sq; sg.active = t[i].active;
     sg.touched = t[i].touched;
     sg.n = t[i].numel; sg.zero = t[i].zero_grad;
-    // the grid each tensor would get as a launch of its own (launch_adam_active / launch_adam_touched); the largest wins
-    int64_t b;
-    if (sg.touched) {
-      const int64_t nwords = ((sg.n + ADAM_CHUNK - 1) / ADAM_CHUNK + 3) / 4;
-      const int64_t per_block = 4 * (int64_t)ADAM_SLOTS * ADAM_GROUP;
-      b = (nwords + per_block - 1) / per_block;
-    } else {
-      const int64_t nslabs = (sg.n + ADAM_SLAB - 1) / ADAM_SLAB;
-      b = (nslabs + 4 * ADAM_UN - 1) / (4 * ADAM_UN);
-    }
+    const int64_t b = adam_blocks(sg.n, sg.touched != nullptr);
     most = b > most ? b : most;
   }
   if (k.count == 0) return hipSuccess;
-  const AdamDevK dev{reinterpret_cast<const AdamScalars*>(table), step_dev, table_len};
-  int64_t blocks = most < 1 ? 1 : most;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  adam_active_multi_kernel<<<(unsigned)blocks, 256, 0, s>>>(k, adam_scalars(lr, b1, b2, eps, step), guard, dev);
-  return hipGetLastError();
-}
-
-hipError_t launch_adam_touched(float* p, float* g, float* m, float* v, unsigned char* active, unsigned char* touched,
-                               int64_t n, double lr, double b1, double b2, double eps, int step, int zero_grad,
-                               const float* guard, hipStream_t s, const float* table, const int32_t* step_dev,
-                               int table_len) {
-  if (n == 0) return hipSuccess;
-  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
-  const AdamDevK dev{reinterpret_cast<const AdamScalars*>(table), step_dev, table_len};
-  const int64_t nwords = ((n + ADAM_CHUNK - 1) / ADAM_CHUNK + 3) / 4;
-  const int64_t per_block = 4 * (int64_t)ADAM_SLOTS * ADAM_GROUP;      // slabs four wavefronts look at per round
-  int64_t blocks = (nwords + per_block - 1) / per_block;
-  if (blocks > 256 * 16) blocks = 256 * 16;
-  if (zero_grad) adam_touched_kernel<true><<<(unsigned)blocks, 256, 0, s>>>(p, g, m, v, active, touched, n, a, guard, dev);
-  else adam_touched_kernel<false><<<(unsigned)blocks, 256, 0, s>>>(p, g, m, v, active, touched, n, a, guard, dev);
+  const AdamDevK dev{reinterpret_cast<const AdamScalars*>(when.table), when.step_dev, when.table_len};
+  const AdamScalars a = when.table ? AdamScalars{} : adam_scalars(when.lr, when.beta1, when.beta2, when.eps, when.step);
+  const unsigned blocks = (unsigned)most;
+  const AdamSegK& g = k.seg[0];
+  if (count > 1) adam_active_multi_kernel<<<blocks, 256, 0, s>>>(k, a, guard, dev);
+  else if (g.touched && g.zero) adam_touched_kernel<true><<<blocks, 256, 0, s>>>(g.p, g.g, g.m, g.v, g.active, g.touched, g.n, a, guard, dev);
+  else if (g.touched) adam_touched_kernel<false><<<blocks, 256, 0, s>>>(g.p, g.g, g.m, g.v, g.active, g.touched, g.n, a, guard, dev);
+  else if (g.zero) adam_active_kernel<true><<<blocks, 256, 0, s>>>(g.p, g.g, g.m, g.v, g.active, g.n, a, guard, dev);
+  else adam_active_kernel<false><<<blocks, 256, 0, s>>>(g.p, g.g, g.m, g.v, g.active, g.n, a, guard, dev);
   return hipGetLastError();
 }
 
 hipError_t launch_adam(float* p, float* g, float* m, float* v, int64_t n, double lr, double b1,
                        double b2, double eps, int step, int zero_grad, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  double bc1 = 1.0 - pow(b1, (double)step);
-  double bc2 = 1.0 - pow(b2, (double)step);
-  AdamScalars a;
-  a.one_minus_b1 = (float)(1.0 - b1);
-  a.b2 = (float)b2;
-  a.one_minus_b2 = (float)(1.0 - b2);
-  a.neg_step_size = (float)(-(lr / bc1));
-  a.bc2_sqrt = (float)sqrt(bc2);
-  a.eps = (float)eps;
+  const AdamScalars a = adam_scalars(lr, b1, b2, eps, step);
   bool aligned = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0;
   int64_t n4 = aligned ? n / 4 : 0;
   int64_t work = n4 > 0 ? n4 : n;

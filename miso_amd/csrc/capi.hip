@@ -14,8 +14,8 @@
 //    pointers are looked at, miso_atlas_sdf_fwd has no such return.
 //  * the tracker steps check grid shape, mlp and packed in the fused forward, BEHIND their first launch (the head).
 //  * miso_sdf_bwd_rows refuses the host-side gradient flags (OVERWRITE, SDF_SORTED, ZEROED); miso_sdf_bwd ignores them.
-//  * miso_adam_dense asks no alignment of its four arrays; miso_adam_touched asks 4-byte alignment of `active` even
-//    for numel == 0, miso_adam_step_dev and the multi-tensor calls only where `touched` is given.
+//  * miso_adam_dense asks no alignment of its four arrays; miso_adam_step asks 16 bytes of them, and 4 bytes of the
+//    flag arrays where `touched` is given (even for numel == 0).
 #include <stdlib.h>
 #include <string.h>
 
@@ -921,21 +921,12 @@ int miso_adam_dense(float* param, float* grad, float* exp_avg, float* exp_avg_sq
                           zero_grad, (hipStream_t)stream);
 }
 
-int miso_adam_active(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active, int64_t numel,
-                     double lr, double beta1, double beta2, double eps, int32_t step, int zero_grad,
-                     const float* guard, void* stream) {
-  if (step < 1 || !adam_tensor_ok(param, grad, exp_avg, exp_avg_sq, active, nullptr, numel)) return MISO_E_BADARG;
-  return (int)launch_adam_active(param, grad, exp_avg, exp_avg_sq, active, numel, lr, beta1, beta2, eps, step,
-                                 zero_grad, guard, (hipStream_t)stream, nullptr, nullptr, 0);
-}
-
-int miso_adam_touched(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active, uint8_t* touched,
-                      int64_t numel, double lr, double beta1, double beta2, double eps, int32_t step, int zero_grad,
-                      const float* guard, void* stream) {
-  if (step < 1 || !adam_tensor_ok(param, grad, exp_avg, exp_avg_sq, active, touched, numel)) return MISO_E_BADARG;
-  if (!set_if(numel, touched) || !aligned(4, active, touched)) return MISO_E_BADARG;      // here the flags are not optional
-  return (int)launch_adam_touched(param, grad, exp_avg, exp_avg_sq, active, touched, numel, lr, beta1, beta2, eps,
-                                  step, zero_grad, guard, (hipStream_t)stream, nullptr, nullptr, 0);
+// `when` is the host form (table NULL, a step >= 1) or the device form (table, its length, the count on the device)
+int miso_adam_step(const miso_adam_tensor_t* tensors, int32_t n_tensors, const miso_adam_when_t* when, const float* guard,
+                   void* stream) {
+  if (!adam_tensors_ok(tensors, n_tensors) || !when) return MISO_E_BADARG;
+  if (when->table ? when->table_len < 1 || !when->step_dev : when->step < 1) return MISO_E_BADARG;
+  return (int)launch_adam_step(tensors, n_tensors, *when, guard, (hipStream_t)stream);
 }
 
 int miso_adam_scalars_table(double lr, double beta1, double beta2, double eps, int32_t first_step, int32_t count,
@@ -945,47 +936,17 @@ int miso_adam_scalars_table(double lr, double beta1, double beta2, double eps, i
   return MISO_OK;
 }
 
-int miso_loss_total_bump(const float* loss_slots, int32_t n_floats, float* total, int32_t* step, void* stream) {
+int miso_loss_total_bump(const float* loss_slots, int32_t n_floats, float* total, int32_t* step, float* host_ring,
+                         int32_t ring_len, void* stream) {
   if (!loss_slots || n_floats < 1 || !total) return MISO_E_BADARG;
-  return (int)launch_loss_total_bump(loss_slots, n_floats, total, step, nullptr, 0, (hipStream_t)stream);
-}
-
-int miso_loss_total_bump_host(const float* loss_slots, int32_t n_floats, float* total, int32_t* step2, float* host_ring,
-                              int32_t ring_len, void* stream) {
-  if (!loss_slots || n_floats < 1 || !total || !step2 || !host_ring || ring_len < 1 || (ring_len & (ring_len - 1)))
-    return MISO_E_BADARG;
-  return (int)launch_loss_total_bump(loss_slots, n_floats, total, step2, host_ring, ring_len, (hipStream_t)stream);
+  if (host_ring && (!step || ring_len < 1 || (ring_len & (ring_len - 1)))) return MISO_E_BADARG;
+  return (int)launch_loss_total_bump(loss_slots, n_floats, total, step, host_ring, host_ring ? ring_len : 0,
+                                     (hipStream_t)stream);
 }
 
 int miso_adam_bump(int32_t* step, const float* guard, void* stream) {
   if (!step) return MISO_E_BADARG;
   return (int)launch_adam_bump(step, guard, (hipStream_t)stream);
-}
-
-int miso_adam_step_dev(float* param, float* grad, float* exp_avg, float* exp_avg_sq, uint8_t* active, uint8_t* touched,
-                       int64_t numel, const float* table, int32_t table_len, const int32_t* step, int zero_grad,
-                       const float* guard, void* stream) {
-  if (table_len < 1 || !table || !step || !adam_tensor_ok(param, grad, exp_avg, exp_avg_sq, active, touched, numel))
-    return MISO_E_BADARG;
-  if (touched)
-    return (int)launch_adam_touched(param, grad, exp_avg, exp_avg_sq, active, touched, numel, 1e-3, 0.9, 0.999, 1e-8, 1,
-                                    zero_grad, guard, (hipStream_t)stream, table, step, table_len);
-  return (int)launch_adam_active(param, grad, exp_avg, exp_avg_sq, active, numel, 1e-3, 0.9, 0.999, 1e-8, 1, zero_grad,
-                                 guard, (hipStream_t)stream, table, step, table_len);
-}
-
-int miso_adam_active_multi(const miso_adam_tensor_t* tensors, int32_t n_tensors, double lr, double beta1, double beta2,
-                           double eps, int32_t step, const float* guard, void* stream) {
-  if (!adam_tensors_ok(tensors, n_tensors) || step < 1) return MISO_E_BADARG;
-  return (int)launch_adam_active_multi(tensors, n_tensors, lr, beta1, beta2, eps, step, nullptr, 0, nullptr, guard,
-                                       (hipStream_t)stream);
-}
-
-int miso_adam_step_dev_multi(const miso_adam_tensor_t* tensors, int32_t n_tensors, const float* table, int32_t table_len,
-                             const int32_t* step, const float* guard, void* stream) {
-  if (!adam_tensors_ok(tensors, n_tensors) || table_len < 1 || !table || !step) return MISO_E_BADARG;
-  return (int)launch_adam_active_multi(tensors, n_tensors, 1e-3, 0.9, 0.999, 1e-8, 1, table, table_len, step, guard,
-                                       (hipStream_t)stream);
 }
 
 int miso_mapping_batch(const float* R, const float* t, int32_t n_poses, const int64_t* table, int64_t table_len,

@@ -97,23 +97,15 @@ hipError_t launch_sample_rays(const miso_ray_frames_t& f, const miso_ray_samplin
                               const float* g, void* workspace, float* coords, int64_t* ids, float* aux, float* pc_world,
                               float* z_vals, int32_t* counts, hipStream_t s);
 
-// ---- adam.hip (table / step_dev: the captured-graph form, miso_adam_step_dev; nullptr = the scalars from the host)
+// ---- adam.hip (launch_adam_step: every flag-driven form -- `when` says where the scalars come from, miso_hip.h)
 void adam_scalars_table(double lr, double b1, double b2, double eps, int first_step, int count, float* out);
 hipError_t launch_adam_bump(int32_t* step, const float* guard, hipStream_t s);
 hipError_t launch_loss_total_bump(const float* slots, int n, float* total, int32_t* step, float* host_ring, int ring_len,
                                   hipStream_t s);
 hipError_t launch_adam(float* p, float* g, float* m, float* v, int64_t n, double lr, double b1, double b2, double eps,
                        int step, int zero_grad, hipStream_t s);
-hipError_t launch_adam_active(float* p, float* g, float* m, float* v, unsigned char* active, int64_t n, double lr,
-                              double b1, double b2, double eps, int step, int zero_grad, const float* guard,
-                              hipStream_t s, const float* table, const int32_t* step_dev, int table_len);
-hipError_t launch_adam_touched(float* p, float* g, float* m, float* v, unsigned char* active, unsigned char* touched,
-                               int64_t n, double lr, double b1, double b2, double eps, int step, int zero_grad,
-                               const float* guard, hipStream_t s, const float* table, const int32_t* step_dev,
-                               int table_len);
-hipError_t launch_adam_active_multi(const miso_adam_tensor_t* t, int count, double lr, double b1, double b2, double eps,
-                                    int step, const float* table, int table_len, const int32_t* step_dev,
-                                    const float* guard, hipStream_t s);
+hipError_t launch_adam_step(const miso_adam_tensor_t* t, int count, const miso_adam_when_t& when, const float* guard,
+                            hipStream_t s);
 
 // ---- loss.hip (launch_zero_words clears n_words 32-bit words with a kernel; see there why not hipMemsetAsync)
 hipError_t launch_zero_fill(float* p, int64_t n, hipStream_t s);

@@ -1858,31 +1858,10 @@ def adam_active_flags(param) -> torch.Tensor:
     return torch.zeros((param.numel() + _lib.ADAM_CHUNK - 1) // _lib.ADAM_CHUNK, device=param.device, dtype=torch.uint8)
 
 
-def adam_active_(param, grad, exp_avg, exp_avg_sq, active, step: int, lr: float, beta1: float = 0.9,
-                 beta2: float = 0.999, eps: float = 1e-8, zero_grad: bool = False, guard: Optional[torch.Tensor] = None,
-                 touched: Optional[torch.Tensor] = None):
-    """adam_dense_ that skips the chunks that cannot move (miso_adam_active): bit-identical results, 4 B per
-    element + 28 B per element of the chunks a gradient has ever reached.  guard: device scalar (the step's loss);
-    if it is NaN the launch leaves parameters, moments and flags alone (the reference's NaN guard on the device).
-    touched: the flags the scatter kernels left for this gradient (sdf_bwd_raw(touched=...)): the launch then reads
-    them instead of the gradient (miso_adam_touched) and clears them -- only valid when nothing but those kernels
-    wrote the gradient since the last step."""
-    _require_hip(param, grad, exp_avg, exp_avg_sq, guard)
-    _check_adam_state(param, grad, exp_avg, exp_avg_sq, active, touched)
-    if touched is not None:
-        _lib.check(_lib.load().miso_adam_touched(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(active),
-                                                 _ptr(touched), param.numel(), lr, beta1, beta2, eps, step,
-                                                 int(zero_grad), _ptr(guard), _stream(param)), "miso_adam_touched")
-        return
-    _lib.check(_lib.load().miso_adam_active(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(active),
-                                            param.numel(), lr, beta1, beta2, eps, step, int(zero_grad),
-                                            _ptr(guard), _stream(param)), "miso_adam_active")
-
-
 def adam_tensors(tensors):
-    """The argument block of adam_active_multi_ / AdamDeviceStep.step_multi_ for ``tensors`` = [(param, grad, exp_avg,
-    exp_avg_sq, active, zero_grad[, touched])]: built once for buffers whose addresses do not change.  touched: the flags
-    the scatter kernels left for that gradient (adam_active_'s ``touched``), or None.  Returns (block, keep-alive)."""
+    """The argument block of adam_step_ for ``tensors`` = [(param, grad, exp_avg, exp_avg_sq, active, zero_grad[,
+    touched])]: built once for buffers whose addresses do not change.  touched: the flags the scatter kernels left for
+    that gradient (adam_active_'s ``touched``), or None.  Returns (block, keep-alive)."""
     assert 1 <= len(tensors) <= _lib.ADAM_MAX_TENSORS
     arr = (_lib.AdamTensor * len(tensors))()
     for a, t7 in zip(arr, tensors):
@@ -1896,13 +1875,48 @@ def adam_tensors(tensors):
     return arr, [tuple(t7[:5]) + ((t7[6],) if len(t7) > 6 else ()) for t7 in tensors]
 
 
-def adam_active_multi_(packed, step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
-                       guard: Optional[torch.Tensor] = None):
-    """adam_active_ for several tensors in ONE launch (miso_adam_active_multi), each bit-identical to its own call;
-    ``packed`` from adam_tensors()."""
+def adam_blocks(rows):
+    """Which tensors share a launch: ``rows`` (as adam_tensors takes them) -> the packed blocks of one step.  2 ..
+    ADAM_MAX_TENSORS rows are ONE block -- as launches of their own the coarse levels of a pyramid are all ramp and tail
+    (cfg-2: 8.5 + 13.4 us for 67 MB next to 74.5 us for 469 MB) -- otherwise a block per row."""
+    rows = list(rows)
+    if 2 <= len(rows) <= _lib.ADAM_MAX_TENSORS:
+        return [adam_tensors(rows)]
+    return [adam_tensors([r]) for r in rows]
+
+
+def adam_when(step: int, lr: float, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8):
+    """The scalars of step ``step`` (1-based) from the host, for adam_step_."""
+    return _lib.AdamWhen(lr, beta1, beta2, eps, step)
+
+
+def adam_step_(packed, when, guard: Optional[torch.Tensor] = None):
+    """One Adam step of a block of adam_tensors() / adam_blocks() in ONE launch (miso_adam_step), each tensor
+    bit-identical to a step of its own.  when: adam_when(...) or AdamDeviceStep.when.  guard: device scalar (the
+    step's loss); if it is NaN the launch leaves parameters, moments and ``active`` alone (the reference's NaN guard on
+    the device)."""
     arr, keep = packed
-    _lib.check(_lib.load().miso_adam_active_multi(arr, len(arr), lr, beta1, beta2, eps, step, _ptr(guard),
-                                                  _stream(keep[0][0])), "miso_adam_active_multi")
+    _require_hip(guard)
+    _lib.check(_lib.load().miso_adam_step(arr, len(arr), C.byref(when), _ptr(guard), _stream(keep[0][0])),
+               "miso_adam_step")
+
+
+def adam_active_(param, grad, exp_avg, exp_avg_sq, active, step: int, lr: float, beta1: float = 0.9,
+                 beta2: float = 0.999, eps: float = 1e-8, zero_grad: bool = False, guard: Optional[torch.Tensor] = None,
+                 touched: Optional[torch.Tensor] = None):
+    """adam_dense_ that skips the chunks that cannot move (miso_adam_step on one tensor): bit-identical results, 4 B per
+    element + 28 B per element of the chunks a gradient has ever reached.  guard: device scalar (the step's loss);
+    if it is NaN the launch leaves parameters, moments and ``active`` alone (the reference's NaN guard on the device).
+    touched: the flags the scatter kernels left for this gradient (sdf_bwd_raw(touched=...)): the launch then reads
+    them instead of the gradient and clears them -- only valid when nothing but those kernels wrote the gradient since
+    the last step."""
+    _require_hip(param, grad, exp_avg, exp_avg_sq, guard)
+    _check_adam_state(param, grad, exp_avg, exp_avg_sq, active, touched)
+    # the row and the scalars by one constructor call each, fields in miso_hip.h's order: per-tensor loops call this
+    row = _lib.AdamTensor(param.data_ptr(), grad.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), active.data_ptr(),
+                          None if touched is None else touched.data_ptr(), param.numel(), int(zero_grad))
+    when = _lib.AdamWhen(lr, beta1, beta2, eps, step)
+    _lib.check(_lib.load().miso_adam_step(C.byref(row), 1, C.byref(when), _ptr(guard), _stream(param)), "miso_adam_step")
 
 
 class HostTotal:
@@ -1921,9 +1935,9 @@ class HostTotal:
 
 
 class AdamDeviceStep:
-    """What a captured step needs to take Adam steps without new kernel arguments (miso_adam_step_dev): the table of
-    per-step scalars (computed by the library's own host code, so the captured step equals the launch-by-launch one
-    bit for bit) and the step count on the device.  ``count`` mirrors the device value on the host."""
+    """What a captured step needs to take Adam steps without new kernel arguments: the table of per-step scalars
+    (computed by the library's own host code, so the captured step equals the launch-by-launch one bit for bit) and the
+    step count on the device, together ``when`` -- what adam_step_ takes.  ``count`` mirrors the device value on the host."""
     MAX_ROWS = 1 << 21
 
     def __init__(self, lr: float, beta1: float, beta2: float, eps: float, device, count: int = 0):
@@ -1941,6 +1955,8 @@ class AdamDeviceStep:
         self.rows = rows
         # [0] the Adam step count, [1] the launches of total_and_bump so far (the slot of ``ring`` a launch writes)
         self.step = torch.zeros(2, dtype=torch.int32, device=device)
+        self.when = _lib.AdamWhen()
+        self.when.table, self.when.table_len, self.when.step_dev = self.table.data_ptr(), rows, self.step.data_ptr()
         # the step's loss as the host sees it: written by the kernel itself (pinned memory mapped into the device), so
         # the NaN guard costs the stream no copy.  ``launches`` mirrors step[1]: whoever EXECUTES total_and_bump (a
         # stream launch or a graph replay, not a capture) calls note_launch().
@@ -1969,26 +1985,11 @@ class AdamDeviceStep:
         _lib.check(_lib.load().miso_adam_bump(_ptr(self.step), _ptr(guard), _stream(self.step)), "miso_adam_bump")
 
     def total_and_bump(self, loss_slots: torch.Tensor, total: torch.Tensor):
-        """total (0-d) = loss_slots.sum() and bump(total) in one launch (miso_loss_total_bump)."""
+        """total (0-d) = loss_slots.sum() and bump(total) in one launch (miso_loss_total_bump), the total also into ``ring``."""
         assert loss_slots.is_contiguous() and loss_slots.dtype == torch.float32 and total.numel() == 1
-        _lib.check(_lib.load().miso_loss_total_bump_host(_ptr(loss_slots), loss_slots.numel(), _ptr(total),
-                                                         _ptr(self.step), C.c_void_p(self.ring.data_ptr()), self.RING,
-                                                         _stream(self.step)), "miso_loss_total_bump_host")
-
-    def step_(self, param, grad, exp_avg, exp_avg_sq, active, touched=None, zero_grad=False, guard=None):
-        _require_hip(param, grad, exp_avg, exp_avg_sq, guard)
-        _lib.check(_lib.load().miso_adam_step_dev(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), _ptr(active),
-                                                  _ptr(touched), param.numel(), _ptr(self.table), self.rows,
-                                                  _ptr(self.step), int(zero_grad), _ptr(guard), _stream(param)),
-                   "miso_adam_step_dev")
-
-    multi = staticmethod(adam_tensors)      # the argument block of step_multi_
-
-    def step_multi_(self, packed, guard=None):
-        """step_ for several tensors in one launch (miso_adam_step_dev_multi); ``packed`` from multi()."""
-        arr = packed[0]
-        _lib.check(_lib.load().miso_adam_step_dev_multi(arr, len(arr), _ptr(self.table), self.rows, _ptr(self.step),
-                                                        _ptr(guard), _stream(self.step)), "miso_adam_step_dev_multi")
+        _lib.check(_lib.load().miso_loss_total_bump(_ptr(loss_slots), loss_slots.numel(), _ptr(total), _ptr(self.step),
+                                                    C.c_void_p(self.ring.data_ptr()), self.RING, _stream(self.step)),
+                   "miso_loss_total_bump")
 
 
 def mapping_batch(R, t, table, frame_ids, coords_frame, target, valid, sign, weight, x_out, rows_out,

@@ -1,4 +1,4 @@
-"""Dense Adam as a torch.optim.Optimizer backed by miso_adam_active (miso_adam_dense's results without the
+"""Dense Adam as a torch.optim.Optimizer backed by miso_adam_step (miso_adam_dense's results without the
 passes over elements that no gradient has ever reached: their moments are zero and their update is exactly zero).
 
 Same update and state layout ('step', 'exp_avg', 'exp_avg_sq') as
@@ -185,19 +185,20 @@ class DenseAdam(torch.optim.Optimizer):
 
     def _launch_batch(self, batch, lr, b1, b2, eps, clear_grads, guard):
         """The kernel-sized tensors of one parameter group: ONE launch when they are at the same step (the levels of a
-        grid are; miso_adam_active_multi), else one each.  The argument block is kept while the addresses stay."""
+        grid are; ops.adam_blocks), else one each.  The argument blocks are kept while the addresses stay."""
         if not batch:
             return
-        same_t = all(b[5] == batch[0][5] for b in batch)
-        if len(batch) < 2 or len(batch) > ops._lib.ADAM_MAX_TENSORS or not same_t:
+        if not all(b[5] == batch[0][5] for b in batch):
             for p, g, m, v, act, t in batch:
                 ops.adam_active_(p, g, m, v, act, t, lr, b1, b2, eps, zero_grad=clear_grads, guard=guard)
             return
         key = tuple(x.data_ptr() for b in batch for x in b[:5]) + (bool(clear_grads),)
-        cache = self.__dict__.get('_multi_block')
+        cache = self.__dict__.get('_adam_blocks')
         if cache is None or cache[0] != key:
-            cache = self.__dict__['_multi_block'] = (key, ops.adam_tensors([b[:5] + (clear_grads,) for b in batch]))
-        ops.adam_active_multi_(cache[1], batch[0][5], lr, b1, b2, eps, guard=guard)
+            cache = self.__dict__['_adam_blocks'] = (key, ops.adam_blocks([b[:5] + (clear_grads,) for b in batch]))
+        when = ops.adam_when(batch[0][5], lr, b1, b2, eps)
+        for block in cache[1]:
+            ops.adam_step_(block, when, guard)
 
     def note_guarded_step(self, guard, stepped, host=None):
         """A step guarded by the device scalar ``guard`` has been launched for the states ``stepped`` (their 'step'

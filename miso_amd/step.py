@@ -229,40 +229,30 @@ class MappingStep:
                             self.need_levels, self.grads, touched=self.touched)
 
     def _adam_block(self):
-        """-> (multi, rows) of both Adam drivers.  rows: per level with a gradient (param, grad, exp_avg, exp_avg_sq, active,
-        zero_grad, touched); zero_grad: the Adam launch clears the gradient, the next backward that ADDS to it needs no
-        fill.  multi: the argument block that steps all of them in ONE launch (each by its gradient or by its `touched`
-        flags), or False: a launch per level -- as launches of their own the coarse levels of a pyramid are all ramp and
-        tail (cfg-2: 8.5 + 13.4 us for 67 MB next to 74.5 us for 469 MB).  The block bakes raw pointers in: it is keyed by
-        them, so a level whose storage was rebound -- f.data = ..., a replaced gradient or moment buffer -- gets a new
-        block instead of an update of stale memory."""
+        """-> the packed blocks (ops.adam_blocks) of both Adam drivers, over the rows of the levels with a gradient: (param,
+        grad, exp_avg, exp_avg_sq, active, zero_grad, touched); zero_grad: the Adam launch clears the gradient, the next
+        backward that ADDS to it needs no fill.  A block bakes raw pointers in: the blocks are keyed by them, so a level
+        whose storage was rebound -- f.data = ..., a replaced gradient or moment buffer -- gets a new block instead of an
+        update of stale memory."""
         key = tuple(t.data_ptr() for p, g, st in zip(self.features, self.grads, self.adam_state) if g is not None
                     for t in (p, g, st[0], st[1], st[2]))
         if key != self._adam_key:
             rows = [(p, g, st[0], st[1], st[2], self.sorted is None or bool((self._adam_clears >> l) & 1), tch)
                     for l, (p, g, st, tch) in enumerate(zip(self.features, self.grads, self.adam_state, self.touched))
                     if g is not None]
-            one = 2 <= len(rows) <= ops._lib.ADAM_MAX_TENSORS
-            self._adam_key, self._adam_rows, self._adam_multi = key, rows, ops.adam_tensors(rows) if one else False
-        return self._adam_multi, self._adam_rows
+            self._adam_key, self._adam_blocks = key, ops.adam_blocks(rows)
+        return self._adam_blocks
 
     def _optimize(self):
         dev = self.adam_device
         if dev is not None:
             dev.total_and_bump(self.loss_slots, self.total)      # loss sum + step count: one launch
+            when, guard = dev.when, self.total
         else:
             self.t += 1
-        multi, rows = self._adam_block()
-        if multi and dev is not None:
-            dev.step_multi_(multi, guard=self.total)
-        elif multi:
-            ops.adam_active_multi_(multi, self.t, **self.adam)
-        else:
-            for p, g, m, v, act, zero, tch in rows:
-                if dev is not None:
-                    dev.step_(p, g, m, v, act, touched=tch, guard=self.total, zero_grad=zero)
-                else:
-                    ops.adam_active_(p, g, m, v, act, self.t, zero_grad=zero, touched=tch, **self.adam)
+            when, guard = ops.adam_when(self.t, **self.adam), None
+        for block in self._adam_block():
+            ops.adam_step_(block, when, guard)
 
     def _fused_train(self) -> bool:
         """Whether the binned step runs as sort -> sdf_train_kernel -> pull (decided once: the grids do not change)."""

@@ -155,6 +155,14 @@ def adam_tensor():
     return t
 
 
+def adam_when(device=False):
+    w = _lib.AdamWhen()
+    w.lr, w.beta1, w.beta2, w.eps, w.step, w.table_len = 1e-3, 0.9, 0.999, 1e-8, 1, 4      # (host form: table_len unread)
+    if device:
+        w.step, w.table, w.step_dev = 0, P(), P()
+    return w
+
+
 def align_pair(lattice=False):
     p = _lib.AlignPair()
     p.dst_grid = grid()
@@ -502,29 +510,30 @@ def build_recipes():
     four, hyper = ("param", "grad", "exp_avg", "exp_avg_sq"), dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8)
     R("miso_adam_dense", null(*four) + val("numel", -1) + val("step", 0), param=P(), grad=P(), exp_avg=P(), exp_avg_sq=P(),
       numel=8, **hyper, step=1, zero_grad=1, stream=None)
-    R("miso_adam_active", null(*four, "active") + off(4, *four) + val("numel", -1) + val("step", 0), param=P(), grad=P(),
-      exp_avg=P(), exp_avg_sq=P(), active=P(), numel=8, **hyper, step=1, zero_grad=1, guard=None, stream=None)
-    R("miso_adam_touched", null(*four, "active", "touched") + off(4, *four) + off(1, "active", "touched") + val("numel", -1) +
-      val("step", 0), param=P(), grad=P(), exp_avg=P(), exp_avg_sq=P(), active=P(), touched=P(), numel=8, **hyper, step=1,
-      zero_grad=1, guard=None, stream=None)
-    R("miso_adam_step_dev", null(*four, "active", "table", "step") + off(4, *four) + off(1, "active", "touched") +
-      val("numel", -1) + val("table_len", 0), param=P(), grad=P(), exp_avg=P(), exp_avg_sq=P(), active=P(), touched=P(),
-      numel=8, table=P(), table_len=4, step=P(), zero_grad=1, guard=None, stream=None)
+    # miso_adam_step: the per-tensor rules (adam_tensors_ok) on a tensor with `touched`, then the two forms of `when`.
+    # One refusal of the entries it replaced has no counterpart by construction: miso_adam_touched(touched = NULL) --
+    # here a NULL `touched` means "step by reading the gradient", a valid call.
     tens = null("tensors") + val("n_tensors", 0, _lib.ADAM_MAX_TENSORS + 1) + fld("tensors", "numel", -1)
     for p in four:
         tens += fld("tensors", p, None) + fld_off(4, "tensors", p)
     tens += fld("tensors", "active", None) + fld_off(1, "tensors", "active", "touched")
-    R("miso_adam_active_multi", tens + val("step", 0), tensors=adam_tensor(), n_tensors=1, **hyper, step=1, guard=None,
-      stream=None)
-    R("miso_adam_step_dev_multi", tens + null("table", "step") + val("table_len", 0), tensors=adam_tensor(), n_tensors=1,
-      table=P(), table_len=4, step=P(), guard=None, stream=None)
+    R("miso_adam_step", tens + null("when") + fld("when", "step", 0) + fld("when", "table", P()), tensors=adam_tensor(),
+      n_tensors=1, when=adam_when(), guard=None, stream=None)      # when.table set, step_dev NULL: neither form
+    R("miso_adam_step", tens + null("when") + fld("when", "table", None) + fld("when", "step_dev", None) +
+      fld("when", "table_len", 0), variant="device", tensors=adam_tensor(), n_tensors=1, when=adam_when(device=True),
+      guard=None, stream=None)                                     # when.table NULL: the host form with step = 0
+    no_flags = adam_tensor()
+    no_flags.touched = None
+    R("miso_adam_step", null("tensors") + fld("tensors", "numel", -1) + fld("tensors", "active", None) +
+      [f for p in four for f in fld("tensors", p, None) + fld_off(4, "tensors", p)], variant="by_gradient",
+      tensors=no_flags, n_tensors=1, when=adam_when(), guard=None, stream=None)
     R("miso_adam_scalars_table", val("first_step", 0) + val("count", -1) + null("host_out"), host=True, **hyper,
       first_step=1, count=4, host_out=P())
     R("miso_adam_bump", null("step"), step=P(), guard=None, stream=None)
     R("miso_loss_total_bump", null("loss_slots", "total") + val("n_floats", 0), loss_slots=P(4096), n_floats=1024,
-      total=P(), step=P(), stream=None)
-    R("miso_loss_total_bump_host", null("loss_slots", "total", "step2", "host_ring") + val("n_floats", 0) +
-      val("ring_len", 0, 3), loss_slots=P(4096), n_floats=1024, total=P(), step2=P(), host_ring=P(), ring_len=4, stream=None)
+      total=P(), step=P(), host_ring=None, ring_len=0, stream=None)
+    R("miso_loss_total_bump", null("loss_slots", "total", "step") + val("n_floats", 0) + val("ring_len", 0, 3),
+      variant="host_ring", loss_slots=P(4096), n_floats=1024, total=P(), step=P(), host_ring=P(), ring_len=4, stream=None)
     R("miso_mapping_batch", null("R", "t", "table", "frame_ids", "coords_frame", "target", "coords_world", "loss_rows") +
       off(4, "loss_rows") + val("n", -1) + val("n_poses", 0) + val("table_len", 0) +
       [(f"col_strides[{i}]=-1", "col_strides", int64s(*[-1 if j == i else 1 for j in range(4)])) for i in range(4)],

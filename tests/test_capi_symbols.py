@@ -125,9 +125,15 @@ def test_round2_entry_points_validate_arguments_without_gpu():
     assert lib.miso_adam_scalars_table(1e-3, 0.9, 0.999, 1e-8, 0, 4, ctypes.c_void_p(host.data_ptr())) == E
     assert lib.miso_adam_scalars_table(1e-3, 0.9, 0.999, 1e-8, 1, 4, None) == E
     assert lib.miso_adam_bump(None, None, None) == E
-    assert lib.miso_adam_step_dev(None, None, None, None, None, None, 8, None, 1, None, 0, None, None) == E
-    assert lib.miso_adam_touched(None, None, None, None, None, None, 8, 1e-3, 0.9, 0.999, 1e-8, 1, 0, None, None) == E
-    assert lib.miso_adam_touched(None, None, None, None, None, None, 0, 1e-3, 0.9, 0.999, 1e-8, 0, 0, None, None) == E   # step 0
+    tensor, when = _lib.AdamTensor(), _lib.AdamWhen()
+    tensor.numel, when.table_len = 8, 1                      # no arrays; a table length without table or count
+    assert lib.miso_adam_step(ctypes.byref(tensor), 1, ctypes.byref(when), None, None) == E
+    when.lr, when.beta1, when.beta2, when.eps, when.step, when.table_len = 1e-3, 0.9, 0.999, 1e-8, 1, 0
+    assert lib.miso_adam_step(ctypes.byref(tensor), 1, ctypes.byref(when), None, None) == E          # no arrays
+    tensor.numel, when.step = 0, 0
+    assert lib.miso_adam_step(ctypes.byref(tensor), 1, ctypes.byref(when), None, None) == E          # step 0
+    assert lib.miso_adam_step(None, 1, ctypes.byref(when), None, None) == E
+    assert lib.miso_adam_step(ctypes.byref(tensor), 1, None, None, None) == E
     assert lib.miso_mapping_batch(None, None, 1, None, 1, None, None, None, None, None, None, None, 0, 0, None, None, 0, None) == E
     assert lib.miso_mapping_loss_rows(7, 1.0, 0.0, 0.0, None, None, 0, None, None, None) == E
     assert lib.miso_mapping_loss_rows(1, 1.0, 0.0, 0.0, None, None, 4, None, None, None) == E

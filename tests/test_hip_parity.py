@@ -310,7 +310,7 @@ def test_adam_dense_vs_torch():
 
 @pytest.mark.parametrize("numel", [256 * 40, 256 * 37 + 130, 1027, 5])
 def test_adam_active_is_bit_identical_to_dense(numel):
-    """miso_adam_active steps only the chunks a gradient has ever reached; everything -- parameters, both moments,
+    """miso_adam_step by the gradient steps only the chunks a gradient has ever reached; everything -- parameters, both moments,
     cleared gradients -- must equal the dense kernel bit for bit over a run in which chunks wake up at different
     steps, some never, and one gradient is NaN.  Also checked against torch.optim.Adam."""
     from miso_amd import ops, _lib
@@ -358,9 +358,9 @@ def test_adam_active_is_bit_identical_to_dense(numel):
 @pytest.mark.parametrize("numel", [256 * 40, 256 * 37 + 130, 1027, 5, 64 * 3, 64 * 4 + 1, 256 * 3 + 64 * 2 + 7,
                                    256 * 8 * 16 * 5 + 64 * 3 + 9])
 def test_adam_touched_ragged_sizes_equal_the_gradient_scan(numel):
-    """miso_adam_touched on sizes that end inside a slab / inside a chunk / inside a flag word, flags written by hand
+    """miso_adam_step by `touched` on sizes that end inside a slab / inside a chunk / inside a flag word, flags written by hand
     (touched = the chunks of this step's non-zero gradients): parameters, moments, `active`, cleared gradients and
-    cleared flags equal miso_adam_active's bit for bit over a run with chunks waking up at different steps and a NaN
+    cleared flags equal miso_adam_step by the gradient's bit for bit over a run with chunks waking up at different steps and a NaN
     guard."""
     from miso_amd import ops, _lib
     CH = _lib.ADAM_CHUNK
@@ -1159,8 +1159,8 @@ def test_align_plan_rejects_bad_arguments():
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", ["unsorted", "sorted_thin", "sorted_crowd"])
 def test_adam_touched_flags_equal_gradient_scan(path):
-    """miso_adam_touched (Adam driven by the flags the scatter kernels leave in miso_level_t.grad_touched) against
-    miso_adam_active (Adam that reads the gradient to find what moved): parameters, both moments, the active flags and
+    """miso_adam_step by `touched` (Adam driven by the flags the scatter kernels leave in miso_level_t.grad_touched) against
+    miso_adam_step by the gradient (Adam that reads the gradient to find what moved): parameters, both moments, the active flags and
     the cleared gradients bit for bit over four steps with different batches, one of them with a NaN loss guard; the
     flags are all cleared afterwards.  unsorted: float atomics from the decoder backward, gradients cleared by Adam.
     sorted_thin: owner-computes pull (overwrite).  sorted_crowd: matrix-core push + atomics of a fine level."""
@@ -1483,14 +1483,15 @@ def test_adam_device_step_host_ring_and_multi_tensor_launch():
     g.manual_seed(3)
     many = fresh()
     devs = [ops.AdamDeviceStep(1e-3, 0.9, 0.999, 1e-8, DEV, count=0) for _ in range(2)]
-    packed = devs[1].multi([tuple(t) for t in many])
+    singles = [ops.adam_tensors([tuple(t)]) for t in one]
+    packed = ops.adam_tensors([tuple(t) for t in many])
     for it, guard_val in enumerate((0.5, 0.25, float("nan"), 0.125)):
         guard = torch.full((1,), guard_val, device=DEV)
         for d_ in devs:
             d_.bump(guard)
-        for p, gr, m, v, act, zero, tch in one:
-            devs[0].step_(p, gr, m, v, act, zero_grad=zero, guard=guard, touched=tch)
-        devs[1].step_multi_(packed, guard=guard)
+        for block in singles:
+            ops.adam_step_(block, devs[0].when, guard)
+        ops.adam_step_(packed, devs[1].when, guard)
         for a_, b_ in zip(one, many):
             for x_, y_ in zip(a_[:5], b_[:5]):
                 assert torch.equal(x_, y_)
@@ -1507,3 +1508,121 @@ def test_adam_device_step_host_ring_and_multi_tensor_launch():
                 fl = (a_[1].reshape(-1, ops._lib.ADAM_CHUNK) != 0).any(dim=1).to(torch.uint8)
                 a_[6].copy_(fl), b_[6].copy_(fl)
     assert devs[0].step.tolist()[0] == 3 and float(one[0][2].abs().sum()) > 0
+
+
+# one unified call over a mixed block against the same tensors stepped one at a time.  Each size ends at a boundary of the
+# kernels: 1 and 63 inside a chunk, 256 = one whole slab, 257 = a slab and a ragged element, 4 160 = one 16-slab flag
+# group and a partial slab, 131 392 = the first size at which the `touched` form launches a second workgroup
+# (4 * ADAM_SLOTS * ADAM_GROUP = 512 slabs per workgroup).
+_MIXED_SIZES = (1, 63, 256, 257, 4160, 131392)
+_MIXED_TOUCHED = (True, False, False, True, True, True)      # stepped by the flags | by reading the gradient
+_MIXED_ZERO = (True, False, True, False, True, False)
+_MIXED_GUARDS = (0.5, float("nan"), 0.25, 0.125)              # step 2 is skipped
+_MIXED_HYPER = (1e-2, 0.9, 0.999, 1e-8)
+
+
+def _mixed_block_inputs():
+    """(parameters, gradients per step) on the host: a quarter of the chunks wake at step 1, another quarter at step 3,
+    the rest never; every tensor's last chunk (the ragged one) moves from step 1 and its first from step 3."""
+    from miso_amd import _lib
+    CH = _lib.ADAM_CHUNK
+    g = torch.Generator().manual_seed(17)
+    params, grads = [], [[] for _ in _MIXED_GUARDS]
+    for n in _MIXED_SIZES:
+        params.append(torch.randn(n, generator=g))
+        nchunks = (n + CH - 1) // CH
+        q = torch.rand(nchunks, generator=g)
+        wake = torch.where(q < 0.25, 1, torch.where(q < 0.5, 3, 99))
+        wake[0], wake[-1] = 3, 1
+        for t in range(len(_MIXED_GUARDS)):
+            on = (wake <= t + 1).repeat_interleave(CH)[:n]
+            grads[t].append(torch.randn(n, generator=g) * 1e-2 * on * (torch.rand(n, generator=g) < 0.5))
+    return params, grads
+
+
+def _mixed_block_run(make_step):
+    """The four steps through make_step(rows) -> step(number, guard); -> per step, per tensor the bits of (param, grad,
+    exp_avg, exp_avg_sq, active, touched) on the host."""
+    from miso_amd import ops, _lib
+    CH = _lib.ADAM_CHUNK
+    params, grads = _mixed_block_inputs()
+    rows = []
+    for p0, zero, flags in zip(params, _MIXED_ZERO, _MIXED_TOUCHED):
+        p = p0.to(DEV)
+        rows.append((p, torch.zeros_like(p), torch.zeros_like(p), torch.zeros_like(p), ops.adam_active_flags(p), zero,
+                     ops.adam_active_flags(p) if flags else None))
+    step, snaps, count = make_step(rows), [], 0
+    for t, guard_val in enumerate(_MIXED_GUARDS):
+        for row, gr in zip(rows, grads[t]):
+            row[1].copy_(gr)
+            if row[6] is not None:      # as the scatter kernels would have left them for this gradient
+                nz = torch.nn.functional.pad(gr != 0, (0, row[6].numel() * CH - gr.numel())).reshape(-1, CH).any(1)
+                row[6].copy_(nz.to(torch.uint8))
+        step(count + 1, torch.full((1,), guard_val, device=DEV))
+        count += guard_val == guard_val
+        snaps.append([tuple(None if x is None else (x.view(torch.int32) if x.dtype == torch.float32 else x).cpu().clone()
+                            for x in row[:5] + row[6:]) for row in rows])
+    return snaps
+
+
+_mixed_block_reference = []
+
+
+def _mixed_block_one_at_a_time():
+    """The reference, computed once: every tensor through ops.adam_active_ with the scalars from the host."""
+    from miso_amd import ops
+    if not _mixed_block_reference:
+        def make_step(rows):
+            def step(number, guard):
+                for p, gr, m, v, act, zero, tch in rows:
+                    ops.adam_active_(p, gr, m, v, act, number, *_MIXED_HYPER, zero_grad=zero, guard=guard, touched=tch)
+            return step
+        _mixed_block_reference.append(_mixed_block_run(make_step))
+    return _mixed_block_reference[0]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("scalars", ["host", "device"])
+def test_adam_step_over_a_mixed_block_equals_one_tensor_at_a_time(scalars):
+    """miso_adam_step on ONE block of six tensors -- sizes at the kernels' boundaries, some stepped by `touched` and some
+    by their gradient, zero_grad mixed -- equals the same tensors stepped one at a time through ops.adam_active_, bit for
+    bit after each of four steps: parameters, both moments, `active`, the cleared `touched` and the zeroed gradients.
+    Chunks wake at steps 1 and 3, step 2 has a NaN guard; once with the scalars from the host, once with
+    AdamDeviceStep.when."""
+    from miso_amd import ops
+    want = _mixed_block_one_at_a_time()
+    made = []
+
+    def make_step(rows):
+        packed = ops.adam_tensors(rows)
+        if scalars == "host":
+            return lambda number, guard: ops.adam_step_(packed, ops.adam_when(number, *_MIXED_HYPER), guard)
+        dev = ops.AdamDeviceStep(*_MIXED_HYPER, DEV, count=0)
+        made.append(dev)
+
+        def step(number, guard):
+            dev.bump(guard)
+            ops.adam_step_(packed, dev.when, guard)
+        return step
+
+    got = _mixed_block_run(make_step)
+    for t, (step_want, step_got) in enumerate(zip(want, got)):
+        for n, zero, a, b in zip(_MIXED_SIZES, _MIXED_ZERO, step_want, step_got):
+            for name, x, y in zip(("param", "grad", "exp_avg", "exp_avg_sq", "active", "touched"), a, b):
+                assert (x is None) == (y is None), (t, n, name)
+                if x is not None:
+                    assert torch.equal(x, y), (t, n, name)
+            if b[5] is not None:
+                assert int(b[5].sum()) == 0, (t, n)                 # consumed: the flags are cleared
+            if zero:
+                # ... and the gradient where asked (the snapshots hold bits: an input's -0.0 is a zero)
+                assert int(((b[1] & 0x7fffffff) != 0).sum()) == 0, (t, n)
+    if made:
+        assert made[0].step.tolist()[0] == 3
+    # the run is one in which things happen: the NaN step changed no parameter, moment or `active` byte, the others did,
+    # and the big tensor ends with chunks that moved and chunks that never did
+    for a1, a2 in zip(got[0], got[1]):
+        assert all(torch.equal(a1[i], a2[i]) for i in (0, 2, 3, 4))
+    assert not any(torch.equal(got[1][-1][i], got[2][-1][i]) for i in (0, 2, 3, 4))
+    big = got[-1][-1][4]
+    assert 0 < int(big.sum()) < big.numel()

@@ -154,8 +154,8 @@ def test_both_adam_drivers_of_the_mapping_step_take_the_same_steps(n, sort):
         for _ in range(3):
             st.run()
         torch.cuda.synchronize()
-        multi, rows = st._adam_block()
-        assert multi and len(multi[0]) == len(rows) == 2               # one launch for both levels, in both drivers
+        blocks = st._adam_block()
+        assert len(blocks) == 1 and len(blocks[0][0]) == 2              # one launch for both levels, in both drivers
         out[mode] = [t for f, s in zip(fs, st.adam_state) for t in (f, *s)]
     for k, (a, b) in enumerate(zip(out["host"], out["device"])):
         diff = (a.float() - b.float()).abs().max().item()

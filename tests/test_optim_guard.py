@@ -1,5 +1,5 @@
 """DenseAdam's NaN-guard bookkeeping with the loss handed over through a host slot (ops.HostTotal), on the host alone: a
-stand-in slot that becomes ready on demand.  (The kernel side -- miso_loss_total_bump_host writing the pinned ring -- is
+stand-in slot that becomes ready on demand.  (The kernel side -- miso_loss_total_bump writing the pinned ring -- is
 tests/test_hip_parity.py::test_adam_device_step_host_ring_and_multi_tensor_launch.)"""
 import math
 

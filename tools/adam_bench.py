@@ -1,5 +1,5 @@
-"""Dense Adam over one level (dev): miso_adam_active (finds the moving chunks by reading the gradient) against
-miso_adam_touched (reads the flags the scatter kernels left), by level size and fraction of moving chunks."""
+"""Dense Adam over one level (dev): miso_adam_step by the gradient (finds the moving chunks by reading the gradient) against
+by `touched` (reads the flags the scatter kernels left), by level size and fraction of moving chunks."""
 import os
 import sys
 

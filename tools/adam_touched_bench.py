@@ -1,4 +1,4 @@
-"""dev: miso_adam_touched on a 145 M-float level (the Newer College fine level) for synthetic flag patterns -- what
+"""dev: miso_adam_step driven by `touched` on a 145 M-float level (the Newer College fine level) for synthetic flag patterns -- what
 bounds it: the flag scan, the number of stepped chunks, or where they lie?"""
 import os
 import sys
