@@ -442,7 +442,29 @@ int miso_overlap_count(const float* pose, const float* coords_src, int64_t n, co
  *                     own (the order in which the next pair stage takes the pairs up: those with most in-bound
  *                     vertices first -- scheduling only, zero = the list's order).
  * Once the relative change falls below rel_change_thresh (base.py:157-158) the stopped flag is set and further
- * iterations change nothing. */
+ * iterations change nothing.
+ *
+ * The SDF residuals (miso_align_t.residual != 0; all of its new fields zero: the latent residual, as before).  The same
+ * two calls run the SDF-space fine-tune (pairwise_loss_sdf, grid_opt/align/miso.py:14-113; residual 1) and the
+ * inter-map loss of Vox-Fusion++ (grid_opt/align/vfpp.py; residual 2) with the pair stage of pair_sdf.hip in place of
+ * the latent one: per source row p, q = R_d^T (R_s p + t_s - t_d) (the arithmetic and the bound test of the latent
+ * stage and the overlap gate), s = decoder(encode(dst levels, q)) and its gradient in q, r = ref - s, and the 24 sums of
+ * miso_pair_latent over the in-bound rows with term r^2 (loss_type 2), |r| (1, derivative -sign(r), sign(0) = 0) or
+ * w r^2 with w = gm_scale / (gm_scale + r^2)^2 held constant (3, Geman-McClure).  The per-pair descriptor is read as
+ *   coords_src   (n,3) rows in the source frame (pose independent: staged once per loop);
+ *   feats_src    the reference column ref: residual 1: the source submap's SDF at the rows, row pitch ld_feats >= 1;
+ *                residual 2: the measured SDF of the rows kept (|gt| < trunc_dist), CONTIGUOUS, and ld_feats carries the
+ *                source's full row count n_rows >= n instead (the reference's mean is over all rows, masked or not:
+ *                the pair loss is weight * sum / n_rows, not / (count * n_ch)); n_rows >= 2^24: MISO_E_TOOLARGE;
+ *   dst_grid     every level the decoder reads; the bound, the gate and src_boxes as in the latent form.
+ * In residual 1 the pair loss is weight * sum / max(count, 1); a pair with no in-bound row has loss 0 and gradient 0.
+ * miso_align_plan_build refuses, before anything is launched: residual outside 0..2, residual != 0 with mlp or packed
+ * NULL (or packed not 16-byte aligned), a loss type the residual does not have (latent: 1, 2; residual 1: 1, 2, 3;
+ * residual 2: 2; gm_scale <= 0 with loss type 3) -- MISO_E_BADARG; a (grid, decoder) that miso_sdf_supported does not
+ * cover or whose launch does not fit a workgroup's LDS, pairs whose destination grids differ in (C, L) or in
+ * MISO_F_EXACT_F32, the border / align-corners / normalised-coordinate flags -- MISO_E_UNSUPPORTED.  mlp is host memory
+ * and is read by miso_align_plan_build and miso_align_iteration_a; the plan blob, its size and the state layout are
+ * those of the latent form. */
 typedef struct {
   miso_grid_t dst_grid;
   const float* coords_src;  /* (n,3) */
@@ -473,7 +495,7 @@ int miso_align_src_boxes(const float* coords, int64_t n, float* boxes, void* str
 
 typedef struct {
   int32_t n_submaps, n_pairs;
-  int32_t loss_type;         /* 1 = L1 (row-wise 2-norm), 2 = L2 */
+  int32_t loss_type;         /* 1 = L1 (row-wise 2-norm), 2 = L2; with residual != 0 also 3 = Geman-McClure */
   int32_t ring_iters, save_poses;
   int32_t vec4;              /* set by miso_align_plan_build */
   int64_t max_n, max_gate_n, max_gate_rows; /* set by miso_align_plan_build: longest source list, longest point-list gate,
@@ -492,6 +514,12 @@ typedef struct {
    * Zero: iteration_a forms them itself (first iteration; after the caller wrote the corrections; a repeated
    * iteration_a). */
   int32_t poses_ready;
+  /* The SDF residuals (see above); all zero: the latent residual. */
+  int32_t residual;          /* 0 latent, 1 SDF against the source submap's SDF, 2 SDF against the measurement */
+  const miso_mlp_t* mlp;     /* residual != 0: the decoder (host memory) ... */
+  const float* packed;       /* ... and its packed weights (miso_mlp_pack, device) */
+  float gm_scale;            /* loss_type 3 */
+  int32_t sdf_shape;         /* set by miso_align_plan_build (residual != 0): C | L << 8 | exact-fp32 << 16 of the grids */
 } miso_align_t;
 
 int64_t miso_align_plan_bytes(int32_t n_pairs);

@@ -145,7 +145,9 @@ __global__ __launch_bounds__(EPI_A_THREADS) void align_epilogue_a_kernel(AlignK 
       const AlignPairK& d = k.plan[p];
       const double* o = s_out + 24 * i;
       // (the count and n_ch are small integers: denom is exact in fp32, as the reference's clamp(min=1) * n_ch)
-      const float denom = fmaxf((float)o[1], 1.0f) * (k.loss_type == 2 ? d.n_ch : 1.0f);
+      // (residual 2, the measured SDF: n_ch carries the source's full row count, and the reference's mean is over all of
+      // its rows, in bound or not)
+      const float denom = k.residual == 2 ? fmaxf(d.n_ch, 1.0f) : fmaxf((float)o[1], 1.0f) * (k.loss_type == 2 ? d.n_ch : 1.0f);
       const float val = (float)(o[0] / (double)denom);
       const bool finite = (val == val) && !isinf(val);          // nan_to_num passes no gradient otherwise
       const float gate = d.gate_p ? ((cnt[p] / (float)d.gate_n) > k.overlap_thresh ? 1.0f : 0.0f) : 1.0f;
@@ -314,7 +316,8 @@ hipError_t launch_align_a(const AlignK& k, int64_t max_n, int64_t max_gate_n, in
   const int32_t* stopped = reinterpret_cast<const int32_t*>(k.state + k.L.ctrl) + CTRL_STOPPED;
   hipError_t e = launch_pair_batch(k.plan, k.P, max_n, max_gate_n, vec4, k.state + k.L.pose, k.loss_type,
                                    reinterpret_cast<double*>(k.state + k.L.out), k.state + k.L.cnt, stopped,
-                                   max_gate_rows, reinterpret_cast<const int32_t*>(k.state + k.L.order), s);
+                                   max_gate_rows, reinterpret_cast<const int32_t*>(k.state + k.L.order),
+                                   k.residual ? &k.sdf : nullptr, s);
   if (e != hipSuccess) return e;
   align_epilogue_a_kernel<<<1, EPI_A_THREADS, 0, s>>>(k);
   return hipGetLastError();

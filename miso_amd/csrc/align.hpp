@@ -1,6 +1,7 @@
 // Kernel-side structs of the fused alignment iteration (align.hip, capi.hip).
 #pragma once
 #include "common.hpp"
+#include "pair_stage.hpp"
 
 namespace miso {
 
@@ -23,6 +24,8 @@ struct AlignK {
   const AlignPairK* plan;
   float* state;
   AlignLayout L;
+  int residual;      // miso_align_t.residual: 0 latent, 1 SDF against the source submap, 2 SDF against the measurement
+  PairSdfK sdf;      // residual != 0
 };
 
 // so3_exp_map(log_rot, eps = 1e-4) of pytorch3d as restated in miso_amd/so3.py, fp32, same op order

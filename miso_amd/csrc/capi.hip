@@ -704,9 +704,22 @@ int64_t miso_align_plan_bytes(int32_t n_pairs) {
   return n_pairs < 0 ? 0 : (int64_t)(n_pairs > 0 ? n_pairs : 1) * (int64_t)sizeof(AlignPairK);
 }
 
+// the loss types a residual has: latent L1 | L2; SDF against the source submap L1 | L2 | GM; against the measurement L2
+static bool align_loss_ok(int residual, int loss_type, float gm_scale) {
+  if (residual == 0) return mapping_loss_ok(loss_type);
+  if (residual == 1) return mapping_loss_ok(loss_type) || (loss_type == 3 && gm_scale > 0.0f);
+  return residual == 2 && loss_type == 2;
+}
+
 int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, void* plan_host) {
   if (!cfg || cfg->n_pairs < 0 || cfg->n_submaps < 1 || cfg->n_submaps > 64) return MISO_E_BADARG;
   if (cfg->n_pairs > 0 && (!pairs || !plan_host)) return MISO_E_BADARG;
+  const int residual = cfg->residual;
+  if (residual < 0 || residual > 2) return MISO_E_BADARG;
+  if (residual && (!cfg->mlp || !cfg->packed || !aligned(16, cfg->packed))) return MISO_E_BADARG;
+  // (the latent form has always left the loss type to the iteration calls: kept)
+  if ((residual || cfg->loss_type == 3) && !align_loss_ok(residual, cfg->loss_type, cfg->gm_scale)) return MISO_E_BADARG;
+  int sdf_C = 0, sdf_L = 0, sdf_exact = -1;
   AlignPairK* out = reinterpret_cast<AlignPairK*>(plan_host);
   bool v4_all = true;
   int64_t max_n = 0, max_gate = 0, max_rows = 0;
@@ -716,14 +729,26 @@ int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, voi
       return MISO_E_BADARG;
     if (in.n < 0 || in.gate_n < 0 || !set_if(in.n, in.coords_src, in.feats_src)) return MISO_E_BADARG;
     if (!fits_fp32_count(in.gate_n)) return MISO_E_TOOLARGE;
+    if (residual == 2 && !fits_fp32_count(in.ld_feats)) return MISO_E_TOOLARGE;      // ld_feats: the source's full row count
     AlignPairK& d = out[p];
     memset(&d, 0, sizeof(d));
     bool v4;
     if (int rc = convert_grid(&in.dst_grid, &d.g, true, &v4)) return rc;
     if (d.g.flags & (MISO_F_COORDS_NORMALIZED | MISO_F_ALIGN_CORNERS | MISO_F_PAD_BORDER)) return MISO_E_UNSUPPORTED;
-    if (in.ld_feats < d.g.F) return MISO_E_BADARG;
+    if (residual) {
+      // one kernel instantiation and one arithmetic serve every pair of the launch
+      int C_, L_, H_, NH_;
+      if (int rc = fused_shape(d.g, v4, cfg->mlp, &C_, &L_, &H_, &NH_)) return rc;
+      if (!pair_sdf_covered(C_, L_, H_, NH_)) return MISO_E_UNSUPPORTED;
+      const int exact = (d.g.flags & MISO_F_EXACT_F32) ? 1 : 0;
+      if (sdf_exact >= 0 && (C_ != sdf_C || L_ != sdf_L || exact != sdf_exact)) return MISO_E_UNSUPPORTED;
+      sdf_C = C_; sdf_L = L_; sdf_exact = exact;
+      if (in.ld_feats < (residual == 2 ? in.n : 1)) return MISO_E_BADARG;
+    } else if (in.ld_feats < d.g.F) {
+      return MISO_E_BADARG;
+    }
     v4_all = v4_all && v4;
-    d.p = in.coords_src; d.fsrc = in.feats_src; d.ld = in.ld_feats; d.n = in.n;
+    d.p = in.coords_src; d.fsrc = in.feats_src; d.ld = residual == 2 ? 1 : in.ld_feats; d.n = in.n;
     d.gate_p = in.gate_n > 0 ? in.gate_coords : nullptr; d.gate_n = in.gate_n;
     if (in.gate_n > 0 && in.gate_axis[0]) {
       if (!in.gate_axis[1] || !in.gate_axis[2]) return MISO_E_BADARG;
@@ -739,7 +764,8 @@ int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, voi
     } else if (in.gate_n > 0 && !in.gate_coords) {
       return MISO_E_BADARG;
     }
-    d.src = in.src; d.dst = in.dst; d.n_ch = (float)d.g.F;
+    d.src = in.src; d.dst = in.dst;
+    d.n_ch = residual == 0 ? (float)d.g.F : (residual == 1 ? 1.0f : (float)in.ld_feats);
     d.boxes = in.n > 0 ? in.src_boxes : nullptr;
     if (in.n > max_n) max_n = in.n;
     if (d.gate_p && !d.gate_ax[0] && in.gate_n > max_gate) max_gate = in.gate_n;      // point-list gates only (grid sizing)
@@ -748,6 +774,7 @@ int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, voi
   cfg->max_n = max_n;
   cfg->max_gate_n = max_gate;
   cfg->max_gate_rows = max_rows;
+  cfg->sdf_shape = sdf_exact >= 0 ? (sdf_C | (sdf_L << 8) | (sdf_exact << 16)) : 0;
   return MISO_OK;
 }
 
@@ -766,8 +793,18 @@ int64_t miso_align_state_layout(int32_t n_submaps, int32_t n_pairs, int32_t ring
 static int align_k(const miso_align_t* c, AlignK* k) {
   if (!c || c->n_submaps < 1 || c->n_submaps > 64 || c->n_pairs < 0 || c->ring_iters < 0) return MISO_E_BADARG;
   if (!c->R0 || !c->t0 || !c->state || (c->n_pairs > 0 && !c->plan)) return MISO_E_BADARG;
-  if (!mapping_loss_ok(c->loss_type) || !aligned(16, c->state)) return MISO_E_BADARG;
+  if (c->residual < 0 || c->residual > 2 || !align_loss_ok(c->residual, c->loss_type, c->gm_scale)) return MISO_E_BADARG;
+  if (!aligned(16, c->state)) return MISO_E_BADARG;
+  if (c->residual && (!c->mlp || !c->packed || !aligned(16, c->packed))) return MISO_E_BADARG;
   memset(k, 0, sizeof(*k));
+  k->residual = c->residual;
+  if (c->residual && c->n_pairs > 0) {      // (a plan without a pair launches no pair stage)
+    PairSdfK& f = k->sdf;
+    f.C = c->sdf_shape & 255; f.L = (c->sdf_shape >> 8) & 255; f.exact = ((c->sdf_shape >> 16) & 1) != 0;
+    f.H = c->mlp->hidden_dim; f.NH = c->mlp->n_linear - 2;
+    f.packed = c->packed; f.gm_scale = c->gm_scale;
+    if (c->mlp->in_dim != f.C * f.L || !pair_sdf_covered(f.C, f.L, f.H, f.NH)) return MISO_E_UNSUPPORTED;
+  }
   k->S = c->n_submaps; k->P = c->n_pairs; k->loss_type = c->loss_type; k->ring_iters = c->ring_iters;
   k->save_poses = c->save_poses;
   k->align_weight = c->align_weight; k->overlap_thresh = c->overlap_thresh; k->reg_weight = c->reg_weight;

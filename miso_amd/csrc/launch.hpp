@@ -7,6 +7,7 @@
 namespace miso {
 
 struct AlignK;    // align.hpp
+struct PairSdfK;  // pair_stage.hpp
 struct GradPlan;  // grad_plan.hpp (with plan_grad, the host-side plan of a binned call's grid gradient)
 struct PullBatch;
 
@@ -66,7 +67,8 @@ hipError_t launch_grad_pull(const GridK& g, const GradPlan& plan, const PullBatc
 // ---- grad_pull_mc.hip (called by launch_grad_pull for a plan of form PULL_MC)
 hipError_t launch_grad_pull_mc(const GridK& g, const GradPlan& plan, const PullBatch& batch, hipStream_t s);
 
-// ---- pair_latent.hip (launch_pair_batch: called by launch_align_a)
+// ---- pair_latent.hip (launch_pair_batch: called by launch_align_a; sdf != nullptr: the SDF residual of pair_sdf.hip in
+//      place of the latent one, the overlap gate in a launch of its own in front of it)
 hipError_t launch_src_boxes(const float* p, int64_t n, float* boxes, hipStream_t s);
 hipError_t launch_overlap_count(const float* pose, const float* p, int64_t n, const float* bmin, const float* bmax,
                                 float* out, hipStream_t s);
@@ -74,7 +76,15 @@ hipError_t launch_pair_latent(const GridK& g, bool vec4, const float* pose, cons
                               int64_t n, int loss_type, double* out, hipStream_t s);
 hipError_t launch_pair_batch(const AlignPairK* plan_dev, int n_pairs, int64_t max_n, int64_t max_gate_n, bool vec4,
                              const float* pose_all, int loss_type, double* out_all, float* cnt_all,
-                             const int32_t* stopped, int64_t max_gate_rows, const int32_t* order, hipStream_t s);
+                             const int32_t* stopped, int64_t max_gate_rows, const int32_t* order, const PairSdfK* sdf,
+                             hipStream_t s);
+
+// ---- pair_sdf.hip (pair_sdf_covered: shape in the kernel table and its launch fits a workgroup's LDS, both arithmetics;
+//      launch_pair_sdf_stage: called by launch_pair_batch for a plan whose residual is an SDF one)
+bool pair_sdf_covered(int C, int L, int H, int NH);
+hipError_t launch_pair_sdf_stage(const PairSdfK& k, const AlignPairK* plan_dev, int n_pairs, int64_t max_n,
+                                 const float* pose_all, int loss_type, double* out_all, const int32_t* stopped,
+                                 const int32_t* order, hipStream_t s);
 
 // ---- align.hip
 hipError_t launch_align_a(const AlignK& k, int64_t max_n, int64_t max_gate_n, int64_t max_gate_rows, bool vec4,

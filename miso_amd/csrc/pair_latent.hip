@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 #include "launch.hpp"
+#include "pair_stage.hpp"
 
 namespace miso {
 
@@ -31,34 +32,9 @@ struct PairK {
   double* out;         // 24 doubles, zeroed by the launcher
   const float* boxes;  // per run of ALIGN_BOX_VERTS vertices {min xyz, max xyz}, or nullptr (AlignPairK::boxes)
 };
-constexpr float BOX_SLACK = 2e-3f;      // metres, plus terms in the size of the coordinates (pair_latent_body)
-
-// hardware fp64 add at L2 (global_atomic_add_f64, no return value)
-__device__ __forceinline__ void atomic_add_f64(double* p, double v) {
-  (void)__builtin_amdgcn_global_atomic_fadd_f64((__attribute__((address_space(1))) double*)(p), v);
-}
-
 // One workgroup's share (grid-stride from block bx of nbx) of one pair.  pose_s / pose_d: R[9] t[3] of the source
 // and the destination submap.  Shared by the single-pair kernel and the batched one (one launch for all pairs of an
 // alignment iteration, grid.y = pair, descriptors in device memory).
-// src -> world -> dst of one source vertex (transform_points_to, then transfrom_points_from: utils_geometry.py:214-240)
-// in ONE fixed arithmetic: d = (Rs p + ts) - td with the row sums as fma chains, q = Rd^T d likewise.  Every in-bound
-// decision -- pass 1 and pass 2 of the pair stage, the point-list and the lattice form of the overlap gate -- is taken on
-// these bits.  Written as plain products and sums, the copies of this expression came out of the compiler with different
-// contractions, and the two forms of the gate disagreed on one vertex of 4 M for two submaps 0.35 degrees apart
-// (test_lattice_overlap_gate_counts_equal_the_point_list_gate).
-__device__ __forceinline__ void src_to_dst(const float (&Rs)[9], const float (&ts)[3], const float (&Rd)[9],
-                                           const float (&td)[3], float px, float py, float pz, float (&d)[3],
-                                           float (&q)[3]) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const float w = __fadd_rn(__fmaf_rn(Rs[3 * r + 2], pz, __fmaf_rn(Rs[3 * r + 1], py, __fmul_rn(Rs[3 * r], px))), ts[r]);
-    d[r] = __fsub_rn(w, td[r]);
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) q[c] = __fmaf_rn(Rd[6 + c], d[2], __fmaf_rn(Rd[3 + c], d[1], __fmul_rn(Rd[c], d[0])));
-}
-
 template <bool VEC4>
 __device__ __forceinline__ void pair_latent_body(const GridK& g, const float* __restrict__ pose_s,
                                                  const float* __restrict__ pose_d, const PairK& k, unsigned bx,
@@ -608,7 +584,8 @@ hipError_t launch_pair_latent(const GridK& g, bool vec4, const float* pose, cons
 // The pair stage of one fused alignment iteration (align.hip): overlap counts, then the pair residuals.
 hipError_t launch_pair_batch(const AlignPairK* plan_dev, int n_pairs, int64_t max_n, int64_t max_gate_n, bool vec4,
                              const float* pose_all, int loss_type, double* out_all, float* cnt_all,
-                             const int32_t* stopped, int64_t max_gate_rows, const int32_t* order, hipStream_t s) {
+                             const int32_t* stopped, int64_t max_gate_rows, const int32_t* order, const PairSdfK* sdf,
+                             hipStream_t s) {
   if (n_pairs <= 0) return hipSuccess;
   // gate workgroups per pair: point-list gates (max_gate_n: the longest list) grid-stride whatever the count, lattice
   // gates (max_gate_rows) want one workgroup per GATE_ROWS rows -- and no more: sized by the lattice's VERTEX count (4 M)
@@ -622,8 +599,14 @@ hipError_t launch_pair_batch(const AlignPairK* plan_dev, int n_pairs, int64_t ma
     const unsigned lat = (unsigned)((max_gate_rows + GATE_ROWS - 1) / GATE_ROWS);
     if (lat > gate_blocks) gate_blocks = lat;
   }
-  if (gate_blocks && max_n <= 0)
+  if (gate_blocks && (max_n <= 0 || sdf))
     overlap_count_batch_kernel<<<dim3(gate_blocks, (unsigned)n_pairs), 256, 0, s>>>(plan_dev, pose_all, cnt_all, stopped);
+  // the SDF residual: a kernel of its own shape (decoder image in LDS, one wavefront per 64 rows), so the gate is not
+  // merged into its launch
+  if (sdf) {
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_pair_sdf_stage(*sdf, plan_dev, n_pairs, max_n, pose_all, loss_type, out_all, stopped, order, s);
+  }
   if (max_n > 0) {
     unsigned blocks = (unsigned)((max_n + 2047) / 2048);
     // ~7000 workgroups in all (seven rounds of the 1024 that are resident at four waves per SIMD), at least 128 and at

@@ -230,6 +230,110 @@ def pairwise_loss_sdf(grid_atlas: GridAtlas, data_loader, src_id: int, dst_id: i
     return {key: val * align_weight}
 
 
+def draw_batches(dataset, num_batches: int, device):
+    """``num_batches`` draws of the loader generic_align_multiple_submaps builds, as [(model_input, gt)]."""
+    from torch.utils.data import DataLoader
+    loader = DataLoader(dataset, shuffle=True, batch_size=1, num_workers=0, collate_fn=utils.collate_batch_of_one)
+    return [utils.get_batch(loader, device) for _ in range(num_batches)]
+
+
+def source_rows(grid_atlas: GridAtlas, batches, src_id: int):
+    """The rows of ``src_id``'s keyframes in the given batches, in its frame -- what pairwise_loss_sdf forms as
+    ``coords_from`` -- with the batches' gt columns at those rows: (coords (n,3), sdf (n,1), sdf_valid (n,1)), or None
+    when no row belongs to the submap.  Depends on the keyframe-in-submap poses only, which alignment does not touch."""
+    from miso_amd.grid_opt.loss import transform_by_keyframe
+    coords, sdf, valid = [], [], []
+    with torch.no_grad():
+        for model_input, gt in batches:
+            kf = model_input['sample_frame_ids'][0, :, 0]
+            rows = torch.nonzero(grid_atlas.submap_id_for_kf_batch(kf_ids=kf) == src_id, as_tuple=False).squeeze(1)
+            if rows.numel() == 0:
+                continue
+            coords.append(transform_by_keyframe(model_input['coords_frame'][0, rows, :], kf[rows],
+                                                lambda k: grid_atlas.updated_kf_pose_in_submap(k, src_id)))
+            sdf.append(gt['sdf'][0][rows, :])
+            valid.append(gt['sdf_valid'][0][rows, :])
+    if not coords:
+        return None
+    return torch.cat(coords).detach().float(), torch.cat(sdf).float(), torch.cat(valid)
+
+
+def sdf_pair_inputs(grid_atlas: GridAtlas, batches, pairs, check_intersection=True, measured_trunc=None):
+    """Per-pair inputs of ops.AlignPlan's SDF residuals, staged once per loop (host syncs are fine here).  Per source
+    submap: the rows of its keyframes in ``batches``, in its frame (source_rows).
+      residual "sdf" (measured_trunc None): the rows with sdf_valid == 1 and ``ref`` = the source submap's own SDF there,
+        under no_grad through the forward the op-by-op route calls (GridNet.forward);
+      residual "sdf_measured" (align/vfpp.py): the rows with |gt sdf| < measured_trunc, ``ref`` = the measured SDF, and
+        ``n_rows`` = all rows of the source, the divisor of the reference's mean.
+    The destination side is every level its decoder reads; the overlap gate reads the source's finest-level vertices as
+    in the latent stage.  A pair whose source has no row in the batches is left out, as the op-by-op loss returns {}."""
+    staged, out = {}, []
+    for src_id, dst_id in pairs:
+        sub_from, sub_to = grid_atlas.get_submap(src_id), grid_atlas.get_submap(dst_id)
+        if src_id not in staged:
+            rows = source_rows(grid_atlas, batches, src_id)
+            if rows is not None:
+                coords, sdf, valid = rows
+                if measured_trunc is None:
+                    keep = torch.nonzero(valid[:, 0] == 1, as_tuple=False)[:, 0]
+                    coords = coords[keep].contiguous()
+                    with torch.no_grad():
+                        ref = sub_from(coords) if coords.shape[0] else coords.new_zeros((0, 1))
+                else:
+                    keep = torch.nonzero(torch.abs(sdf[:, 0]) < measured_trunc, as_tuple=False)[:, 0]
+                    ref, coords = sdf[keep], coords[keep].contiguous()
+                rows = (coords, ref.detach().reshape(-1, 1).contiguous(), int(valid.shape[0]))
+            staged[src_id] = rows
+        if staged[src_id] is None:
+            continue
+        coords, ref, n_rows = staged[src_id]
+        out.append(dict(src=src_id, dst=dst_id, coords=coords, ref=ref, n_rows=n_rows,
+                        feats_dst=[g.feature.detach() for g in sub_to.features],
+                        meta_dst=sub_to.features[0].grid_meta(sub_to.ignore_level_),
+                        gate_pts=grid_atlas._finest_vertices(src_id) if check_intersection else None,
+                        gate_dims=tuple(int(v) for v in reversed(sub_from.features[-1].feature.shape[2:]))))
+    return out
+
+
+def fused_sdf_refusal(grid_atlas: GridAtlas, device, use_bound=True, stability_thresh=0, subsample_points=None):
+    """None when the SDF residuals of ops.AlignPlan cover this atlas and these options, else the reason in words: bound
+    mask on, no stability pruning, no subsampling, atlas on the GPU, frozen decoders that are equal across the submaps and in
+    the fused kernels' table."""
+    if not use_bound or stability_thresh > 0 or subsample_points is not None:
+        return "options outside the fused route (bound mask off, stability pruning or subsampling)"
+    if not (str(device).startswith('cuda') and grid_atlas.get_submap(0).features[0].feature.is_cuda):
+        return "the atlas is not on the GPU"
+    packs = [grid_atlas.get_submap(s)._fused_decoder() for s in range(grid_atlas.num_submaps)]
+    if any(p is None for p in packs):
+        return "decoder or grid shape outside the fused kernels' table"
+    # one launch decodes with one set of weights: the submaps' decoders must be copies of one another (they are, when
+    # they come from one pretrained model; GridAtlas.forward decodes with submap 0's for the same reason)
+    def same(a, b):
+        return (a is None and b is None) or (a is not None and b is not None and a.shape == b.shape and torch.equal(a, b))
+    for p in packs[1:]:
+        if p is not packs[0] and not (len(p.weights) == len(packs[0].weights)
+                                      and all(same(a, b) for a, b in zip(p.weights, packs[0].weights))
+                                      and all(same(a, b) for a, b in zip(p.biases, packs[0].biases))):
+            return "the submaps' decoders differ"
+    return None
+
+
+def sdf_finetune_loss(grid_atlas: GridAtlas, batches, align_weight=3000, align_loss="L2", use_bound=True,
+                      stability_thresh=0, subsample_points=None, gm_scale_sdf=0.1, device="cuda:0"):
+    """The pair-loss callable of the SDF fine-tune (pairwise_loss_sdf) with a ``fused`` dict, so that
+    generic_align_multiple_submaps takes base.fused_alignment_loop with ops.AlignPlan(residual="sdf") on the rows of
+    ``batches``.  Called pair by pair (a driver that does not take the fused route) it is pairwise_loss_sdf itself, drawing
+    from the loader it is given.  The caller has asked fused_sdf_refusal."""
+    def sdf(atlas, loader, a, b):
+        return pairwise_loss_sdf(atlas, loader, a, b, align_weight=align_weight, align_loss=align_loss,
+                                 use_bound=use_bound, stability_thresh=stability_thresh,
+                                 subsample_points=subsample_points, gm_scale_sdf=gm_scale_sdf, device=device)
+    sdf.fused = dict(align_loss=align_loss, align_weight=align_weight, residual="sdf", gm_scale=gm_scale_sdf,
+                     decoder=grid_atlas.get_submap(0)._fused_decoder(),
+                     inputs=lambda atlas, pairs, chk: sdf_pair_inputs(atlas, batches, pairs, check_intersection=chk))
+    return sdf
+
+
 def latent_loss_for_level(grid_atlas: GridAtlas, level: int, align_weight=3000, align_loss="L2", use_bound=True,
                           stability_thresh=0, subsample_points=None, device="cuda:0"):
     """The pair-loss callable generic_align_multiple_submaps takes (``loss(atlas, loader, src, dst) -> dict``) for
@@ -267,9 +371,16 @@ def align_multiple_submaps_hierarchical(grid_atlas: GridAtlas, dataset, level_it
                                         use_bound=True, stability_thresh=0, subsample_points=None,
                                         latent_levels=None, skip_finetune=False, submap_pairs=None,
                                         pose_reg_weight=0, pose_thresh_m=1.0, pose_thresh_rad=1.0,
-                                        gm_scale_sdf=0.1, device="cuda:0", verbose=True, save_iterations=False):
+                                        gm_scale_sdf=0.1, device="cuda:0", verbose=True, save_iterations=False,
+                                        finetune_fused=False, finetune_batches=1):
     """Coarse-to-fine alignment in latent space, optional SDF-space fine-tune (reference :217-322).
-    ``info`` keys (hier_latent_level{l}_{loss}, hier_sdf_{loss}, cpu/gpu_time_sec) as upstream."""
+    ``info`` keys (hier_latent_level{l}_{loss}, hier_sdf_{loss}, cpu/gpu_time_sec) as upstream.
+
+    finetune_fused (off by default): the fine-tune stage on the device (ops.AlignPlan(residual="sdf"),
+    csrc/pair_sdf.hip) where the options are the covered ones -- L2 / L1 / GM, bound mask on, no stability pruning, no
+    subsampling, atlas on the GPU, single process.  It differs from the reference in one thing: the stage draws
+    ``finetune_batches`` batches ONCE and every iteration and pair works on that fixed sample set, where the reference
+    draws a fresh batch per pair and iteration.  Anything else takes the op-by-op loop, with a log line saying why."""
     grid_atlas.precompute_coordinates_for_alignment()
     info = dict()
     cpu_total = gpu_total = 0
@@ -294,7 +405,25 @@ def align_multiple_submaps_hierarchical(grid_atlas: GridAtlas, dataset, level_it
                                      use_bound=use_bound, stability_thresh=stability_thresh,
                                      subsample_points=subsample_points, gm_scale_sdf=gm_scale_sdf, device=device)
         name = f'hier_sdf_{sdf_loss_type}'
-        res = generic_align_multiple_submaps(grid_atlas, dataset, (name, sdf), num_iters=finetune_iters, **common)
+        res = None
+        if finetune_fused:
+            from miso_amd._lib import NotCovered
+            why = fused_sdf_refusal(grid_atlas, device, use_bound=use_bound, stability_thresh=stability_thresh,
+                                    subsample_points=subsample_points)
+            if why is None:
+                fused_sdf = sdf_finetune_loss(grid_atlas, draw_batches(dataset, finetune_batches, device),
+                                              align_weight=align_weight, align_loss=sdf_loss_type, use_bound=use_bound,
+                                              stability_thresh=stability_thresh, subsample_points=subsample_points,
+                                              gm_scale_sdf=gm_scale_sdf, device=device)
+                try:
+                    res = generic_align_multiple_submaps(grid_atlas, dataset, (name, fused_sdf),
+                                                         num_iters=finetune_iters, **common)
+                except NotCovered as exc:      # refused at plan build: nothing has run yet
+                    why = str(exc)
+            if why is not None:
+                logger.info(f"AlignMulti_{name}: the fine-tune stage runs op by op ({why}).")
+        if res is None:
+            res = generic_align_multiple_submaps(grid_atlas, dataset, (name, sdf), num_iters=finetune_iters, **common)
         cpu_total += res['cpu_time_sec']
         gpu_total += res['gpu_time_sec']
         info[name] = res

@@ -1,0 +1,116 @@
+"""Vox-Fusion++'s inter-map loss as an alignment baseline (reference: grid_opt/align/vfpp.py, eq. (9)-(10) of the paper):
+the destination submap's SDF at the source's observed samples against the MEASURED SDF there.
+
+The reference reads the batch keys 'submap_idxs' / 'coords_kf' / 'keyframe_idxs' (its ScanNet form) or
+'coords_submap' (its SubmapSdf3D form), which none of its current datasets write; this module reads what they write and
+what align/miso.py and align/icp.py read: 'sample_frame_ids' and 'coords_frame', the submap of a row being the owner of
+its keyframe.  Both ``dataset_name`` values therefore select the one loss below, which is the ScanNet form's formula
+(truncation mask, in-bound mask, mean over ALL rows).
+
+With the default options and the atlas on the GPU ``align_multiple_submaps_vfpp`` runs the whole loop on the device
+(ops.AlignPlan(residual="sdf_measured"), csrc/pair_sdf.hip) on ONE batch drawn at the start, where the reference draws a
+fresh one per pair and iteration.  MIPS-Fusion (reference align/mips.py) is not built."""
+import logging
+
+import numpy as np
+import torch
+
+import miso_amd.grid_opt.utils.utils as utils
+import miso_amd.grid_opt.utils.utils_geometry as utils_geometry
+from miso_amd.grid_opt.align.base import *   # noqa: F401,F403
+from miso_amd.grid_opt.align.base import generic_align_multiple_submaps, generic_align_submap_pair
+from miso_amd.grid_opt.models.grid_atlas import GridAtlas
+
+logger = logging.getLogger(__name__)
+
+_DATASET_NAMES = ('ScanNet', 'SubmapSdf3D')
+
+
+def pairwise_loss_vfpp(grid_atlas: GridAtlas, data_loader, src_id: int, dst_id: int, sdf_weight=3000, use_bound=True,
+                       stability_thresh=0, subsample_points=None, trunc_dist=0.15, device="cuda:0"):
+    """{'vfpp_{src}_{dst}': sdf_weight * mean over ALL of src's rows of where(mask, dst(x_dst) - gt, 0)^2} with mask =
+    |gt| < trunc_dist [and x_dst in dst's bound] [and dst's stability above the threshold]; {} when the batch holds no
+    row of ``src_id``.  The source's pose is held by whoever optimises; the gradient reaches the submap poses through
+    x_dst alone."""
+    from miso_amd.grid_opt.loss import transform_by_keyframe
+    assert src_id < grid_atlas.num_submaps and dst_id < grid_atlas.num_submaps
+    sub_to = grid_atlas.get_submap(dst_id)
+    model_input, gt = utils.get_batch(data_loader, device)
+    kf_all = model_input['sample_frame_ids'][0, :, 0]
+    rows = torch.nonzero(grid_atlas.submap_id_for_kf_batch(kf_ids=kf_all) == src_id, as_tuple=False).squeeze(1)
+    if rows.numel() == 0:
+        logger.warning(f"No samples found for submap {src_id}!")
+        return {}
+    coords_from = transform_by_keyframe(model_input['coords_frame'][0, rows, :], kf_all[rows],
+                                        lambda k: grid_atlas.updated_kf_pose_in_submap(k, src_id))
+    R_from, t_from = grid_atlas.updated_submap_pose(src_id, device)
+    R_to, t_to = grid_atlas.updated_submap_pose(dst_id, device)
+    coords_to = utils_geometry.transfrom_points_from(utils_geometry.transform_points_to(coords_from, R_from, t_from),
+                                                     R_to, t_to)
+    gt_sdf = gt['sdf'][0][rows, :]
+    mask = torch.abs(gt_sdf) < trunc_dist
+    if subsample_points is not None:
+        k = min(subsample_points, coords_to.shape[0])
+        pick = np.random.choice(coords_to.shape[0], k, replace=False)
+        coords_to, gt_sdf, mask = coords_to[pick], gt_sdf[pick], mask[pick]
+    if use_bound:
+        mask = mask & utils_geometry.coords_in_bound(coords_to, sub_to.bound)
+    if stability_thresh > 0:
+        mu, _ = torch.min(sub_to.query_stability(coords_to), dim=1, keepdim=True)
+        mask = mask & (mu > stability_thresh)
+    pred = sub_to(coords_to)
+    resid = torch.where(mask, pred - gt_sdf, torch.zeros_like(pred))
+    return {f'vfpp_{src_id}_{dst_id}': torch.mean(resid ** 2) * sdf_weight}
+
+
+def _loss_func(dataset_name, **opts):
+    if dataset_name not in _DATASET_NAMES:
+        raise ValueError(f"Invalid dataset name: {dataset_name}!")
+
+    def vfpp(atlas, loader, a, b):
+        return pairwise_loss_vfpp(atlas, loader, a, b, **opts)
+    return vfpp
+
+
+def align_submap_pair_vfpp(grid_atlas: GridAtlas, dataset, src_id: int, dst_id: int, dataset_name="SubmapSdf3D",
+                           num_iters=10, lr=1e-2, sdf_weight=3000, use_bound=True, stability_thresh=0,
+                           subsample_points=None, device="cuda:0", verbose=True):
+    """Align ``dst_id`` to ``src_id`` by optimising dst's pose alone on the loss above (generic_align_submap_pair)."""
+    loss = _loss_func(dataset_name, sdf_weight=sdf_weight, use_bound=use_bound, stability_thresh=stability_thresh,
+                      subsample_points=subsample_points, device=device)
+    return generic_align_submap_pair(grid_atlas, dataset, src_id, dst_id, ('vfpp', loss), num_iters=num_iters, lr=lr,
+                                     verbose=verbose)
+
+
+def align_multiple_submaps_vfpp(grid_atlas: GridAtlas, dataset, dataset_name='SubmapSdf3D', num_iters=10, lr=1e-2,
+                                sdf_weight=3000, use_bound=True, stability_thresh=0, subsample_points=None,
+                                pose_reg_weight=0, pose_thresh_m=1.0, pose_thresh_rad=1.0, device="cuda:0", verbose=True,
+                                trunc_dist=0.15, save_iterations=False, submap_pairs=None):
+    """Adam over the poses of submaps 1..S-1 on the summed pair losses (generic_align_multiple_submaps).  With the default
+    options (bound mask on, no stability pruning, no subsampling), the atlas on the GPU and a decoder in the fused
+    kernels' table the loop runs on the device on one batch drawn here; otherwise, and when the plan refuses the shape,
+    op by op with a log line.  ``trunc_dist``, ``save_iterations`` and ``submap_pairs`` are additions."""
+    from miso_amd._lib import NotCovered
+    from miso_amd.grid_opt.align import miso as _miso
+    loss = _loss_func(dataset_name, sdf_weight=sdf_weight, use_bound=use_bound, stability_thresh=stability_thresh,
+                      subsample_points=subsample_points, trunc_dist=trunc_dist, device=device)
+    common = dict(num_iters=num_iters, lr=lr, verbose=verbose, pose_reg_weight=pose_reg_weight,
+                  pose_thresh_m=pose_thresh_m, pose_thresh_rad=pose_thresh_rad, save_iterations=save_iterations,
+                  submap_pairs=submap_pairs)
+    why = _miso.fused_sdf_refusal(grid_atlas, device, use_bound=use_bound, stability_thresh=stability_thresh,
+                                  subsample_points=subsample_points)
+    if why is None:
+        batches = _miso.draw_batches(dataset, 1, device)
+
+        def fused_loss(atlas, loader, a, b):
+            return loss(atlas, loader, a, b)
+        fused_loss.fused = dict(align_loss='L2', align_weight=sdf_weight, residual="sdf_measured",
+                                decoder=grid_atlas.get_submap(0)._fused_decoder(),
+                                inputs=lambda atlas, pairs, chk: _miso.sdf_pair_inputs(
+                                    atlas, batches, pairs, check_intersection=chk, measured_trunc=trunc_dist))
+        try:
+            return generic_align_multiple_submaps(grid_atlas, dataset, ('vfpp', fused_loss), **common)
+        except NotCovered as exc:      # refused at plan build: nothing has run yet
+            why = str(exc)
+    logger.info(f"AlignMulti_vfpp runs op by op ({why}).")
+    return generic_align_multiple_submaps(grid_atlas, dataset, ('vfpp', loss), **common)

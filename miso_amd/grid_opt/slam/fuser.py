@@ -44,7 +44,8 @@ class Fuser:
             pose_thresh_m=a.get('pose_thresh_m', 10.0),
             pose_thresh_rad=math.radians(a.get('pose_thresh_deg', 45.0)),
             verbose=a.get('verbose', False), save_iterations=a.get('save_iterations', False),
-            device=self.cfg.get('device', 'cuda:0'))
+            device=self.cfg.get('device', 'cuda:0'),
+            finetune_fused=a.get('finetune_fused', False))      # the SDF fine-tune on the device: off unless asked for
         self.model.print_submap_pose_info()
         return info
 

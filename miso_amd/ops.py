@@ -2234,11 +2234,22 @@ class AlignPlan:
     (n, >= F), ``feats_dst`` (list of level tensors, levels 0..level), ``meta_dst`` (GridMeta) and ``gate_pts``
     ((m,3) finest-level vertices of src, or None: no overlap gate) with, optionally, ``gate_dims`` = (nx, ny, nz) when
     those vertices are FeatureGrid.vertex_positions' meshgrid -- the gate then reads three short tables instead of m
-    points."""
+    points.
+
+    residual: "latent" (above), "sdf" -- the SDF-space fine-tune, pairwise_loss_sdf (grid_opt/align/miso.py:14-113; L2 /
+    L1 / GM with ``gm_scale``) -- or "sdf_measured" -- Vox-Fusion++'s inter-map loss (grid_opt/align/vfpp.py; L2).  In
+    the SDF modes ``decoder`` is the DecoderPack of the destination submaps, ``feats_dst`` / ``meta_dst`` are ALL levels
+    the decoder reads, ``coords`` the source rows in the source frame, and a pair carries ``ref`` (n,) or (n,1) where the
+    latent mode carries ``feats_src``: the source submap's SDF at the rows ("sdf"), or the measured SDF of the rows kept
+    with ``n_rows`` = the source's full row count, the divisor of the reference's mean ("sdf_measured").  A decoder or
+    grid the kernel table does not hold raises _lib.NotCovered."""
+
+    _RESIDUALS = {"latent": 0, "sdf": 1, "sdf_measured": 2}
 
     def __init__(self, R0, t0, pairs, *, loss_type="L2", align_weight=3000.0, overlap_thresh=1e-2, lr=1e-2,
                  betas=(0.9, 0.999), eps=1e-8, reg_weight=0.0, reg_thresh_rad=1.0, reg_thresh_m=1.0,
-                 rel_change_thresh=0.0, ring_iters=0, save_poses=False, cull=None):
+                 rel_change_thresh=0.0, ring_iters=0, save_poses=False, cull=None, residual="latent",
+                 decoder: "DecoderPack" = None, gm_scale=0.1):
         """cull (default on, None included): one box per run of 64 source vertices
         (miso_align_src_boxes, built once per source list) lets the residual kernel skip runs that cannot reach the
         destination bound at the current poses without reading them -- same sums, fewer bytes."""
@@ -2250,7 +2261,16 @@ class AlignPlan:
         self._R0 = R0.detach().reshape(S, 9).contiguous().clone()
         self._t0 = t0.detach().reshape(S, 3).contiguous().clone()
         cfg = _lib.Align()
-        cfg.n_submaps, cfg.n_pairs, cfg.loss_type = S, P, _LOSS_TYPES[loss_type]
+        self.residual = residual
+        cfg.residual = self._RESIDUALS[residual]
+        cfg.n_submaps, cfg.n_pairs = S, P
+        cfg.loss_type = {"L1": 1, "L2": 2, "GM": 3}[loss_type] if cfg.residual else _LOSS_TYPES[loss_type]
+        if cfg.residual:
+            if decoder is None:
+                raise ValueError("AlignPlan: the SDF residuals need the decoder (a DecoderPack)")
+            self._decoder = decoder                                 # (its weight tensors: the Mlp struct points at them)
+            self._mlp, self._packed = decoder.require()             # NotCovered: the caller's other route
+            cfg.mlp, cfg.packed, cfg.gm_scale = C.pointer(self._mlp), self._packed.data_ptr(), float(gm_scale)
         cfg.ring_iters, cfg.save_poses = int(ring_iters), int(bool(save_poses))
         cfg.align_weight, cfg.overlap_thresh = float(align_weight), float(overlap_thresh)
         cfg.reg_weight, cfg.reg_thresh_rad, cfg.reg_thresh_m = float(reg_weight), float(reg_thresh_rad), float(reg_thresh_m)
@@ -2263,13 +2283,22 @@ class AlignPlan:
         for i, pr in enumerate(pairs):
             feats_dst = [f.detach() for f in pr["feats_dst"]]
             coords = pr["coords"].detach().contiguous()
-            fsrc = _rows(pr["feats_src"].detach())
+            if cfg.residual:
+                fsrc = pr["ref"].detach().reshape(-1, 1).contiguous()
+                assert fsrc.shape[0] == coords.shape[0] and fsrc.dtype == torch.float32
+            else:
+                fsrc = _rows(pr["feats_src"].detach())
             _require_hip(coords, fsrc, *feats_dst)
             d = descs[i]
             d.dst_grid = _fill_grid(feats_dst, pr["meta_dst"])
             d.coords_src, d.feats_src = coords.data_ptr(), fsrc.data_ptr()
             d.n = coords.shape[0]
-            d.ld_feats = fsrc.stride(0) if d.n else _feature_dim(feats_dst)
+            if cfg.residual == 2:
+                d.ld_feats = int(pr["n_rows"])                       # the full row count travels in the pitch's field
+            elif cfg.residual == 1:
+                d.ld_feats = 1
+            else:
+                d.ld_feats = fsrc.stride(0) if d.n else _feature_dim(feats_dst)
             gate = pr.get("gate_pts")
             if gate is not None:
                 gate = gate.detach().contiguous()
