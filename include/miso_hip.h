@@ -98,7 +98,7 @@ extern "C" {
 #define MISO_F_PAD_BORDER 2u       /* padding_mode='border' (MISO uses 'zeros') */
 #define MISO_F_COORDS_NORMALIZED 4u /* x is already in [-1,1]: skip normalize_coordinates */
 #define MISO_F_CROWDED 64u         /* hint: the batch crowds a few tiles (ray samples around surfaces and cameras), so
-                                     miso_sdf_bwd_sorted pushes every eligible coarse level through the matrix
+                                     miso_sdf_bwd on a binned batch pushes every eligible coarse level through the matrix
                                      cores whatever the average density per tile (default: from 100 samples per tile) */
 #define MISO_F_EXACT_F32 128u      /* fused encode+decoder entries (miso_sdf_*): evaluate the decoder's products as exact fp32
                                      FMA chains on v_mfma_f32_32x32x2_f32 (rounds 1-5).  Default since round 6: every fp32 operand
@@ -109,17 +109,17 @@ extern "C" {
                                      then queried exactly as GridNet.forward queries it (zeros padding decides what a point
                                      outside the grid sees; the level mask of the plan's grid is honoured): save_mesh(submap,
                                      submap.bound, ...) on a lattice generated in the kernel */
-#define MISO_F_FULL_TRIPS 256u     /* miso_sdf_train on a small unbinned batch (<= 65 536 samples): 64-point trips per wavefront as
+#define MISO_F_FULL_TRIPS 256u     /* miso_sdf_train on a small caller-order batch (<= 65 536 samples): 64-point trips per wavefront as
                                      for large batches, instead of the default 32-point trips (same arithmetic per point; the
                                      32-point form halves a wavefront's chain of matrix instructions where the batch is one
                                      chunk per wavefront anyway).  For tests and A/B runs. */
-#define MISO_F_GRAD_SDF_SORTED 16u  /* miso_sdf_bwd_sorted: grad_sdf is in the binned order (what
-                                       miso_sdf_fwd_sorted_loss writes), not the caller's */
-#define MISO_F_GRAD_ZEROED 32u      /* with MISO_F_GRAD_OVERWRITE: the levels miso_sdf_bwd_sorted ADDS to with atomics
+#define MISO_F_GRAD_SDF_SORTED 16u  /* miso_sdf_bwd on a binned batch: grad_sdf is in the binned order (what
+                                       miso_sdf_fwd_loss writes for one), not the caller's */
+#define MISO_F_GRAD_ZEROED 32u      /* with MISO_F_GRAD_OVERWRITE: the levels miso_sdf_bwd ADDS to with atomics
                                        (miso_sdf_bwd_scattered_levels) are zero on entry -- e.g. cleared by the Adam
                                        launch that consumed them (zero_grad) -- so the library skips its fill */
-#define MISO_F_GRAD_OVERWRITE 8u    /* miso_sdf_bwd_sorted: level[l].grad = sum instead of += (the library
-                                       clears what it still scatters; the caller never zero-fills) */
+#define MISO_F_GRAD_OVERWRITE 8u    /* miso_sdf_bwd on a binned batch: level[l].grad = sum instead of += (the
+                                       library clears what it still scatters; the caller never zero-fills) */
 
 /* One feature-grid level: logical tensor (1,C,Z,Y,X) (grid_modules.py:54-57)
  * with arbitrary element strides, so both the reference's NCDHW layout and the
@@ -163,71 +163,24 @@ typedef struct {
 const char* miso_version(void);
 const char* miso_error_string(int code);
 
-/* feats[n, F] (row stride `ld_out` floats, F = sum of C over levels) =
- * concat_l trilinear(level l, x[n]) ; x is (N,3) row-major metres. */
-int miso_encode_fwd(const miso_grid_t* grid, const float* x, int64_t n,
-                    float* feats, int64_t ld_out, void* stream);
-
-/* First backward.  grad_feats (N,F) row stride ld_g.  For each level with
- * level[l].grad != NULL: grad += scatter (caller zero-initialises).  grad_x (N,3)
- * may be NULL; when non-NULL level[l].data must be valid. */
-int miso_encode_bwd(const miso_grid_t* grid, const float* x, int64_t n,
-                    const float* grad_feats, int64_t ld_g, float* grad_x, void* stream);
-
-/* Second backward (double backward of the encode).  gg_grid->level[l].data is
- * the cotangent of grad_grid (NULL per level = zero), gg_x (N,3) the cotangent of
- * grad_x (NULL = zero).  Outputs: gg_out (N,F) written; grid->level[l].grad +=
- * scatter where non-NULL; g_x (N,3) written where non-NULL. */
-int miso_encode_bwd2(const miso_grid_t* grid, const miso_grid_t* gg_grid, const float* x,
-                     int64_t n, const float* grad_feats, int64_t ld_g, const float* gg_x,
-                     float* gg_out, int64_t ld_gg, float* g_x, void* stream);
-
-/* --- fused encode + decoder (out_dim == 1) --------------------------------
- * miso_sdf_fwd / miso_sdf_bwd* treat the decoder's weights as constants; a trainable decoder adds miso_sdf_wgrad (below,
- * after the binned entry points) for its weight and bias gradients and re-packs (miso_mlp_pack) after every update. */
-/* Size in floats of the packed-weight buffer for this decoder, or 0 if the fused
- * kernels do not cover the shape (then use miso_encode_* + a library GEMM). */
-int64_t miso_mlp_packed_floats(const miso_mlp_t* mlp);
-int miso_mlp_pack(const miso_mlp_t* mlp, float* packed, void* stream);
-/* 1 if (grid, mlp) is covered by miso_sdf_fwd/bwd, else 0 */
-int miso_sdf_supported(const miso_grid_t* grid, const miso_mlp_t* mlp);
-/* Dynamic LDS (bytes) of the one-launch training kernel (miso_sdf_train / miso_sdf_train_sorted) for this (levels, C,
- * hidden width, hidden layers) shape -- scattering != 0: the form that scatters some level from the kernel (cell records
- * beside the d-feat tiles); 0: every level deferred to the pull.  Returns 0 when the shape is not covered or the figure
- * exceeds the device's LDS per workgroup (160 KB on gfx950): a caller routes such a shape to the two-launch path instead
- * of failing in the launch. */
-int64_t miso_sdf_train_lds_bytes(const miso_grid_t* grid, const miso_mlp_t* mlp, int32_t scattering);
-
-/* uint32 words of ReLU sign bits per point: (n_linear-1) * hidden_dim/32 */
-int64_t miso_sdf_mask_words(const miso_mlp_t* mlp);
-
-/* sdf[n] = MLP(encode(x[n])).  relu_mask: NULL (inference) or
- * ceil(n/64)*64*miso_sdf_mask_words(mlp) uint32 words that miso_sdf_bwd consumes. */
-int miso_sdf_fwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                 const float* x, int64_t n, float* sdf, uint32_t* relu_mask, void* stream);
-
-/* grad_sdf (N) -> scatter into level[l].grad (non-NULL levels) and/or grad_x. */
-int miso_sdf_bwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                 const float* x, int64_t n, const float* grad_sdf, const uint32_t* relu_mask,
-                 float* grad_x, void* stream);
-
-/* miso_sdf_bwd that also hands out the d-feat rows (N, F) it forms on the way (row n = d loss / d feats of point n, F =
- * sum of C): the quantity the SECOND backward differentiates when the reference runs torch.autograd.grad(sdf, x,
- * create_graph=True) for its eikonal / smoothness terms (grid_opt/loss_isdf.py:96-152, :367-377; loss.py:638-665) --
- * d sdf / d x = J_E(x; G)^T rows, so miso_encode_bwd2 with grad_feats = these rows is the whole double backward (a ReLU
- * decoder is piecewise linear).  dfeat_rows NULL: exactly miso_sdf_bwd.  Caller-order points only. */
-int miso_sdf_bwd_rows(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
-                      const float* grad_sdf, const uint32_t* relu_mask, float* grad_x, float* dfeat_rows, void* stream);
-
-/* --- spatially binned batches ----------------------------------------------
+/* --- the points of a call: in the caller's order, or spatially binned --------
  * Counting sort of a point batch by coarse tile (tiles_per_axis^3 tiles over the
  * bound).  No reference counterpart: the reference gathers every level with
  * independent random accesses (grid_modules.py:86-94); binning is what lets the
  * gathers of neighbouring lanes share cache lines and the backward form the grid
- * gradient owner-computes, without atomics (miso_grad_pull).  Results of the
- * *_sorted calls are identical to the unsorted ones up to fp32 summation order;
- * sdf, grad_sdf (unless MISO_F_GRAD_SDF_SORTED) and grad_x stay in the caller's
- * (original) point order. */
+ * gradient owner-computes, without atomics (miso_grad_pull).
+ *
+ * THE POINT ARGUMENTS.  Every entry below that reads points takes `const float* x` and `const miso_sorted_t* sorted`
+ * (miso_grad_pull and miso_grad_pull_dx, which exist for a binned batch only, take `sorted` alone and require it):
+ *   sorted != NULL  the binned form.  `sorted` must be a whole binning: tile_offsets and tiles_per_axis valid, and for
+ *                   n > 0 x_sorted or xn_sorted, and perm (miso_sdf_train alone does without perm, and needs xn_sorted);
+ *                   xn_sorted 16-byte aligned.  x is ignored.
+ *   sorted == NULL  the caller-order form.  x (N,3) row-major metres must be set when n > 0.  What belongs to the binned
+ *                   form must be absent: n_live and workspace NULL, MISO_F_GRAD_SDF_SORTED clear (miso_sdf_bwd,
+ *                   miso_sdf_wgrad).
+ * Anything else is MISO_E_BADARG; `sorted` is looked at after the grid (and decoder) arguments, so a call with several
+ * faults reports the grid's or the decoder's code first.  The two forms of one call give identical results up to fp32 summation order; sdf,
+ * grad_sdf (unless MISO_F_GRAD_SDF_SORTED), feature rows and grad_x are in the caller's (original) point order in both. */
 /* tiles_per_axis (here and wherever a binning is named): a plain count 1..16 (cubic binning), or per-axis counts of 1..32
  * packed with MISO_TILES_XYZ -- e.g. (25, 13, 25) puts at most 8 vertices of a 200 x 100 x 200 level (ScanNet's fine
  * level, configs/rgbd/scannet.yaml:23-24) on a tile and axis, which is what the owner-computes gradient can own.  A packed
@@ -239,11 +192,11 @@ typedef struct {
   const float* x_sorted;       /* (N,3) points grouped by tile                   */
   const float* xn_sorted;      /* (N,4) the same normalised to [-1,1] as {x, y, z, i}, 16-B aligned; NULL = absent.  i = the
                                   point's ORIGINAL index as a 32-bit integer bit pattern (what perm[] holds) */
-  const int32_t* perm;         /* (N) sorted position -> original index.  NULL is accepted by miso_sdf_train_sorted only
+  const int32_t* perm;         /* (N) sorted position -> original index.  NULL is accepted by miso_sdf_train only
                                   (it takes the index from xn_sorted[p].w): a mapping step that runs nothing else on the
                                   batch saves the sort one scattered 4-byte store per point */
   const int32_t* tile_offsets; /* (number of tiles + 1) start of every tile in x_sorted; tile (tx,ty,tz) = (tz Ty + ty) Tx + tx */
-  /* Optional scratch of the owner-computes gradient (miso_grad_pull, miso_sdf_bwd_sorted):
+  /* Optional scratch of the owner-computes gradient (miso_grad_pull, miso_sdf_bwd, miso_sdf_train):
    * miso_pull_queue_ints(n) int32, ZEROED ONCE by the caller when allocated (the library leaves it
    * zeroed after every call).  With it, tiles that hold far more points than the average are cut
    * into slices that run on separate wavefronts -- a batch hugging surfaces instead of filling the
@@ -257,18 +210,60 @@ int64_t miso_sort_workspace_bytes(int64_t n, int32_t tiles_per_axis);
 int miso_sort_points(const miso_grid_t* grid, const float* x, int64_t n, int32_t tiles_per_axis,
                      void* workspace, float* x_sorted /* may be NULL */, float* xn_sorted /* may be NULL */,
                      int32_t* perm /* may be NULL when xn_sorted is given */, int32_t* tile_offsets, void* stream);
-/* miso_encode_fwd over a binned batch: the gathers of neighbouring lanes share cache lines
- * (105 -> 39 us at 262144 points); feats rows are written in the caller's order. */
-int miso_encode_fwd_sorted(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, float* feats,
-                           int64_t ld_out, void* stream);
-int miso_sdf_fwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                        const miso_sorted_t* sorted, int64_t n, float* sdf, uint32_t* relu_mask,
-                        void* stream);
-/* miso_sdf_fwd_sorted with the mapping loss folded in (the trainer step of
+
+/* feats[n, F] (row stride `ld_out` floats, F = sum of C over levels) =
+ * concat_l trilinear(level l, point n); x / sorted: THE POINT ARGUMENTS.  Over a binned batch the gathers of
+ * neighbouring lanes share cache lines (105 -> 39 us at 262144 points). */
+int miso_encode_fwd(const miso_grid_t* grid, const float* x, const miso_sorted_t* sorted, int64_t n,
+                    float* feats, int64_t ld_out, void* stream);
+
+/* First backward.  grad_feats (N,F) row stride ld_g.  For each level with
+ * level[l].grad != NULL: grad += scatter (caller zero-initialises).  grad_x (N,3)
+ * may be NULL; when non-NULL level[l].data must be valid.  x / sorted: THE POINT ARGUMENTS (binned: grad_x, and any level
+ * the pull cannot own, with tile-ordered gathers). */
+int miso_encode_bwd(const miso_grid_t* grid, const float* x, const miso_sorted_t* sorted, int64_t n,
+                    const float* grad_feats, int64_t ld_g, float* grad_x, void* stream);
+
+/* Second backward (double backward of the encode).  gg_grid->level[l].data is
+ * the cotangent of grad_grid (NULL per level = zero), gg_x (N,3) the cotangent of
+ * grad_x (NULL = zero).  Outputs: gg_out (N,F) written; grid->level[l].grad +=
+ * scatter where non-NULL; g_x (N,3) written where non-NULL.  x / sorted: THE POINT ARGUMENTS; all per-point rows
+ * (grad_feats, gg_x, gg_out, g_x) are in the caller's order. */
+int miso_encode_bwd2(const miso_grid_t* grid, const miso_grid_t* gg_grid, const float* x, const miso_sorted_t* sorted,
+                     int64_t n, const float* grad_feats, int64_t ld_g, const float* gg_x,
+                     float* gg_out, int64_t ld_gg, float* g_x, void* stream);
+
+/* --- fused encode + decoder (out_dim == 1) --------------------------------
+ * miso_sdf_fwd / miso_sdf_bwd treat the decoder's weights as constants; a trainable decoder adds miso_sdf_wgrad (below)
+ * for its weight and bias gradients and re-packs (miso_mlp_pack) after every update. */
+/* Size in floats of the packed-weight buffer for this decoder, or 0 if the fused
+ * kernels do not cover the shape (then use miso_encode_* + a library GEMM). */
+int64_t miso_mlp_packed_floats(const miso_mlp_t* mlp);
+int miso_mlp_pack(const miso_mlp_t* mlp, float* packed, void* stream);
+/* 1 if (grid, mlp) is covered by miso_sdf_fwd/bwd, else 0 */
+int miso_sdf_supported(const miso_grid_t* grid, const miso_mlp_t* mlp);
+/* Dynamic LDS (bytes) of the one-launch training kernel (miso_sdf_train) for this (levels, C,
+ * hidden width, hidden layers) shape -- scattering != 0: the form that scatters some level from the kernel (cell records
+ * beside the d-feat tiles); 0: every level deferred to the pull.  Returns 0 when the shape is not covered or the figure
+ * exceeds the device's LDS per workgroup (160 KB on gfx950): a caller routes such a shape to the two-launch path instead
+ * of failing in the launch. */
+int64_t miso_sdf_train_lds_bytes(const miso_grid_t* grid, const miso_mlp_t* mlp, int32_t scattering);
+
+/* uint32 words of ReLU sign bits per point: (n_linear-1) * hidden_dim/32 */
+int64_t miso_sdf_mask_words(const miso_mlp_t* mlp);
+
+/* sdf[n] = MLP(encode(point n)); x / sorted: THE POINT ARGUMENTS.  relu_mask: NULL (inference) or
+ * ceil(n/64)*64*miso_sdf_mask_words(mlp) uint32 words that miso_sdf_bwd over the same x / sorted consumes. */
+int miso_sdf_fwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
+                 const float* x, const miso_sorted_t* sorted, int64_t n, float* sdf, uint32_t* relu_mask,
+                 void* stream);
+
+/* miso_sdf_fwd with the mapping loss folded in (the trainer step of
  * grid_opt/trainer.py:196-228 with MisoLossMapping): right after a point's SDF the kernel
  * evaluates the loss terms of miso_mapping_loss for it and writes d loss / d sdf to
- * grad_sdf_sorted[p] (binned order: pass it to miso_sdf_bwd_sorted with
- * MISO_F_GRAD_SDF_SORTED).
+ * grad_sdf in the order of the points read: binned order with `sorted` (pass it to miso_sdf_bwd with
+ * MISO_F_GRAD_SDF_SORTED), caller order without (feed it to miso_sdf_bwd).  Replaces miso_sdf_fwd +
+ * miso_mapping_loss_rows and the clear of their two sums.
  * loss_inputs (N,4), 16-B aligned, caller order: {target, valid, sign, weight} per point
  * (valid / sign compare against 1.0 as in miso_mapping_loss; use valid = weight = 1, sign = 0
  * for absent masks).
@@ -277,45 +272,69 @@ int miso_sdf_fwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
  * workgroup ends at about the same time).  The loss is the column sum: [.,0] weight_sdf * sdf
  * term, [.,1] weight_fs * free-space term.
  * sdf (caller order) may be NULL.
- * n_live (one int32 on the DEVICE, or NULL): number of live rows when the batch is a fixed-capacity
+ * n_live (binned form; one int32 on the DEVICE, or NULL): number of live rows when the batch is a fixed-capacity
  * buffer whose other rows are neutral padding (valid = sign = weight = 0, as miso_sample_rays
  * leaves them).  The reference's means run over the rows of the batch (loss.py:627-635, :698-700),
  * so with padding they must divide by the live count, which only the device knows; NULL = n. */
 #define MISO_LOSS_SLOTS 512
-int miso_sdf_fwd_sorted_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                             const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf,
-                             float weight_fs, float trunc_dist, const float* loss_inputs, float* sdf,
-                             uint32_t* relu_mask, float* grad_sdf_sorted, float* loss_slots,
-                             const int32_t* n_live, void* stream);
-/* The whole binned training step behind one call: forward + mapping loss + decoder backward in ONE launch
- * (sdf_train_kernel: the ReLU sign bits and d loss / d sdf never leave the registers), then the owner-computes pull /
- * matrix-core push of every level's gradient from the d-feat rows left in `workspace`
- * (miso_sdf_bwd_workspace_floats floats, 16-byte aligned).  Same results as miso_sdf_fwd_sorted_loss followed by
- * miso_sdf_bwd_sorted with MISO_F_GRAD_SDF_SORTED (same arithmetic, same order of operations per point).  Requires a
- * frozen decoder and at least one level with a gradient (MISO_E_UNSUPPORTED otherwise).  A level the pull cannot form
- * (bricks of more than 8 vertices per tile and axis: not in miso_grad_pull_levels) is scattered with float atomics from
- * the same launch, as miso_sdf_bwd_sorted scatters it.  grid->flags: MISO_F_GRAD_OVERWRITE / _ZEROED / MISO_F_CROWDED as
- * for miso_sdf_bwd_sorted.  sdf (caller order) may be NULL. */
-int miso_sdf_train_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                          const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
-                          float trunc_dist, const float* loss_inputs, float* sdf, float* loss_slots,
-                          const int32_t* n_live, float* workspace, void* stream);
-/* The same step for an unbinned (small) batch, x (N,3) and loss_inputs (N,4) in the caller's order: forward + mapping
- * loss + decoder backward + the atomic scatter of every level's gradient in ONE launch (what miso_sdf_fwd_loss +
- * miso_sdf_bwd do in two).  The gradients are ADDED to `grad` (clear them first, or let miso_adam_step clear them: zero_grad). */
-int miso_sdf_train(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
-                   int loss_type, float weight_sdf, float weight_fs, float trunc_dist, const float* loss_inputs,
-                   float* sdf /* may be NULL */, float* loss_slots, void* stream);
-/* The forward half for an unbinned (small) batch: x (N,3) and loss_inputs in the caller's order, grad_sdf (N) in that order too
- * (feed it to miso_sdf_bwd).  Replaces miso_sdf_fwd + miso_mapping_loss_rows and the clear of their two sums. */
-int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
-                      int loss_type, float weight_sdf, float weight_fs, float trunc_dist, const float* loss_inputs,
-                      float* sdf /* may be NULL */, uint32_t* relu_mask, float* grad_sdf, float* loss_slots,
-                      void* stream);
+int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
+                      const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
+                      float trunc_dist, const float* loss_inputs, float* sdf /* may be NULL */, uint32_t* relu_mask,
+                      float* grad_sdf, float* loss_slots, const int32_t* n_live, void* stream);
+
+/* grad_sdf (N) -> scatter into level[l].grad (non-NULL levels) and/or grad_x.  x / sorted: THE POINT ARGUMENTS.
+ * workspace (binned form; 16-B aligned, miso_sdf_bwd_workspace_floats floats, may be NULL): with it and
+ * sorted->xn_sorted the grid gradient is formed owner-computes (grad_pull.hip): every tile
+ * gathers the contributions to the vertices it owns and writes them once, without atomics.
+ * Levels the pull cannot own (more than 8 vertices per tile and axis, non-default sampling
+ * flags) keep the atomic scatter. */
+int64_t miso_sdf_bwd_workspace_floats(const miso_grid_t* grid, int64_t n);
+int miso_sdf_bwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
+                 const float* x, const miso_sorted_t* sorted, int64_t n, const float* grad_sdf,
+                 const uint32_t* relu_mask, float* grad_x, float* workspace, void* stream);
+/* Levels (bit l) whose gradient miso_sdf_bwd forms by the matrix-core push instead of the pull (grad_pull.hip:
+ * per run of tile-sorted samples a (samples x 25)^T (samples x 5 C) product on v_mfma_f32_32x32x2_f32, added to the
+ * zero-filled level with atomics): a batch that averages >= 100 samples per tile (a constant of the library), 4 or 8 channels,
+ * and every tile's samples within 5 vertices per axis (a tile owns <= 3).  n = batch size.  Informational: the entry
+ * point decides by itself. */
+uint32_t miso_sdf_bwd_push_levels(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n);
+/* Levels (bit l, among those with a grad pointer) that miso_sdf_bwd on a binned batch forms by ADDING with atomics -- the
+ * decoder pass's scatter for levels the pull cannot own, and the push -- as opposed to the pull's plain stores.  With
+ * MISO_F_GRAD_OVERWRITE these are the levels the call zero-fills first, unless MISO_F_GRAD_ZEROED says they are
+ * zero already. */
+uint32_t miso_sdf_bwd_scattered_levels(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n);
+
+/* The caller-order miso_sdf_bwd that also hands out the d-feat rows (N, F) it forms on the way (row n = d loss / d feats
+ * of point n, F = sum of C): the quantity the SECOND backward differentiates when the reference runs
+ * torch.autograd.grad(sdf, x, create_graph=True) for its eikonal / smoothness terms (grid_opt/loss_isdf.py:96-152,
+ * :367-377; loss.py:638-665) -- d sdf / d x = J_E(x; G)^T rows, so miso_encode_bwd2 with grad_feats = these rows is the
+ * whole double backward (a ReLU decoder is piecewise linear).  dfeat_rows NULL: exactly miso_sdf_bwd with sorted and
+ * workspace NULL (MISO_F_GRAD_SDF_SORTED is refused either way). */
+int miso_sdf_bwd_rows(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
+                      const float* grad_sdf, const uint32_t* relu_mask, float* grad_x, float* dfeat_rows, void* stream);
+
+/* The whole training step behind one call: forward + mapping loss + decoder backward in ONE launch (sdf_train_kernel:
+ * the ReLU sign bits and d loss / d sdf never leave the registers).  Requires a frozen decoder and at least one level
+ * with a gradient (MISO_E_UNSUPPORTED otherwise).  x / sorted: THE POINT ARGUMENTS; loss_inputs (N,4), loss_slots and
+ * n_live as for miso_sdf_fwd_loss; sdf (caller order) may be NULL.
+ *   Binned: then the owner-computes pull / matrix-core push of every level's gradient from the d-feat rows left in
+ * `workspace` (required: miso_sdf_bwd_workspace_floats floats, 16-byte aligned).  Same results as miso_sdf_fwd_loss
+ * followed by miso_sdf_bwd with MISO_F_GRAD_SDF_SORTED (same arithmetic, same order of operations per point).  A level
+ * the pull cannot form (bricks of more than 8 vertices per tile and axis: not in miso_grad_pull_levels) is scattered with
+ * float atomics from the same launch, as miso_sdf_bwd scatters it.  grid->flags: MISO_F_GRAD_OVERWRITE / _ZEROED /
+ * MISO_F_CROWDED as for miso_sdf_bwd.
+ *   Caller order (a small batch): the atomic scatter of every level's gradient from the same launch (what
+ * miso_sdf_fwd_loss + miso_sdf_bwd do in two).  The gradients are ADDED to `grad` (clear them first, or let
+ * miso_adam_step clear them: zero_grad). */
+int miso_sdf_train(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
+                   const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
+                   float trunc_dist, const float* loss_inputs, float* sdf /* may be NULL */, float* loss_slots,
+                   const int32_t* n_live, float* workspace, void* stream);
+
 /* The owner-computes gradient on its own: rows of d loss / d feats (row pitch ld_d floats,
  * a multiple of 4; 16-B aligned base) -> level[l].grad for every level with a non-NULL grad,
  * written (MISO_F_GRAD_OVERWRITE) or accumulated, without atomics.  Rows are in the binned
- * order (rows_in_caller_order = 0: what miso_sdf_bwd_sorted leaves in its workspace) or in the
+ * order (rows_in_caller_order = 0: what miso_sdf_bwd leaves in its workspace) or in the
  * caller's order (1: row perm[p] belongs to sorted point p -- the grad_output of
  * F.grid_sample as autograd hands it over).  Every level with a grad must be pullable:
  * miso_grad_pull_levels returns that set as a bit mask (<= 8 vertices per tile and axis,
@@ -330,15 +349,6 @@ uint32_t miso_grad_pull_levels(const miso_grid_t* grid, int32_t tiles_per_axis);
 int miso_grad_pull_on_matrix_cores(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n, int64_t ld_d);
 int miso_grad_pull(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, const float* dfeat,
                    int64_t ld_d, int32_t rows_in_caller_order, void* stream);
-/* miso_encode_bwd over a binned batch: grad_x (and any level the pull cannot own) with
- * tile-ordered gathers; grad_feats / grad_x rows stay in the caller's order. */
-int miso_encode_bwd_sorted(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n,
-                           const float* grad_feats, int64_t ld_g, float* grad_x, void* stream);
-/* miso_encode_bwd2 over a binned batch (tile-ordered gathers); all per-point rows (grad_feats,
- * gg_x, gg_out, g_x) stay in the caller's order. */
-int miso_encode_bwd2_sorted(const miso_grid_t* grid, const miso_grid_t* gg_grid, const miso_sorted_t* sorted,
-                            int64_t n, const float* grad_feats, int64_t ld_g, const float* gg_x, float* gg_out,
-                            int64_t ld_gg, float* g_x, void* stream);
 /* The same for the SECOND backward: the g_input output of gridsample_grad2.grad2_3d
  * (gridsample_cuda.cu:462-481), level[l].grad (+)= sum_i (sum_a gg_x[i,a] * d w_corner / d x_a) *
  * grad_feats[i, channels of l] -- the scatter half of miso_encode_bwd2, which is then called with
@@ -346,36 +356,15 @@ int miso_encode_bwd2_sorted(const miso_grid_t* grid, const miso_grid_t* gg_grid,
 int miso_grad_pull_dx(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, const float* grad_feats,
                       int64_t ld_g, const float* gg_x, void* stream);
 
-/* workspace (16-B aligned, miso_sdf_bwd_workspace_floats floats, may be NULL): with it and
- * sorted->xn_sorted the grid gradient is formed owner-computes (grad_pull.hip): every tile
- * gathers the contributions to the vertices it owns and writes them once, without atomics.
- * Levels the pull cannot own (more than 8 vertices per tile and axis, non-default sampling
- * flags) keep the atomic scatter. */
-/* Levels (bit l) whose gradient miso_sdf_bwd_sorted forms by the matrix-core push instead of the pull (grad_pull.hip:
- * per run of tile-sorted samples a (samples x 25)^T (samples x 5 C) product on v_mfma_f32_32x32x2_f32, added to the
- * zero-filled level with atomics): a batch that averages >= 100 samples per tile (a constant of the library), 4 or 8 channels,
- * and every tile's samples within 5 vertices per axis (a tile owns <= 3).  n = batch size.  Informational: the entry
- * point decides by itself. */
-uint32_t miso_sdf_bwd_push_levels(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n);
-/* Levels (bit l, among those with a grad pointer) that miso_sdf_bwd_sorted forms by ADDING with atomics -- the decoder
- * pass's scatter for levels the pull cannot own, and the push -- as opposed to the pull's plain stores.  With
- * MISO_F_GRAD_OVERWRITE these are the levels the call zero-fills first, unless MISO_F_GRAD_ZEROED says they are
- * zero already. */
-uint32_t miso_sdf_bwd_scattered_levels(const miso_grid_t* grid, int32_t tiles_per_axis, int64_t n);
-int64_t miso_sdf_bwd_workspace_floats(const miso_grid_t* grid, int64_t n);
-int miso_sdf_bwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                        const miso_sorted_t* sorted, int64_t n, const float* grad_sdf,
-                        const uint32_t* relu_mask, float* grad_x, float* workspace, void* stream);
-
 /* --- decoder weight gradients (trainable decoder) ---------------------------
  * For every nn.Linear l of the decoder: grads->weight[l][out][in] = sum_p delta_l[p][out] a_{l-1}[p][in] and
  * grads->bias[l][out] = sum_p delta_l[p][out], where a_{-1} is the encoded feature row, a_l the ReLU outputs (recomputed
  * in exact fp32) and delta_l the cotangent of grad_sdf at layer l's output, gated by relu_mask -- the sign bits the
  * forward wrote, in either decoder arithmetic.  The outputs are WRITTEN, not accumulated, and are deterministic (no
  * atomics: per-workgroup partial sums in `workspace`, added in a fixed order; n == 0 writes zeros).
- *   sorted == NULL: x, relu_mask and grad_sdf in the caller's order (miso_sdf_fwd / miso_sdf_bwd).
- *   sorted != NULL: x is ignored, relu_mask is in the binned order (miso_sdf_fwd_sorted), grad_sdf in the caller's
- *                   order, or in the binned order with flags = MISO_F_GRAD_SDF_SORTED (the only flag accepted).
+ * x / sorted: THE POINT ARGUMENTS.  relu_mask is in the order of the miso_sdf_fwd that wrote it over the same x / sorted;
+ * grad_sdf in the caller's order, or for a binned batch in the binned order with flags = MISO_F_GRAD_SDF_SORTED (the only
+ * flag accepted).
  * workspace: miso_sdf_wgrad_workspace_floats(grid, mlp, n) floats, 16-byte aligned (0 floats: shape not covered, or
  * n == 0; at most a few MB). */
 int64_t miso_sdf_wgrad_workspace_floats(const miso_grid_t* grid, const miso_mlp_t* mlp, int64_t n);
@@ -660,12 +649,12 @@ int64_t miso_sample_rays_workspace_bytes(int64_t n_rays, int32_t n_frames);
  * dropped and the remaining rays packed to the front, ray order kept.
  * Outputs, capacity n_rays*S rows each: coords_frame (rows,3) in the keyframe frame,
  * sample_frame_ids (rows) int64, aux (rows,4) = {sdf, valid, sign, weight} -- the row layout
- * miso_sdf_fwd_sorted_loss reads -- with valid = |sdf| < trunc_dist, sign = -1 / 0 / +1 beyond the
+ * miso_sdf_fwd_loss reads -- with valid = |sdf| < trunc_dist, sign = -1 / 0 / +1 beyond the
  * truncation band, weight = 1; optional pc_world (rows,3) and z_vals (rows) (NULL to skip).
  * Rows past the packed ones are neutral padding: aux = 0 (no loss, no gradient), coordinates and frame id
  * borrowed from a live sample so that a padded batch keeps the spatial spread of the live one.
  * counts (4 x int32, device) = {rays after the first filter, rays kept, live rows = kept * S, 0};
- * &counts[2] is what miso_sdf_fwd_sorted_loss takes as n_live. */
+ * &counts[2] is what miso_sdf_fwd_loss takes as n_live. */
 int miso_sample_rays(const miso_ray_frames_t* frames, const miso_ray_sampling_t* sampling, int64_t n_rays,
                      const int64_t* pix_b, const int64_t* pix_h, const int64_t* pix_w, const float* u,
                      const float* g, void* workspace, float* coords_frame, int64_t* sample_frame_ids,
@@ -731,7 +720,7 @@ int miso_adam_scalars_table(double lr, double beta1, double beta2, double eps, i
 /* Once per step and in front of its miso_adam_step: step[0] += 1 unless *guard is NaN (the reference's NaN guard skips
  * optimizer.step(), so the count must not move). */
 int miso_adam_bump(int32_t* step, const float* guard /* or NULL */, void* stream);
-/* total[0] = sum of n_floats floats (the loss slots of miso_sdf_fwd_sorted_loss / miso_sdf_fwd_loss: 2 * MISO_LOSS_SLOTS,
+/* total[0] = sum of n_floats floats (the loss slots of miso_sdf_fwd_loss / miso_sdf_train: 2 * MISO_LOSS_SLOTS,
  * i.e. both terms of the mapping loss) and, with step != NULL, miso_adam_bump(step, total) in the same launch.
  * host_ring != NULL: the total is ALSO handed to the host.  `step` is then device int32[2] = {Adam step count, launches
  * so far} and must be set; host_ring is PINNED HOST memory mapped into the device, 2 * ring_len words, zeroed once;
@@ -753,7 +742,7 @@ int miso_rigid_by_index(const float* R, const float* t, const int64_t* idx, cons
                         int32_t n_poses, int transpose, float* y, void* stream);
 
 /* The input side of one mapping step in one launch (MisoLossMapping.world_coords, grid_opt/loss.py:763-774, plus
- * the label layout of miso_sdf_fwd_sorted_loss / miso_mapping_loss_rows): k = table[clamp(frame_ids[i], 0,
+ * the label layout of miso_sdf_fwd_loss / miso_mapping_loss_rows): k = table[clamp(frame_ids[i], 0,
  * table_len - 1)] clamped into [0, n_poses), coords_world[i] = R[k] coords_frame[i] + t[k] (operation order of
  * miso_rigid_by_index), loss_rows[i] = {target[i], valid[i], sign[i], weight[i]} (valid / sign / weight may be NULL:
  * 1 / 0 / 1).  table: int64 keyframe-id -> pose-index (device).  loss_rows 16-B aligned.

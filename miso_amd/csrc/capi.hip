@@ -9,11 +9,13 @@
 //    from the other fused calls (and from miso_mlp_pack, which says UNSUPPORTED for packed == NULL too).
 //  * a loss type out of range is MISO_E_BADARG from the mapping-loss and alignment calls, MISO_E_UNSUPPORTED from
 //    miso_lm_normal_eq, miso_lm_track_step and miso_track_adam_step.
-//  * n == 0: miso_sdf_fwd_loss and miso_sdf_fwd_sorted_loss zero the loss slots without looking at grid, mlp or packed,
-//    miso_sdf_train* check them first; miso_atlas_sdf_bwd and miso_atlas_sphere_trace return before their per-point
+//  * n == 0: miso_sdf_fwd_loss zeroes the loss slots without looking at grid, mlp or packed (at `sorted` it does look),
+//    miso_sdf_train checks them first; miso_atlas_sdf_bwd and miso_atlas_sphere_trace return before their per-point
 //    pointers are looked at, miso_atlas_sdf_fwd has no such return.
 //  * the tracker steps check grid shape, mlp and packed in the fused forward, BEHIND their first launch (the head).
-//  * miso_sdf_bwd_rows refuses the host-side gradient flags (OVERWRITE, SDF_SORTED, ZEROED); miso_sdf_bwd ignores them.
+//  * miso_sdf_bwd_rows refuses the host-side gradient flags (OVERWRITE, SDF_SORTED, ZEROED); of a caller-order batch
+//    miso_sdf_bwd refuses SDF_SORTED and ignores the other two -- and so do its callers here: miso_sdf_bwd_rows without
+//    rows, and miso_lm_track_step and miso_track_adam_step (behind their first launch, like their other grid checks).
 //  * miso_adam_dense asks no alignment of its four arrays; miso_adam_step asks 16 bytes of them, and 4 bytes of the
 //    flag arrays where `touched` is given (even for numel == 0).
 #include <stdlib.h>
@@ -240,7 +242,7 @@ hipError_t zero_loss_slots(float* loss_slots, hipStream_t stream) {
   return launch_zero_words(loss_slots, MISO_LOSS_SLOTS * 2, stream);
 }
 
-// perm_optional: the entry point can take the original index from xn_sorted[p].w (miso_sdf_train_sorted)
+// perm_optional: the entry point can take the original index from xn_sorted[p].w (miso_sdf_train)
 int check_sorted(const miso_sorted_t* s, int64_t n, bool perm_optional = false) {
   if (!s || !s->tile_offsets) return MISO_E_BADARG;
   if (n > 0 && (!s->x_sorted && !s->xn_sorted)) return MISO_E_BADARG;   // an empty batch has no buffers
@@ -259,6 +261,20 @@ const float* sorted_points(GridK* g, const miso_sorted_t* sorted) {
   }
   g->xstride = 4;
   return sorted->xn_sorted;
+}
+
+// The points of a call, by the one rule of miso_hip.h (at miso_sorted_t).  sorted != NULL, the binned form: `sorted` is
+// checked, *x and *perm are taken from it and g reads the points it has (the caller's x is ignored).  sorted == NULL,
+// the caller's order: *x as given, which n > 0 points need, and no perm.
+int use_points(GridK* g, const float** x, const int** perm, const miso_sorted_t* sorted, int64_t n,
+               bool perm_optional = false) {
+  *perm = nullptr;
+  if (sorted) {
+    if (int rc = check_sorted(sorted, n, perm_optional)) return rc;
+    *x = sorted_points(g, sorted);
+    *perm = sorted->perm;
+  }
+  return n > 0 && !*x ? MISO_E_BADARG : MISO_OK;
 }
 
 int mc_check_dims(int32_t nx, int32_t ny, int32_t nz) {
@@ -284,41 +300,31 @@ const char* miso_error_string(int code) {
   }
 }
 
-int miso_encode_fwd(const miso_grid_t* grid, const float* x, int64_t n, float* feats, int64_t ld_out,
-                    void* stream) {
-  if (n < 0 || !set_if(n, x, feats)) return MISO_E_BADARG;
+int miso_encode_fwd(const miso_grid_t* grid, const float* x, const miso_sorted_t* sorted, int64_t n, float* feats,
+                    int64_t ld_out, void* stream) {
+  if (n < 0 || !set_if(n, feats)) return MISO_E_BADARG;
   GridK g; bool v4;
   if (int rc = convert_grid(grid, &g, true, &v4)) return rc;
   if (ld_out < g.F) return MISO_E_BADARG;
-  return (int)launch_encode_fwd(g, v4, x, n, feats, ld_out, nullptr, (hipStream_t)stream);
+  const int* perm;
+  if (int rc = use_points(&g, &x, &perm, sorted, n)) return rc;
+  return (int)launch_encode_fwd(g, v4, x, n, feats, ld_out, perm, (hipStream_t)stream);
 }
 
-static int encode_bwd_impl(const miso_grid_t* grid, const float* x, int64_t n, const float* grad_feats,
-                           int64_t ld_g, float* grad_x, const miso_sorted_t* sorted, void* stream) {
+int miso_encode_bwd(const miso_grid_t* grid, const float* x, const miso_sorted_t* sorted, int64_t n,
+                    const float* grad_feats, int64_t ld_g, float* grad_x, void* stream) {
   if (n < 0 || !set_if(n, grad_feats)) return MISO_E_BADARG;
   GridK g; bool v4;
   if (int rc = convert_grid(grid, &g, grad_x != nullptr, &v4)) return rc;
   if (ld_g < g.F) return MISO_E_BADARG;
-  const int* perm = nullptr;
-  if (sorted) { x = sorted_points(&g, sorted); perm = sorted->perm; }
-  if (n > 0 && !x) return MISO_E_BADARG;
+  const int* perm;
+  if (int rc = use_points(&g, &x, &perm, sorted, n)) return rc;
   return (int)launch_encode_bwd(g, v4, x, n, grad_feats, ld_g, grad_x, perm, (hipStream_t)stream);
 }
 
-int miso_encode_bwd(const miso_grid_t* grid, const float* x, int64_t n, const float* grad_feats,
-                    int64_t ld_g, float* grad_x, void* stream) {
-  return encode_bwd_impl(grid, x, n, grad_feats, ld_g, grad_x, nullptr, stream);
-}
-
-int miso_encode_bwd_sorted(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n,
-                           const float* grad_feats, int64_t ld_g, float* grad_x, void* stream) {
-  if (int rc = check_sorted(sorted, n)) return rc;
-  return encode_bwd_impl(grid, nullptr, n, grad_feats, ld_g, grad_x, sorted, stream);
-}
-
-static int encode_bwd2_impl(const miso_grid_t* grid, const miso_grid_t* gg_grid, const float* x, int64_t n,
-                            const float* grad_feats, int64_t ld_g, const float* gg_x, float* gg_out,
-                            int64_t ld_gg, float* g_x, const miso_sorted_t* sorted, void* stream) {
+int miso_encode_bwd2(const miso_grid_t* grid, const miso_grid_t* gg_grid, const float* x, const miso_sorted_t* sorted,
+                     int64_t n, const float* grad_feats, int64_t ld_g, const float* gg_x, float* gg_out,
+                     int64_t ld_gg, float* g_x, void* stream) {
   if (n < 0 || !set_if(n, grad_feats, gg_out)) return MISO_E_BADARG;
   GridK g; bool v4;
   if (int rc = convert_grid(grid, &g, true, &v4)) return rc;
@@ -336,24 +342,10 @@ static int encode_bwd2_impl(const miso_grid_t* grid, const miso_grid_t* gg_grid,
       g.lv[l].gg = b.data;
     }
   }
-  const int* perm = nullptr;
-  if (sorted) { x = sorted_points(&g, sorted); perm = sorted->perm; }
-  if (n > 0 && !x) return MISO_E_BADARG;
+  const int* perm;
+  if (int rc = use_points(&g, &x, &perm, sorted, n)) return rc;
   return (int)launch_encode_bwd2(g, v4, x, n, grad_feats, ld_g, gg_x, gg_out, ld_gg, g_x, perm,
                                  (hipStream_t)stream);
-}
-
-int miso_encode_bwd2(const miso_grid_t* grid, const miso_grid_t* gg_grid, const float* x, int64_t n,
-                     const float* grad_feats, int64_t ld_g, const float* gg_x, float* gg_out,
-                     int64_t ld_gg, float* g_x, void* stream) {
-  return encode_bwd2_impl(grid, gg_grid, x, n, grad_feats, ld_g, gg_x, gg_out, ld_gg, g_x, nullptr, stream);
-}
-
-int miso_encode_bwd2_sorted(const miso_grid_t* grid, const miso_grid_t* gg_grid, const miso_sorted_t* sorted,
-                            int64_t n, const float* grad_feats, int64_t ld_g, const float* gg_x, float* gg_out,
-                            int64_t ld_gg, float* g_x, void* stream) {
-  if (int rc = check_sorted(sorted, n)) return rc;
-  return encode_bwd2_impl(grid, gg_grid, nullptr, n, grad_feats, ld_g, gg_x, gg_out, ld_gg, g_x, sorted, stream);
 }
 
 int64_t miso_mlp_packed_floats(const miso_mlp_t* mlp) {
@@ -392,31 +384,53 @@ int miso_sdf_supported(const miso_grid_t* grid, const miso_mlp_t* mlp) {
   return fused_query(&f, grid, mlp, false) == MISO_OK ? 1 : 0;
 }
 
-static int sdf_fwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                        const float* x, int64_t n, float* sdf, uint32_t* relu_mask,
-                        const miso_sorted_t* sorted, void* stream, const LossInK* loss = nullptr) {
+// the forward of miso_sdf_fwd and, with `loss`, of miso_sdf_fwd_loss
+static int sdf_fwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
+                   const miso_sorted_t* sorted, int64_t n, float* sdf, uint32_t* relu_mask, void* stream,
+                   const LossInK* loss) {
   LossInK lin;
   memset(&lin, 0, sizeof(lin));
   if (loss) lin = *loss;
   if (n < 0 || (n > 0 && !sdf && !loss)) return MISO_E_BADARG;
   FusedCall f;
   if (int rc = fused_call(&f, grid, mlp, packed, true)) return rc;
-  const int* perm = nullptr;
-  if (sorted) { x = sorted_points(&f.g, sorted); perm = sorted->perm; }
-  if (n > 0 && !x) return MISO_E_BADARG;
+  const int* perm;
+  if (int rc = use_points(&f.g, &x, &perm, sorted, n)) return rc;
   return (int)launch_sdf_fwd(f.C, f.L, f.H, f.NH, f.g, packed, x, n, sdf, relu_mask, perm, lin, (hipStream_t)stream);
 }
 
-static int sdf_bwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                        const float* x, int64_t n, const float* grad_sdf, const uint32_t* relu_mask,
-                        float* grad_x, const miso_sorted_t* sorted, float* workspace, void* stream) {
+int miso_sdf_fwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
+                 const miso_sorted_t* sorted, int64_t n, float* sdf, uint32_t* relu_mask, void* stream) {
+  return sdf_fwd(grid, mlp, packed, x, sorted, n, sdf, relu_mask, stream, nullptr);
+}
+
+int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
+                      const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
+                      float trunc_dist, const float* loss_inputs, float* sdf, uint32_t* relu_mask, float* grad_sdf,
+                      float* loss_slots, const int32_t* n_live, void* stream) {
+  if (!mapping_loss_ok(loss_type) || !loss_slots || n < 0 || !set_if(n, loss_inputs, grad_sdf) || !aligned(16, loss_inputs))
+    return MISO_E_BADARG;
+  if (!sorted && n_live) return MISO_E_BADARG;      // a padded batch is a binned one
+  if (n == 0) {                                     // kept as found: of an empty batch only `sorted` is looked at
+    if (int rc = sorted ? check_sorted(sorted, n) : MISO_OK) return rc;
+    return (int)zero_loss_slots(loss_slots, (hipStream_t)stream);
+  }
+  const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, grad_sdf, loss_slots, n, n_live);
+  return sdf_fwd(grid, mlp, packed, x, sorted, n, sdf, relu_mask, stream, &lin);
+}
+
+int miso_sdf_bwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
+                 const miso_sorted_t* sorted, int64_t n, const float* grad_sdf, const uint32_t* relu_mask,
+                 float* grad_x, float* workspace, void* stream) {
   if (n < 0 || !set_if(n, grad_sdf, relu_mask)) return MISO_E_BADARG;
   FusedCall f;
   if (int rc = fused_call(&f, grid, mlp, packed, grad_x != nullptr)) return rc;
+  const bool gsdf_sorted = (grid->flags & MISO_F_GRAD_SDF_SORTED) != 0;
+  if (!sorted && (workspace || gsdf_sorted)) return MISO_E_BADARG;      // the binned form's
   const GridK& g = f.g;
   GridK gp = g;                                   // sample positions as the kernels read them
-  if (sorted) x = sorted_points(&gp, sorted);
-  if (n > 0 && !x) return MISO_E_BADARG;
+  const int* perm;
+  if (int rc = use_points(&gp, &x, &perm, sorted, n)) return rc;
   // owned levels leave their d-feat rows in the workspace (a pushed level's go the same way); the rest is scattered
   const GradPlan plan = plan_grad(g, grad_ask(GRAD_BWD, f.vec4, grid, sorted, n, g.F, workspace, false), pull_knobs());
   const bool want_grid = plan.want != 0;
@@ -427,24 +441,12 @@ static int sdf_bwd_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const fl
   if (e != hipSuccess) return (int)e;
   if (n == 0 && !plan.owned) return MISO_OK;
   if (n > 0) {
-    e = launch_sdf_bwd(f.C, f.L, f.H, f.NH, gp, packed, x, n, grad_sdf, relu_mask, grad_x, want_grid,
-                       sorted ? sorted->perm : nullptr, plan.owned ? workspace : nullptr, plan.owned,
-                       sorted && (grid->flags & MISO_F_GRAD_SDF_SORTED), st);
+    e = launch_sdf_bwd(f.C, f.L, f.H, f.NH, gp, packed, x, n, grad_sdf, relu_mask, grad_x, want_grid, perm,
+                       plan.owned ? workspace : nullptr, plan.owned, gsdf_sorted, st);
     if (e != hipSuccess) return (int)e;
   }
   if (!plan.owned) return MISO_OK;
   return (int)launch_grad_pull(g, plan, pull_batch(sorted, workspace, nullptr, nullptr), st);
-}
-
-int miso_sdf_fwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
-                 int64_t n, float* sdf, uint32_t* relu_mask, void* stream) {
-  return sdf_fwd_impl(grid, mlp, packed, x, n, sdf, relu_mask, nullptr, stream);
-}
-
-int miso_sdf_bwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
-                 int64_t n, const float* grad_sdf, const uint32_t* relu_mask, float* grad_x,
-                 void* stream) {
-  return sdf_bwd_impl(grid, mlp, packed, x, n, grad_sdf, relu_mask, grad_x, nullptr, nullptr, stream);
 }
 
 // The first backward with its d-feat rows handed out: what the SECOND backward (create_graph=True: eikonal / smoothness
@@ -453,7 +455,7 @@ int miso_sdf_bwd(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* pa
 int miso_sdf_bwd_rows(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
                       const float* grad_sdf, const uint32_t* relu_mask, float* grad_x, float* dfeat_rows, void* stream) {
   if (!grid || !mlp) return MISO_E_BADARG;
-  if (!dfeat_rows) return sdf_bwd_impl(grid, mlp, packed, x, n, grad_sdf, relu_mask, grad_x, nullptr, nullptr, stream);
+  if (!dfeat_rows) return miso_sdf_bwd(grid, mlp, packed, x, nullptr, n, grad_sdf, relu_mask, grad_x, nullptr, stream);
   if (n < 0 || !set_if(n, grad_sdf, relu_mask, x) || !aligned(16, dfeat_rows)) return MISO_E_BADARG;
   if (grid->flags & (MISO_F_GRAD_OVERWRITE | MISO_F_GRAD_SDF_SORTED | MISO_F_GRAD_ZEROED)) return MISO_E_BADARG;
   FusedCall f;
@@ -480,47 +482,6 @@ int miso_sort_points(const miso_grid_t* grid, const float* x, int64_t n, int32_t
   if (int rc = convert_grid(grid, &g, false, nullptr)) return rc;
   return (int)launch_sort(g, x, n, tiles_per_axis, workspace, x_sorted, xn_sorted, perm, tile_offsets,
                           (hipStream_t)stream);
-}
-
-int miso_sdf_fwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                        const miso_sorted_t* sorted, int64_t n, float* sdf, uint32_t* relu_mask,
-                        void* stream) {
-  if (int rc = check_sorted(sorted, n)) return rc;
-  return sdf_fwd_impl(grid, mlp, packed, nullptr, n, sdf, relu_mask, sorted, stream);
-}
-
-int miso_encode_fwd_sorted(const miso_grid_t* grid, const miso_sorted_t* sorted, int64_t n, float* feats,
-                           int64_t ld_out, void* stream) {
-  if (int rc = check_sorted(sorted, n)) return rc;
-  if (n < 0 || !set_if(n, feats)) return MISO_E_BADARG;
-  GridK g; bool v4;
-  if (int rc = convert_grid(grid, &g, true, &v4)) return rc;
-  if (ld_out < g.F) return MISO_E_BADARG;
-  const float* x = sorted_points(&g, sorted);
-  return (int)launch_encode_fwd(g, v4, x, n, feats, ld_out, sorted->perm, (hipStream_t)stream);
-}
-
-int miso_sdf_fwd_sorted_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                             const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf,
-                             float weight_fs, float trunc_dist, const float* loss_inputs, float* sdf,
-                             uint32_t* relu_mask, float* grad_sdf_sorted, float* loss_slots,
-                             const int32_t* n_live, void* stream) {
-  if (int rc = check_sorted(sorted, n)) return rc;
-  if (!mapping_loss_ok(loss_type) || !loss_slots || !set_if(n, loss_inputs, grad_sdf_sorted) || !aligned(16, loss_inputs))
-    return MISO_E_BADARG;
-  if (n == 0) return (int)zero_loss_slots(loss_slots, (hipStream_t)stream);
-  const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, grad_sdf_sorted, loss_slots, n, n_live);
-  return sdf_fwd_impl(grid, mlp, packed, nullptr, n, sdf, relu_mask, sorted, stream, &lin);
-}
-
-int miso_sdf_fwd_loss(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
-                      int loss_type, float weight_sdf, float weight_fs, float trunc_dist, const float* loss_inputs,
-                      float* sdf, uint32_t* relu_mask, float* grad_sdf, float* loss_slots, void* stream) {
-  if (!mapping_loss_ok(loss_type) || !loss_slots || n < 0 || !set_if(n, x, loss_inputs, grad_sdf) || !aligned(16, loss_inputs))
-    return MISO_E_BADARG;
-  if (n == 0) return (int)zero_loss_slots(loss_slots, (hipStream_t)stream);
-  const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, grad_sdf, loss_slots, n, nullptr);
-  return sdf_fwd_impl(grid, mlp, packed, x, n, sdf, relu_mask, nullptr, stream, &lin);
 }
 
 // The plan a binned backward or training step of n samples follows with every buffer in place: what the four queries
@@ -580,14 +541,6 @@ int64_t miso_sdf_bwd_workspace_floats(const miso_grid_t* grid, int64_t n) {
   return n * g.F;
 }
 
-int miso_sdf_bwd_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                        const miso_sorted_t* sorted, int64_t n, const float* grad_sdf,
-                        const uint32_t* relu_mask, float* grad_x, float* workspace, void* stream) {
-  if (int rc = check_sorted(sorted, n)) return rc;
-  return sdf_bwd_impl(grid, mlp, packed, nullptr, n, grad_sdf, relu_mask, grad_x, sorted, workspace,
-                      stream);
-}
-
 int64_t miso_sdf_wgrad_workspace_floats(const miso_grid_t* grid, const miso_mlp_t* mlp, int64_t n) {
   FusedCall f;
   if (n < 0 || fused_query(&f, grid, mlp, false)) return 0;
@@ -595,14 +548,12 @@ int64_t miso_sdf_wgrad_workspace_floats(const miso_grid_t* grid, const miso_mlp_
 }
 
 // The decoder's weight and bias gradients (decoder_wgrad.hip): the sign bits and the point order are those of the forward
-// that wrote relu_mask (miso_sdf_fwd: caller order, sorted == NULL; miso_sdf_fwd_sorted: binned order).
+// that wrote relu_mask (miso_sdf_fwd over the same x / sorted).
 int miso_sdf_wgrad(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
                    const float* grad_sdf, const uint32_t* relu_mask, const miso_sorted_t* sorted, uint32_t flags,
                    const miso_mlp_grad_t* grads, float* workspace, int64_t workspace_floats, void* stream) {
   if (!grid || !mlp || !grads || n < 0 || !set_if(n, grad_sdf, relu_mask)) return MISO_E_BADARG;
   if ((flags & ~MISO_F_GRAD_SDF_SORTED) || ((flags & MISO_F_GRAD_SDF_SORTED) && !sorted)) return MISO_E_BADARG;
-  if (sorted)
-    if (int rc = check_sorted(sorted, n)) return rc;
   FusedCall f;
   if (int rc = fused_call(&f, grid, mlp, packed, n > 0)) return rc;
   WgradOutK out;
@@ -614,9 +565,9 @@ int miso_sdf_wgrad(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* 
   }
   const int64_t need = sdf_wgrad_workspace_floats(f.C, f.L, f.H, f.NH, n);
   if (need > 0 && (!workspace || workspace_floats < need || !aligned(16, workspace))) return MISO_E_BADARG;
-  if (sorted) x = sorted_points(&f.g, sorted);
-  if (n > 0 && !x) return MISO_E_BADARG;
-  return (int)launch_sdf_wgrad(f.C, f.L, f.H, f.NH, f.g, packed, x, n, grad_sdf, relu_mask, sorted ? sorted->perm : nullptr,
+  const int* perm;
+  if (int rc = use_points(&f.g, &x, &perm, sorted, n)) return rc;
+  return (int)launch_sdf_wgrad(f.C, f.L, f.H, f.NH, f.g, packed, x, n, grad_sdf, relu_mask, perm,
                                (flags & MISO_F_GRAD_SDF_SORTED) != 0, out, workspace, (hipStream_t)stream);
 }
 
@@ -624,17 +575,21 @@ int miso_sdf_wgrad(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* 
 // (sdf_train_kernel).  sorted != nullptr: a binned batch -- the levels the pull / push can form get their gradient from
 // the d-feat rows left in `workspace`, the others (bricks beyond the pull's reach) are scattered with float atomics from
 // the kernel itself.  sorted == nullptr: an unbinned batch (x in the caller's order), every level scattered.
-static int sdf_train_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
-                          const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
-                          float trunc_dist, const float* loss_inputs, float* sdf, float* loss_slots,
-                          const int32_t* n_live, float* workspace, void* stream) {
+int miso_sdf_train(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x,
+                   const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
+                   float trunc_dist, const float* loss_inputs, float* sdf, float* loss_slots, const int32_t* n_live,
+                   float* workspace, void* stream) {
   if (!mapping_loss_ok(loss_type) || !loss_slots || n < 0 || !set_if(n, loss_inputs)) return MISO_E_BADARG;
   if (!aligned(16, loss_inputs, workspace)) return MISO_E_BADARG;
-  if (sorted && !sorted->xn_sorted && n > 0) return MISO_E_BADARG;
-  if (!sorted && n > 0 && !x) return MISO_E_BADARG;
+  // the binned step leaves d-feat rows in the workspace and reads the float4 points; the other form has neither
+  if (sorted ? n > 0 && (!workspace || !sorted->xn_sorted) : n_live || workspace) return MISO_E_BADARG;
   FusedCall f;
   if (int rc = fused_call(&f, grid, mlp, packed, true)) return rc;
   const GridK& g = f.g;
+  GridK gp = g;                                   // sample positions as the kernel reads them
+  const int* perm;
+  if (int rc = use_points(&gp, &x, &perm, sorted, n, true)) return rc;
+  if (sorted && !perm) gp.flags |= MISO_F_INDEX_IN_XN;
   // owned levels are formed from the d-feat rows (pull or push); the rest is scattered from the kernel
   const GradPlan plan = plan_grad(g, grad_ask(GRAD_TRAIN, f.vec4, grid, sorted, n, g.F, workspace, false), pull_knobs());
   if (!plan.want || plan.refuse) return MISO_E_UNSUPPORTED;
@@ -646,32 +601,12 @@ static int sdf_train_impl(const miso_grid_t* grid, const miso_mlp_t* mlp, const 
     if (e != hipSuccess) return (int)e;
   } else {
     const LossInK lin = loss_in(loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs, nullptr, loss_slots, n, n_live);
-    GridK gp = g;
-    if (sorted) x = sorted_points(&gp, sorted);
-    if (sorted && !sorted->perm) gp.flags |= MISO_F_INDEX_IN_XN;
-    e = launch_sdf_train(f.C, f.L, f.H, f.NH, gp, packed, x, n, sdf, sorted ? sorted->perm : nullptr, lin,
-                         plan.owned ? workspace : nullptr, plan.owned, plan.scatter != 0, st);
+    e = launch_sdf_train(f.C, f.L, f.H, f.NH, gp, packed, x, n, sdf, perm, lin, plan.owned ? workspace : nullptr,
+                         plan.owned, plan.scatter != 0, st);
     if (e != hipSuccess) return (int)e;
   }
   if (!plan.owned) return MISO_OK;
   return (int)launch_grad_pull(g, plan, pull_batch(sorted, workspace, nullptr, nullptr), st);
-}
-
-int miso_sdf_train_sorted(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed,
-                          const miso_sorted_t* sorted, int64_t n, int loss_type, float weight_sdf, float weight_fs,
-                          float trunc_dist, const float* loss_inputs, float* sdf, float* loss_slots,
-                          const int32_t* n_live, float* workspace, void* stream) {
-  if (int rc = check_sorted(sorted, n, true)) return rc;
-  if (n > 0 && !workspace) return MISO_E_BADARG;
-  return sdf_train_impl(grid, mlp, packed, nullptr, sorted, n, loss_type, weight_sdf, weight_fs, trunc_dist,
-                        loss_inputs, sdf, loss_slots, n_live, workspace, stream);
-}
-
-int miso_sdf_train(const miso_grid_t* grid, const miso_mlp_t* mlp, const float* packed, const float* x, int64_t n,
-                   int loss_type, float weight_sdf, float weight_fs, float trunc_dist, const float* loss_inputs,
-                   float* sdf, float* loss_slots, void* stream) {
-  return sdf_train_impl(grid, mlp, packed, x, nullptr, n, loss_type, weight_sdf, weight_fs, trunc_dist, loss_inputs,
-                        sdf, loss_slots, nullptr, nullptr, stream);
 }
 
 int miso_pair_latent(const miso_grid_t* dst_grid, const float* pose, const float* coords_src,
@@ -880,9 +815,9 @@ int miso_track_adam_step(const miso_grid_t* grid, const miso_mlp_t* mlp, const f
   if (int rc = (int)launch_lm_track_head(k.s, st)) return rc;
   lm_track_use_clean(&k.s);
   if (a->n > 0) {
-    if (int rc = sdf_fwd_impl(grid, mlp, packed, a->coords_world, a->n, a->sdf, a->relu_mask, nullptr, stream)) return rc;
+    if (int rc = miso_sdf_fwd(grid, mlp, packed, a->coords_world, nullptr, a->n, a->sdf, a->relu_mask, stream)) return rc;
     if (int rc = (int)launch_track_loss(k, st)) return rc;
-    if (int rc = sdf_bwd_impl(grid, mlp, packed, a->coords_world, a->n, t->grad_pred, a->relu_mask, a->grad, nullptr, nullptr, stream))
+    if (int rc = miso_sdf_bwd(grid, mlp, packed, a->coords_world, nullptr, a->n, t->grad_pred, a->relu_mask, a->grad, nullptr, stream))
       return rc;
   }
   return (int)launch_track_tail(k, st);
@@ -900,8 +835,8 @@ int miso_lm_track_step(const miso_grid_t* grid, const miso_mlp_t* mlp, const flo
   if (int rc = (int)launch_lm_track_head(k, st)) return rc;
   lm_track_use_clean(&k);
   if (a->n > 0) {
-    if (int rc = sdf_fwd_impl(grid, mlp, packed, a->coords_world, a->n, a->sdf, a->relu_mask, nullptr, stream)) return rc;
-    if (int rc = sdf_bwd_impl(grid, mlp, packed, a->coords_world, a->n, a->ones, a->relu_mask, a->grad, nullptr, nullptr, stream)) return rc;
+    if (int rc = miso_sdf_fwd(grid, mlp, packed, a->coords_world, nullptr, a->n, a->sdf, a->relu_mask, stream)) return rc;
+    if (int rc = miso_sdf_bwd(grid, mlp, packed, a->coords_world, nullptr, a->n, a->ones, a->relu_mask, a->grad, nullptr, stream)) return rc;
   }
   return (int)launch_lm_track_tail(k, a->grad, a->sdf, a->loss_type, a->gm_scale, st);
 }

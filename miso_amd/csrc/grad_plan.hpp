@@ -6,7 +6,7 @@
 
 namespace miso {
 
-enum GradCaller { GRAD_BWD, GRAD_TRAIN, GRAD_PULL };      // miso_sdf_bwd_sorted | miso_sdf_train* | miso_grad_pull(_dx)
+enum GradCaller { GRAD_BWD, GRAD_TRAIN, GRAD_PULL };      // miso_sdf_bwd | miso_sdf_train | miso_grad_pull(_dx)
 enum PullForm {
   PULL_NONE,       // nothing left to pull (no owned level, or all of them pushed)
   PULL_MC,         // grad_pull_mc_kernel

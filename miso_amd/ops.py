@@ -95,6 +95,14 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _points(x: Optional[torch.Tensor], sorted_batch: Optional["SortedBatch"]):
+    """The two point arguments of an entry (miso_hip.h, at miso_sorted_t): the binned batch where there is one -- the
+    library then ignores x -- else the points in the caller's order."""
+    if sorted_batch is not None:
+        return None, C.byref(sorted_batch.struct)
+    return _ptr(x), None
+
+
 def _grid_header(meta: GridMeta) -> _lib.Grid:
     """A Grid with the bound and the flags of ``meta`` and no level yet (the process-wide _EXACT_F32 is _fill_grid's)."""
     g = _lib.Grid()
@@ -157,12 +165,8 @@ def encode_fwd_raw(x, features, meta: GridMeta, sorted_batch: Optional["SortedBa
     out = torch.empty((n, _feature_dim(features)), device=x.device, dtype=torch.float32)
     g = _fill_grid(features, meta)
     ld = out.stride(0) if n else out.shape[1]
-    if sorted_batch is not None:
-        _lib.check(_lib.load().miso_encode_fwd_sorted(C.byref(g), C.byref(sorted_batch.struct), n, _ptr(out), ld,
-                                                      _stream(x)), "miso_encode_fwd_sorted")
-    else:
-        _lib.check(_lib.load().miso_encode_fwd(C.byref(g), _ptr(x), n, _ptr(out), ld, _stream(x)),
-                   "miso_encode_fwd")
+    _lib.check(_lib.load().miso_encode_fwd(C.byref(g), *_points(x, sorted_batch), n, _ptr(out), ld, _stream(x)),
+               "miso_encode_fwd")
     return out
 
 
@@ -216,12 +220,9 @@ def encode_bwd_raw(x, features, meta: GridMeta, gout, need_x: bool, need_f: Sequ
         gx = torch.empty((n, 3), device=x.device, dtype=torch.float32) if need_x else None
         g = _fill_grid(features, meta, [gr if r else None for gr, r in zip(grads, rest)])
         ld = gout.stride(0) if n else _feature_dim(features)
-        if sorted_batch is not None:      # the batch is binned already: gather in tile order
-            _lib.check(lib.miso_encode_bwd_sorted(C.byref(g), C.byref(sorted_batch.struct), n, _ptr(gout), ld, _ptr(gx),
-                                                  _stream(x)), "miso_encode_bwd_sorted")
-        else:
-            _lib.check(lib.miso_encode_bwd(C.byref(g), _ptr(x), n, _ptr(gout), ld, _ptr(gx), _stream(x)),
-                       "miso_encode_bwd")
+        # (a batch that is binned already is gathered in tile order)
+        _lib.check(lib.miso_encode_bwd(C.byref(g), *_points(x, sorted_batch), n, _ptr(gout), ld, _ptr(gx), _stream(x)),
+                   "miso_encode_bwd")
     return gx, grads
 
 
@@ -262,15 +263,10 @@ def encode_bwd2_raw(x, features, meta: GridMeta, gout, ggx, ggf, need_x: bool, n
         ggx = ggx.contiguous()
     gg_out = torch.empty((n, F), device=x.device, dtype=torch.float32)
     g_x = torch.empty((n, 3), device=x.device, dtype=torch.float32) if need_x else None
-    sb = sorted_batch      # a binned copy exists (the forward's, or the pull's above): gather in tile order as well
-    if sb is not None:
-        _lib.check(_lib.load().miso_encode_bwd2_sorted(
-            C.byref(g), C.byref(gg) if gg is not None else None, C.byref(sb.struct), n, _ptr(gout),
-            gout.stride(0) if n else F, _ptr(ggx), _ptr(gg_out), F, _ptr(g_x), _stream(x)), "miso_encode_bwd2_sorted")
-    else:
-        _lib.check(_lib.load().miso_encode_bwd2(
-            C.byref(g), C.byref(gg) if gg is not None else None, _ptr(x), n, _ptr(gout),
-            gout.stride(0) if n else F, _ptr(ggx), _ptr(gg_out), F, _ptr(g_x), _stream(x)), "miso_encode_bwd2")
+    # (where a binned copy exists -- the forward's, or the pull's above -- the gathers run in tile order as well)
+    _lib.check(_lib.load().miso_encode_bwd2(
+        C.byref(g), C.byref(gg) if gg is not None else None, *_points(x, sorted_batch), n, _ptr(gout),
+        gout.stride(0) if n else F, _ptr(ggx), _ptr(gg_out), F, _ptr(g_x), _stream(x)), "miso_encode_bwd2")
     return gg_out, g_x, grads
 
 
@@ -547,13 +543,8 @@ def sdf_fwd_raw(x, features, meta, pack: DecoderPack, want_mask: bool, out=None,
     elif mask is None:
         mask = sdf_mask_buffer(pack, n, x.device)
     g = _fill_grid(features, meta)
-    if sorted_batch is not None:
-        _lib.check(_lib.load().miso_sdf_fwd_sorted(C.byref(g), C.byref(m), _ptr(packed),
-                                                   C.byref(sorted_batch.struct), n, _ptr(sdf), _ptr(mask),
-                                                   _stream(x)), "miso_sdf_fwd_sorted")
-    else:
-        _lib.check(_lib.load().miso_sdf_fwd(C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _ptr(sdf),
-                                            _ptr(mask), _stream(x)), "miso_sdf_fwd")
+    _lib.check(_lib.load().miso_sdf_fwd(C.byref(g), C.byref(m), _ptr(packed), *_points(x, sorted_batch), n, _ptr(sdf),
+                                        _ptr(mask), _stream(x)), "miso_sdf_fwd")
     return sdf, mask
 
 
@@ -583,14 +574,11 @@ def sdf_bwd_raw(x, features, meta, pack: DecoderPack, gsdf, mask, need_x, need_f
     if gsdf_sorted:
         assert sorted_batch is not None
         g.flags |= _lib.F_GRAD_SDF_SORTED
-    if sorted_batch is not None:
-        ws = sorted_batch.bwd_workspace(n * _feature_dim(features)) if any(gr is not None for gr in grads) else None
-        _lib.check(_lib.load().miso_sdf_bwd_sorted(C.byref(g), C.byref(m), _ptr(packed),
-                                                   C.byref(sorted_batch.struct), n, _ptr(gsdf), _ptr(mask),
-                                                   _ptr(gx), _ptr(ws), _stream(x)), "miso_sdf_bwd_sorted")
-    else:
-        _lib.check(_lib.load().miso_sdf_bwd(C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _ptr(gsdf),
-                                            _ptr(mask), _ptr(gx), _stream(x)), "miso_sdf_bwd")
+    ws = None      # the binned form's: the d-feat rows of the levels the pull forms
+    if sorted_batch is not None and any(gr is not None for gr in grads):
+        ws = sorted_batch.bwd_workspace(n * _feature_dim(features))
+    _lib.check(_lib.load().miso_sdf_bwd(C.byref(g), C.byref(m), _ptr(packed), *_points(x, sorted_batch), n, _ptr(gsdf),
+                                        _ptr(mask), _ptr(gx), _ptr(ws), _stream(x)), "miso_sdf_bwd")
     return gx, grads
 
 
@@ -670,25 +658,25 @@ def _check_loss_args(n: int, loss_inputs, loss_slots, n_live=None):
     assert n_live is None or (n_live.is_cuda and n_live.dtype == torch.int32 and n_live.numel() == 1)
 
 
-def sdf_fwd_loss_raw(features, meta, pack: DecoderPack, sorted_batch: SortedBatch, loss_inputs, mask, gsdf_sorted,
-                     loss_slots, loss_type="L1", weight_sdf=1.0, weight_fs=0.0, trunc_dist=0.0, sdf_out=None,
-                     n_live=None):
-    """Binned forward with the mapping loss folded in (miso_sdf_fwd_sorted_loss).  loss_inputs (N,4):
+def sdf_fwd_loss_raw(features, meta, pack: DecoderPack, sorted_batch: Optional[SortedBatch], loss_inputs, mask,
+                     gsdf_sorted, loss_slots, loss_type="L1", weight_sdf=1.0, weight_fs=0.0, trunc_dist=0.0, sdf_out=None,
+                     n_live=None, *, x=None):
+    """Binned forward with the mapping loss folded in (miso_sdf_fwd_loss over a binned batch).  loss_inputs (N,4):
     {target, valid, sign, weight} per point, caller order.  Writes d loss / d sdf in binned order to
     ``gsdf_sorted`` (feed it to sdf_bwd_raw(..., gsdf_sorted=True)) and the per-workgroup loss sums to
     ``loss_slots`` ((LOSS_SLOTS,2) floats, fully overwritten; the loss is loss_slots.sum(0)).
     sdf_out (N,1), caller order, is optional.  n_live: one int32 on the device = live rows of a padded batch
-    (the means divide by it instead of N)."""
-    _require_hip(loss_inputs, gsdf_sorted, loss_slots, *features)
+    (the means divide by it instead of N).  x with sorted_batch None: sdf_fwd_loss_unsorted_raw's form of the call."""
+    _require_hip(x, loss_inputs, gsdf_sorted, loss_slots, *features)
     m, packed = pack.require()
-    n = sorted_batch.n
+    n = x.shape[0] if sorted_batch is None else sorted_batch.n
     _check_loss_args(n, loss_inputs, loss_slots, n_live)
-    assert gsdf_sorted.is_contiguous() and gsdf_sorted.numel() == n
+    assert (x is None or x.is_contiguous()) and gsdf_sorted.is_contiguous() and gsdf_sorted.numel() == n
     g = _fill_grid(features, meta)
-    _lib.check(_lib.load().miso_sdf_fwd_sorted_loss(
-        C.byref(g), C.byref(m), _ptr(packed), C.byref(sorted_batch.struct), n, _LOSS_TYPES[loss_type],
-        float(weight_sdf), float(weight_fs), float(trunc_dist), _ptr(loss_inputs), _ptr(sdf_out), _ptr(mask),
-        _ptr(gsdf_sorted), _ptr(loss_slots), _ptr(n_live), _stream(gsdf_sorted)), "miso_sdf_fwd_sorted_loss")
+    _lib.check(_lib.load().miso_sdf_fwd_loss(
+        C.byref(g), C.byref(m), _ptr(packed), *_points(x, sorted_batch), n, _LOSS_TYPES[loss_type], float(weight_sdf),
+        float(weight_fs), float(trunc_dist), _ptr(loss_inputs), _ptr(sdf_out), _ptr(mask), _ptr(gsdf_sorted),
+        _ptr(loss_slots), _ptr(n_live), _stream(gsdf_sorted)), "miso_sdf_fwd_loss")
 
 
 def sdf_train_supported(features, meta, grads, pack: Optional["DecoderPack"] = None) -> bool:
@@ -720,57 +708,44 @@ def sdf_train_scattered_levels(features, meta, grads, tiles=None) -> int:
     return want & ~pulled
 
 
-def sdf_train_raw(features, meta, pack: DecoderPack, sorted_batch: SortedBatch, loss_inputs, loss_slots, grads,
-                  loss_type="L1", weight_sdf=1.0, weight_fs=0.0, trunc_dist=0.0, sdf_out=None, n_live=None,
-                  touched=None, zeroed: bool = False):
-    """One binned training step of a frozen-decoder submap in one library call (miso_sdf_train_sorted): forward +
-    mapping loss + decoder backward as ONE launch -- which also scatters the levels the pull cannot form, with float
-    atomics -- then the pull / push of the other levels' gradient (overwrite semantics: ``grads`` need no zero-fill).
-    Same results as sdf_fwd_loss_raw + sdf_bwd_raw(gsdf_sorted=True, overwrite=True)."""
-    _require_hip(loss_inputs, loss_slots, *features)
+def sdf_train_raw(features, meta, pack: DecoderPack, sorted_batch: Optional[SortedBatch], loss_inputs, loss_slots,
+                  grads, loss_type="L1", weight_sdf=1.0, weight_fs=0.0, trunc_dist=0.0, sdf_out=None, n_live=None,
+                  touched=None, zeroed: bool = False, *, x=None):
+    """One binned training step of a frozen-decoder submap in one library call (miso_sdf_train over a binned batch):
+    forward + mapping loss + decoder backward as ONE launch -- which also scatters the levels the pull cannot form, with
+    float atomics -- then the pull / push of the other levels' gradient (overwrite semantics: ``grads`` need no
+    zero-fill).  Same results as sdf_fwd_loss_raw + sdf_bwd_raw(gsdf_sorted=True, overwrite=True).
+    x with sorted_batch None: sdf_train_unsorted_raw's form of the call."""
+    _require_hip(x, loss_inputs, loss_slots, *features)
     m, packed = pack.require()
-    n = sorted_batch.n
+    n = x.shape[0] if sorted_batch is None else sorted_batch.n
+    assert x is None or x.is_contiguous()
     _check_loss_args(n, loss_inputs, loss_slots, n_live)
     g = _fill_grid(features, meta, grads, touched=touched)
-    g.flags |= _lib.F_GRAD_OVERWRITE
-    if zeroed:
-        g.flags |= _lib.F_GRAD_ZEROED
-    ws = sorted_batch.bwd_workspace(n * _feature_dim(features))
-    _lib.check(_lib.load().miso_sdf_train_sorted(
-        C.byref(g), C.byref(m), _ptr(packed), C.byref(sorted_batch.struct), n, _LOSS_TYPES[loss_type], float(weight_sdf),
+    ws = None
+    if sorted_batch is not None:      # the binned form's: overwrite semantics, d-feat rows for the pull
+        g.flags |= _lib.F_GRAD_OVERWRITE | (_lib.F_GRAD_ZEROED if zeroed else 0)
+        ws = sorted_batch.bwd_workspace(n * _feature_dim(features))
+    _lib.check(_lib.load().miso_sdf_train(
+        C.byref(g), C.byref(m), _ptr(packed), *_points(x, sorted_batch), n, _LOSS_TYPES[loss_type], float(weight_sdf),
         float(weight_fs), float(trunc_dist), _ptr(loss_inputs), _ptr(sdf_out), _ptr(loss_slots), _ptr(n_live), _ptr(ws),
-        _stream(loss_inputs)), "miso_sdf_train_sorted")
+        _stream(loss_inputs)), "miso_sdf_train")
 
 
 def sdf_train_unsorted_raw(x, features, meta, pack: DecoderPack, loss_inputs, loss_slots, grads, loss_type="L1",
                            weight_sdf=1.0, weight_fs=0.0, trunc_dist=0.0, sdf_out=None, touched=None):
-    """One training step of a frozen-decoder submap on an UNBINNED (small) batch in one launch (miso_sdf_train):
+    """One training step of a frozen-decoder submap on an UNBINNED (small) batch in one launch (miso_sdf_train over x):
     forward + mapping loss + decoder backward + the atomic scatter of every level's gradient, ADDED to ``grads``.
     Same results as sdf_fwd_loss_unsorted_raw + sdf_bwd_raw up to the order of the float atomics."""
-    _require_hip(x, loss_inputs, loss_slots, *features)
-    m, packed = pack.require()
-    n = x.shape[0]
-    assert x.is_contiguous()
-    _check_loss_args(n, loss_inputs, loss_slots)
-    g = _fill_grid(features, meta, grads, touched=touched)
-    _lib.check(_lib.load().miso_sdf_train(
-        C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _LOSS_TYPES[loss_type], float(weight_sdf), float(weight_fs),
-        float(trunc_dist), _ptr(loss_inputs), _ptr(sdf_out), _ptr(loss_slots), _stream(x)), "miso_sdf_train")
+    sdf_train_raw(features, meta, pack, None, loss_inputs, loss_slots, grads, loss_type=loss_type, weight_sdf=weight_sdf,
+                  weight_fs=weight_fs, trunc_dist=trunc_dist, sdf_out=sdf_out, touched=touched, x=x)
 
 
 def sdf_fwd_loss_unsorted_raw(x, features, meta, pack: DecoderPack, loss_inputs, mask, gsdf, loss_slots, loss_type="L1",
                               weight_sdf=1.0, weight_fs=0.0, trunc_dist=0.0, sdf_out=None):
-    """sdf_fwd_loss_raw for an unbinned (small) batch: everything in the caller's order (miso_sdf_fwd_loss)."""
-    _require_hip(x, loss_inputs, gsdf, loss_slots, *features)
-    m, packed = pack.require()
-    n = x.shape[0]
-    _check_loss_args(n, loss_inputs, loss_slots)
-    assert x.is_contiguous() and gsdf.is_contiguous() and gsdf.numel() == n
-    g = _fill_grid(features, meta)
-    _lib.check(_lib.load().miso_sdf_fwd_loss(
-        C.byref(g), C.byref(m), _ptr(packed), _ptr(x), n, _LOSS_TYPES[loss_type], float(weight_sdf), float(weight_fs),
-        float(trunc_dist), _ptr(loss_inputs), _ptr(sdf_out), _ptr(mask), _ptr(gsdf), _ptr(loss_slots), _stream(x)),
-        "miso_sdf_fwd_loss")
+    """sdf_fwd_loss_raw for an unbinned (small) batch: everything in the caller's order (miso_sdf_fwd_loss over x)."""
+    sdf_fwd_loss_raw(features, meta, pack, None, loss_inputs, mask, gsdf, loss_slots, loss_type=loss_type,
+                     weight_sdf=weight_sdf, weight_fs=weight_fs, trunc_dist=trunc_dist, sdf_out=sdf_out, x=x)
 
 
 def grad_pull_raw(features, meta, sorted_batch: SortedBatch, dfeat, grads, overwrite: bool = True,

@@ -333,22 +333,24 @@ def build_recipes():
     packed = P(1 << 16)
     PK = null("packed") + off(4, "packed")
 
-    # ---- encode
-    R("miso_encode_fwd", null("grid", "x", "feats") + val("n", -1) + val("ld_out", F - 1) + grid_faults("grid", True),
-      grid=g, x=P(), n=N, feats=P(), ld_out=F, stream=None)
+    # ---- encode (every call that reads points has two recipes: "/x" the caller's order, "/sorted" a binned batch)
+    enc_fwd = null("grid", "feats") + val("n", -1) + val("ld_out", F - 1) + grid_faults("grid", True)
+    R("miso_encode_fwd", enc_fwd + null("x"), variant="x", grid=g, x=P(), sorted=None, n=N, feats=P(), ld_out=F,
+      stream=None)
+    R("miso_encode_fwd", enc_fwd + sorted_faults("sorted"), variant="sorted", grid=g, x=None, sorted=s, n=N, feats=P(),
+      ld_out=F, stream=None)
     enc_bwd = null("grid", "grad_feats") + val("n", -1) + val("ld_g", F - 1) + grid_faults("grid", True)
-    R("miso_encode_bwd", enc_bwd + null("x"), grid=g, x=P(), n=N, grad_feats=P(), ld_g=F, grad_x=P(), stream=None)
-    R("miso_encode_bwd_sorted", enc_bwd + sorted_faults("sorted"),
-      grid=g, sorted=s, n=N, grad_feats=P(), ld_g=F, grad_x=P(), stream=None)
+    R("miso_encode_bwd", enc_bwd + null("x"), variant="x", grid=g, x=P(), sorted=None, n=N, grad_feats=P(), ld_g=F,
+      grad_x=P(), stream=None)
+    R("miso_encode_bwd", enc_bwd + sorted_faults("sorted"), variant="sorted", grid=g, x=None, sorted=s, n=N,
+      grad_feats=P(), ld_g=F, grad_x=P(), stream=None)
     bwd2 = (null("grid", "grad_feats", "gg_out") + val("n", -1) + val("ld_g", F - 1) + val("ld_gg", F - 1) +
             grid_faults("grid", True) + fld("gg_grid", "n_levels", 1) + fld("gg_grid", "level[1].C", 8) +
             fld("gg_grid", "level[0].sZ", 40))
-    R("miso_encode_bwd2", bwd2 + null("x"), grid=g, gg_grid=grid(), x=P(), n=N, grad_feats=P(), ld_g=F, gg_x=P(),
-      gg_out=P(), ld_gg=F, g_x=P(), stream=None)
-    R("miso_encode_bwd2_sorted", bwd2 + sorted_faults("sorted"), grid=g, gg_grid=grid(), sorted=s, n=N, grad_feats=P(),
+    R("miso_encode_bwd2", bwd2 + null("x"), variant="x", grid=g, gg_grid=grid(), x=P(), sorted=None, n=N, grad_feats=P(),
       ld_g=F, gg_x=P(), gg_out=P(), ld_gg=F, g_x=P(), stream=None)
-    R("miso_encode_fwd_sorted", null("grid", "feats") + val("n", -1) + val("ld_out", F - 1) + grid_faults("grid", True) +
-      sorted_faults("sorted"), grid=g, sorted=s, n=N, feats=P(), ld_out=F, stream=None)
+    R("miso_encode_bwd2", bwd2 + sorted_faults("sorted"), variant="sorted", grid=g, gg_grid=grid(), x=None, sorted=s, n=N,
+      grad_feats=P(), ld_g=F, gg_x=P(), gg_out=P(), ld_gg=F, g_x=P(), stream=None)
 
     # ---- decoder queries and packing
     mq = (null("mlp") + fld("mlp", "n_linear", 1, 5) + fld("mlp", "out_dim", 2) + fld("mlp", "in_dim", 0, 33) +
@@ -365,40 +367,43 @@ def build_recipes():
 
     # ---- fused forward / backward
     fused = null("grid") + grid_faults("grid", True) + fused_faults("grid", "mlp") + PK + val("n", -1)
-    R("miso_sdf_fwd", fused + null("x", "sdf"), grid=g, mlp=m, packed=packed, x=P(), n=N, sdf=P(), relu_mask=P(4096),
-      stream=None)
-    R("miso_sdf_fwd_sorted", fused + null("sdf") + sorted_faults("sorted"), grid=g, mlp=m, packed=packed, sorted=s, n=N,
+    # (the "/x" recipes also hand over, one at a time, what belongs to the binned form: n_live, workspace, GRAD_SDF_SORTED)
+    R("miso_sdf_fwd", fused + null("x", "sdf"), variant="x", grid=g, mlp=m, packed=packed, x=P(), sorted=None, n=N,
       sdf=P(), relu_mask=P(4096), stream=None)
+    R("miso_sdf_fwd", fused + null("sdf") + sorted_faults("sorted"), variant="sorted", grid=g, mlp=m, packed=packed,
+      x=None, sorted=s, n=N, sdf=P(), relu_mask=P(4096), stream=None)
     bwd = fused + null("grad_sdf", "relu_mask")
-    R("miso_sdf_bwd", bwd + null("x"), grid=g, mlp=m, packed=packed, x=P(), n=N, grad_sdf=P(), relu_mask=P(4096),
-      grad_x=P(), stream=None)
-    R("miso_sdf_bwd_sorted", bwd + sorted_faults("sorted"), grid=gg, mlp=m, packed=packed, sorted=s, n=N, grad_sdf=P(),
-      relu_mask=P(4096), grad_x=P(), workspace=P(), stream=None)
-    R("miso_sdf_bwd_sorted", val("n", ROWS_2GB), variant="tiles_xyz", grid=gg, mlp=m, packed=packed,
+    R("miso_sdf_bwd", bwd + null("x") + val("workspace", P()) + fld("grid", "flags", 16), variant="x", grid=g, mlp=m,
+      packed=packed, x=P(), sorted=None, n=N, grad_sdf=P(), relu_mask=P(4096), grad_x=P(), workspace=None, stream=None)
+    R("miso_sdf_bwd", bwd + sorted_faults("sorted"), variant="sorted", grid=gg, mlp=m, packed=packed, x=None, sorted=s,
+      n=N, grad_sdf=P(), relu_mask=P(4096), grad_x=P(), workspace=P(), stream=None)
+    R("miso_sdf_bwd", val("n", ROWS_2GB), variant="tiles_xyz", grid=gg, mlp=m, packed=packed, x=None,
       sorted=binned(TILES_XYZ), n=N, grad_sdf=P(), relu_mask=P(4096), grad_x=P(), workspace=P(), stream=None)
     R("miso_sdf_bwd_rows", bwd + null("x") + off(4, "dfeat_rows") + fld("grid", "flags", 8, 16, 32),
       grid=g, mlp=m, packed=packed, x=P(), n=N, grad_sdf=P(), relu_mask=P(4096), grad_x=P(), dfeat_rows=P(), stream=None)
-    R("miso_sdf_bwd_rows", bwd + null("x"), variant="no_rows", grid=g, mlp=m, packed=packed, x=P(), n=N, grad_sdf=P(),
+    R("miso_sdf_bwd_rows", bwd + null("x") + fld("grid", "flags", 16), variant="no_rows", grid=g, mlp=m, packed=packed, x=P(), n=N, grad_sdf=P(),
       relu_mask=P(4096), grad_x=P(), dfeat_rows=None, stream=None)
     loss_in = LOSS_FAULTS + null("loss_slots", "loss_inputs") + off(4, "loss_inputs")
-    R("miso_sdf_fwd_sorted_loss", fused + sorted_faults("sorted") + loss_in + null("grad_sdf_sorted"), grid=g, mlp=m,
-      packed=packed, sorted=s, n=N, **LOSS, loss_inputs=P(), sdf=P(), relu_mask=P(4096), grad_sdf_sorted=P(),
+    R("miso_sdf_fwd_loss", fused + loss_in + null("x", "grad_sdf") + val("n_live", P()), variant="x", grid=g, mlp=m,
+      packed=packed, x=P(), sorted=None, n=N, **LOSS, loss_inputs=P(), sdf=P(), relu_mask=P(4096), grad_sdf=P(),
       loss_slots=P(4096), n_live=None, stream=None)
-    R("miso_sdf_fwd_loss", fused + loss_in + null("x", "grad_sdf"), grid=g, mlp=m, packed=packed, x=P(), n=N, **LOSS,
-      loss_inputs=P(), sdf=P(), relu_mask=P(4096), grad_sdf=P(), loss_slots=P(4096), stream=None)
+    R("miso_sdf_fwd_loss", fused + sorted_faults("sorted") + loss_in + null("grad_sdf"), variant="sorted", grid=g, mlp=m,
+      packed=packed, x=None, sorted=s, n=N, **LOSS, loss_inputs=P(), sdf=P(), relu_mask=P(4096), grad_sdf=P(),
+      loss_slots=P(4096), n_live=None, stream=None)
     train = fused + loss_in + fld("grid", "ignore_mask", 3)          # no level left whose gradient the step forms
-    R("miso_sdf_train_sorted", train + sorted_faults("sorted", perm_optional=True) + null("workspace") + off(4, "workspace"),
-      grid=gg, mlp=m, packed=packed, sorted=s, n=N, **LOSS, loss_inputs=P(), sdf=P(), loss_slots=P(4096), n_live=None,
-      workspace=P(), stream=None)
-    R("miso_sdf_train_sorted", val("n", ROWS_2GB), variant="tiles_xyz", grid=gg, mlp=m, packed=packed,
+    R("miso_sdf_train", train + null("x") + val("n_live", P()) + val("workspace", P()), variant="x", grid=gg, mlp=m,
+      packed=packed, x=P(), sorted=None, n=N, **LOSS, loss_inputs=P(), sdf=P(), loss_slots=P(4096), n_live=None,
+      workspace=None, stream=None)
+    R("miso_sdf_train", train + sorted_faults("sorted", perm_optional=True) + null("workspace") + off(4, "workspace"),
+      variant="sorted", grid=gg, mlp=m, packed=packed, x=None, sorted=s, n=N, **LOSS, loss_inputs=P(), sdf=P(),
+      loss_slots=P(4096), n_live=None, workspace=P(), stream=None)
+    R("miso_sdf_train", val("n", ROWS_2GB), variant="tiles_xyz", grid=gg, mlp=m, packed=packed, x=None,
       sorted=binned(TILES_XYZ), n=N, **LOSS, loss_inputs=P(), sdf=P(), loss_slots=P(4096), n_live=None, workspace=P(),
       stream=None)
     both = binned()
     both.x_sorted = P()          # with metric points too, the binned step's own "no normalised points" refusal is reached
-    R("miso_sdf_train_sorted", fld("sorted", "xn_sorted", None), variant="x_sorted", grid=gg, mlp=m, packed=packed, sorted=both,
-      n=N, **LOSS, loss_inputs=P(), sdf=P(), loss_slots=P(4096), n_live=None, workspace=P(), stream=None)
-    R("miso_sdf_train", train + null("x"), grid=gg, mlp=m, packed=packed, x=P(), n=N, **LOSS, loss_inputs=P(), sdf=P(),
-      loss_slots=P(4096), stream=None)
+    R("miso_sdf_train", fld("sorted", "xn_sorted", None), variant="x_sorted", grid=gg, mlp=m, packed=packed, x=None,
+      sorted=both, n=N, **LOSS, loss_inputs=P(), sdf=P(), loss_slots=P(4096), n_live=None, workspace=P(), stream=None)
     wg = (null("grid", "mlp", "grads", "grad_sdf", "relu_mask", "workspace") + PK + val("n", -1) + val("flags", 1, 16) +
           grid_faults("grid", True) + fused_faults("grid", "mlp") + fld("grads", "weight[1]", None) + off(4, "workspace") +
           val("workspace_floats", 0))

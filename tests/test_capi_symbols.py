@@ -66,13 +66,13 @@ def test_argument_validation_without_gpu():
     lib = _lib.load()
     g = _lib.Grid()
     g.n_levels = 0
-    assert lib.miso_encode_fwd(ctypes.byref(g), None, 0, None, 0, None) == 2001
+    assert lib.miso_encode_fwd(ctypes.byref(g), None, None, 0, None, 0, None) == 2001
     g.n_levels = 1
     g.level[0].C = 4; g.level[0].X = 2; g.level[0].Y = 2; g.level[0].Z = 2
     g.level[0].sC = 1; g.level[0].sX = 4; g.level[0].sY = 8; g.level[0].sZ = 16
-    assert lib.miso_encode_fwd(ctypes.byref(g), None, 0, None, 4, None) == 2001  # data NULL
+    assert lib.miso_encode_fwd(ctypes.byref(g), None, None, 0, None, 4, None) == 2001  # data NULL
     g.flags = 128
-    assert lib.miso_encode_fwd(ctypes.byref(g), None, 0, None, 4, None) == 2001  # bad flag
+    assert lib.miso_encode_fwd(ctypes.byref(g), None, None, 0, None, 4, None) == 2001  # bad flag
     m = _lib.Mlp()
     m.in_dim, m.hidden_dim, m.out_dim, m.n_linear = 24, 64, 1, 3
     assert lib.miso_mlp_packed_floats(ctypes.byref(m)) > 0
@@ -312,8 +312,8 @@ def test_function_signatures_equal_the_headers_as_a_compiler_sees_them(tmp_path)
         return {**sigs, name: (res, args)}
 
     def to_int32(args):
-        assert args[4] is C.c_int64
-        args[4] = C.c_int32
+        assert args[5] is C.c_int64
+        args[5] = C.c_int32
 
     def swap_float_double(args):                      # (lr, beta1 .. eps) are doubles; make the first one a float
         assert args[5] is C.c_double

@@ -157,8 +157,8 @@ def _grid(case, channels_last=True):
 @pytest.mark.parametrize("variant", ["channels_last", "ncdhw", "sorted_batch", "no_lean"])
 @pytest.mark.parametrize("name", CASES)
 def test_atomic_scatter_is_exact(name, variant, monkeypatch):
-    """miso_encode_bwd / miso_encode_bwd_sorted: float atomics in whatever order the hardware serves them.  With a
-    gradient buffer the launch is always the weight-form encode_bwd_kernel (launch_encode_bwd); MISO_ENCODE_NO_LEAN keeps
+    """miso_encode_bwd in both its forms (caller order, binned): float atomics in whatever order the hardware serves them.
+    With a gradient buffer the launch is always the weight-form encode_bwd_kernel (launch_encode_bwd); MISO_ENCODE_NO_LEAN keeps
     grad_x in that kernel when it is asked for alone, so `no_lean` runs the scatter with grad_x formed beside it."""
     from miso_amd import ops
     dc = _dev_case(name)

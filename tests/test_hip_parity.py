@@ -549,7 +549,7 @@ def test_mapping_loss_kernel_vs_oracle():
 def test_mapping_step_matches_autograd_and_adam(binned, lt):
     """MappingStep (captured launch sequence) == autograd through the same ops, and with
     Adam == torch.optim.Adam on the CPU oracle after 3 iterations.  binned: sort + forward +
-    backward with the loss folded in (miso_sdf_bwd_sorted_loss) + pull."""
+    backward with the loss folded in (miso_sdf_fwd_loss over the binned batch) + pull."""
     from miso_amd import ops
     from miso_amd.step import MappingStep
     case, feats, bound, ws, bs, x0, meta, fd, pack = setup_case("small")
@@ -816,15 +816,15 @@ def test_capi_rejects_bad_arguments_before_launching():
     out = torch.empty(n, sum(f.shape[1] for f in fdd), device=DEV)
     st = ops._stream(x)
     BAD, UNSUP = _lib.E_BADARG, _lib.E_UNSUPPORTED
-    assert lib.miso_encode_fwd(C.byref(g), ops._ptr(x), -1, ops._ptr(out), out.stride(0), st) == BAD
-    assert lib.miso_encode_fwd(C.byref(g), None, n, ops._ptr(out), out.stride(0), st) == BAD
-    assert lib.miso_encode_fwd(C.byref(g), ops._ptr(x), n, ops._ptr(out), 1, st) == BAD          # ld < F
+    assert lib.miso_encode_fwd(C.byref(g), ops._ptr(x), None, -1, ops._ptr(out), out.stride(0), st) == BAD
+    assert lib.miso_encode_fwd(C.byref(g), None, None, n, ops._ptr(out), out.stride(0), st) == BAD
+    assert lib.miso_encode_fwd(C.byref(g), ops._ptr(x), None, n, ops._ptr(out), 1, st) == BAD    # ld < F
     g2 = ops._fill_grid(fdd, meta)
     g2.flags = 1 << 20                                                                           # unknown flag
-    assert lib.miso_encode_fwd(C.byref(g2), ops._ptr(x), n, ops._ptr(out), out.stride(0), st) == BAD
+    assert lib.miso_encode_fwd(C.byref(g2), ops._ptr(x), None, n, ops._ptr(out), out.stride(0), st) == BAD
     g3 = ops._fill_grid(fdd, meta)
     g3.n_levels = 0
-    assert lib.miso_encode_fwd(C.byref(g3), ops._ptr(x), n, ops._ptr(out), out.stride(0), st) == BAD
+    assert lib.miso_encode_fwd(C.byref(g3), ops._ptr(x), None, n, ops._ptr(out), out.stride(0), st) == BAD
     # sort: tiles out of range, misaligned normalised buffer
     sb = ops.SortedBatch(n, DEV)
     assert lib.miso_sort_points(C.byref(g), ops._ptr(x), n, 17, ops._ptr(sb.workspace), None, ops._ptr(sb.xn_sorted),
@@ -838,7 +838,8 @@ def test_capi_rejects_bad_arguments_before_launching():
     C.memmove(C.byref(m2), C.byref(m), C.sizeof(m2))
     m2.hidden_dim = 48
     sdf = torch.empty(n, 1, device=DEV)
-    assert lib.miso_sdf_fwd(C.byref(g), C.byref(m2), ops._ptr(packed), ops._ptr(x), n, ops._ptr(sdf), None, st) == UNSUP
+    assert lib.miso_sdf_fwd(C.byref(g), C.byref(m2), ops._ptr(packed), ops._ptr(x), None, n, ops._ptr(sdf), None,
+                            st) == UNSUP
     assert lib.miso_lm_normal_eq(ops._ptr(x), ops._ptr(x), ops._ptr(x), ops._ptr(sdf), ops._ptr(sdf), n, 7, 0.1,
                                  ops._ptr(sdf), st) == UNSUP
     assert b"argument" in lib.miso_error_string(BAD).lower() or len(lib.miso_error_string(BAD)) > 0
@@ -885,7 +886,7 @@ def test_capi_rejects_bad_arguments_before_launching():
     torch.cuda.synchronize()
     assert int(cnt.sum()) == n and bool(((pooled == 1.0) | (pooled == 0.0)).all())
     # and a well-formed call still works afterwards
-    assert lib.miso_encode_fwd(C.byref(g), ops._ptr(x), n, ops._ptr(out), out.stride(0), st) == 0
+    assert lib.miso_encode_fwd(C.byref(g), ops._ptr(x), None, n, ops._ptr(out), out.stride(0), st) == 0
     torch.cuda.synchronize()
 
 
@@ -1626,3 +1627,39 @@ def test_adam_step_over_a_mixed_block_equals_one_tensor_at_a_time(scalars):
     assert not any(torch.equal(got[1][-1][i], got[2][-1][i]) for i in (0, 2, 3, 4))
     big = got[-1][-1][4]
     assert 0 < int(big.sum()) < big.numel()
+
+
+def test_x_is_ignored_when_sorted_is_given():
+    """The point arguments of an entry (miso_hip.h, at miso_sorted_t): with `sorted` set, x is not read.  miso_encode_fwd
+    and miso_sdf_fwd over 130 points binned at 2 tiles per axis (several tiles, three 64-point blocks, the last one
+    ragged) on the smallest fused shape: x = NULL and x = a device buffer of N x 3 NaNs give the same bits."""
+    import ctypes as C
+    from miso_amd import _lib, ops
+    lib = _lib.load()
+    n, Cc, size, H = 130, 4, 48, 32
+    g = torch.Generator().manual_seed(3)
+    feats = [(torch.randn(1, Cc, size, size, size, generator=g) * 0.05).to(DEV)
+             .contiguous(memory_format=torch.channels_last_3d)]
+    lin = [torch.randn(o, i, generator=g) * 0.3 for o, i in ((H, Cc), (H, H), (1, H))]
+    pack = ops.DecoderPack([w.to(DEV) for w in lin], [torch.randn(w.shape[0], generator=g).to(DEV) for w in lin])
+    bound = torch.tensor([[-1.0, 1.0], [-0.5, 1.5], [0.0, 2.0]])
+    meta = ops.GridMeta.from_bound(bound)
+    assert ops.sdf_fused_supported(feats, meta, pack)
+    ext = bound[:, 1] - bound[:, 0]
+    x = (torch.rand(n, 3, generator=g) * ext * 1.1 + bound[:, 0] - 0.05 * ext).to(DEV)      # a few points outside
+    sb = ops.SortedBatch(n, DEV, tiles=2).sort(x, meta)
+    assert int((sb.tile_offsets[1:] > sb.tile_offsets[:-1]).sum()) > 1          # more than one tile holds points
+    nans = torch.full((n, 3), float("nan"), device=DEV)
+    grid, (m, packed), st = ops._fill_grid(feats, meta), pack.require(), ops._stream(x)
+    outs = []
+    for xp in (None, ops._ptr(nans)):
+        enc = torch.full((n, Cc), float("nan"), device=DEV)
+        sdf = torch.full((n, 1), float("nan"), device=DEV)
+        assert lib.miso_encode_fwd(C.byref(grid), xp, C.byref(sb.struct), n, ops._ptr(enc), Cc, st) == 0
+        assert lib.miso_sdf_fwd(C.byref(grid), C.byref(m), ops._ptr(packed), xp, C.byref(sb.struct), n, ops._ptr(sdf), None,
+                                st) == 0
+        torch.cuda.synchronize()
+        outs.append((enc, sdf))
+    for a, b in zip(*outs):
+        assert torch.isfinite(a).all() and a.abs().max() > 0
+        assert torch.equal(a.view(torch.int32), b.view(torch.int32))

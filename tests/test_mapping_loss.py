@@ -380,7 +380,7 @@ def _aux(c, target, valid, sign, weight):
 
 
 def _fwd_loss(c, aux, lt, ws, wf, td, n_live=None):
-    """sdf_fwd_kernel with the loss folded in (binned: miso_sdf_fwd_sorted_loss; unbinned: miso_sdf_fwd_loss):
+    """sdf_fwd_kernel with the loss folded in (miso_sdf_fwd_loss, over a binned batch and over caller-order points):
     -> slots (LOSS_SLOTS, 2) float64, gsdf in the CALLER's order, sdf."""
     from miso_amd import ops
     n = c.n
@@ -401,7 +401,7 @@ def _fwd_loss(c, aux, lt, ws, wf, td, n_live=None):
 
 
 def _train(c, aux, lt, ws, wf, td, n_live=None, full_trips=False):
-    """sdf_train_kernel (binned: miso_sdf_train_sorted, every level pulled and OVERWRITTEN; unbinned: miso_sdf_train, every
+    """sdf_train_kernel (miso_sdf_train; binned: every level pulled and OVERWRITTEN; unbinned: every
     level scattered INTO zeroed gradients -- in 32-point trips at this size, in 64-point trips under MISO_F_FULL_TRIPS)
     -> slots float64, sdf, level gradients."""
     import dataclasses

@@ -1,6 +1,6 @@
-"""sdf_train_kernel (miso_sdf_train_sorted: forward + mapping loss + decoder backward in ONE launch, then the pull) against
-the two-launch form it replaces (miso_sdf_fwd_sorted_loss + miso_sdf_bwd_sorted): same SDF and loss bit for bit (the
-forward is the same instruction sequence), the same d-feat rows -- hence gradients equal up to the pull's summation
+"""sdf_train_kernel (miso_sdf_train over a binned batch: forward + mapping loss + decoder backward in ONE launch, then the
+pull) against the two-launch form it replaces (miso_sdf_fwd_loss + miso_sdf_bwd over the same batch): same SDF and loss
+bit for bit (the forward is the same instruction sequence), the same d-feat rows -- hence gradients equal up to the pull's summation
 order -- over the fused shape table, both losses, free-space term, invalid / NaN-labelled rows, padded batches (n_live),
 a crowded batch whose coarse level goes through the matrix-core push, and an ignored level.  Plus: a level the pull
 cannot own is scattered from the train kernel itself, and unbinned batches (miso_sdf_train) against their two launches.
@@ -282,8 +282,8 @@ def _setup_lin(C, sizes, H, n, seed, **kw):
 @pytest.mark.parametrize("lt", ["L1", "L2"])
 @pytest.mark.parametrize("shape", list(range(len(SHAPES))) + ["scat"])
 def test_train_kernel_vs_cpu_oracle(shape, lt):
-    """miso_sdf_train_sorted (sdf_train_kernel: forward + mapping loss + decoder backward in one launch, then the pull /
-    push; `scat`: a 200-vertex level the pull cannot own is scattered from the kernel, sdf_train_kernel<..,SCAT>) against
+    """miso_sdf_train over a binned batch (sdf_train_kernel: forward + mapping loss + decoder backward in one launch, then
+    the pull / push; `scat`: a 200-vertex level the pull cannot own is scattered from the kernel, sdf_train_kernel<..,SCAT>) against
     the oracle: SDF to 1e-5, both loss terms to 1e-6, every level's gradient to 1e-4 of its largest entry (ReLU ties
     apart), with invalid rows, free-space rows, per-sample weights and points outside the bound."""
     from miso_amd import ops
@@ -341,7 +341,7 @@ def test_unbinned_train_kernel_vs_cpu_oracle(n):
 
 
 def test_train_kernel_takes_the_index_from_xn_when_the_batch_has_no_perm_array():
-    """miso_sort_points leaves the original index in xn_sorted[p].w; miso_sdf_train_sorted accepts a batch without perm[]
+    """miso_sort_points leaves the original index in xn_sorted[p].w; miso_sdf_train accepts a batch without perm[]
     (MappingStep's fused step: one scattered store per point less in the sort).  Same results bit for bit as with
     perm[]; every other entry point refuses such a batch."""
     from miso_amd import ops
