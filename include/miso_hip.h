@@ -447,9 +447,23 @@ int miso_overlap_count(const float* pose, const float* coords_src, int64_t n, co
  *                the pair loss is weight * sum / n_rows, not / (count * n_ch)); n_rows >= 2^24: MISO_E_TOOLARGE;
  *   dst_grid     every level the decoder reads; the bound, the gate and src_boxes as in the latent form.
  * In residual 1 the pair loss is weight * sum / max(count, 1); a pair with no in-bound row has loss 0 and gradient 0.
- * miso_align_plan_build refuses, before anything is launched: residual outside 0..2, residual != 0 with mlp or packed
+ *
+ * Residual 3, the projected match of MIPS-Fusion (grid_opt/align/mips.py, its eq. 19-20): the same kernel, the same q, s
+ * and g = grad_q s, with g held constant.  The reference projects q onto the destination's surface, match_dst = q - s g,
+ * maps it back to the source frame and penalises its distance to the row p; since p maps to q, p - match_src =
+ * s M^T g with M = R_d^T R_s.  miso_align_t.constraint selects
+ *   1  point-to-plane: term (s a)^2 with a = g . (M n), n the row's source normal: feats_src holds (n,3) normals with
+ *      row pitch ld_feats >= 3 (pose independent, staged once like ref);
+ *   2  point-to-point: term s^2 |g|^2, the pair loss = weight * sum / (3 max(count, 1)) (the reference's mean runs over
+ *      the three components); feats_src is not read and may be NULL.
+ * The 24 sums keep their meaning -- term sum, in-bound count, the cotangent to q, d / d R_d, d / d R_s -- with the
+ * explicit dependence of a on M folded into the two 3x3 blocks.  loss_type must be 2.
+ *
+ * miso_align_plan_build refuses, before anything is launched: residual outside 0..3, residual 3 without constraint 1 or
+ * 2, a constraint other than 0 with any other residual, residual != 0 with mlp or packed
  * NULL (or packed not 16-byte aligned), a loss type the residual does not have (latent: 1, 2; residual 1: 1, 2, 3;
- * residual 2: 2; gm_scale <= 0 with loss type 3) -- MISO_E_BADARG; a (grid, decoder) that miso_sdf_supported does not
+ * residual 2 and 3: 2; gm_scale <= 0 with loss type 3), point-to-plane with feats_src NULL or ld_feats < 3 --
+ * MISO_E_BADARG; a (grid, decoder) that miso_sdf_supported does not
  * cover or whose launch does not fit a workgroup's LDS, pairs whose destination grids differ in (C, L) or in
  * MISO_F_EXACT_F32, the border / align-corners / normalised-coordinate flags -- MISO_E_UNSUPPORTED.  mlp is host memory
  * and is read by miso_align_plan_build and miso_align_iteration_a; the plan blob, its size and the state layout are
@@ -504,11 +518,13 @@ typedef struct {
    * iteration_a). */
   int32_t poses_ready;
   /* The SDF residuals (see above); all zero: the latent residual. */
-  int32_t residual;          /* 0 latent, 1 SDF against the source submap's SDF, 2 SDF against the measurement */
+  int32_t residual;          /* 0 latent, 1 SDF against the source submap's SDF, 2 SDF against the measurement,
+                              * 3 the projected match (with constraint) */
   const miso_mlp_t* mlp;     /* residual != 0: the decoder (host memory) ... */
   const float* packed;       /* ... and its packed weights (miso_mlp_pack, device) */
   float gm_scale;            /* loss_type 3 */
   int32_t sdf_shape;         /* set by miso_align_plan_build (residual != 0): C | L << 8 | exact-fp32 << 16 of the grids */
+  int32_t constraint;        /* residual 3: 1 point-to-plane, 2 point-to-point; 0 with every other residual */
 } miso_align_t;
 
 int64_t miso_align_plan_bytes(int32_t n_pairs);

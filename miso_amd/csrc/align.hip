@@ -147,6 +147,8 @@ __global__ __launch_bounds__(EPI_A_THREADS) void align_epilogue_a_kernel(AlignK 
       // (the count and n_ch are small integers: denom is exact in fp32, as the reference's clamp(min=1) * n_ch)
       // (residual 2, the measured SDF: n_ch carries the source's full row count, and the reference's mean is over all of
       // its rows, in bound or not)
+      // (residual 3, the projected match, L2: n_ch is 1 for point-to-plane and 3 for point-to-point, whose mean is over
+      // the three components of every row kept)
       const float denom = k.residual == 2 ? fmaxf(d.n_ch, 1.0f) : fmaxf((float)o[1], 1.0f) * (k.loss_type == 2 ? d.n_ch : 1.0f);
       const float val = (float)(o[0] / (double)denom);
       const bool finite = (val == val) && !isinf(val);          // nan_to_num passes no gradient otherwise

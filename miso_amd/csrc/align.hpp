@@ -24,7 +24,8 @@ struct AlignK {
   const AlignPairK* plan;
   float* state;
   AlignLayout L;
-  int residual;      // miso_align_t.residual: 0 latent, 1 SDF against the source submap, 2 SDF against the measurement
+  int residual;      // miso_align_t.residual: 0 latent, 1 SDF against the source submap, 2 SDF against the measurement,
+                     // 3 the projected match (sdf.constraint says which form)
   PairSdfK sdf;      // residual != 0
 };
 

@@ -639,18 +639,27 @@ int64_t miso_align_plan_bytes(int32_t n_pairs) {
   return n_pairs < 0 ? 0 : (int64_t)(n_pairs > 0 ? n_pairs : 1) * (int64_t)sizeof(AlignPairK);
 }
 
-// the loss types a residual has: latent L1 | L2; SDF against the source submap L1 | L2 | GM; against the measurement L2
+// the loss types a residual has: latent L1 | L2; SDF against the source submap L1 | L2 | GM; against the measurement L2;
+// the projected match L2
 static bool align_loss_ok(int residual, int loss_type, float gm_scale) {
   if (residual == 0) return mapping_loss_ok(loss_type);
   if (residual == 1) return mapping_loss_ok(loss_type) || (loss_type == 3 && gm_scale > 0.0f);
-  return residual == 2 && loss_type == 2;
+  return (residual == 2 || residual == 3) && loss_type == 2;
+}
+
+// residual in 0..3, and the constraint that goes with it: 1 (point-to-plane) or 2 (point-to-point) with the projected
+// match, 0 with every other residual
+static bool align_residual_ok(int residual, int constraint) {
+  if (residual < 0 || residual > 3) return false;
+  return residual == 3 ? (constraint == 1 || constraint == 2) : constraint == 0;
 }
 
 int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, void* plan_host) {
   if (!cfg || cfg->n_pairs < 0 || cfg->n_submaps < 1 || cfg->n_submaps > 64) return MISO_E_BADARG;
   if (cfg->n_pairs > 0 && (!pairs || !plan_host)) return MISO_E_BADARG;
   const int residual = cfg->residual;
-  if (residual < 0 || residual > 2) return MISO_E_BADARG;
+  if (!align_residual_ok(residual, cfg->constraint)) return MISO_E_BADARG;
+  const bool reads_fsrc = !(residual == 3 && cfg->constraint == 2);      // (point-to-point has no column of its own)
   if (residual && (!cfg->mlp || !cfg->packed || !aligned(16, cfg->packed))) return MISO_E_BADARG;
   // (the latent form has always left the loss type to the iteration calls: kept)
   if ((residual || cfg->loss_type == 3) && !align_loss_ok(residual, cfg->loss_type, cfg->gm_scale)) return MISO_E_BADARG;
@@ -662,7 +671,8 @@ int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, voi
     const miso_align_pair_t& in = pairs[p];
     if (in.src < 0 || in.src >= cfg->n_submaps || in.dst < 0 || in.dst >= cfg->n_submaps || in.src == in.dst)
       return MISO_E_BADARG;
-    if (in.n < 0 || in.gate_n < 0 || !set_if(in.n, in.coords_src, in.feats_src)) return MISO_E_BADARG;
+    if (in.n < 0 || in.gate_n < 0 || !set_if(in.n, in.coords_src)) return MISO_E_BADARG;
+    if (reads_fsrc && !set_if(in.n, in.feats_src)) return MISO_E_BADARG;
     if (!fits_fp32_count(in.gate_n)) return MISO_E_TOOLARGE;
     if (residual == 2 && !fits_fp32_count(in.ld_feats)) return MISO_E_TOOLARGE;      // ld_feats: the source's full row count
     AlignPairK& d = out[p];
@@ -678,7 +688,8 @@ int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, voi
       const int exact = (d.g.flags & MISO_F_EXACT_F32) ? 1 : 0;
       if (sdf_exact >= 0 && (C_ != sdf_C || L_ != sdf_L || exact != sdf_exact)) return MISO_E_UNSUPPORTED;
       sdf_C = C_; sdf_L = L_; sdf_exact = exact;
-      if (in.ld_feats < (residual == 2 ? in.n : 1)) return MISO_E_BADARG;
+      // the pitch of the column read: ref (1), the source normals (3); residual 2: the full row count instead
+      if (reads_fsrc && in.ld_feats < (residual == 2 ? in.n : (residual == 3 ? 3 : 1))) return MISO_E_BADARG;
     } else if (in.ld_feats < d.g.F) {
       return MISO_E_BADARG;
     }
@@ -700,7 +711,8 @@ int miso_align_plan_build(const miso_align_pair_t* pairs, miso_align_t* cfg, voi
       return MISO_E_BADARG;
     }
     d.src = in.src; d.dst = in.dst;
-    d.n_ch = residual == 0 ? (float)d.g.F : (residual == 1 ? 1.0f : (float)in.ld_feats);
+    d.n_ch = residual == 0 ? (float)d.g.F : (residual == 1 ? 1.0f : (residual == 2 ? (float)in.ld_feats
+                                                                                    : (cfg->constraint == 2 ? 3.0f : 1.0f)));
     d.boxes = in.n > 0 ? in.src_boxes : nullptr;
     if (in.n > max_n) max_n = in.n;
     if (d.gate_p && !d.gate_ax[0] && in.gate_n > max_gate) max_gate = in.gate_n;      // point-list gates only (grid sizing)
@@ -728,7 +740,7 @@ int64_t miso_align_state_layout(int32_t n_submaps, int32_t n_pairs, int32_t ring
 static int align_k(const miso_align_t* c, AlignK* k) {
   if (!c || c->n_submaps < 1 || c->n_submaps > 64 || c->n_pairs < 0 || c->ring_iters < 0) return MISO_E_BADARG;
   if (!c->R0 || !c->t0 || !c->state || (c->n_pairs > 0 && !c->plan)) return MISO_E_BADARG;
-  if (c->residual < 0 || c->residual > 2 || !align_loss_ok(c->residual, c->loss_type, c->gm_scale)) return MISO_E_BADARG;
+  if (!align_residual_ok(c->residual, c->constraint) || !align_loss_ok(c->residual, c->loss_type, c->gm_scale)) return MISO_E_BADARG;
   if (!aligned(16, c->state)) return MISO_E_BADARG;
   if (c->residual && (!c->mlp || !c->packed || !aligned(16, c->packed))) return MISO_E_BADARG;
   memset(k, 0, sizeof(*k));
@@ -737,7 +749,7 @@ static int align_k(const miso_align_t* c, AlignK* k) {
     PairSdfK& f = k->sdf;
     f.C = c->sdf_shape & 255; f.L = (c->sdf_shape >> 8) & 255; f.exact = ((c->sdf_shape >> 16) & 1) != 0;
     f.H = c->mlp->hidden_dim; f.NH = c->mlp->n_linear - 2;
-    f.packed = c->packed; f.gm_scale = c->gm_scale;
+    f.packed = c->packed; f.gm_scale = c->gm_scale; f.constraint = c->constraint;
     if (c->mlp->in_dim != f.C * f.L || !pair_sdf_covered(f.C, f.L, f.H, f.NH)) return MISO_E_UNSUPPORTED;
   }
   k->S = c->n_submaps; k->P = c->n_pairs; k->loss_type = c->loss_type; k->ring_iters = c->ring_iters;

@@ -25,14 +25,22 @@ namespace miso {
 
 constexpr int PAIR_SDF_WAVES = 4;
 
-template <int C, int L, int H, int NH, bool SPLIT>
+// KIND: 0 the SDF residuals above; the projected match of MIPS-Fusion (grid_opt/align/mips.py, miso_align_t.residual 3):
+// 1 point-to-plane, 2 point-to-point.  With g = grad_q s held constant and the projected point q - s g mapped back to the
+// source frame, p - match_src = s M^T g, M = Rd^T Rs (the rest of the reference's expression is p - p):
+//   plane   a = g . (M n), n = the source normal of the row (feats_src, pitch ld); term (s a)^2; cotangent to q
+//           2 s a^2 g; and, M standing in a explicitly, d term / d M = 2 s^2 a g n^T, summed as S2 (9 more accumulators)
+//           and folded into the two 3x3 blocks in the fp64 tail: R_s S2^T to d / d R_d, R_d S2 to d / d R_s
+//   point   term s^2 |g|^2 (the mean is over 3 count elements: n_ch = 3 in the plan); cotangent to q 2 s |g|^2 g; the
+//           dependence of |M^T g|^2 on M is normal to the rotation manifold and is not summed
+template <int C, int L, int H, int NH, bool SPLIT, int KIND>
 __global__ __launch_bounds__(64 * PAIR_SDF_WAVES) void pair_sdf_stage_kernel(
     const AlignPairK* __restrict__ plan, const float* __restrict__ pose_all, int loss_type, float gm_scale,
     const float* __restrict__ packed, double* __restrict__ out_all, const int32_t* __restrict__ stopped,
     const int32_t* __restrict__ order) {
   constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2, NF = 2 * KS0, MW = (NH + 1) * RT;
   constexpr int FP = dfeat_pitch(F);
-  constexpr int NACC = 14;
+  constexpr int NACC = KIND == 1 ? 23 : 14;
   if (stopped && *stopped) return;
   // launch slot blockIdx.y -> pair, as in pair_stage_kernel
   const int o_ = order ? order[blockIdx.y] : 0;
@@ -96,7 +104,7 @@ __global__ __launch_bounds__(64 * PAIR_SDF_WAVES) void pair_sdf_stage_kernel(
                                fmaxf(fabsf(bmin[2]), fabsf(bmax[2])));
 
   // per lane: {term, in-bound count, G = sum g (3), S = sum p (x) g (9)}; the two 3x3 sums of the output are linear in S
-  // and G and are formed once per workgroup in double (pair_latent_body)
+  // and G and are formed once per workgroup in double (pair_latent_body).  KIND 1: then S2 = sum 2 s^2 a g (x) n (9)
   float acc[NACC];
 #pragma unroll
   for (int i = 0; i < NACC; ++i) acc[i] = 0.0f;
@@ -199,9 +207,26 @@ __global__ __launch_bounds__(64 * PAIR_SDF_WAVES) void pair_sdf_stage_kernel(
         dq[2] += sz_ * ax[2].mult;
       }
       // ---- residual, term and d term / d s ----------------------------------------------------------------------------
-      const float r = d.fsrc[i * d.ld] - sdf;
+      const float r = KIND == 0 ? d.fsrc[i * d.ld] - sdf : 0.0f;      // (the projected match has no reference column)
       float term, coef;
-      if (loss_type == 2) {
+      if constexpr (KIND == 1) {
+        const float* nr = d.fsrc + i * d.ld;
+        const float nn[3] = {nr[0], nr[1], nr[2]};
+        float a = 0.0f;
+#pragma unroll
+        for (int r_ = 0; r_ < 3; ++r_) a += dq[r_] * (M[r_][0] * nn[0] + M[r_][1] * nn[1] + M[r_][2] * nn[2]);
+        const float c_ = sdf * a;
+        term = c_ * c_; coef = 2.0f * (c_ * a);
+        const float c2 = 2.0f * (sdf * c_);
+#pragma unroll
+        for (int r_ = 0; r_ < 3; ++r_)
+#pragma unroll
+          for (int b = 0; b < 3; ++b) acc[14 + r_ * 3 + b] += (c2 * dq[r_]) * nn[b];
+      } else if constexpr (KIND == 2) {
+        const float g2 = (dq[0] * dq[0] + dq[1] * dq[1]) + dq[2] * dq[2];
+        const float sg = sdf * g2;
+        term = sdf * sg; coef = 2.0f * sg;
+      } else if (loss_type == 2) {
         term = r * r; coef = -2.0f * r;
       } else if (loss_type == 1) {      // |r|_2 of a one-column row; vector_norm's backward: sign(0) = 0
         term = fabsf(r); coef = r > 0.0f ? -1.0f : (r < 0.0f ? 1.0f : 0.0f);
@@ -249,9 +274,13 @@ __global__ __launch_bounds__(64 * PAIR_SDF_WAVES) void pair_sdf_stage_kernel(
       const int a = (t - 5) / 3, b = (t - 5) % 3;
       v = ((double)pose_s[3 * a] * T[5 + b] + (double)pose_s[3 * a + 1] * T[8 + b]) + (double)pose_s[3 * a + 2] * T[11 + b] +
           ((double)pose_s[9 + a] - (double)pose_d[9 + a]) * T[2 + b];
+      if constexpr (KIND == 1)      // + (Rs S2^T)_ab
+        v += ((double)pose_s[3 * a] * T[14 + 3 * b] + (double)pose_s[3 * a + 1] * T[15 + 3 * b]) + (double)pose_s[3 * a + 2] * T[16 + 3 * b];
     } else {                  // sum (Rd g)_a p_b = sum_c Rd[a][c] S[b][c]
       const int a = (t - 14) / 3, b = (t - 14) % 3;
       v = ((double)pose_d[3 * a] * T[5 + 3 * b] + (double)pose_d[3 * a + 1] * T[6 + 3 * b]) + (double)pose_d[3 * a + 2] * T[7 + 3 * b];
+      if constexpr (KIND == 1)      // + (Rd S2)_ab
+        v += ((double)pose_d[3 * a] * T[14 + b] + (double)pose_d[3 * a + 1] * T[17 + b]) + (double)pose_d[3 * a + 2] * T[20 + b];
     }
     if (v != 0.0) atomic_add_f64(out + t, v);
   }
@@ -286,7 +315,9 @@ static hipError_t launch_pair_sdf_t(FusedShape<C, L, H, NH>, const PairSdfK& k, 
   unsigned cap = 2048u / (unsigned)n_pairs;
   cap = cap < 16u ? 16u : (cap > 512u ? 512u : cap);
   if (blocks > cap) blocks = cap;
-  auto kern = split ? pair_sdf_stage_kernel<C, L, H, NH, true> : pair_sdf_stage_kernel<C, L, H, NH, false>;
+  auto kern = k.constraint == 1 ? (split ? pair_sdf_stage_kernel<C, L, H, NH, true, 1> : pair_sdf_stage_kernel<C, L, H, NH, false, 1>)
+            : k.constraint == 2 ? (split ? pair_sdf_stage_kernel<C, L, H, NH, true, 2> : pair_sdf_stage_kernel<C, L, H, NH, false, 2>)
+                                : (split ? pair_sdf_stage_kernel<C, L, H, NH, true, 0> : pair_sdf_stage_kernel<C, L, H, NH, false, 0>);
   hipError_t e = allow_dynamic_lds((const void*)kern, lds);
   if (e != hipSuccess) return e;
   kern<<<dim3(blocks, (unsigned)n_pairs), 64 * PAIR_SDF_WAVES, lds, s>>>(plan_dev, pose_all, loss_type, k.gm_scale, k.packed,

@@ -37,6 +37,7 @@ struct PairSdfK {
   bool exact;             // MISO_F_EXACT_F32 of the destination grids
   const float* packed;    // miso_mlp_pack's output
   float gm_scale;
+  int constraint;         // miso_align_t.constraint: 0 the SDF residuals; 1 / 2 the projected match, plane / point
 };
 
 }  // namespace miso

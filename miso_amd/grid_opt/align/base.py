@@ -115,8 +115,8 @@ def fused_alignment_loop(grid_atlas, fused, submap_pairs, check_intersection, lr
     under the reference's own alignment config (verbose: True, save_iterations: True, configs/rgbd/scannet.yaml:65-66).
 
     fused: dict(inputs=callable(atlas, pairs, check_intersection) -> list of pair dicts for ops.AlignPlan,
-    align_loss, align_weight[, overlap_thresh][, residual, decoder, gm_scale: ops.AlignPlan's keyword arguments of the
-    same names, for the SDF residuals]).  reduce / my_pairs: the multi-rank hook of miso_amd.dist -- this
+    align_loss, align_weight[, overlap_thresh][, residual, decoder, gm_scale, constraint: ops.AlignPlan's keyword
+    arguments of the same names, for the SDF residuals]).  reduce / my_pairs: the multi-rank hook of miso_amd.dist -- this
     rank evaluates ``my_pairs`` only and ``reduce(flat)`` sums the 6S + 1 floats over ranks between the two halves
     of the iteration.  Returns the ``iteration_results`` dict."""
     from miso_amd import ops
@@ -132,9 +132,9 @@ def fused_alignment_loop(grid_atlas, fused, submap_pairs, check_intersection, lr
                          reg_weight=pose_reg_weight if pose_reg_weight > 0 else 0.0, reg_thresh_rad=pose_thresh_rad,
                          reg_thresh_m=pose_thresh_m, rel_change_thresh=rel_change_thresh, ring_iters=total_iters,
                          save_poses=save_iterations,
-                         # the SDF residuals (align/miso.py sdf_finetune_loss, align/vfpp.py): which pair stage, with
-                         # which decoder
-                         **{k: fused[k] for k in ('residual', 'decoder', 'gm_scale') if k in fused})
+                         # the SDF residuals (align/miso.py sdf_finetune_loss, align/vfpp.py, align/mips.py): which pair
+                         # stage, with which decoder
+                         **{k: fused[k] for k in ('residual', 'decoder', 'gm_scale', 'constraint') if k in fused})
     with torch.no_grad():
         dr = torch.cat([p.detach().reshape(1, 3) for p in grid_atlas.rotation_corrections], dim=0)
         dt = torch.cat([p.detach().reshape(1, 3) for p in grid_atlas.translation_corrections], dim=0)

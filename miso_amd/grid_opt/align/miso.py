@@ -258,13 +258,17 @@ def source_rows(grid_atlas: GridAtlas, batches, src_id: int):
     return torch.cat(coords).detach().float(), torch.cat(sdf).float(), torch.cat(valid)
 
 
-def sdf_pair_inputs(grid_atlas: GridAtlas, batches, pairs, check_intersection=True, measured_trunc=None):
+def sdf_pair_inputs(grid_atlas: GridAtlas, batches, pairs, check_intersection=True, measured_trunc=None,
+                    surf_thresh=None):
     """Per-pair inputs of ops.AlignPlan's SDF residuals, staged once per loop (host syncs are fine here).  Per source
     submap: the rows of its keyframes in ``batches``, in its frame (source_rows).
       residual "sdf" (measured_trunc None): the rows with sdf_valid == 1 and ``ref`` = the source submap's own SDF there,
         under no_grad through the forward the op-by-op route calls (GridNet.forward);
       residual "sdf_measured" (align/vfpp.py): the rows with |gt sdf| < measured_trunc, ``ref`` = the measured SDF, and
-        ``n_rows`` = all rows of the source, the divisor of the reference's mean.
+        ``n_rows`` = all rows of the source, the divisor of the reference's mean;
+      residual "mips" (align/mips.py; surf_thresh set): the rows with |gt sdf| < surf_thresh and, in place of ``ref``,
+        ``normals`` (n,3) = the gradient of the source submap's SDF at them, from one forward and one autograd.grad of the
+        GridNet, the route the op-by-op loss takes (the point-to-point form does not read them).
     The destination side is every level its decoder reads; the overlap gate reads the source's finest-level vertices as
     in the latent stage.  A pair whose source has no row in the batches is left out, as the op-by-op loss returns {}."""
     staged, out = {}, []
@@ -274,7 +278,17 @@ def sdf_pair_inputs(grid_atlas: GridAtlas, batches, pairs, check_intersection=Tr
             rows = source_rows(grid_atlas, batches, src_id)
             if rows is not None:
                 coords, sdf, valid = rows
-                if measured_trunc is None:
+                if surf_thresh is not None:
+                    keep = torch.nonzero(torch.abs(sdf[:, 0]) < surf_thresh, as_tuple=False)[:, 0]
+                    coords = coords[keep].contiguous()
+                    ref = coords.new_zeros((0, 3))
+                    if coords.shape[0]:
+                        with torch.enable_grad():
+                            pts = coords.clone().requires_grad_(True)
+                            s_src = sub_from(pts)
+                            (ref,) = torch.autograd.grad(s_src, pts, grad_outputs=torch.ones_like(s_src))
+                    ref = ref.float()
+                elif measured_trunc is None:
                     keep = torch.nonzero(valid[:, 0] == 1, as_tuple=False)[:, 0]
                     coords = coords[keep].contiguous()
                     with torch.no_grad():
@@ -282,12 +296,13 @@ def sdf_pair_inputs(grid_atlas: GridAtlas, batches, pairs, check_intersection=Tr
                 else:
                     keep = torch.nonzero(torch.abs(sdf[:, 0]) < measured_trunc, as_tuple=False)[:, 0]
                     ref, coords = sdf[keep], coords[keep].contiguous()
-                rows = (coords, ref.detach().reshape(-1, 1).contiguous(), int(valid.shape[0]))
+                rows = (coords, ref.detach().reshape(-1, 1 if surf_thresh is None else 3).contiguous(), int(valid.shape[0]))
             staged[src_id] = rows
         if staged[src_id] is None:
             continue
         coords, ref, n_rows = staged[src_id]
-        out.append(dict(src=src_id, dst=dst_id, coords=coords, ref=ref, n_rows=n_rows,
+        column = dict(ref=ref) if surf_thresh is None else dict(normals=ref)
+        out.append(dict(src=src_id, dst=dst_id, coords=coords, n_rows=n_rows, **column,
                         feats_dst=[g.feature.detach() for g in sub_to.features],
                         meta_dst=sub_to.features[0].grid_meta(sub_to.ignore_level_),
                         gate_pts=grid_atlas._finest_vertices(src_id) if check_intersection else None,

@@ -9,7 +9,7 @@ its keyframe.  Both ``dataset_name`` values therefore select the one loss below,
 
 With the default options and the atlas on the GPU ``align_multiple_submaps_vfpp`` runs the whole loop on the device
 (ops.AlignPlan(residual="sdf_measured"), csrc/pair_sdf.hip) on ONE batch drawn at the start, where the reference draws a
-fresh one per pair and iteration.  MIPS-Fusion (reference align/mips.py) is not built."""
+fresh one per pair and iteration.  MIPS-Fusion's baseline (reference align/mips.py) is align/mips.py here."""
 import logging
 
 import numpy as np

@@ -2217,14 +2217,20 @@ class AlignPlan:
     the decoder reads, ``coords`` the source rows in the source frame, and a pair carries ``ref`` (n,) or (n,1) where the
     latent mode carries ``feats_src``: the source submap's SDF at the rows ("sdf"), or the measured SDF of the rows kept
     with ``n_rows`` = the source's full row count, the divisor of the reference's mean ("sdf_measured").  A decoder or
-    grid the kernel table does not hold raises _lib.NotCovered."""
+    grid the kernel table does not hold raises _lib.NotCovered.
 
-    _RESIDUALS = {"latent": 0, "sdf": 1, "sdf_measured": 2}
+    "mips" -- MIPS-Fusion's projected-match residual (grid_opt/align/mips.py; L2) with ``constraint`` =
+    "point_to_plane" | "point_to_point": the SDF modes' inputs, ``coords`` being the source's surface rows, and in place
+    of ``ref`` a pair carries ``normals`` (n,3) fp32, the source submap's SDF gradient at the rows (point-to-plane; not
+    read for point-to-point).  The pair loss is weight * sum / count, over 3 count for point-to-point."""
+
+    _RESIDUALS = {"latent": 0, "sdf": 1, "sdf_measured": 2, "mips": 3}
+    _CONSTRAINTS = {None: 0, "point_to_plane": 1, "point_to_point": 2}
 
     def __init__(self, R0, t0, pairs, *, loss_type="L2", align_weight=3000.0, overlap_thresh=1e-2, lr=1e-2,
                  betas=(0.9, 0.999), eps=1e-8, reg_weight=0.0, reg_thresh_rad=1.0, reg_thresh_m=1.0,
                  rel_change_thresh=0.0, ring_iters=0, save_poses=False, cull=None, residual="latent",
-                 decoder: "DecoderPack" = None, gm_scale=0.1):
+                 decoder: "DecoderPack" = None, gm_scale=0.1, constraint=None):
         """cull (default on, None included): one box per run of 64 source vertices
         (miso_align_src_boxes, built once per source list) lets the residual kernel skip runs that cannot reach the
         destination bound at the current poses without reading them -- same sums, fewer bytes."""
@@ -2238,6 +2244,10 @@ class AlignPlan:
         cfg = _lib.Align()
         self.residual = residual
         cfg.residual = self._RESIDUALS[residual]
+        if (residual == "mips") != (constraint is not None) or constraint not in self._CONSTRAINTS:
+            raise ValueError(f"AlignPlan: residual {residual!r} with constraint {constraint!r}")
+        self.constraint = constraint
+        cfg.constraint = self._CONSTRAINTS[constraint]
         cfg.n_submaps, cfg.n_pairs = S, P
         cfg.loss_type = {"L1": 1, "L2": 2, "GM": 3}[loss_type] if cfg.residual else _LOSS_TYPES[loss_type]
         if cfg.residual:
@@ -2258,7 +2268,12 @@ class AlignPlan:
         for i, pr in enumerate(pairs):
             feats_dst = [f.detach() for f in pr["feats_dst"]]
             coords = pr["coords"].detach().contiguous()
-            if cfg.residual:
+            if cfg.residual == 3:
+                fsrc = None
+                if cfg.constraint == 1:
+                    fsrc = pr["normals"].detach().contiguous()
+                    assert fsrc.shape == coords.shape and fsrc.dtype == torch.float32
+            elif cfg.residual:
                 fsrc = pr["ref"].detach().reshape(-1, 1).contiguous()
                 assert fsrc.shape[0] == coords.shape[0] and fsrc.dtype == torch.float32
             else:
@@ -2266,9 +2281,11 @@ class AlignPlan:
             _require_hip(coords, fsrc, *feats_dst)
             d = descs[i]
             d.dst_grid = _fill_grid(feats_dst, pr["meta_dst"])
-            d.coords_src, d.feats_src = coords.data_ptr(), fsrc.data_ptr()
+            d.coords_src, d.feats_src = coords.data_ptr(), (fsrc.data_ptr() if fsrc is not None else None)
             d.n = coords.shape[0]
-            if cfg.residual == 2:
+            if cfg.residual == 3:
+                d.ld_feats = 3
+            elif cfg.residual == 2:
                 d.ld_feats = int(pr["n_rows"])                       # the full row count travels in the pitch's field
             elif cfg.residual == 1:
                 d.ld_feats = 1
