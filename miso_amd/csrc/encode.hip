@@ -14,6 +14,30 @@
 
 namespace miso {
 
+// The eight corners of a cell for a kernel that loads first and lets a zero weight drop what is out of range.  corner()
+// gives such a corner offset 0, a valid address -- but vertex 0 may hold NaN or inf, and 0 x NaN would then reach every
+// row that has lost a corner, where ATen skips the corner.  Here a corner out of range re-reads an IN-RANGE corner of
+// its own cell instead: if that value is not finite the row is not finite anyway (ATen: a non-finite vertex reaches
+// the rows that have it as an in-range corner, whatever its weight), and if it is finite the product is the +-0 it
+// always was.  The arithmetic behind the loads is untouched, so finite grids keep every bit.  (Selecting the loaded
+// VALUE to zero does the same and was tried first: the select moved the compiler's choice of the products it fuses
+// into the sums, and grad_x of encode_bwd_kernel changed in its last bits)
+// reread_in_range rewrites the offsets that corner() gave, after the weights are formed (the parent's loops, so the
+// compiler packs them as before); it returns false when no corner is in range -- outside the level, a NaN or inf
+// coordinate: the level then adds nothing, and no vertex is read.
+__device__ __forceinline__ bool reread_in_range(const bool (&inb)[8], int (&off)[8]) {
+  int safe = 0;
+  bool any_in = false;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    safe = inb[k] ? off[k] : safe;
+    any_in = any_in || inb[k];
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) off[k] = inb[k] ? off[k] : safe;
+  return any_in;
+}
+
 template <bool VEC4>
 __global__ __launch_bounds__(256) void encode_fwd_kernel(GridK g, const float* __restrict__ x,
                                                         int64_t n, float* __restrict__ out,
@@ -35,8 +59,16 @@ __global__ __launch_bounds__(256) void encode_fwd_kernel(GridK g, const float* _
     const Cell c = level_cell(g, lv, px, py, pz, a);
     int off[8];
     float w[8];
+    bool inb[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) w[k] = corner_weight<0>(c, k, corner(c, lv, k, off[k])).w;
+    for (int k = 0; k < 8; ++k) {
+      inb[k] = corner(c, lv, k, off[k]);
+      w[k] = corner_weight<0>(c, k, inb[k]).w;
+    }
+    if (!reread_in_range(inb, off)) {
+      for (int ch = 0; ch < lv.C; ++ch) o[lv.foff + ch] = 0.0f;
+      continue;
+    }
     if (VEC4) {
       for (int ch = 0; ch < lv.C; ch += 4) {
         float4 v[8];
@@ -92,6 +124,7 @@ __global__ __launch_bounds__(256) void encode_bwd_kernel(GridK g, const float* _
       const CornerW cw = corner_weight<1>(c, k, inb[k]);
       w[k] = cw.w; dwx[k] = cw.dx; dwy[k] = cw.dy; dwz[k] = cw.dz;
     }
+    if (!reread_in_range(inb, off)) continue;      // (nothing to scatter, and +0 for grad_x)
     float ax_ = 0.f, ay_ = 0.f, az_ = 0.f;
     if (VEC4) {
       for (int ch = 0; ch < lv.C; ch += 4) {
@@ -160,11 +193,14 @@ __global__ __launch_bounds__(256) void encode_bwd_x_kernel(GridK g, const float*
     float d[8];
     int off[8];
     bool inb[8];
+    // No corner in range: outside the level, or a NaN / inf coordinate, whose t is not finite -- the tree would form
+    // 0 + t x 0 = NaN where the weight form (weights selected to zero) answers 0.  The level adds nothing.
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       inb[k] = corner(c, lv, k, off[k]);
       d[k] = 0.0f;
     }
+    if (!reread_in_range(inb, off)) continue;
     for (int ch = 0; ch < lv.C; ch += 4) {
       const float4 gv = *reinterpret_cast<const float4*>(go + lv.foff + ch);
       float4 v[8];

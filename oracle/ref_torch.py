@@ -33,7 +33,7 @@ gradcheck / error measurement).
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -88,6 +88,9 @@ def trilinear_gather(feature: torch.Tensor, xn: torch.Tensor,
     ``(i0+1-ix)`` / ``(ix-i0)`` products, out-of-range corners contribute zero
     (``zeros``) or coordinates are clipped first (``border``); corner naming and
     weights as in third_party/cuda_gridsample_grad2/gridsample_cuda.cu:302-342.
+
+    For FINITE grids: an out-of-range corner's clamped neighbour is multiplied by a 0 mask, so a NaN or inf vertex
+    there would reach rows that ATen (and the kernels) keep finite; ``trilinear_first64`` selects instead.
     """
     assert feature.ndim == 5 and feature.shape[0] == 1
     assert padding_mode in ("zeros", "border")
@@ -645,6 +648,117 @@ def _trilinear_jet(feature, ix, dtype):
         der[:, :, 2] += v * (sg[2] * wt[0] * wt[1])[:, None]
         mag += v.abs()
     return val, der, mag
+
+
+# --------------------------------------------------------------------------- #
+# The sampled value and its first coordinate gradient at the kernel's own fp32 index coordinate (trilinear.hpp)
+# --------------------------------------------------------------------------- #
+def mult32(bound_axis, size, align_corners=False):
+    """The kernel's d ix / d x on one axis as an fp32 scalar tensor, rounded where axis_norm / axis_from_norm round:
+    fl(fl(2 / len) * (0.5 * size)), 0.5 * (size - 1) under align_corners (0.5 * size is exact).  A binned batch forms
+    the same number as gscale * mult (gscale = fl(2 / len) on the host, mult = 0.5 * size).  bound_axis: (min, max), or
+    None for normalised coordinates (mult alone, exact)."""
+    half = torch.tensor(0.5, dtype=torch.float32) * torch.tensor(float(size - 1 if align_corners else size),
+                                                                 dtype=torch.float32)
+    if bound_axis is None:
+        return half
+    lo, hi = (torch.tensor(float(v), dtype=torch.float32) for v in bound_axis)
+    return (torch.tensor(2.0, dtype=torch.float32) / (hi - lo)) * half
+
+
+def sample_index32(x32, bound, sizes_xyz, align_corners=False, padding_mode="zeros"):
+    """One level's index coordinate and d ix / d x as the kernels form them (axis_norm, axis_from_norm), carried to fp64
+    exactly: x32 (N,3) fp32 metres -- normalised coordinates where ``bound`` is None -- -> (ix (N,3), mult (N,3)) fp64.
+    ``border`` padding replays the clip in fp32: ix <= 0 -> 0, ix >= size - 1 -> size - 1, and mult = 0 at and beyond
+    both limits (ATen's clip_coordinates_set_grad).  A NaN coordinate stays NaN (no comparison holds)."""
+    xn = x32 if bound is None else norm32(x32, bound)
+    ix, mult = [], []
+    for a, size in enumerate(sizes_xyz):
+        i = index32(xn[:, a], size, align_corners).double()
+        m = mult32(None if bound is None else bound[a], size, align_corners).double().expand(i.shape[0]).clone()
+        if padding_mode == "border":
+            clip = (i <= 0) | (i >= size - 1)
+            i = torch.where(clip, i.clamp(0, size - 1), i)
+            m = torch.where(clip, torch.zeros_like(m), m)
+        ix.append(i)
+        mult.append(m)
+    return torch.stack(ix, 1), torch.stack(mult, 1)
+
+
+def _trilinear_jet_select(feature, ix):
+    """_trilinear_jet in fp64 with out-of-range corners SELECTED to zero (torch.where), as ATen skips them
+    (within_bounds_3d): a NaN or inf vertex reaches exactly the rows that have it as an in-range corner of their
+    cell, whatever its weight (0 x NaN = NaN there), and no other.  A row with a non-finite index coordinate has no
+    corner in range (axis_cell).  -> value (N,C), d value / d ix (N,C,3), sum_k |v_k| w_k (N,C), sum_k |v_k| over the
+    in-range corners (N,C), sum_k |v_k| x the other two axes' weights (N,C,3)."""
+    _, c, d, h, w = feature.shape
+    flat = feature.detach().reshape(c, d * h * w).double()
+    ix = ix.double()
+    bad = ~torch.isfinite(ix).all(1)
+    ix = torch.where(bad[:, None], torch.full_like(ix, -4.0), ix)
+    i0 = torch.floor(ix)
+    fr = ix - i0
+    i0 = i0.clamp(-2, max(w, h, d) + 1).long()
+    n = ix.shape[0]
+    zero = torch.zeros((), dtype=torch.float64)
+    val, yw, yc = (torch.zeros(n, c, dtype=torch.float64) for _ in range(3))
+    der, yd = (torch.zeros(n, c, 3, dtype=torch.float64) for _ in range(2))
+    for k in range(8):
+        o = (k & 1, (k >> 1) & 1, k >> 2)
+        xi, yi, zi = i0[:, 0] + o[0], i0[:, 1] + o[1], i0[:, 2] + o[2]
+        inb = (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h) & (zi >= 0) & (zi < d)
+        lin = ((zi.clamp(0, d - 1) * h + yi.clamp(0, h - 1)) * w + xi.clamp(0, w - 1))
+        v = torch.where(inb[:, None], flat[:, lin].t(), zero)
+        wt = [fr[:, a] if o[a] else 1 - fr[:, a] for a in range(3)]
+        sg = [1.0 if o[a] else -1.0 for a in range(3)]
+        w3 = (wt[0] * wt[1] * wt[2])[:, None]
+        val += v * w3
+        yw += v.abs() * w3
+        yc += v.abs()
+        for a, (p, q) in enumerate(((1, 2), (0, 2), (0, 1))):
+            der[:, :, a] += v * (sg[a] * wt[p] * wt[q])[:, None]
+            yd[:, :, a] += v.abs() * (wt[p] * wt[q])[:, None]
+    return val, der, yw, yc, yd
+
+
+class First64(NamedTuple):
+    """trilinear_first64's answer.  value (N,F) and grad_x (N,3); the absolute-value yardsticks of each:
+    value_w = sum_k |v_k| w_k and value_c = sum_k |v_k| over the in-range corners (N,F);
+    grad_w = sum_levels |mult| sum_c |gF_c| sum_k |v_ck| x (the other two axes' weights) and
+    grad_c = sum_levels |mult| sum_k sum_c |gF_c| |v_ck| (N,3)."""
+    value: torch.Tensor
+    grad_x: torch.Tensor
+    value_w: torch.Tensor
+    value_c: torch.Tensor
+    grad_w: torch.Tensor
+    grad_c: torch.Tensor
+
+
+def trilinear_first64(features, ix, gout, mults):
+    """The multi-level trilinear sample and its first coordinate gradient in fp64.  features: the levels (1,C,Z,Y,X);
+    ix: per level the (N,3) index coordinates (x, y, z) -- sample_index32's, the kernel's own, so that a row on a cell
+    plane is in the same cell on both sides -- or None for an ignored level (zero columns, nothing in grad_x); gout
+    (N,F) the cotangent of the value; mults: per level (N,3) d ix / d x (the gscale x mult of the kernels; 0 on an axis
+    the border clip holds).  The cell is the one of floor(ix) (ATen's); out-of-range corners are selected to zero, so
+    non-finite grid values propagate as in ATen (_trilinear_jet_select).  Rows with a non-finite index coordinate are
+    zero in both outputs."""
+    n = gout.shape[0]
+    F_ = sum(int(f.shape[1]) for f in features)
+    value, value_w, value_c = (torch.zeros(n, F_, dtype=torch.float64) for _ in range(3))
+    grad_x, grad_w, grad_c = (torch.zeros(n, 3, dtype=torch.float64) for _ in range(3))
+    foff = 0
+    for f, i, m in zip(features, ix, mults):
+        c = int(f.shape[1])
+        if i is not None:
+            val, der, yw, yc, yd = _trilinear_jet_select(f, i)
+            g = gout[:, foff:foff + c].double()
+            m = m.double()
+            value[:, foff:foff + c], value_w[:, foff:foff + c], value_c[:, foff:foff + c] = val, yw, yc
+            grad_x += m * (g[:, :, None] * der).sum(1)
+            grad_w += m.abs() * (g.abs()[:, :, None] * yd).sum(1)
+            grad_c += m.abs() * (g.abs() * yc).sum(1)[:, None]
+        foff += c
+    return First64(value, grad_x, value_w, value_c, grad_w, grad_c)
 
 
 def pair_latent_sums64(p, fsrc, feats_dst, bound, pose, loss_type="L2", ignore_mask=0, dtype=torch.float64,
