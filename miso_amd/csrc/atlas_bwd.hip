@@ -170,11 +170,13 @@ __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK 
 #pragma unroll
         for (int k = 0; k < 3; ++k) gxw[k] += (ps[k] * dxl[0] + ps[3 + k] * dxl[1]) + ps[6 + k] * dxl[2];
         if (b.pose_slots) {
-          const float xw[3] = {wx, wy, wz};
+          // dxl is zero outside the submap, but 0 x inf and 0 x NaN are not: a lane that is not inside (a NaN or inf
+          // world coordinate is inside nothing) takes part with a zero point
+          const float xw[3] = {inside ? wx : 0.f, inside ? wy : 0.f, inside ? wz : 0.f};
           float mine = 0.0f;      // lane i < 12 keeps element i of the wavefront's sum
 #pragma unroll
           for (int i = 0; i < 12; ++i) {
-            const float v = wave_sum(i < 9 ? dxl[i / 3] * xw[i % 3] : dxl[i - 9]);      // (dxl is zero outside the submap)
+            const float v = wave_sum(i < 9 ? dxl[i / 3] * xw[i % 3] : dxl[i - 9]);
             if (lane == i) mine = v;
           }
           if (lane < 12) __hip_atomic_fetch_add(s_pose + s * 12 + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);

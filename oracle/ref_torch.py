@@ -1158,3 +1158,180 @@ def adam6_64(param, g, m, v, t, lr, betas=(0.9, 0.999), eps=1e-8):
     v = b2 * v + (1 - b2) * g * g
     bc1, bc2 = 1 - b1 ** int(t), 1 - b2 ** int(t)
     return param - lr / bc1 * m / (v.sqrt() / math.sqrt(bc2) + eps), m, v
+
+
+# --------------------------------------------------------------------------- #
+# The fused atlas query and its backward (atlas_eval.hpp, atlas.hip, atlas_bwd.hip)
+# --------------------------------------------------------------------------- #
+def atlas_to_submap32(x32, poses12, bounds=None):
+    """The atlas kernels' frame change in fp32, operation for operation (atlas_eval.hpp, the loop of atlas_eval and
+    atlas_to_submap): per submap s and axis j, with p = poses12[s] = {R_submap_world row-major, t_submap_world},
+    v = x p[3j]; v = fma(y, p[3j+1], v); v = fma(z, p[3j+2], v); xl_j = v + p[9+j].
+    The source writes __fmul_rn / __fmaf_rn / __fadd_rn; the gfx950 code (hipcc -O3 -S) of atlas_sdf_kernel and of
+    atlas_trace_kernel is, per submap, three v_mul_f32, six v_fmac_f32 (y's three, then z's three) and three v_add_f32
+    in every instantiation; atlas_sdf_bwd_kernel, in atlas_mean and again in its per-submap loop, forms row 0 with
+    v_mul_f32 / two v_fmac_f32 / v_add_f32 and rows 1 and 2 as a pair with v_pk_mul_f32, two v_pk_fma_f32 and
+    v_pk_add_f32 -- per component the same four operations in the same order.  Nothing is contracted with the
+    translation or reassociated, and the bound test is six ordered compares (v_cmp_ge_f32 / v_cmp_le_f32), so a NaN
+    coordinate is outside.
+    x32 (N,3), poses12 (S,12) fp32 -> xl (S,N,3) fp32 and, with ``bounds`` (per submap (3,2) rows [min, max]), the
+    inclusive in-bound mask (N,S): min <= xl <= max on every axis in fp32 (coords_in_bound).  A NaN or inf world
+    coordinate gives a NaN or inf xl on every axis it reaches (inf x 0 = NaN) and is inside nothing.  A membership that
+    differs from the kernel's on one row: look at that row for the double rounding of _fma32 first."""
+    x = torch.as_tensor(x32, dtype=torch.float32).reshape(-1, 3)
+    p = torch.as_tensor(poses12, dtype=torch.float32).reshape(-1, 12)
+    xl = torch.empty(p.shape[0], x.shape[0], 3, dtype=torch.float32)
+    for s in range(p.shape[0]):
+        for j in range(3):
+            v = x[:, 0] * p[s, 3 * j]
+            v = _fma32(x[:, 1], p[s, 3 * j + 1], v)
+            v = _fma32(x[:, 2], p[s, 3 * j + 2], v)
+            xl[s, :, j] = v + p[s, 9 + j]
+    if bounds is None:
+        return xl
+    b = torch.as_tensor(bounds, dtype=torch.float32).reshape(-1, 3, 2)
+    inside = ((xl >= b[:, None, :, 0]) & (xl <= b[:, None, :, 1])).all(2)
+    return xl, inside.t().contiguous()
+
+
+def _trilinear_scatter64(shape, ix, g):
+    """The transpose of _trilinear_jet_select's value: rows g (N,C) fp64 at index coordinates ix (N,3) added into a
+    dense (1,C,D,H,W) fp64 gradient, vertex k of a row's cell receiving g w_k, out-of-range corners and rows with a
+    non-finite ix nothing.  -> (gradient, the same sum over |g| w_k)."""
+    _, c, d, h, w = shape
+    ix = ix.double()
+    bad = ~torch.isfinite(ix).all(1)
+    ix = torch.where(bad[:, None], torch.full_like(ix, -4.0), ix)
+    i0 = torch.floor(ix)
+    fr = ix - i0
+    i0 = i0.clamp(-2, max(w, h, d) + 1).long()
+    out, mag = (torch.zeros(d * h * w, c, dtype=torch.float64) for _ in range(2))
+    for k in range(8):
+        o = (k & 1, (k >> 1) & 1, k >> 2)
+        xi, yi, zi = i0[:, 0] + o[0], i0[:, 1] + o[1], i0[:, 2] + o[2]
+        inb = (xi >= 0) & (xi < w) & (yi >= 0) & (yi < h) & (zi >= 0) & (zi < d)
+        lin = ((zi.clamp(0, d - 1) * h + yi.clamp(0, h - 1)) * w + xi.clamp(0, w - 1))
+        wt = [fr[:, a] if o[a] else 1 - fr[:, a] for a in range(3)]
+        term = torch.where(inb[:, None], g * (wt[0] * wt[1] * wt[2])[:, None], torch.zeros((), dtype=torch.float64))
+        out.index_add_(0, lin, term)
+        mag.index_add_(0, lin, term.abs())
+    back = lambda t: t.t().reshape(1, c, d, h, w)
+    return back(out), back(mag)
+
+
+class Atlas64(NamedTuple):
+    """atlas64's answer.  Every ``*_y`` is the absolute-value yardstick of the field before it: the same sums with |.| of
+    every term."""
+    xl: torch.Tensor            # (S,N,3) fp32: atlas_to_submap32
+    inside: torch.Tensor        # (N,S) bool
+    count: torch.Tensor         # (N,) int64
+    feat: torch.Tensor          # (N,F) the mean feature row
+    feat_y: torch.Tensor        # (N,F) sum_s value_w_s / max(count, 1)
+    sdf: torch.Tensor           # (N,) the decoder on the mean
+    sdf_y: torch.Tensor
+    sdf_zero: torch.Tensor      # () the decoder on the zero row
+    tie: torch.Tensor           # (N,) bool: a pre-activation of either layer within ``tie`` of zero
+    gsdf: torch.Tensor          # (N,) the cotangent used (zero on the tie rows under zero_ties)
+    dfeat: torch.Tensor         # (N,F) d mean / max(count, 1): the row every inside submap's levels receive
+    dxl: torch.Tensor           # (S,N,3) d sdf-sum / d x_local per submap (zero where not inside)
+    dxl_y: torch.Tensor
+    gx: torch.Tensor            # (N,3) sum_s R_s^T dxl_s
+    gx_y: torch.Tensor
+    gposes: torch.Tensor        # (S,12) [sum_n dxl (x) x_world, sum_n dxl]
+    gposes_y: torch.Tensor
+    grids: list                 # per submap, per level: dense (1,C,Z,Y,X) fp64 (zeros: ignored level; None: locked)
+    grids_y: list
+
+
+def atlas64(features, bounds, poses12, x32, weights, biases, gsdf, ignore=None, locked=(), inside=None, tie=1e-6,
+            zero_ties=False):
+    """The fused atlas query (atlas.hip) and its backward (atlas_bwd.hip) in fp64.  Membership and the local coordinates
+    are the fp32 restatement's (atlas_to_submap32); everything after is fp64 at the kernel's own fp32 index coordinates
+    (sample_index32, _trilinear_jet_select): the masked mean over the submaps a row is inside (count 0 -> divisor 1),
+    a three-linear ReLU decoder on it, and for the cotangent gsdf (N,) of the SDF: d feats_s = d mean / count for every
+    submap the row is inside (the mask and the count are constants), d x_local per submap by the sampler's first
+    derivative, gx = sum_s R_s^T dxl_s, gposes[s] = [sum_n dxl (x) x_world, sum_n dxl] over the rows inside s, and the
+    dense level gradients.  features: per submap the levels (1,C,Z,Y,X); bounds: per submap (3,2); poses12 (S,12);
+    ignore: per submap None or one bool per level (zero columns, nothing in dxl, a zero gradient); locked: the submaps
+    without level gradients (None); inside: a membership (N,S) to use INSTEAD of the restatement's (planted faults);
+    zero_ties: rows with a pre-activation of either layer within ``tie`` of zero carry a zero cotangent (the ReLU's
+    derivative is the kernel's to choose there: the rule of tests/test_split_precision.py).
+    Rows with a non-finite world coordinate are inside nothing: a zero feature row, the zero-row SDF, exactly zero
+    gradients, and no term in any sum.  Yardsticks: Atlas64."""
+    f64 = torch.float64
+    x32 = torch.as_tensor(x32, dtype=torch.float32).reshape(-1, 3)
+    poses12 = torch.as_tensor(poses12, dtype=torch.float32).reshape(-1, 12)
+    S, n = poses12.shape[0], x32.shape[0]
+    xl, member = atlas_to_submap32(x32, poses12, bounds)
+    if inside is not None:
+        member = inside
+    member = member & torch.isfinite(x32).all(1)[:, None]
+    count = member.sum(1)
+    den = count.clamp(min=1).to(f64)[:, None]
+    F_ = sum(int(f.shape[1]) for f in features[0])
+    nan = torch.tensor(float("nan"), dtype=f64)
+    jets = []                                   # per submap, per level: None or (c0, C, ix, mult, der, yd)
+    total, total_y = torch.zeros(n, F_, dtype=f64), torch.zeros(n, F_, dtype=f64)
+    for s in range(S):
+        row, c0 = [], 0
+        for l, f in enumerate(features[s]):
+            c = int(f.shape[1])
+            if ignore is not None and ignore[s] is not None and ignore[s][l]:
+                row.append(None)
+            else:
+                ix, mult = sample_index32(xl[s], bounds[s], (f.shape[4], f.shape[3], f.shape[2]))
+                ix = torch.where(member[:, s, None], ix, nan)
+                val, der, yw, _, yd = _trilinear_jet_select(f, ix)
+                total[:, c0:c0 + c] += val
+                total_y[:, c0:c0 + c] += yw
+                row.append((c0, c, ix, mult, der, yd))
+            c0 += c
+        jets.append(row)
+    feat, feat_y = total / den, total_y / den
+    W = [w.detach().to(f64) for w in weights]
+    B = [torch.zeros(w.shape[0], dtype=f64) if b is None else b.detach().to(f64) for w, b in zip(W, biases)]
+    assert len(W) == 3, "the fused decoders have one hidden layer pair: three linears"
+    pre1 = feat @ W[0].t() + B[0]
+    pre2 = torch.relu(pre1) @ W[1].t() + B[1]
+    sdf = (torch.relu(pre2) @ W[2].t() + B[2])[:, 0]
+    y1 = feat_y @ W[0].abs().t() + B[0].abs()
+    y2 = y1 @ W[1].abs().t() + B[1].abs()
+    sdf_y = (y2 @ W[2].abs().t() + B[2].abs())[:, 0]
+    sdf_zero = (torch.relu(torch.relu(B[0]) @ W[1].t() + B[1]) @ W[2].t() + B[2])[0]
+    sdf = torch.where(count == 0, sdf_zero, sdf)      # (one value for the zero row, whatever the batch it is summed in)
+    near = torch.minimum(pre1.abs().min(1).values, pre2.abs().min(1).values) < tie
+    # backward
+    g = torch.as_tensor(gsdf).detach().reshape(-1).to(f64)
+    if zero_ties:
+        g = torch.where(near, torch.zeros_like(g), g)
+    on1, on2 = (pre1 > 0).to(f64), (pre2 > 0).to(f64)
+    dmean = ((((g[:, None] * W[2]) * on2) @ W[1]) * on1) @ W[0]
+    dmean_y = ((((g.abs()[:, None] * W[2].abs()) * on2) @ W[1].abs()) * on1) @ W[0].abs()
+    dfe, dfe_y = dmean / den, dmean_y / den
+    dxl, dxl_y = torch.zeros(S, n, 3, dtype=f64), torch.zeros(S, n, 3, dtype=f64)
+    grids, grids_y = [], []
+    for s in range(S):
+        gs, gys = [], []
+        for l, f in enumerate(features[s]):
+            j = jets[s][l]
+            if j is None:
+                gs.append(None if s in locked else torch.zeros(f.shape, dtype=f64))
+                gys.append(None if s in locked else torch.zeros(f.shape, dtype=f64))
+                continue
+            c0, c, ix, mult, der, yd = j
+            dxl[s] += mult * (dfe[:, c0:c0 + c, None] * der).sum(1)
+            dxl_y[s] += mult.abs() * (dfe_y[:, c0:c0 + c, None] * yd).sum(1)
+            if s in locked:
+                gs.append(None), gys.append(None)
+            else:
+                a, b = _trilinear_scatter64(f.shape, ix, dfe[:, c0:c0 + c])
+                gs.append(a), gys.append(_trilinear_scatter64(f.shape, ix, dfe_y[:, c0:c0 + c])[0])
+        grids.append(gs), grids_y.append(gys)
+    Rm = poses12[:, :9].to(f64).view(S, 3, 3)                        # x_local = R x_world + t
+    gx = torch.einsum("sjk,snj->nk", Rm, dxl)
+    gx_y = torch.einsum("sjk,snj->nk", Rm.abs(), dxl_y)
+    xw = torch.where(torch.isfinite(x32), x32, torch.zeros_like(x32)).to(f64)      # (rows inside nothing add no term)
+    gposes = torch.cat((torch.einsum("snj,nk->sjk", dxl, xw).reshape(S, 9), dxl.sum(1)), 1)
+    gposes_y = torch.cat((torch.einsum("snj,nk->sjk", dxl_y, xw.abs()).reshape(S, 9), dxl_y.sum(1)), 1)
+    return Atlas64(xl, member, count, feat, feat_y, sdf, sdf_y, sdf_zero, near, g, dfe, dxl, dxl_y, gx, gx_y, gposes, gposes_y,
+                   grids, grids_y)
