@@ -19,6 +19,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MISO_HIP_LIB") or os.path.join(_HERE, "libmiso_hip.so")
 
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hip.h")
+HASH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hash.h")     # hash-indexed levels: tables of its own
 
 
 class HeaderError(RuntimeError):
@@ -57,11 +58,14 @@ def _declarator(text, where):
     return (m[1] or "").strip(), m[2], m[3]
 
 
-def read_header(text):
+def read_header(text, base=None):
     """The C ABI as miso_hip.h declares it: (constants, structs, signatures), keyed by the C names.  The header is
-    plain C in a narrow style (see its declarations); anything outside that style raises HeaderError, never skips."""
+    plain C in a narrow style (see its declarations); anything outside that style raises HeaderError, never skips.
+    base: (constants, structs) of the header this one includes -- its declarations may use them; what comes back is
+    this header's own."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     consts, structs, sigs, code, cpp_only = {}, {}, {}, [], False
+    known_consts, known_structs = (dict(base[0]), dict(base[1])) if base else ({}, {})
     for line in text.split("\n"):
         d = line.split()
         if not d or not d[0].startswith("#"):
@@ -73,7 +77,7 @@ def read_header(text):
             m = re.fullmatch(r"#define (MISO_\w+) (\d+)u?", " ".join(d))
             if m:
                 consts[m[1]] = int(m[2])
-            elif d[1:] != ["MISO_HIP_H"] and not d[1].startswith("MISO_TILES_XYZ("):  # guard; ops.pack_tiles
+            elif d[1:] not in (["MISO_HIP_H"], ["MISO_HASH_H"]) and not d[1].startswith("MISO_TILES_XYZ("):  # guards; ops.pack_tiles
                 raise HeaderError(f"cannot read '{line.strip()}'")
         elif d[:2] == ["#ifdef", "__cplusplus"] or d[0] == "#endif":
             cpp_only = d[0] == "#ifdef"
@@ -81,9 +85,9 @@ def read_header(text):
             raise HeaderError(f"cannot read '{line.strip()}'")
 
     def count(n, where):
-        if not n.isdigit() and n not in consts:
+        if not n.isdigit() and n not in consts and n not in known_consts:
             raise HeaderError(f"{where}: unknown array size '{n}'")
-        return int(consts.get(n, n))
+        return int(consts.get(n, known_consts.get(n, n)))
 
     def struct(m):
         name, fields = m[2], []
@@ -93,7 +97,7 @@ def read_header(text):
                 spec = s if i == 0 else spec
                 if bool(s) != (i == 0) or (i and "*" in spec):   # in C a '*' belongs to one declarator, not to the list
                     raise HeaderError(f"{name}: cannot split '{decl.strip()}'")
-                t = _ctype(spec, structs, f"{name}.{field}")
+                t = _ctype(spec, {**known_structs, **structs}, f"{name}.{field}")
                 fields.append((field, t if n is None else t * count(n, name)))
         camel = "".join(w.capitalize() for w in name[len("miso_"):-len("_t")].split("_"))
         structs[name] = type(camel, (C.Structure,), {"_fields_": fields})
@@ -107,7 +111,8 @@ def read_header(text):
         args = [] if m[3].strip() == "void" else [_declarator(a, m[2]) for a in m[3].split(",")]
         if any(n is not None or not spec for spec, _, n in args):
             raise HeaderError(f"{m[2]}: cannot read '{m[3].strip()}'")
-        sigs[m[2]] = (_ctype(m[1], structs, m[2]), [_ctype(spec, structs, f"{m[2]}({arg})") for spec, arg, _ in args])
+        every = {**known_structs, **structs}
+        sigs[m[2]] = (_ctype(m[1], every, m[2]), [_ctype(spec, every, f"{m[2]}({arg})") for spec, arg, _ in args])
     return consts, structs, sigs
 
 
@@ -116,6 +121,11 @@ with open(HEADER_PATH) as _f:
 # the names the package uses: MISO_F_CROWDED -> F_CROWDED, MISO_MAX_LEVELS -> MAX_LEVELS, miso_lm_track_t -> LmTrack ...
 globals().update({k[len("MISO_"):]: v for k, v in CONSTANTS.items()})
 globals().update({s.__name__: s for s in STRUCTS.values()})
+# include/miso_hash.h, read the same way into tables of its own: SIGNATURES / STRUCTS describe miso_hip.h alone
+with open(HASH_HEADER_PATH) as _f:
+    HASH_CONSTANTS, HASH_STRUCTS, HASH_SIGNATURES = read_header(_f.read(), base=(CONSTANTS, STRUCTS))
+globals().update({k[len("MISO_"):]: v for k, v in HASH_CONSTANTS.items()})      # HASH_LOG2_MIN, HASH_LOG2_MAX
+globals().update({s.__name__: s for s in HASH_STRUCTS.values()})                # HashLevel, HashGrid
 
 _lib = None
 
@@ -130,7 +140,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C miso_amd/csrc`.  miso_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **HASH_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -54,6 +54,7 @@ def pairwise_loss_latent(grid_atlas: GridAtlas, data_loader, src_id: int, dst_id
     same points mapped src -> world -> dst, over the channels of levels 0..level."""
     key = f'align_latent_level{level}_{src_id}_{dst_id}'
     assert src_id < grid_atlas.num_submaps and dst_id < grid_atlas.num_submaps
+    grid_atlas.require_regular_levels("latent alignment (pairwise_loss_latent)")
     if covariance_thresh is not None:
         raise NotImplementedError
     end_ch = fdim * (level + 1)
@@ -396,12 +397,14 @@ def align_multiple_submaps_hierarchical(grid_atlas: GridAtlas, dataset, level_it
     subsampling, atlas on the GPU, single process.  It differs from the reference in one thing: the stage draws
     ``finetune_batches`` batches ONCE and every iteration and pair works on that fixed sample set, where the reference
     draws a fresh batch per pair and iteration.  Anything else takes the op-by-op loop, with a log line saying why."""
-    grid_atlas.precompute_coordinates_for_alignment()
+    levels = range(grid_atlas.num_levels) if latent_levels is None else latent_levels
+    regular = all(getattr(s, 'grid_type', 'regular') == 'regular' for s in grid_atlas.submaps)
+    if regular or len(levels) > 0:      # (a hash atlas with no latent stage asked: the SDF fine-tune alone, no vertex lists)
+        grid_atlas.precompute_coordinates_for_alignment()
     info = dict()
     cpu_total = gpu_total = 0
     common = dict(lr=lr, submap_pairs=submap_pairs, pose_reg_weight=pose_reg_weight, pose_thresh_m=pose_thresh_m,
                   pose_thresh_rad=pose_thresh_rad, verbose=verbose, save_iterations=save_iterations)
-    levels = range(grid_atlas.num_levels) if latent_levels is None else latent_levels
     for lvl in levels:
         latent = latent_loss_for_level(grid_atlas, lvl, align_weight=align_weight, align_loss=align_loss,
                                        use_bound=use_bound, stability_thresh=stability_thresh,

@@ -87,6 +87,9 @@ class Encoder(torch.nn.Module):
         return self.grid_corrections[self.correction_key(model_id, level)]
 
     def register_grid_model(self, model: GridNet):
+        if getattr(model, 'grid_type', 'regular') != 'regular':
+            raise ValueError(f"the encoder initialisation predicts dense (1, C, Z, Y, X) corrections: it needs grid.type "
+                             f"'regular', not {model.grid_type!r}")
         model_id = len(self.grid_nets)
         self.grid_nets[self.grid_key(model_id)] = model
         for level in range(model.num_levels):

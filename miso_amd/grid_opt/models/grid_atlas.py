@@ -283,6 +283,8 @@ class GridAtlas(BaseNet):
         if not probe.is_cuda:
             return None
         subs = [self.get_submap(s) for s in self.active_submaps]
+        if any(getattr(sm, 'grid_type', 'regular') != 'regular' for sm in subs):
+            return None      # hash-indexed levels are (R, C) tables: the per-submap loop serves them, nothing is re-laid
         for sm in subs:
             for g in sm.features:
                 # (a pickle the reference wrote holds NCDHW features; the kernels read channels-last rows: re-laid once)
@@ -471,10 +473,18 @@ class GridAtlas(BaseNet):
         """Voxel centres of the finest level, built once per submap (the reference rebuilds
         the tensor on the host for every pair in every alignment iteration)."""
         cache = self.__dict__.setdefault('_vertex_cache', {})
-        grid = self.get_submap(submap_id).features[-1]
-        key = (submap_id, tuple(grid.feature.shape))
+        levels = self.get_submap(submap_id).features
+        grid, centres = levels[-1], None
+        if hasattr(grid, 'cell_centres'):
+            # hash-indexed levels: the voxel centres from the geometry (a table has no vertex list), of the finest level
+            # that is still a lattice one can list -- at most 2^24 voxels; the share of a regular lattice inside a box
+            # hardly depends on its pitch
+            fit = [g for g in levels if g.dims[0] * g.dims[1] * g.dims[2] <= 1 << 24]
+            grid = fit[-1] if fit else levels[0]
+            centres = grid.cell_centres
+        key = (submap_id, tuple(grid.feature.shape), getattr(grid, 'dims', None))
         if key not in cache:
-            cache[key] = grid.vertex_positions().to(self.device)
+            cache[key] = (centres or grid.vertex_positions)().to(self.device)
         return cache[key]
 
     # ---- parameter groups ---------------------------------------------------------------------------
@@ -494,9 +504,17 @@ class GridAtlas(BaseNet):
         return [p for s in self.submaps for p in s.params_at_level(level)]
 
     # ---- alignment coordinate cache -------------------------------------------------------------------
+    def require_regular_levels(self, what: str):
+        """Latent alignment compares vertex lists of dense levels; a hash-indexed submap has none."""
+        kinds = {getattr(s, 'grid_type', 'regular') for s in self.submaps} - {'regular'}
+        if kinds:
+            raise ValueError(f"{what} needs regular levels (grid.type 'regular'); this atlas has grid.type "
+                             f"{sorted(kinds)[0]!r} submaps")
+
     def precompute_coordinates_for_alignment(self, norm_thresh=1e-5):
         """Per (submap, level): voxel centres whose multi-level feature norm exceeds the
         threshold, cached detached (reference :565-579)."""
+        self.require_regular_levels("latent alignment (precompute_coordinates_for_alignment)")
         self._coords_for_alignment = dict()
         for level in range(self.num_levels):
             for s in range(self.num_submaps):

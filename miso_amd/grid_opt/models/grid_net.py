@@ -12,7 +12,7 @@ import miso_amd.grid_opt.utils.utils as utils
 import miso_amd.grid_opt.utils.utils_geometry as utils_geometry
 from miso_amd import ops
 from .base_net import BaseNet
-from .grid_modules import FeatureGrid
+from .grid_modules import FeatureGrid, HashFeatureGrid
 from .modules import MLPNet
 
 logger = logging.getLogger(__name__)
@@ -42,8 +42,13 @@ class GridNet(BaseNet):
         self.second_order_grid_sample = bool(g.get('second_order_grid_sample', False))
         self.fdim = g['feature_dim']
         self.grid_type = g['type']
-        if self.grid_type != 'regular':
-            raise ValueError(f"grid type {self.grid_type!r} is outside the MI355X hot path (regular grids only)")
+        if self.grid_type not in ('regular', 'hash'):
+            raise ValueError(f"grid type {self.grid_type!r} is outside the MI355X hot path ('regular' or 'hash')")
+        # 'hash': every level is looked up through a table of at most 2^log2_hashmap_size rows (HashFeatureGrid); the
+        # queries go through ops.hash_encode and every fused route declines (_fused_decoder)
+        level_cls, extra = FeatureGrid, {}
+        if self.grid_type == 'hash':
+            level_cls, extra = HashFeatureGrid, dict(log2_hashmap_size=int(g.get('log2_hashmap_size', 19)))
         self.features = nn.ModuleList()
         self.feature_stability = nn.ModuleList()
         self.bases = nn.ModuleList()
@@ -52,12 +57,12 @@ class GridNet(BaseNet):
             cell = g['base_cell_size'] / (g['per_level_scale'] ** level)
             self.cell_sizes.append(cell)
             common = dict(d=self.d, bound=self.bound, cell_size=cell, dtype=self.dtype,
-                          second_order_grid_sample=self.second_order_grid_sample)
-            self.features.append(FeatureGrid(fdim=self.fdim, name=f"feat-{level}",
-                                             initial_feature=self.initial_features.get(level),
-                                             init_stddev=g['init_stddev'], **common))
-            self.feature_stability.append(FeatureGrid(fdim=1, name=f"stab-{level}", initial_feature=None,
-                                                      init_stddev=0.0, **common))
+                          second_order_grid_sample=self.second_order_grid_sample, **extra)
+            self.features.append(level_cls(fdim=self.fdim, name=f"feat-{level}",
+                                           initial_feature=self.initial_features.get(level),
+                                           init_stddev=g['init_stddev'], **common))
+            self.feature_stability.append(level_cls(fdim=1, name=f"stab-{level}", initial_feature=None,
+                                                    init_stddev=0.0, **common))
             self.bases.append(None)
         self.ignore_level_ = np.zeros(self.num_levels).astype(bool)
 
@@ -270,6 +275,8 @@ class GridNet(BaseNet):
         a decoder with trainable weights qualifies too -- ops.sdf_fused then forms their gradients in HIP."""
         if self.decoder is None or not self.pos_invariant or not isinstance(self.decoder, MLPNet):
             return None
+        if self.grid_type != 'regular':      # the fused kernels address dense levels: forward is encode + MLPNet
+            return None
         pack = self.decoder.decoder_pack(trainable=trainable)
         if pack is None:
             return None
@@ -326,7 +333,15 @@ class GridNet(BaseNet):
             gx, _ = ops.sdf_bwd_raw(xd, feats, meta, pack, torch.ones_like(sdf), mask, True, [False] * len(feats))
             return sdf, gx
         xr = x.detach().clone().requires_grad_(True)
-        sdf = self(xr)
+        if self.grid_type == 'hash' and x.is_cuda:
+            # forward() with the tables detached: autograd.grad below asks for x alone, but the encode's backward cannot see
+            # that and would zero-fill and scatter a gradient for every unlocked table, to have it dropped
+            grids = list(self.features)
+            feats = ops.hash_encode(xr, [g.feature.detach() for g in grids], grids[0].grid_meta(self.ignore_level_),
+                                    [g.dims for g in grids], grids[0].log2_hashmap_size)
+            sdf = utils.grid_decode(feats, xr, self.decoder, self.pos_invariant)
+        else:
+            sdf = self(xr)
         (gx,) = torch.autograd.grad(sdf, xr, torch.ones_like(sdf))
         return sdf.detach(), gx.detach()
 

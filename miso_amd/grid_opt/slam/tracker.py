@@ -88,6 +88,8 @@ class Tracker:
             return False
         pack = grid._fused_decoder()
         if pack is None:
+            if getattr(grid, 'grid_type', 'regular') != 'regular':
+                logger.info(f"Tracking window: grid.type {grid.grid_type!r} has no fused window, the Trainer runs.")
             return False
         kf_key = optimize_kfs[0]
         kf = grid.pose_key_to_id(f'KF{kf_key}')

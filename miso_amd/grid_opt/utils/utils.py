@@ -65,6 +65,8 @@ def grid_interp_regular(reg_grids, x, ignore_level=None):
     All levels are sampled by ONE kernel launch (no per-level launch, no cat)."""
     grids = list(reg_grids)
     meta = grids[0].grid_meta(_ignore_mask(len(grids), ignore_level))
+    if hasattr(grids[0], 'log2_hashmap_size'):      # HashFeatureGrid levels (grid.type 'hash'): tables, one launch as well
+        return ops.hash_encode(x, [g.feature for g in grids], meta, [g.dims for g in grids], grids[0].log2_hashmap_size)
     return ops.encode(x, [g.feature for g in grids], meta)
 
 

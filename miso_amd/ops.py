@@ -356,6 +356,124 @@ def grid_sample_3d(input: torch.Tensor, grid: torch.Tensor, padding_mode: str = 
 
 
 # --------------------------------------------------------------------------- #
+# hash-indexed levels (include/miso_hash.h, csrc/hash_encode.hip)
+# --------------------------------------------------------------------------- #
+HASH_CHANNELS = (1, 2, 4, 8)
+
+
+class NoDoubleBackward(RuntimeError):
+    """A backward with create_graph=True went through ops.hash_encode, which has a first backward only."""
+
+
+def hash_level_rows(dims, log2: int):
+    """(rows, dense-indexed?) of a level of dims = (X, Y, Z) vertices behind a table of at most 2**log2 rows: X Y Z rows
+    in the dense grid's flat channels-last order where that fits, else 2**log2 hashed rows (miso_hash_rows)."""
+    X, Y, Z = (int(v) for v in dims)
+    log2 = int(log2)
+    if not 1 <= min(X, Y, Z) <= max(X, Y, Z) < 1 << 31:
+        raise ValueError(f"a level has 1 .. 2^31 - 1 vertices per axis, got {(X, Y, Z)}")
+    if not _lib.HASH_LOG2_MIN <= log2 <= _lib.HASH_LOG2_MAX:
+        raise ValueError(f"log2_hashmap_size must be {_lib.HASH_LOG2_MIN}..{_lib.HASH_LOG2_MAX}, got {log2}")
+    rows = int(_lib.load().miso_hash_rows(X, Y, Z, log2))      # the rule is the library's (hash_index.hpp)
+    return rows, rows == X * Y * Z
+
+
+def _fill_hash_grid(tables, meta: GridMeta, dims, log2: int, grads=None) -> "_lib.HashGrid":
+    if not 1 <= len(tables) <= _lib.MAX_LEVELS:
+        raise ValueError(f"1..{_lib.MAX_LEVELS} levels supported, got {len(tables)}")
+    if len(dims) != len(tables):
+        raise ValueError(f"{len(tables)} tables but {len(dims)} level shapes")
+    g = _lib.HashGrid()
+    g.flags = meta.flags
+    g.bound_min[:] = meta.bound_min
+    g.bound_max[:] = meta.bound_max
+    g.n_levels = len(tables)
+    g.ignore_mask = meta.ignore_mask
+    for l, (t, d) in enumerate(zip(tables, dims)):
+        rows, dense = hash_level_rows(d, log2)
+        if t.ndim != 2 or t.shape[0] != rows or t.shape[1] not in HASH_CHANNELS or not t.is_contiguous():
+            raise ValueError(f"level {l}: the table of a {tuple(d)} level at log2 {log2} is ({rows}, C) contiguous with C in "
+                             f"{HASH_CHANNELS}, got {tuple(t.shape)} with strides {t.stride()}")
+        lv = g.level[l]
+        lv.table = t.data_ptr()
+        if grads is not None and grads[l] is not None:
+            assert grads[l].shape == t.shape and grads[l].is_contiguous(), "grad must share the table layout"
+            lv.grad = grads[l].data_ptr()
+        lv.rows, lv.C = rows, t.shape[1]
+        lv.X, lv.Y, lv.Z = (int(v) for v in d)
+        lv.log2_rows = 0 if dense else int(log2)
+    return g
+
+
+def hash_encode_fwd_raw(x, tables, meta: GridMeta, dims, log2: int) -> torch.Tensor:
+    _require_hip(x, *tables)
+    x = x.contiguous()
+    n = x.shape[0]
+    out = torch.empty((n, sum(int(t.shape[1]) for t in tables)), device=x.device, dtype=torch.float32)
+    g = _fill_hash_grid(tables, meta, dims, log2)
+    _lib.check(_lib.load().miso_hash_encode_fwd(C.byref(g), _ptr(x), n, _ptr(out), out.shape[1], _stream(x)),
+               "miso_hash_encode_fwd")
+    return out
+
+
+def hash_encode_bwd_raw(x, tables, meta: GridMeta, dims, log2: int, gout, need_x: bool, need_t: Sequence[bool]):
+    """-> (grad_x or None, [table gradient or None per level]): one launch for whatever is asked."""
+    _require_hip(x, gout, *tables)
+    x = x.contiguous()
+    gout = _rows(gout)
+    n = x.shape[0]
+    grads = [torch.zeros_like(t) if w else None for t, w in zip(tables, need_t)]
+    gx = torch.empty((n, 3), device=x.device, dtype=torch.float32) if need_x else None
+    if need_x or any(need_t):
+        g = _fill_hash_grid(tables, meta, dims, log2, grads)
+        ld = gout.stride(0) if n else sum(int(t.shape[1]) for t in tables)
+        _lib.check(_lib.load().miso_hash_encode_bwd(C.byref(g), _ptr(x), n, _ptr(gout), ld, _ptr(gx), _stream(x)),
+                   "miso_hash_encode_bwd")
+    return gx, grads
+
+
+class _HashEncodeBackward(torch.autograd.Function):
+    """The first backward as a Function of its own, so that a create_graph=True backward meets a node that says what
+    is missing (NoDoubleBackward) instead of silently treating the gradients as constants."""
+
+    @staticmethod
+    def forward(ctx, gout, x, meta, dims, log2, need_x, need_t, *tables):
+        gx, grads = hash_encode_bwd_raw(x, tables, meta, dims, log2, gout, need_x, need_t)
+        return (gx, *grads)
+
+    @staticmethod
+    def backward(ctx, *_):
+        raise NoDoubleBackward("ops.hash_encode has no second backward: hash-indexed levels train with first-order losses "
+                               "(grad_method 'finitediff' for the Eikonal term), not create_graph=True")
+
+
+class _HashEncode(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, meta, dims, log2, *tables):
+        out = hash_encode_fwd_raw(x, tables, meta, dims, log2)
+        ctx.save_for_backward(x, *tables)
+        ctx.meta, ctx.dims, ctx.log2 = meta, dims, log2
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, *tables = ctx.saved_tensors
+        need_x = ctx.needs_input_grad[0]
+        need_t = tuple(ctx.needs_input_grad[4:])
+        if _ONLY_X and torch.is_grad_enabled():
+            need_t = (False,) * len(tables)            # (coordinate_gradient_only: see there)
+        res = _HashEncodeBackward.apply(gout, x, ctx.meta, ctx.dims, ctx.log2, need_x, need_t, *tables)
+        return (res[0], None, None, None, *res[1:])
+
+
+def hash_encode(x: torch.Tensor, tables: Sequence[torch.Tensor], meta: GridMeta, dims, log2: int) -> torch.Tensor:
+    """(N,3) metres -> (N, sum C): ``encode`` for levels whose vertices are looked up through a table.  tables[l] is
+    (rows, C) with rows = hash_level_rows(dims[l], log2); dims[l] = (X, Y, Z) vertices of level l over the bound of
+    ``meta``.  Sampled exactly as ``encode`` samples the dense level of that shape; first-order autograd only."""
+    return _HashEncode.apply(x, meta, tuple(tuple(int(v) for v in d) for d in dims), int(log2), *tables)
+
+
+# --------------------------------------------------------------------------- #
 # fused encode + decoder
 # --------------------------------------------------------------------------- #
 class DecoderPack:
