@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("MISO_HIP_LIB") or os.path.join(_HERE, "libmiso_hip.so
 
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hip.h")
 HASH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hash.h")     # hash-indexed levels: tables of its own
+HASH_SDF_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hash_sdf.h")     # their fused SDF query: likewise
 
 
 class HeaderError(RuntimeError):
@@ -77,7 +78,7 @@ def read_header(text, base=None):
             m = re.fullmatch(r"#define (MISO_\w+) (\d+)u?", " ".join(d))
             if m:
                 consts[m[1]] = int(m[2])
-            elif d[1:] not in (["MISO_HIP_H"], ["MISO_HASH_H"]) and not d[1].startswith("MISO_TILES_XYZ("):  # guards; ops.pack_tiles
+            elif d[1:] not in (["MISO_HIP_H"], ["MISO_HASH_H"], ["MISO_HASH_SDF_H"]) and not d[1].startswith("MISO_TILES_XYZ("):  # guards; ops.pack_tiles
                 raise HeaderError(f"cannot read '{line.strip()}'")
         elif d[:2] == ["#ifdef", "__cplusplus"] or d[0] == "#endif":
             cpp_only = d[0] == "#ifdef"
@@ -126,6 +127,10 @@ with open(HASH_HEADER_PATH) as _f:
     HASH_CONSTANTS, HASH_STRUCTS, HASH_SIGNATURES = read_header(_f.read(), base=(CONSTANTS, STRUCTS))
 globals().update({k[len("MISO_"):]: v for k, v in HASH_CONSTANTS.items()})      # HASH_LOG2_MIN, HASH_LOG2_MAX
 globals().update({s.__name__: s for s in HASH_STRUCTS.values()})                # HashLevel, HashGrid
+# include/miso_hash_sdf.h: function declarations over the types of the two headers above, again in tables of its own
+with open(HASH_SDF_HEADER_PATH) as _f:
+    HASH_SDF_CONSTANTS, HASH_SDF_STRUCTS, HASH_SDF_SIGNATURES = read_header(
+        _f.read(), base=({**CONSTANTS, **HASH_CONSTANTS}, {**STRUCTS, **HASH_STRUCTS}))
 
 _lib = None
 
@@ -140,7 +145,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C miso_amd/csrc`.  miso_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **HASH_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **HASH_SIGNATURES, **HASH_SDF_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "align.hpp"
+#include "checks.hpp"
 #include "grad_plan.hpp"
 #include "launch.hpp"
 #include "version.inc"
@@ -35,11 +36,7 @@ namespace {
 inline bool fits32(int64_t n) { return n < ((int64_t)1 << 31); }            // a size the 32-bit index math holds
 inline bool fits_fp32_count(int64_t n) { return n < ((int64_t)1 << 24); }   // ... an fp32 counter holds exactly
 inline bool fits_voxel_key(int64_t n) { return n < ((int64_t)1 << 22); }    // ... the index field of the voxel sort key holds
-template <class... P> inline bool aligned(uintptr_t bytes, const P*... p) {   // NULL passes: optional pointers
-  return ((... | (uintptr_t)p) & (bytes - 1)) == 0;
-}
-template <class... P> inline bool all_set(const P*... p) { return (... && (p != nullptr)); }
-template <class... P> inline bool set_if(int64_t n, const P*... p) { return n <= 0 || all_set(p...); }   // non-NULL when n > 0
+// (aligned, all_set, set_if: checks.hpp)
 inline bool mapping_loss_ok(int loss_type) { return loss_type == 1 || loss_type == 2; }                  // L1 | L2
 
 int convert_grid(const miso_grid_t* in, GridK* out, bool need_data, bool* vec4) {

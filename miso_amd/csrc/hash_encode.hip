@@ -12,66 +12,9 @@
 // 24 derivative weights beside 32 gathered values.
 #include <string.h>
 
-#include "common.hpp"
-#include "hash_index.hpp"
+#include "hash_grid.hpp"
 
 namespace miso {
-
-struct HashLevelK {
-  const float* table;
-  float* grad;
-  int32_t X, Y, Z, C;
-  uint32_t mask;    // rows - 1 of a hashed level, 0 = dense-indexed
-  int32_t foff;     // first output column of this level
-};
-
-struct HashGridK {
-  int32_t n_levels;
-  uint32_t ignore_mask;
-  uint32_t flags;
-  int32_t F;
-  float bmin[3], bmax[3];
-  HashLevelK lv[MISO_MAX_LEVELS];
-};
-
-// The cell of a point in a hashed level: make_cell reads the three sizes of a LevelK and nothing else.
-__device__ __forceinline__ Cell hash_cell(const HashGridK& g, const HashLevelK& lv, float px, float py, float pz,
-                                          Axis (&a)[3]) {
-  LevelK shape = {};
-  shape.X = lv.X; shape.Y = lv.Y; shape.Z = lv.Z;
-  return level_cell(g.bmin, g.bmax, g.flags, shape, px, py, pz, a);
-}
-
-// The rows of the eight corners.  A corner out of range is never hashed: as in encode.hip (reread_in_range) it re-reads
-// an in-range corner of its own cell under its zero weight, so a non-finite table entry reaches the rows it reaches in
-// the dense encode and no others.  false: no corner in range (outside the level, a NaN or inf coordinate).
-__device__ __forceinline__ bool corner_rows(const Cell& c, const HashLevelK& lv, const bool (&inb)[8], uint32_t (&row)[8]) {
-  uint32_t safe = 0;
-  bool any_in = false;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    row[k] = inb[k] ? hash_row(c.i0 + (k & 1), c.j0 + ((k >> 1) & 1), c.k0 + (k >> 2), lv.X, lv.Y, lv.mask) : 0u;
-    safe = inb[k] ? row[k] : safe;
-    any_in = any_in || inb[k];
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k) row[k] = inb[k] ? row[k] : safe;
-  return any_in;
-}
-
-// V consecutive floats of a row, as one load (V = 4: 16 bytes; the tables are 16-byte aligned and a row is C floats)
-template <int V>
-__device__ __forceinline__ void load_vec(const float* __restrict__ p, float (&v)[V]) {
-  if constexpr (V == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else if constexpr (V == 2) {
-    const float2 t = *reinterpret_cast<const float2*>(p);
-    v[0] = t.x; v[1] = t.y;
-  } else {
-    v[0] = *p;
-  }
-}
 
 // v w + acc with the product rounded before the sum (see fwd_level)
 __device__ __forceinline__ float mul_then_add(float v, float w, float acc) {
@@ -226,13 +169,9 @@ __global__ __launch_bounds__(256) void hash_bwd_tables_kernel(HashGridK g, const
   }
 }
 
-}  // namespace miso
-
-using namespace miso;
-
 namespace {
-
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }      // NULL passes: optional pointers
+}  // namespace
 
 // Every check of a grid argument, then the kernel-side copy.  need_table: the call reads the tables.
 int convert_hash_grid(const miso_hash_grid_t* in, HashGridK* out, bool need_table) {
@@ -267,10 +206,23 @@ int convert_hash_grid(const miso_hash_grid_t* in, HashGridK* out, bool need_tabl
   return MISO_OK;
 }
 
-// (the table-gradient launch has up to 8 lanes per point)
-inline bool blocks_fit(int64_t n) { return n < ((int64_t)1 << 56) && (n * 8 + 255) / 256 < ((int64_t)1 << 31); }
+hipError_t launch_hash_bwd(const HashGridK& g, const float* x, int64_t n, const float* gf, int64_t ld, float* gx,
+                           hipStream_t s) {
+  if (gx) {
+    hash_bwd_x_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g, x, n, gf, ld, gx);
+    if (hipError_t e = hipGetLastError()) return e;
+  }
+  int cmax = 0;      // the widest level that takes a gradient sizes the launch: n C lanes per level
+  for (int l = 0; l < g.n_levels; ++l)
+    if (g.lv[l].grad && !((g.ignore_mask >> l) & 1u) && g.lv[l].C > cmax) cmax = g.lv[l].C;
+  if (cmax == 0) return hipSuccess;
+  hash_bwd_tables_kernel<<<dim3((unsigned)((n * cmax + 255) / 256), (unsigned)g.n_levels), 256, 0, s>>>(g, x, n, gf, ld);
+  return hipGetLastError();
+}
 
-}  // namespace
+}  // namespace miso
+
+using namespace miso;
 
 extern "C" {
 
@@ -299,17 +251,7 @@ int miso_hash_encode_bwd(const miso_hash_grid_t* grid, const float* x, int64_t n
   if (ld_g < g.F) return MISO_E_BADARG;
   if (!blocks_fit(n)) return MISO_E_TOOLARGE;
   if (n == 0) return MISO_OK;
-  if (grad_x) {
-    hash_bwd_x_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(g, x, n, grad_feats, ld_g, grad_x);
-    if (hipError_t e = hipGetLastError()) return (int)e;
-  }
-  int cmax = 0;      // the widest level that takes a gradient sizes the launch: n C lanes per level
-  for (int l = 0; l < g.n_levels; ++l)
-    if (g.lv[l].grad && !((g.ignore_mask >> l) & 1u) && g.lv[l].C > cmax) cmax = g.lv[l].C;
-  if (cmax == 0) return MISO_OK;
-  hash_bwd_tables_kernel<<<dim3((unsigned)((n * cmax + 255) / 256), (unsigned)g.n_levels), 256, 0, (hipStream_t)stream>>>(
-      g, x, n, grad_feats, ld_g);
-  return (int)hipGetLastError();
+  return (int)launch_hash_bwd(g, x, n, grad_feats, ld_g, grad_x, (hipStream_t)stream);
 }
 
 }  // extern "C"

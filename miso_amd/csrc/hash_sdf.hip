@@ -1,0 +1,228 @@
+// Fused SDF query of hash-indexed levels (include/miso_hash_sdf.h): hash_sdf_fwd_kernel is sdf_fwd_kernel
+// (sdf_fused.hip) with the corner rows looked up through the tables of hash_grid.hpp -- the same persistent wavefronts
+// of 64 points, the same weights in LDS at the same PackLayout offsets, the same decoder chains and epilogue; only the
+// gather differs: hash_cell + corner_rows + 16-byte row loads, summed corner by corner with fma (the PIN_FMA form of
+// decoder.hpp's gather_level).  A table that lists a dense level's vertices therefore gives sdf_fwd_kernel's bits, sign
+// words included.  Points arrive in the caller's order; there is no binned form and no loss.
+//
+// The backward is composed, not written: the decoder's backward chain depends on the grid through C and L alone, so
+// launch_sdf_bwd in its lean form (no gradient buffer on any level, no grad_x: nothing of x or the grid is touched)
+// writes the d-feat rows (n, F), and hash_encode.hip's two backward kernels consume them as their grad_feats.
+//
+// Registers of hash_sdf_fwd_kernel<C, L, H, NH, SPLIT> (gfx950, hipcc -O3, -Rpass-analysis=kernel-resource-usage): VGPRs
+// and the wavefronts per SIMD they allow; no AGPRs, scratch 0 and no static LDS in every instantiation (the LDS is
+// dynamic: launch_hash_fwd_t sizes it as launch_fwd_t does).  __launch_bounds__(256, 2) asks for the two workgroups
+// per CU that the 512-block cap launches; the H = 32 decoders over C = 4 fit three or four.
+//   shape            split: VGPRs (waves)   exact: VGPRs (waves)
+//   <4, 1, 32, 1>     142 (3)                117 (4)
+//   <4, 1, 64, 1>     210 (2)                192 (2)
+//   <4, 2, 32, 1>     162 (3)                125 (4)
+//   <4, 2, 64, 1>     224 (2)                208 (2)
+//   <4, 3, 64, 1>     236 (2)                218 (2)
+//   <4, 4, 64, 1>     251 (2)                228 (2)
+//   <8, 1, 64, 1>     214 (2)                198 (2)
+//   <8, 2, 64, 1>     232 (2)                212 (2)
+//   <8, 3, 64, 1>     248 (2)                216 (2)
+//   <8, 4, 64, 1>     256 (2)                226 (2)
+//   <8, 3, 32, 1>     194 (2)                170 (2)
+#include <string.h>
+
+#include "checks.hpp"
+#include "hash_grid.hpp"
+#include "sdf_fused.hpp"
+#include "../../include/miso_hash_sdf.h"
+
+namespace miso {
+
+template <int C, int L, int H, int NH, bool SPLIT>
+__global__ __launch_bounds__(256, MISO_FWD_OCC) void hash_sdf_fwd_kernel(HashGridK g, const float* __restrict__ packed,
+                                                                        const float* __restrict__ x, int64_t n,
+                                                                        float* __restrict__ sdf,
+                                                                        uint32_t* __restrict__ mask) {
+  constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2;
+  constexpr int MW = (NH + 1) * RT;  // mask words per lane
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const PackLayout pl(F, H, NH);
+  // LDS as sdf_fwd_kernel stages it: the exact form the fp32 forward pack [0, fwd_end); the split form the bf16x3
+  // forward block [s_w0, s_fwd_end) followed by the biases and output weights [o_b0, fwd_end)
+  const int n_split = pl.s_fwd_end - pl.s_w0;
+  if (SPLIT) {
+    for (int i = threadIdx.x * 4; i < n_split; i += blockDim.x * 4)
+      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
+    for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
+      *reinterpret_cast<float4*>(smem + n_split + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
+  } else {
+    for (int i = threadIdx.x * 4; i < pl.fwd_end; i += blockDim.x * 4)
+      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + i);
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
+  const int64_t nchunks = (n + 63) / 64;
+  const float* w0p = smem + pl.o_w0;
+  const float* whp = smem + pl.o_wh;
+  const float* b0 = smem + pl.o_b0;
+  const float* bh = smem + pl.o_bh;
+  const float* wo = smem + pl.o_wo;
+  const uint32_t* s_fwd = reinterpret_cast<const uint32_t*>(smem);      // SPLIT
+  const float* s_bias = smem + n_split;                                 // SPLIT
+  const float bo = SPLIT ? s_bias[pl.o_bo - pl.o_b0] : smem[pl.o_bo];
+
+  ChunkSched sched(nchunks, wave, 4, false);
+  for (int64_t chunk = sched.cur; chunk < sched.end; chunk += sched.step) {
+    asm volatile("" ::: "memory");  // see sdf_fwd_kernel: the LDS reads of biases / weights stay inside the loop
+    const int64_t p = chunk * 64 + lane;
+    const bool valid = p < n;
+    float f[2 * KS0];
+#pragma unroll
+    for (int i = 0; i < 2 * KS0; ++i) f[i] = 0.0f;
+    memory_phase(true);
+    if (valid) {
+      const float px = x[p * 3 + 0], py = x[p * 3 + 1], pz = x[p * 3 + 2];
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        if ((g.ignore_mask >> l) & 1u) continue;      // zeros
+        const HashLevelK& lv = g.lv[l];
+        Axis a[3];
+        const Cell c = hash_cell(g, lv, px, py, pz, a);
+        bool inb[8];
+        float w[8];
+        uint32_t row[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          inb[k] = corner_in(c, k);
+          w[k] = corner_weight<0>(c, k, inb[k]).w;
+        }
+        if (!corner_rows(c, lv, inb, row)) continue;      // no corner in range: zeros, nothing is read
+#pragma unroll
+        for (int q = 0; q < C; q += 4) {
+          float v[8][4];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) load_vec<4>(lv.table + (size_t)row[k] * C + q, v[k]);
+#pragma unroll
+          for (int k = 0; k < 8; ++k)      // corner by corner, as gather_level sums
+#pragma unroll
+            for (int e = 0; e < 4; ++e) f[l * C + q + e] = __builtin_fmaf(v[k][e], w[k], f[l * C + q + e]);
+        }
+      }
+    }
+    memory_phase(false);
+    uint32_t mw[MW];
+    float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
+    if constexpr (SPLIT) {
+      u32x4 no_mask[H / 16][2];
+      decoder_fwd_split<F, H, NH, false, true, false>(s_fwd, s_bias, lane, f, mw, no_mask, p0, p1, poison);
+    } else {
+      decoder_fwd_exact<F, H, NH>(w0p, whp, b0, bh, wo, lane, f, mw, p0, p1);
+    }      // exact fp32 chains
+    p0 += __shfl_xor(p0, 32);
+    p1 += __shfl_xor(p1, 32);
+    const float sdf_v = SPLIT ? ((hi ? p1 : p0) + bo) + poison : (hi ? p1 : p0) + bo;
+    if (valid) sdf[p] = sdf_v;
+    if (mask) {
+      uint32_t* mo = mask + (chunk * 64 + lane) * MW;
+#pragma unroll
+      for (int i = 0; i < MW; ++i) mo[i] = mw[i];
+    }
+  }
+}
+
+template <int C, int L, int H, int NH>
+static hipError_t launch_hash_fwd_t(FusedShape<C, L, H, NH>, const HashGridK& g, const float* packed, bool exact,
+                                    const float* x, int64_t n, float* sdf, uint32_t* mask, hipStream_t s) {
+  PackLayout pl(C * L, H, NH);
+  const bool split = use_split(exact);
+  size_t lds = (size_t)(split ? pl.s_fwd_end - pl.s_w0 + (pl.n_bias() + 3) / 4 * 4 : (pl.fwd_end + 3) / 4 * 4) * sizeof(float);
+  int64_t nchunks = (n + 63) / 64;
+  unsigned blocks = (unsigned)((nchunks + 3) / 4);
+  if (blocks > 512u) blocks = 512u;      // persistent: two workgroups per CU
+  auto k = split ? hash_sdf_fwd_kernel<C, L, H, NH, true> : hash_sdf_fwd_kernel<C, L, H, NH, false>;
+  hipError_t e = allow_lds((const void*)k, lds);
+  if (e != hipSuccess) return e;
+  k<<<blocks, 256, lds, s>>>(g, packed, x, n, sdf, mask);
+  return hipGetLastError();
+}
+
+}  // namespace miso
+
+using namespace miso;
+
+namespace {
+
+// grid + decoder as the kernels take them: (C, L, H, NH) is the fused kernels' table key
+struct HashSdfCall { HashGridK g; int C, L, H, NH; };
+
+int hash_sdf_call(HashSdfCall* f, const miso_hash_grid_t* grid, const miso_mlp_t* m, bool need_table) {
+  if (int rc = convert_hash_grid(grid, &f->g, need_table)) return rc;
+  if (!m) return MISO_E_BADARG;
+  if (m->n_linear < 2 || m->n_linear > MISO_MAX_LINEAR) return MISO_E_UNSUPPORTED;
+  const HashGridK& g = f->g;
+  for (int l = 0; l < g.n_levels; ++l)
+    if (g.lv[l].C != g.lv[0].C) return MISO_E_UNSUPPORTED;
+  if (m->in_dim != g.F || m->out_dim != 1) return MISO_E_UNSUPPORTED;
+  f->C = g.lv[0].C; f->L = g.n_levels; f->H = m->hidden_dim; f->NH = m->n_linear - 2;
+  return fused_shape_supported(f->C, f->L, f->H, f->NH) ? MISO_OK : MISO_E_UNSUPPORTED;      // (C in {4, 8}: the table's)
+}
+
+// what both launching entries ask of the decoder arguments and the batch, before the grid is looked at
+int hash_sdf_args(const float* packed, uint32_t decoder_flags, int64_t n) {
+  if (n < 0 || !set_if(n, packed) || !aligned(16, packed)) return MISO_E_BADARG;      // packed is read with 16-byte loads
+  return (decoder_flags & ~MISO_F_EXACT_F32) ? MISO_E_BADARG : MISO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int miso_hash_sdf_supported(const miso_hash_grid_t* grid, const miso_mlp_t* mlp) {
+  HashSdfCall f;
+  return hash_sdf_call(&f, grid, mlp, false) == MISO_OK ? 1 : 0;
+}
+
+int64_t miso_hash_sdf_bwd_workspace_floats(const miso_hash_grid_t* grid, int64_t n) {
+  HashGridK g;
+  if (n <= 0 || !blocks_fit(n) || convert_hash_grid(grid, &g, false) != MISO_OK) return 0;
+  return n * g.F;
+}
+
+int miso_hash_sdf_fwd(const miso_hash_grid_t* grid, const miso_mlp_t* mlp, const float* packed, uint32_t decoder_flags,
+                      const float* x, int64_t n, float* sdf, uint32_t* relu_mask, void* stream) {
+  if (int rc = hash_sdf_args(packed, decoder_flags, n)) return rc;
+  if (!set_if(n, x, sdf)) return MISO_E_BADARG;
+  HashSdfCall f;
+  if (int rc = hash_sdf_call(&f, grid, mlp, true)) return rc;
+  if (!blocks_fit(n)) return MISO_E_TOOLARGE;
+  if (n == 0) return MISO_OK;
+  const bool exact = (decoder_flags & MISO_F_EXACT_F32) != 0;
+  return (int)with_fused_shape(f.C, f.L, f.H, f.NH, hipErrorInvalidValue, [&](auto shape) {
+    return launch_hash_fwd_t(shape, f.g, packed, exact, x, n, sdf, relu_mask, (hipStream_t)stream);
+  });
+}
+
+int miso_hash_sdf_bwd(const miso_hash_grid_t* grid, const miso_mlp_t* mlp, const float* packed, uint32_t decoder_flags,
+                      const float* x, int64_t n, const float* grad_sdf, const uint32_t* relu_mask, float* grad_x,
+                      float* workspace, void* stream) {
+  if (int rc = hash_sdf_args(packed, decoder_flags, n)) return rc;
+  if (!set_if(n, x, grad_sdf, relu_mask, workspace) || !aligned(16, workspace)) return MISO_E_BADARG;
+  HashSdfCall f;
+  if (int rc = hash_sdf_call(&f, grid, mlp, grad_x != nullptr)) return rc;
+  if (!blocks_fit(n)) return MISO_E_TOOLARGE;
+  if (n == 0) return MISO_OK;
+  // The decoder's backward chain in its lean form: a grid of the same (C, L) whose levels carry no data and no gradient
+  // buffer, no grad_x -- sdf_bwd_kernel then reads grad_sdf and the sign words, writes the d-feat rows, and touches
+  // neither x nor a level.
+  GridK stub;
+  memset(&stub, 0, sizeof(stub));
+  stub.n_levels = f.L;
+  stub.ignore_mask = f.g.ignore_mask;
+  stub.flags = decoder_flags & MISO_F_EXACT_F32;
+  stub.xstride = 3;
+  stub.F = f.g.F;
+  for (int l = 0; l < f.L; ++l) { stub.lv[l].C = f.C; stub.lv[l].foff = l * f.C; }
+  hipStream_t st = (hipStream_t)stream;
+  if (hipError_t e = launch_sdf_bwd(f.C, f.L, f.H, f.NH, stub, packed, nullptr, n, grad_sdf, relu_mask, nullptr, true, nullptr,
+                                    workspace, 0u, false, st))
+    return (int)e;
+  return (int)launch_hash_bwd(f.g, x, n, workspace, f.g.F, grad_x, st);
+}
+
+}  // extern "C"

@@ -45,7 +45,10 @@ class GridNet(BaseNet):
         if self.grid_type not in ('regular', 'hash'):
             raise ValueError(f"grid type {self.grid_type!r} is outside the MI355X hot path ('regular' or 'hash')")
         # 'hash': every level is looked up through a table of at most 2^log2_hashmap_size rows (HashFeatureGrid); the
-        # queries go through ops.hash_encode and every fused route declines (_fused_decoder)
+        # queries go through ops.hash_encode and every fused route declines (_fused_decoder).  grid.hash_fused (default
+        # False; no meaning for 'regular'): forward() and sdf_and_gradient() of a hash net with a frozen decoder run the
+        # table gather and the decoder as one launch instead (_fused_hash_decoder, ops.hash_sdf_fused)
+        self.hash_fused = bool(g.get('hash_fused', False))
         level_cls, extra = FeatureGrid, {}
         if self.grid_type == 'hash':
             level_cls, extra = HashFeatureGrid, dict(log2_hashmap_size=int(g.get('log2_hashmap_size', 19)))
@@ -284,12 +287,35 @@ class GridNet(BaseNet):
         meta = self.features[0].grid_meta(self.ignore_level_)
         return pack if ops.sdf_fused_supported(feats, meta, pack) else None
 
+    def _hash_args(self, detach=False):
+        """(tables, meta, dims, log2) of a hash net as the ops.hash_* calls take them"""
+        grids = list(self.features)
+        return ([g.feature.detach() if detach else g.feature for g in grids], grids[0].grid_meta(self.ignore_level_),
+                [g.dims for g in grids], grids[0].log2_hashmap_size)
+
+    def _fused_hash_decoder(self):
+        """DecoderPack if grid.hash_fused is on and table gather + decoder can run as one kernel for this model
+        (ops.hash_sdf_fused: a hash grid, a position-invariant MLPNet with a frozen pack, tensors on the device, a shape
+        the kernels cover), else None.  _fused_decoder() stays None for a hash grid: the routes that ask it address
+        dense levels."""
+        if not getattr(self, 'hash_fused', False) or self.grid_type != 'hash':
+            return None
+        if self.decoder is None or not self.pos_invariant or not isinstance(self.decoder, MLPNet):
+            return None
+        pack = self.decoder.decoder_pack()
+        if pack is None:
+            return None
+        return pack if ops.hash_sdf_supported(*self._hash_args(), pack) else None
+
     def forward(self, x: torch.Tensor, noise_std=0):
         self._check_coords(x)
         pack = self._fused_decoder(trainable=_FUSED_WGRAD) if x.is_cuda else None
+        hpack = self._fused_hash_decoder() if pack is None and x.is_cuda else None
         if pack is not None:
             meta = self.features[0].grid_meta(self.ignore_level_)
             pred = ops.sdf_fused(x, [g.feature for g in self.features], meta, pack)
+        elif hpack is not None:
+            pred = ops.hash_sdf_fused(x, *self._hash_args(), hpack)
         else:
             feats = self.query_feature(x)
             pred = utils.grid_decode(feats, x, self.decoder, self.pos_invariant)
@@ -331,6 +357,13 @@ class GridNet(BaseNet):
             xd = x.detach().contiguous()
             sdf, mask = ops.sdf_fwd_raw(xd, feats, meta, pack, True)
             gx, _ = ops.sdf_bwd_raw(xd, feats, meta, pack, torch.ones_like(sdf), mask, True, [False] * len(feats))
+            return sdf, gx
+        hpack = self._fused_hash_decoder() if x.is_cuda else None
+        if hpack is not None:      # the same two calls over the tables: no autograd graph, no table gradient
+            args = self._hash_args(detach=True)
+            xd = x.detach().contiguous()
+            sdf, mask = ops.hash_sdf_fwd_raw(xd, *args, hpack, True)
+            gx, _, _ = ops.hash_sdf_bwd_raw(xd, *args, hpack, torch.ones_like(sdf), mask, True, [False] * len(args[0]))
             return sdf, gx
         xr = x.detach().clone().requires_grad_(True)
         if self.grid_type == 'hash' and x.is_cuda:

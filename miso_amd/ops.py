@@ -769,6 +769,116 @@ def sdf_mask_buffer(pack: DecoderPack, n: int, device) -> torch.Tensor:
     return torch.empty(((n + 63) // 64) * 64 * sdf_mask_words(pack), device=device, dtype=torch.int32)
 
 
+# --------------------------------------------------------------------------- #
+# fused gather + decoder over hash-indexed levels (include/miso_hash_sdf.h, csrc/hash_sdf.hip)
+# --------------------------------------------------------------------------- #
+def _hash_sdf_grid(tables, meta: GridMeta, dims, log2: int, grads=None):
+    """-> (HashGrid, decoder_flags): the decoder arithmetic travels beside the grid, whose flags are the sampling flags
+    alone -- the process-wide exact_fp32() state, or F_EXACT_F32 in ``meta.flags`` as the dense route reads it."""
+    g = _fill_hash_grid(tables, meta, dims, log2, grads)
+    exact = _EXACT_F32 or bool(meta.flags & _lib.F_EXACT_F32)
+    g.flags = meta.flags & ~_lib.F_EXACT_F32
+    return g, (_lib.F_EXACT_F32 if exact else 0)
+
+
+def hash_sdf_supported(tables, meta: GridMeta, dims, log2: int, pack: DecoderPack) -> bool:
+    """Does hash_sdf_fused cover these tables with this decoder (miso_hash_sdf_supported)?"""
+    if not all(t.is_cuda for t in tables):
+        return False
+    m, _ = pack.get()
+    if m is None:
+        return False
+    g, _ = _hash_sdf_grid(tables, meta, dims, log2)
+    return bool(_lib.load().miso_hash_sdf_supported(C.byref(g), C.byref(m)))
+
+
+def hash_sdf_fwd_raw(x, tables, meta: GridMeta, dims, log2: int, pack: DecoderPack, want_mask: bool, out=None, mask=None):
+    """sdf_fwd_raw over hash-indexed levels, one launch (miso_hash_sdf_fwd): -> (sdf (N,1), ReLU sign words or None)."""
+    _require_hip(x, *tables)
+    m, packed = pack.require()
+    x = x.contiguous()
+    n = x.shape[0]
+    sdf = torch.empty((n, 1), device=x.device, dtype=torch.float32) if out is None else out
+    if not want_mask:
+        mask = None
+    elif mask is None:
+        mask = sdf_mask_buffer(pack, n, x.device)
+    g, dflags = _hash_sdf_grid(tables, meta, dims, log2)
+    _lib.check(_lib.load().miso_hash_sdf_fwd(C.byref(g), C.byref(m), _ptr(packed), dflags, _ptr(x), n, _ptr(sdf), _ptr(mask),
+                                             _stream(x)), "miso_hash_sdf_fwd")
+    return sdf, mask
+
+
+def hash_sdf_bwd_raw(x, tables, meta: GridMeta, dims, log2: int, pack: DecoderPack, gsdf, mask, need_x: bool,
+                     need_t: Sequence[bool]):
+    """First backward of hash_sdf_fwd_raw (miso_hash_sdf_bwd): -> (grad_x or None, [table gradient or None per level],
+    d-feat rows (N,F)).  The decoder's backward chain writes the rows; grad_x and the (zero-filled, then added-to) table
+    gradients are hash_encode_bwd_raw's two launches over them."""
+    _require_hip(x, gsdf, *tables)
+    m, packed = pack.require()
+    x = x.contiguous()
+    gsdf = gsdf.contiguous()
+    n = x.shape[0]
+    grads = [torch.zeros_like(t) if w else None for t, w in zip(tables, need_t)]
+    gx = torch.empty((n, 3), device=x.device, dtype=torch.float32) if need_x else None
+    rows = torch.empty((n, sum(int(t.shape[1]) for t in tables)), device=x.device, dtype=torch.float32)
+    g, dflags = _hash_sdf_grid(tables, meta, dims, log2, grads)
+    _lib.check(_lib.load().miso_hash_sdf_bwd(C.byref(g), C.byref(m), _ptr(packed), dflags, _ptr(x), n, _ptr(gsdf), _ptr(mask),
+                                             _ptr(gx), _ptr(rows), _stream(x)), "miso_hash_sdf_bwd")
+    return gx, grads, rows
+
+
+class _HashSdfFusedBackward(torch.autograd.Function):
+    """The first backward as a Function of its own (see _HashEncodeBackward): a create_graph=True backward meets a node
+    that says what is missing."""
+
+    @staticmethod
+    def forward(ctx, gsdf, x, mask, meta, dims, log2, pack, need_x, need_t, *tables):
+        gx, grads, _ = hash_sdf_bwd_raw(x, tables, meta, dims, log2, pack, gsdf, mask, need_x, need_t)
+        return (gx, *grads)
+
+    @staticmethod
+    def backward(ctx, *_):
+        raise NoDoubleBackward("ops.hash_sdf_fused has no second backward: hash-indexed levels train with first-order "
+                               "losses (grad_method 'finitediff' for the Eikonal term), not create_graph=True")
+
+
+class _HashSdfFused(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, meta, dims, log2, pack, *tables):
+        need = any(ctx.needs_input_grad)
+        sdf, mask = hash_sdf_fwd_raw(x, tables, meta, dims, log2, pack, need)
+        if need:
+            ctx.save_for_backward(x, mask, *tables)
+            # the sign words belong to the arithmetic they were formed with: the backward runs with the same one
+            ctx.meta = GridMeta(meta.bound_min, meta.bound_max, meta.ignore_mask,
+                                meta.flags | (_lib.F_EXACT_F32 if _EXACT_F32 else 0))
+            ctx.dims, ctx.log2, ctx.pack = dims, log2, pack
+        return sdf
+
+    @staticmethod
+    def backward(ctx, gsdf):
+        x, mask, *tables = ctx.saved_tensors
+        need_x = ctx.needs_input_grad[0]
+        need_t = tuple(ctx.needs_input_grad[5:])
+        if _ONLY_X and torch.is_grad_enabled():
+            need_t = (False,) * len(tables)            # (coordinate_gradient_only: see there)
+        res = _HashSdfFusedBackward.apply(gsdf, x, mask, ctx.meta, ctx.dims, ctx.log2, ctx.pack, need_x, need_t, *tables)
+        return (res[0], None, None, None, None, *res[1:])
+
+
+def hash_sdf_fused(x: torch.Tensor, tables: Sequence[torch.Tensor], meta: GridMeta, dims, log2: int,
+                   pack: DecoderPack) -> torch.Tensor:
+    """(N,3) metres -> sdf (N,1): hash_encode + the frozen decoder as one launch, with a first backward to x and to the
+    tables (hash_sdf_bwd_raw).  The decoder's weights are constants here: a pack with a trainable tensor is refused
+    (NotCovered) -- the weight-gradient kernel reads dense grids, so that combination stays op by op."""
+    _require_hip(x, *tables)
+    if pack.trainable():
+        raise NotCovered("ops.hash_sdf_fused takes a frozen decoder: the weight gradients of a trainable one are formed "
+                         "op by op (hash_encode + the decoder under autograd)", _lib.E_UNSUPPORTED, "hash_sdf_fused")
+    return _HashSdfFused.apply(x, meta, tuple(tuple(int(v) for v in d) for d in dims), int(log2), pack, *tables)
+
+
 def _check_loss_args(n: int, loss_inputs, loss_slots, n_live=None):
     """Label rows (n,4), per-workgroup sums (LOSS_SLOTS,2) and, for a padded batch, the live count: one device int32."""
     assert loss_inputs.shape == (n, 4) and loss_inputs.is_contiguous()
