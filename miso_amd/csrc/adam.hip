@@ -76,6 +76,11 @@ __device__ __forceinline__ void st4_stream(float* q, const float4& v) {
   __builtin_nontemporal_store(t, reinterpret_cast<f4v*>(q));
 }
 
+// any bit set: a float4 of gradients that are all == 0 holds a -0
+__device__ __forceinline__ bool has_bits(const float4& t) {
+  return (__float_as_uint(t.x) | __float_as_uint(t.y) | __float_as_uint(t.z) | __float_as_uint(t.w)) != 0u;
+}
+
 template <bool ZERO>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g,
                                                   float* __restrict__ m, float* __restrict__ v,
@@ -164,7 +169,8 @@ __device__ __forceinline__ void adam_active_body(float* __restrict__ p, float* _
       *reinterpret_cast<float4*>(p + i) = pp[u];
       st4_stream(m + i, mm[u]);
       st4_stream(v + i, vv[u]);
-      if (ZERO && any) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+      // (a stepped chunk is left +0 as the dense kernel leaves it: a -0 counts as no gradient, but it is cleared)
+      if (ZERO && (any || has_bits(gg[u]))) *reinterpret_cast<float4*>(g + i) = make_float4(0.f, 0.f, 0.f, 0.f);
     }
   }
   // the ragged end (numel % 256 elements: up to four chunks, the last one partial), element-wise by the first wavefront
@@ -311,7 +317,8 @@ __device__ __forceinline__ void adam_touched_body(float* __restrict__ p, float* 
             *reinterpret_cast<float4*>(m + ii[u]) = mm[u];
             *reinterpret_cast<float4*>(v + ii[u]) = vv[u];
           }
-          if (ZERO && tt[u]) *reinterpret_cast<float4*>(g + ii[u]) = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (ZERO && (tt[u] || (on[u] && !skip && has_bits(gg[u]))))
+            *reinterpret_cast<float4*>(g + ii[u]) = make_float4(0.f, 0.f, 0.f, 0.f);
         }
       }
     }

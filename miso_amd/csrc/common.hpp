@@ -191,7 +191,10 @@ struct AdamScalars {
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamScalars& a) {
 #pragma clang fp contract(off)   // one rounding per torch op, and the same bits from every kernel that inlines this
-  m = m + a.one_minus_b1 * (g - m);                 // exp_avg.lerp_(grad, 1 - beta1)
+  // exp_avg.lerp_(grad, 1 - beta1).  torch's lerp has two forms, chosen by the weight: with the first alone a
+  // beta1 <= 0.5 loses a gradient below an ulp of m (beta1 = 0, m = 1, g = 1e-20: 0 where torch keeps g)
+  const float w = a.one_minus_b1, d = g - m;
+  m = w < 0.5f ? m + w * d : g - d * (1.0f - w);
   v = v * a.b2 + (a.one_minus_b2 * g) * g;          // mul_(beta2).addcmul_(grad, grad, 1 - beta2)
   float denom = sqrtf(v) / a.bc2_sqrt + a.eps;      // (sqrt / bias_correction2_sqrt).add_(eps)
   p = p + (a.neg_step_size * m) / denom;            // addcdiv_(exp_avg, denom, value=-step_size)

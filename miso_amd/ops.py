@@ -2137,6 +2137,17 @@ class HostTotal:
         return float(self.ring[self.slot, 0])
 
 
+def adam_table_rows(beta1: float, beta2: float) -> Optional[int]:
+    """Rows of AdamDeviceStep's table: steps until beta^t <= 1e-9 for the larger beta, and 64 more.  From there on
+    1 - beta^t is 1 in fp32 and further: the scalars no longer change (20 777 for beta2 = 0.999, constant from step
+    16 628), so a count past the table reads its last row.  None: a beta >= 1 never gets there."""
+    import math
+    bmax = max(beta1, beta2)
+    if bmax <= 0:
+        return 64
+    return int(math.ceil(math.log(1e-9) / math.log(bmax))) + 64 if bmax < 1 else None
+
+
 class AdamDeviceStep:
     """What a captured step needs to take Adam steps without new kernel arguments: the table of per-step scalars
     (computed by the library's own host code, so the captured step equals the launch-by-launch one bit for bit) and the
@@ -2144,11 +2155,8 @@ class AdamDeviceStep:
     MAX_ROWS = 1 << 21
 
     def __init__(self, lr: float, beta1: float, beta2: float, eps: float, device, count: int = 0):
-        import math
         self.hyper = (float(lr), float(beta1), float(beta2), float(eps))
-        bmax = max(beta1, beta2)
-        # rows until beta^t has left fp32 (the scalars no longer change): 20 700 for beta2 = 0.999
-        rows = 64 if bmax <= 0 else int(math.ceil(math.log(1e-9) / math.log(bmax))) + 64 if bmax < 1 else None
+        rows = adam_table_rows(beta1, beta2)
         if rows is None or rows > self.MAX_ROWS:
             raise ValueError(f"betas {beta1, beta2}: the step-scalar table would need {rows} rows")
         host = torch.empty((rows, 6), dtype=torch.float32)
