@@ -21,6 +21,7 @@ LIB_PATH = os.environ.get("MISO_HIP_LIB") or os.path.join(_HERE, "libmiso_hip.so
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hip.h")
 HASH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hash.h")     # hash-indexed levels: tables of its own
 HASH_SDF_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hash_sdf.h")     # their fused SDF query: likewise
+HASH_TRACE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "miso_hash_trace.h")     # sphere tracing through them
 
 
 class HeaderError(RuntimeError):
@@ -78,7 +79,7 @@ def read_header(text, base=None):
             m = re.fullmatch(r"#define (MISO_\w+) (\d+)u?", " ".join(d))
             if m:
                 consts[m[1]] = int(m[2])
-            elif d[1:] not in (["MISO_HIP_H"], ["MISO_HASH_H"], ["MISO_HASH_SDF_H"]) and not d[1].startswith("MISO_TILES_XYZ("):  # guards; ops.pack_tiles
+            elif d[1:] not in (["MISO_HIP_H"], ["MISO_HASH_H"], ["MISO_HASH_SDF_H"], ["MISO_HASH_TRACE_H"]) and not d[1].startswith("MISO_TILES_XYZ("):  # guards; ops.pack_tiles
                 raise HeaderError(f"cannot read '{line.strip()}'")
         elif d[:2] == ["#ifdef", "__cplusplus"] or d[0] == "#endif":
             cpp_only = d[0] == "#ifdef"
@@ -131,6 +132,10 @@ globals().update({s.__name__: s for s in HASH_STRUCTS.values()})                
 with open(HASH_SDF_HEADER_PATH) as _f:
     HASH_SDF_CONSTANTS, HASH_SDF_STRUCTS, HASH_SDF_SIGNATURES = read_header(
         _f.read(), base=({**CONSTANTS, **HASH_CONSTANTS}, {**STRUCTS, **HASH_STRUCTS}))
+# include/miso_hash_trace.h: likewise
+with open(HASH_TRACE_HEADER_PATH) as _f:
+    HASH_TRACE_CONSTANTS, HASH_TRACE_STRUCTS, HASH_TRACE_SIGNATURES = read_header(
+        _f.read(), base=({**CONSTANTS, **HASH_CONSTANTS}, {**STRUCTS, **HASH_STRUCTS}))
 
 _lib = None
 
@@ -145,7 +150,7 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "or `make -C miso_amd/csrc`.  miso_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in {**SIGNATURES, **HASH_SIGNATURES, **HASH_SDF_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **HASH_SIGNATURES, **HASH_SDF_SIGNATURES, **HASH_TRACE_SIGNATURES}.items():
         fn = getattr(lib, name)  # AttributeError = ABI mismatch, fail loudly
         fn.restype = res
         fn.argtypes = args

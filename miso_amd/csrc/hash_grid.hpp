@@ -1,7 +1,7 @@
 // A hash-indexed grid as the kernels take it (include/miso_hash.h): the kernel-side structs, the cell of a point in a
-// level, the rows of its eight corners and the row load -- shared by hash_encode.hip (encode, its backward) and
-// hash_sdf.hip (the gather in front of the fused decoder) -- and the host functions of hash_encode.hip that hash_sdf.hip
-// calls: the checks of a grid argument and the backward launches.
+// level, the rows of its eight corners and the row load -- shared by hash_encode.hip (encode, its backward),
+// hash_sdf.hip and hash_trace.hip (the gather in front of the fused decoder: hash_gather_row) -- and the host functions
+// those files call across: the checks of a grid argument, of a (grid, decoder) pair, and the backward launches.
 #pragma once
 #include "common.hpp"
 #include "hash_index.hpp"
@@ -63,6 +63,48 @@ __device__ __forceinline__ void load_vec(const float* __restrict__ p, float (&v)
     v[0] = *p;
   }
 }
+
+// The feature row of one point through the tables, as the fused kernels form it (hash_sdf.hip, hash_trace.hip): per live
+// level hash_cell + the eight corner_weight<0> + corner_rows, then 16-byte row loads summed corner by corner with fma
+// (the PIN_FMA form of decoder.hpp's gather_level).  f[l C + c] is added to: the caller zero-fills.  An ignored level and
+// a level with no corner in range leave their columns alone, and the latter reads nothing.
+template <int C, int L, int NF>
+__device__ __forceinline__ void hash_gather_row(const HashGridK& g, float px, float py, float pz, float (&f)[NF]) {
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    if ((g.ignore_mask >> l) & 1u) continue;      // zeros
+    const HashLevelK& lv = g.lv[l];
+    Axis a[3];
+    const Cell c = hash_cell(g, lv, px, py, pz, a);
+    bool inb[8];
+    float w[8];
+    uint32_t row[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      inb[k] = corner_in(c, k);
+      w[k] = corner_weight<0>(c, k, inb[k]).w;
+    }
+    if (!corner_rows(c, lv, inb, row)) continue;      // no corner in range: zeros, nothing is read
+#pragma unroll
+    for (int q = 0; q < C; q += 4) {
+      float v[8][4];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) load_vec<4>(lv.table + (size_t)row[k] * C + q, v[k]);
+#pragma unroll
+      for (int k = 0; k < 8; ++k)      // corner by corner, as gather_level sums
+#pragma unroll
+        for (int e = 0; e < 4; ++e) f[l * C + q + e] = __builtin_fmaf(v[k][e], w[k], f[l * C + q + e]);
+    }
+  }
+}
+
+// ---- hash_sdf.hip (host): what the C entries of the fused routes (hash_sdf.hip, hash_trace.hip) ask before a launch
+// grid + decoder as the kernels take them: (C, L, H, NH) is the fused kernels' table key
+struct HashSdfCall { HashGridK g; int C, L, H, NH; };
+// every check of (grid, mlp): convert_hash_grid's code, MISO_E_UNSUPPORTED for mixed C or a shape outside the fused table
+int hash_sdf_call(HashSdfCall* f, const miso_hash_grid_t* grid, const miso_mlp_t* m, bool need_table);
+// the decoder arguments and the batch, before the grid is looked at
+int hash_sdf_args(const float* packed, uint32_t decoder_flags, int64_t n);
 
 // ---- hash_encode.hip (host)
 // Every check of a grid argument, then the kernel-side copy.  need_table: the call reads the tables.

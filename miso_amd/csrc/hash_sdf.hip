@@ -14,17 +14,17 @@
 // dynamic: launch_hash_fwd_t sizes it as launch_fwd_t does).  __launch_bounds__(256, 2) asks for the two workgroups
 // per CU that the 512-block cap launches; the H = 32 decoders over C = 4 fit three or four.
 //   shape            split: VGPRs (waves)   exact: VGPRs (waves)
-//   <4, 1, 32, 1>     142 (3)                117 (4)
+//   <4, 1, 32, 1>     144 (3)                117 (4)
 //   <4, 1, 64, 1>     210 (2)                192 (2)
-//   <4, 2, 32, 1>     162 (3)                125 (4)
+//   <4, 2, 32, 1>     156 (3)                126 (4)
 //   <4, 2, 64, 1>     224 (2)                208 (2)
 //   <4, 3, 64, 1>     236 (2)                218 (2)
-//   <4, 4, 64, 1>     251 (2)                228 (2)
-//   <8, 1, 64, 1>     214 (2)                198 (2)
-//   <8, 2, 64, 1>     232 (2)                212 (2)
-//   <8, 3, 64, 1>     248 (2)                216 (2)
-//   <8, 4, 64, 1>     256 (2)                226 (2)
-//   <8, 3, 32, 1>     194 (2)                170 (2)
+//   <4, 4, 64, 1>     250 (2)                228 (2)
+//   <8, 1, 64, 1>     216 (2)                198 (2)
+//   <8, 2, 64, 1>     234 (2)                212 (2)
+//   <8, 3, 64, 1>     250 (2)                216 (2)
+//   <8, 4, 64, 1>     256 (2)                227 (2)
+//   <8, 3, 32, 1>     196 (2)                162 (3)
 #include <string.h>
 
 #include "checks.hpp"
@@ -78,32 +78,7 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) void hash_sdf_fwd_kernel(HashGri
     memory_phase(true);
     if (valid) {
       const float px = x[p * 3 + 0], py = x[p * 3 + 1], pz = x[p * 3 + 2];
-#pragma unroll
-      for (int l = 0; l < L; ++l) {
-        if ((g.ignore_mask >> l) & 1u) continue;      // zeros
-        const HashLevelK& lv = g.lv[l];
-        Axis a[3];
-        const Cell c = hash_cell(g, lv, px, py, pz, a);
-        bool inb[8];
-        float w[8];
-        uint32_t row[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          inb[k] = corner_in(c, k);
-          w[k] = corner_weight<0>(c, k, inb[k]).w;
-        }
-        if (!corner_rows(c, lv, inb, row)) continue;      // no corner in range: zeros, nothing is read
-#pragma unroll
-        for (int q = 0; q < C; q += 4) {
-          float v[8][4];
-#pragma unroll
-          for (int k = 0; k < 8; ++k) load_vec<4>(lv.table + (size_t)row[k] * C + q, v[k]);
-#pragma unroll
-          for (int k = 0; k < 8; ++k)      // corner by corner, as gather_level sums
-#pragma unroll
-            for (int e = 0; e < 4; ++e) f[l * C + q + e] = __builtin_fmaf(v[k][e], w[k], f[l * C + q + e]);
-        }
-      }
+      hash_gather_row<C, L>(g, px, py, pz, f);
     }
     memory_phase(false);
     uint32_t mw[MW];
@@ -142,15 +117,7 @@ static hipError_t launch_hash_fwd_t(FusedShape<C, L, H, NH>, const HashGridK& g,
   return hipGetLastError();
 }
 
-}  // namespace miso
-
-using namespace miso;
-
-namespace {
-
-// grid + decoder as the kernels take them: (C, L, H, NH) is the fused kernels' table key
-struct HashSdfCall { HashGridK g; int C, L, H, NH; };
-
+// (hash_grid.hpp declares the two checks below: hash_trace.hip states its own with them)
 int hash_sdf_call(HashSdfCall* f, const miso_hash_grid_t* grid, const miso_mlp_t* m, bool need_table) {
   if (int rc = convert_hash_grid(grid, &f->g, need_table)) return rc;
   if (!m) return MISO_E_BADARG;
@@ -169,7 +136,9 @@ int hash_sdf_args(const float* packed, uint32_t decoder_flags, int64_t n) {
   return (decoder_flags & ~MISO_F_EXACT_F32) ? MISO_E_BADARG : MISO_OK;
 }
 
-}  // namespace
+}  // namespace miso
+
+using namespace miso;
 
 extern "C" {
 

@@ -11,7 +11,7 @@ def source_files():
     files = [os.path.join(HERE, f) for f in sorted(os.listdir(HERE)) if f.endswith((".hip", ".hpp", ".inc"))
              and f != "version.inc"]
     files.append(os.path.join(HERE, "Makefile"))      # (per-file compiler flags are part of what the library is)
-    for header in ("miso_hip.h", "miso_hash.h", "miso_hash_sdf.h"):
+    for header in ("miso_hip.h", "miso_hash.h", "miso_hash_sdf.h", "miso_hash_trace.h"):
         files.append(os.path.normpath(os.path.join(HERE, "..", "..", "include", header)))
     return files
 

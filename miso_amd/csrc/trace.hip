@@ -16,26 +16,9 @@
 // comparisons keep the reference's form (s < epsilon, dist > max_dist): a NaN field value never stops a ray and its
 // mask stays false, as upstream.
 #include "atlas_eval.hpp"
+#include "trace_math.hpp"      // add_product, norm3
 
 namespace miso {
-
-// c + a b as the two tensor ops it restates: the product rounded, then the sum.  (HIP's __fmul_rn / __fadd_rn are plain
-// operators that the compiler may contract into one v_fma_f32 -- see axis_from_norm in trilinear.hpp; the pragma is what
-// keeps them apart.)
-__device__ __forceinline__ float add_product(float c, float a, float b) {
-#pragma clang fp contract(off)
-  const float ab = a * b;
-  return c + ab;
-}
-
-// |e|: three products, two sums and a root, each rounded.  torch.norm may sum in another order or in a wider type, so
-// the far test agrees with the loop's wherever dist is not within rounding of max_dist.
-__device__ __forceinline__ float norm3(float ex, float ey, float ez) {
-#pragma clang fp contract(off)
-  const float xx = ex * ex, yy = ey * ey, zz = ez * ez;
-  const float sum = (xx + yy) + zz;
-  return __fsqrt_rn(sum);
-}
 
 template <int C, int L, int H, int NH, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void atlas_trace_kernel(AtlasK a, TraceK t, const float* __restrict__ packed) {

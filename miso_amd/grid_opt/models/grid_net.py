@@ -47,7 +47,8 @@ class GridNet(BaseNet):
         # 'hash': every level is looked up through a table of at most 2^log2_hashmap_size rows (HashFeatureGrid); the
         # queries go through ops.hash_encode and every fused route declines (_fused_decoder).  grid.hash_fused (default
         # False; no meaning for 'regular'): forward() and sdf_and_gradient() of a hash net with a frozen decoder run the
-        # table gather and the decoder as one launch instead (_fused_hash_decoder, ops.hash_sdf_fused)
+        # table gather and the decoder as one launch instead (_fused_hash_decoder, ops.hash_sdf_fused), and sphere_trace()
+        # the whole ray loop (ops.hash_sphere_trace)
         self.hash_fused = bool(g.get('hash_fused', False))
         level_cls, extra = FeatureGrid, {}
         if self.grid_type == 'hash':
@@ -327,13 +328,18 @@ class GridNet(BaseNet):
                      epsilon=1e-5, **extras):
         """utils_sdf.sphere_tracing(self, ...) in ONE launch: this grid as a one-submap atlas with an identity pose row
         and no bound test, which is forward() bit for bit (ops.AtlasQuery.trace; extras: want_sdf, want_steps,
-        grad_step).  -> (points (N,3), mask (N,1) bool, extras dict); None when autograd is on, the tensors are on the
-        host or the fused decoder does not cover this model: utils_sdf.sphere_tracing then runs its loop."""
+        grad_step).  A hash net with grid.hash_fused on: ops.hash_sphere_trace over its tables, the same loop around
+        the field of its fused forward().  -> (points (N,3), mask (N,1) bool, extras dict); None when autograd is on, the
+        tensors are on the host or neither fused decoder covers this model: utils_sdf.sphere_tracing then runs its loop."""
         if torch.is_grad_enabled() or not (origins.is_cuda and directions.is_cuda):
             return None
         pack = self._fused_decoder()
         if pack is None:
-            return None
+            hpack = self._fused_hash_decoder()
+            if hpack is None or not ops.hash_trace_supported(*self._hash_args(), hpack):
+                return None
+            return ops.hash_sphere_trace(*self._hash_args(detach=True), hpack, origins, utils.normalize_last_dim(directions),
+                                         min_dist=min_dist, max_dist=max_dist, max_iters=max_iters, epsilon=epsilon, **extras)
         q = self.__dict__.setdefault('_trace_query', ops.AtlasQuery())
         ident = self.__dict__.get('_trace_ident')
         if ident is None or ident.device != origins.device:

@@ -879,6 +879,58 @@ def hash_sdf_fused(x: torch.Tensor, tables: Sequence[torch.Tensor], meta: GridMe
     return _HashSdfFused.apply(x, meta, tuple(tuple(int(v) for v in d) for d in dims), int(log2), pack, *tables)
 
 
+# --------------------------------------------------------------------------- #
+# sphere tracing through hash-indexed levels in one launch (include/miso_hash_trace.h, csrc/hash_trace.hip)
+# --------------------------------------------------------------------------- #
+def hash_trace_supported(tables, meta: GridMeta, dims, log2: int, pack: DecoderPack) -> bool:
+    """Does hash_sphere_trace cover these tables with this decoder (miso_hash_trace_supported)?"""
+    if not all(t.is_cuda for t in tables):
+        return False
+    m, _ = pack.get()
+    if m is None:
+        return False
+    g, _ = _hash_sdf_grid(tables, meta, dims, log2)
+    return bool(_lib.load().miso_hash_trace_supported(C.byref(g), C.byref(m)))
+
+
+def hash_sphere_trace(tables, meta: GridMeta, dims, log2: int, pack: DecoderPack, origins, dirs, *, min_dist, max_dist,
+                      max_iters, epsilon, want_sdf=False, want_steps=False, grad_step=None):
+    """utils_sdf.sphere_tracing (reference grid_opt/utils/utils_sdf.py:197-236) over the field of hash_sdf_fwd_raw in ONE
+    launch (miso_hash_sphere_trace).  origins, dirs: (N,3) device floats, dirs already of unit length.  The decoder
+    arithmetic is hash_sdf_fwd_raw's: exact_fp32() or F_EXACT_F32 in ``meta.flags``.
+    -> (points (N,3), mask (N,1) bool, extras), the shape of AtlasQuery.trace: extras['sdf'] (N,1) the field at the
+    returned points (want_sdf), extras['steps'] (N,) int32 the iterations in which a ray moved (want_steps),
+    extras['grad'] (N,3) central differences with step grad_step at the returned points (grad_step is not None).
+    No autograd; a pack with a trainable tensor is refused (NotCovered)."""
+    if int(max_iters) < 1:
+        raise ValueError(f"max_iters must be at least 1, got {max_iters}")
+    _require_hip(origins, dirs, *tables)
+    if pack.trainable():
+        raise NotCovered("ops.hash_sphere_trace takes a frozen decoder", _lib.E_UNSUPPORTED, "hash_sphere_trace")
+    m, packed = pack.require()
+    assert origins.ndim == 2 and origins.shape[1] == 3 and dirs.shape == origins.shape
+    origins, dirs = origins.detach().contiguous(), dirs.detach().contiguous()
+    n, dev = origins.shape[0], origins.device
+    points = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    mask = torch.empty((n, 1), device=dev, dtype=torch.bool)
+    extras = {}
+    if want_sdf:
+        extras['sdf'] = torch.empty((n, 1), device=dev, dtype=torch.float32)
+    if want_steps:
+        extras['steps'] = torch.empty((n,), device=dev, dtype=torch.int32)
+    if grad_step is not None:
+        extras['grad'] = torch.empty((n, 3), device=dev, dtype=torch.float32)
+    if n == 0:          # (an empty tensor has no address to hand over; nothing to launch)
+        return points, mask, extras
+    g, dflags = _hash_sdf_grid(tables, meta, dims, log2)
+    _lib.check(_lib.load().miso_hash_sphere_trace(
+        C.byref(g), C.byref(m), _ptr(packed), dflags, _ptr(origins), _ptr(dirs), n, float(min_dist), float(max_dist),
+        int(max_iters), float(epsilon), 0.0 if grad_step is None else float(grad_step), _ptr(points), _ptr(mask),
+        _ptr(extras.get('sdf')), _ptr(extras.get('steps')), _ptr(extras.get('grad')), _stream(origins)),
+        "miso_hash_sphere_trace")
+    return points, mask, extras
+
+
 def _check_loss_args(n: int, loss_inputs, loss_slots, n_live=None):
     """Label rows (n,4), per-workgroup sums (LOSS_SLOTS,2) and, for a padded batch, the live count: one device int32."""
     assert loss_inputs.shape == (n, 4) and loss_inputs.is_contiguous()
