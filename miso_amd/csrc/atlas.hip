@@ -22,8 +22,7 @@ template <int C, int L, int H, int NH, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void atlas_sdf_kernel(AtlasK a, const float* __restrict__ packed) {
   using Dec = AtlasDecoder<C, L, H, NH, SPLIT>;
   constexpr int F = C * L;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const Dec dec(smem, packed, a.sdf != nullptr);      // weights to LDS, the zero row's value (atlas_eval.hpp)
+  const Dec dec(packed, a.sdf != nullptr);      // weights to LDS, the zero row's value (atlas_eval.hpp)
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   const int64_t nchunks = (a.n + 63) / 64;
@@ -54,7 +53,7 @@ __global__ __launch_bounds__(256, 2) void atlas_sdf_kernel(AtlasK a, const float
 
 template <int C, int L, int H, int NH>
 static hipError_t launch_atlas_t(FusedShape<C, L, H, NH>, const AtlasK& a, const float* packed, bool split, hipStream_t s) {
-  const AtlasLaunch dims(C * L, H, NH, split, a.sdf != nullptr, a.n);
+  const FwdLaunch dims(C * L, H, NH, split, a.n, 2048u, a.sdf != nullptr);
   auto k = split ? atlas_sdf_kernel<C, L, H, NH, true> : atlas_sdf_kernel<C, L, H, NH, false>;
   hipError_t e = allow_dynamic_lds((const void*)k, dims.lds);
   if (e != hipSuccess) return e;

@@ -42,37 +42,15 @@ __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK 
   constexpr int FP = dfeat_pitch(F), REC = CELL_REC;      // the d-feat tile and the cell records: dfeat_tile.hpp
   constexpr int WAVE_LDS = 64 * FP + 64 * L * REC;
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const PackLayout pl(F, H, NH);
-  // the whole pack, as sdf_train_kernel stages it: forward part [0, fwd_end) and transposed weights [o_whT, total); the
-  // split form: the bf16x3 section [s_w0, total_all), then the biases and output weights [o_b0, fwd_end)
-  const int n_split = pl.total_all - pl.s_w0;
-  const int n_pack = SPLIT ? n_split + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
-  if (SPLIT) {
-    for (int i = threadIdx.x * 4; i < n_split; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
-    for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + n_split + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
-  } else {
-    for (int i = threadIdx.x * 4; i < pl.total; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + i);
-  }
+  const PackImage<SPLIT, true> img(F, H, NH);      // the whole pack (decoder.hpp)
+  img.stage(packed);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
   const int nw = blockDim.x >> 6;
-  float* s_pose = smem + n_pack + nw * WAVE_LDS;      // the block's (S,12) pose partial
+  float* s_pose = img.behind() + nw * WAVE_LDS;      // the block's (S,12) pose partial
   if (b.pose_slots)
     for (int i = threadIdx.x; i < a.n_submaps * 12; i += blockDim.x) s_pose[i] = 0.0f;
   __syncthreads();
-  const float* w0p = smem + pl.o_w0;
-  const float* whp = smem + pl.o_wh;
-  const float* b0 = smem + pl.o_b0;
-  const float* bh = smem + pl.o_bh;
-  const float* wo = smem + pl.o_wo;
-  const float* whT = smem + pl.o_whT;
-  const float* w0T = smem + pl.o_w0T;
-  const uint32_t* s_fwd = reinterpret_cast<const uint32_t*>(smem);                                   // SPLIT
-  const uint32_t* s_bwd = reinterpret_cast<const uint32_t*>(smem) + (pl.s_bfirst - pl.s_w0);        // SPLIT
-  const float* s_bias = smem + n_split;                                                              // SPLIT
-  float* dF = smem + n_pack + wave * WAVE_LDS;                      // this wavefront's d-feat tile [64][FP]
+  float* dF = img.behind() + wave * WAVE_LDS;                       // this wavefront's d-feat tile [64][FP]
   int* rec = reinterpret_cast<int*>(dF + 64 * FP);                  // ... and cell records [64][L][REC]
   const bool want_x = b.gx != nullptr || b.pose_slots != nullptr;
 
@@ -94,8 +72,8 @@ __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK 
     u32x4 maskB[H / 16][2];      // SPLIT: the last ReLU's mask as the first backward product's B operand
     {
       float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
-      if constexpr (SPLIT) decoder_fwd_split<F, H, NH, false, false, true, true>(s_fwd, s_bias, lane, mean, mw, maskB, p0, p1, poison);
-      else decoder_fwd_exact<F, H, NH, true>(w0p, whp, b0, bh, wo, lane, mean, mw, p0, p1);
+      if constexpr (SPLIT) decoder_fwd_split<F, H, NH, false, false, true, true>(img.s_fwd(), img.s_bias(), lane, mean, mw, maskB, p0, p1, poison);
+      else decoder_fwd_exact<F, H, NH, true>(img.w0p(), img.whp(), img.b0(), img.bh(), img.wo(), lane, mean, mw, p0, p1);
     }
     // ================================ decoder backward ==============================================================
     // two tiles of 32 points, lane (hi, c) on point 32 t + c of tile t
@@ -104,8 +82,8 @@ __global__ __launch_bounds__(512) void atlas_sdf_bwd_kernel(AtlasK a, AtlasBwdK 
     ds[0] = __shfl(gl, lane & 31);
     ds[1] = __shfl(gl, 32 + (lane & 31));
     f32x16 df[2];
-    if constexpr (SPLIT) decoder_bwd_split<F, H, NH, false>(s_bwd, lane, maskB, mw, ds, df);
-    else decoder_bwd_exact<F, H, NH>(whT, w0T, wo, lane, mw, ds, df);
+    if constexpr (SPLIT) decoder_bwd_split<F, H, NH, false>(img.s_bwd(), lane, maskB, mw, ds, df);
+    else decoder_bwd_exact<F, H, NH>(img.whT(), img.w0T(), img.wo(), lane, mw, ds, df);
     // ---- accumulator layout -> LDS tile -> one row per lane; d feats_s = d mean / count ------------------------------
     dfeat_to_tile<F, 2>(df, dF, lane & 31, hi);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -236,7 +214,7 @@ struct AtlasBwdPlan {
 static AtlasBwdPlan plan_atlas_bwd(int C, int L, int H, int NH, bool split, int n_submaps, bool poses) {
   const PackLayout pl(C * L, H, NH);
   const int F = C * L, wave_lds = 64 * dfeat_pitch(F) + 64 * L * CELL_REC;
-  const int pack = split ? pl.total_all - pl.s_w0 + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
+  const int pack = image_floats(pl, split, true);
   const int pose = poses ? (n_submaps * 12 + 3) / 4 * 4 : 0;
   const auto bytes = [&](int wavefronts) { return (size_t)(pack + wavefronts * wave_lds + pose) * sizeof(float); };
   const int nw = bytes(8) <= MISO_LDS_LIMIT ? 8 : 4;

@@ -7,44 +7,19 @@
 
 namespace miso {
 
-// Decoder weights in LDS (the bf16x3 split image, or the fp32 pack behind MISO_F_EXACT_F32) and the decoder chain of
-// sdf_fwd_kernel on one feature row per lane.  decode() holds matrix instructions and a cross-lane exchange: every lane
-// of the wavefront must call it (full EXEC).  The gather and the output dot product are asked for with their
-// multiply-adds fused outright (mul_acc in decoder.hpp): this code is inlined into two kernels at several places, and
-// every copy has to give the bits of sdf_fwd_kernel, where the compiler fuses them all.
+// FwdDecoder (decoder.hpp) for an atlas: sdf_fwd_kernel's chain with the multiply-adds of the output dot product fused
+// outright (the gather asks for the same: gather_level<C, true>) -- this code is inlined into several kernels at several
+// places, and every copy has to give the bits of sdf_fwd_kernel, where the compiler fuses them all -- and the decoder's
+// answer to an all-zero feature row.
 template <int C, int L, int H, int NH, bool SPLIT>
-struct AtlasDecoder {
-  static constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2, NF = 2 * KS0, MW = (NH + 1) * RT;
-  const float* smem;
-  const uint32_t* s_fwd;
-  const float* s_bias;
-  PackLayout pl;
-  int lane, hi;
-  float bo = 0.0f;
-  float sdf_empty = 0.0f;      // the decoder's answer to an all-zero feature row (a point inside no submap)
+struct AtlasDecoder : FwdDecoder<C * L, H, NH, SPLIT, true> {
+  using Base = FwdDecoder<C * L, H, NH, SPLIT, true>;
+  using Base::NF;
+  float sdf_empty = 0.0f;      // a point inside no submap
 
-  // stage: all threads of the block; ends in a barrier (a feature-only query stages nothing)
-  __device__ __forceinline__ AtlasDecoder(float* smem_, const float* __restrict__ packed, bool want_sdf)
-      : smem(smem_), pl(F, H, NH) {
-    const int n_split = pl.s_fwd_end - pl.s_w0;
+  // stage: all threads of the block; ends in a barrier (want_sdf = false: a feature-only query stages nothing)
+  __device__ __forceinline__ AtlasDecoder(const float* __restrict__ packed, bool want_sdf) : Base(packed, want_sdf) {
     if (want_sdf) {
-      if (SPLIT) {
-        for (int i = threadIdx.x * 4; i < n_split; i += blockDim.x * 4)
-          *reinterpret_cast<float4*>(smem_ + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
-        for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
-          *reinterpret_cast<float4*>(smem_ + n_split + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
-      } else {
-        for (int i = threadIdx.x * 4; i < pl.fwd_end; i += blockDim.x * 4)
-          *reinterpret_cast<float4*>(smem_ + i) = *reinterpret_cast<const float4*>(packed + i);
-      }
-    }
-    __syncthreads();
-    lane = threadIdx.x & 63;
-    hi = lane >> 5;
-    s_fwd = reinterpret_cast<const uint32_t*>(smem_);
-    s_bias = smem_ + n_split;
-    if (want_sdf) {
-      bo = SPLIT ? s_bias[pl.o_bo - pl.o_b0] : smem_[pl.o_bo];
       float z[NF];
 #pragma unroll
       for (int i = 0; i < NF; ++i) z[i] = 0.0f;
@@ -53,18 +28,8 @@ struct AtlasDecoder {
   }
 
   __device__ __forceinline__ float decode(const float (&f)[NF]) const {
-    uint32_t mw[MW];
-    float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
-    if constexpr (SPLIT) {
-      u32x4 no_mask[H / 16][2];
-      decoder_fwd_split<F, H, NH, false, false, false, true>(s_fwd, s_bias, lane, f, mw, no_mask, p0, p1, poison);
-    } else {
-      decoder_fwd_exact<F, H, NH, true>(smem + pl.o_w0, smem + pl.o_wh, smem + pl.o_b0, smem + pl.o_bh, smem + pl.o_wo, lane, f,
-                                  mw, p0, p1);
-    }
-    p0 += __shfl_xor(p0, 32);
-    p1 += __shfl_xor(p1, 32);
-    return SPLIT ? ((hi ? p1 : p0) + bo) + poison : (hi ? p1 : p0) + bo;
+    uint32_t mw[Base::MW];
+    return Base::template decode<false>(f, mw);
   }
 };
 
@@ -185,21 +150,5 @@ __device__ __forceinline__ bool atlas_mean(const AtlasK& a, bool valid, float wx
   for (int i = 0; i < NF; ++i) mean[i] = (i < F) ? __fdiv_rn(sum[i], den) : 0.0f;
   return any_inside;
 }
-
-// Launch shape of the kernels that run atlas_eval: dynamic LDS for the decoder image (split or fp32 pack; `staged` =
-// false for a feature-only query, which stages nothing) and a persistent grid of four wavefronts per block, one per 64
-// points at a time.
-struct AtlasLaunch {
-  size_t lds;
-  unsigned blocks;
-  AtlasLaunch(int F, int H, int NH, bool split, bool staged, int64_t n) {
-    PackLayout pl(F, H, NH);
-    lds = (size_t)(split ? pl.s_fwd_end - pl.s_w0 + (pl.n_bias() + 3) / 4 * 4 : (pl.fwd_end + 3) / 4 * 4) * sizeof(float);
-    if (!staged) lds = 16;
-    const int64_t nchunks = (n + 63) / 64;
-    blocks = (unsigned)((nchunks + 3) / 4);
-    if (blocks > 2048u) blocks = 2048u;
-  }
-};
 
 }  // namespace miso

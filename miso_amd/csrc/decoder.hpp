@@ -8,8 +8,12 @@
 //   sdf_train.hip      sdf_train_kernel: the split chains (HALF: 32-point trips too); its exact chains are written out
 //                      in the kernel -- through decoder_*_exact ten of its exact instantiations took 1 .. 28 VGPRs more
 //                      and the step was 0.3 - 0.6 % slower (profiles/decoder_shared.json)
-//   atlas_eval.hpp     its decode() (atlas.hip, trace.hip)    --
+//   hash_sdf.hip       hash_sdf_fwd_kernel                    (sdf_bwd_kernel)
+//   atlas_eval.hpp     AtlasDecoder (atlas.hip, trace.hip, hash_trace.hip)
 //   atlas_bwd.hip      atlas_sdf_bwd_kernel                   the same kernel
+//   pair_sdf.hip       pair_sdf_stage_kernel                  the same kernel
+// Where the pack lies in LDS for them is said once, in PackImage below; the kernels that only query go through
+// FwdDecoder and are launched by FwdLaunch.
 // decoder_wgrad.hip keeps chains of its own: it holds every layer's activations and interleaves the outer products of the
 // weight gradients, a different computation.  What happens to d feats behind a backward chain is in dfeat_tile.hpp.
 #pragma once
@@ -126,6 +130,59 @@ struct PackLayout {
     total_all = o;
   }
   __host__ __device__ int n_bias() const { return fwd_end - o_b0; }      // b0, bh, wo, bo: contiguous
+};
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The pack in LDS.  Two images, each in the two arithmetics:
+//   forward  exact: the fp32 forward pack [0, fwd_end);  split: the bf16x3 forward block [s_w0, s_fwd_end), then the
+//            biases and output weights [o_b0, fwd_end)
+//   whole    exact: forward pack and transposed weights [0, total);  split: the bf16x3 section [s_w0, total_all), then
+//            the biases and output weights
+// (sdf_bwd_kernel has a backward-only image of its own, in sdf_fused.hip.)
+// A kernel stages and addresses its image through PackImage; its launcher sizes the dynamic LDS with image_floats, and
+// whatever lies behind the image (d-feat tiles, cell records, a pose partial) starts at that size on both sides.
+__host__ __device__ inline int image_floats(const PackLayout& pl, bool split, bool whole) {
+  return split ? (whole ? pl.total_all : pl.s_fwd_end) - pl.s_w0 + (pl.n_bias() + 3) / 4 * 4
+               : ((whole ? pl.total : pl.fwd_end) + 3) / 4 * 4;
+}
+
+// The image lies at the start of the block's dynamic LDS -- this array, which the kernels declare under the same name.
+// PackImage names it directly, not through a pointer it is handed: with the pointer as a member, the addresses of
+// sdf_train_kernel's weight reads were formed differently and 65 of its 78 instantiations changed registers.
+extern __shared__ __attribute__((aligned(16))) float smem[];
+
+template <bool SPLIT, bool WHOLE>
+struct PackImage {
+  PackLayout pl;
+  __device__ __forceinline__ PackImage(int F, int H, int NH) : pl(F, H, NH) {}
+  __device__ __forceinline__ int n_split() const { return (WHOLE ? pl.total_all : pl.s_fwd_end) - pl.s_w0; }
+  __device__ __forceinline__ int floats() const { return image_floats(pl, SPLIT, WHOLE); }
+  __device__ __forceinline__ float* behind() const { return smem + floats(); }
+  // the copy, by all threads of the block; no barrier: the caller may have more to write in front of it
+  __device__ __forceinline__ void stage(const float* packed) const {
+    if (SPLIT) {
+      for (int i = threadIdx.x * 4; i < n_split(); i += blockDim.x * 4)
+        *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
+      for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
+        *reinterpret_cast<float4*>(smem + n_split() + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
+    } else {
+      for (int i = threadIdx.x * 4; i < (WHOLE ? pl.total : pl.fwd_end); i += blockDim.x * 4)
+        *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + i);
+    }
+  }
+  // exact: the fp32 pack at its PackLayout offsets
+  __device__ __forceinline__ const float* w0p() const { return smem + pl.o_w0; }
+  __device__ __forceinline__ const float* whp() const { return smem + pl.o_wh; }
+  __device__ __forceinline__ const float* b0() const { return smem + pl.o_b0; }
+  __device__ __forceinline__ const float* bh() const { return smem + pl.o_bh; }
+  __device__ __forceinline__ const float* wo() const { return smem + pl.o_wo; }
+  __device__ __forceinline__ const float* whT() const { return smem + pl.o_whT; }      // WHOLE
+  __device__ __forceinline__ const float* w0T() const { return smem + pl.o_w0T; }      // WHOLE
+  // split: decoder_fwd_split's sw and bias, decoder_bwd_split's sb
+  __device__ __forceinline__ const uint32_t* s_fwd() const { return reinterpret_cast<const uint32_t*>(smem); }
+  __device__ __forceinline__ const uint32_t* s_bwd() const { return s_fwd() + (pl.s_bfirst - pl.s_w0); }      // WHOLE
+  __device__ __forceinline__ const float* s_bias() const { return smem + n_split(); }
+  __device__ __forceinline__ float bo() const { return SPLIT ? s_bias()[pl.o_bo - pl.o_b0] : smem[pl.o_bo]; }
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -598,5 +655,65 @@ __device__ __forceinline__ void decoder_bwd_exact(const float* __restrict__ whT,
       df[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, d[rp][1][j], df[1], 0, 0, 0);
     }
 }
+
+// The closing of a forward chain: the two lane halves' partial sums added, this lane's tile chosen, then the output bias
+// and, after a split chain, its poison term -- in this order, a rounding each.  (No HALF form: its one user would be
+// sdf_train_kernel, which keeps these lines written out -- see there.)
+template <bool SPLIT>
+__device__ __forceinline__ float close_fwd(float p0, float p1, int hi, float bo, float poison) {
+  p0 += __shfl_xor(p0, 32);
+  p1 += __shfl_xor(p1, 32);
+  const float p = hi ? p1 : p0;
+  return SPLIT ? (p + bo) + poison : p + bo;
+}
+
+// The forward decoder of the kernels that only query: the forward image in LDS and the chain on one feature row per
+// lane.  decode() holds matrix instructions and a cross-lane exchange: every lane of the wavefront must call it (full
+// EXEC).  PIN_FMA: mul_acc's fused form in the output dot product, for code that is inlined into several kernels and
+// has to give sdf_fwd_kernel's bits in each.
+template <int F, int H, int NH, bool SPLIT, bool PIN_FMA>
+struct FwdDecoder {
+  static constexpr int RT = H / 32, KS0 = (F + 1) / 2, NF = 2 * KS0, MW = (NH + 1) * RT;
+  PackImage<SPLIT, false> img;
+  int lane, hi;
+  float bo = 0.0f;
+
+  // stages (all threads of the block) and ends in a barrier; staged = false: a feature-only query, nothing to decode
+  __device__ __forceinline__ FwdDecoder(const float* __restrict__ packed, bool staged = true)
+      : img(F, H, NH) {
+    if (staged) img.stage(packed);
+    __syncthreads();
+    lane = threadIdx.x & 63;
+    hi = lane >> 5;
+    if (staged) bo = img.bo();
+  }
+
+  // f -> SDF; mw receives the ReLU sign words (BITS = false: a split chain leaves the last layer's unwritten)
+  template <bool BITS>
+  __device__ __forceinline__ float decode(const float (&f)[NF], uint32_t (&mw)[MW]) const {
+    float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
+    if constexpr (SPLIT) {
+      u32x4 no_mask[H / 16][2];
+      decoder_fwd_split<F, H, NH, false, BITS, false, PIN_FMA>(img.s_fwd(), img.s_bias(), lane, f, mw, no_mask, p0, p1, poison);
+    } else {
+      decoder_fwd_exact<F, H, NH, PIN_FMA>(img.w0p(), img.whp(), img.b0(), img.bh(), img.wo(), lane, f, mw, p0, p1);
+    }
+    return close_fwd<SPLIT>(p0, p1, hi, bo, poison);
+  }
+};
+
+// Launch shape of the kernels that run a FwdDecoder: dynamic LDS for the forward image (`staged` = false: a feature-only
+// query, which stages nothing) and a persistent grid of four wavefronts per block, one per 64 points at a time, `cap`
+// blocks at the most.
+struct FwdLaunch {
+  size_t lds;
+  unsigned blocks;
+  FwdLaunch(int F, int H, int NH, bool split, int64_t n, unsigned cap, bool staged = true) {
+    lds = staged ? (size_t)image_floats(PackLayout(F, H, NH), split, false) * sizeof(float) : 16;
+    const int64_t nchunks = (n + 63) / 64;
+    blocks = (unsigned)((nchunks + 3) / 4);
+    if (blocks > cap) blocks = cap;
+  }
+};
 
 }  // namespace miso

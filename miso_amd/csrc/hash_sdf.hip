@@ -1,6 +1,6 @@
 // Fused SDF query of hash-indexed levels (include/miso_hash_sdf.h): hash_sdf_fwd_kernel is sdf_fwd_kernel
 // (sdf_fused.hip) with the corner rows looked up through the tables of hash_grid.hpp -- the same persistent wavefronts
-// of 64 points, the same weights in LDS at the same PackLayout offsets, the same decoder chains and epilogue; only the
+// of 64 points, the same FwdDecoder (decoder.hpp: the forward image in LDS, the chains, the closing); only the
 // gather differs: hash_cell + corner_rows + 16-byte row loads, summed corner by corner with fma (the PIN_FMA form of
 // decoder.hpp's gather_level).  A table that lists a dense level's vertices therefore gives sdf_fwd_kernel's bits, sign
 // words included.  Points arrive in the caller's order; there is no binned form and no loss.
@@ -11,20 +11,20 @@
 //
 // Registers of hash_sdf_fwd_kernel<C, L, H, NH, SPLIT> (gfx950, hipcc -O3, -Rpass-analysis=kernel-resource-usage): VGPRs
 // and the wavefronts per SIMD they allow; no AGPRs, scratch 0 and no static LDS in every instantiation (the LDS is
-// dynamic: launch_hash_fwd_t sizes it as launch_fwd_t does).  __launch_bounds__(256, 2) asks for the two workgroups
+// dynamic: FwdLaunch sizes it, as for sdf_fwd_kernel).  __launch_bounds__(256, 2) asks for the two workgroups
 // per CU that the 512-block cap launches; the H = 32 decoders over C = 4 fit three or four.
 //   shape            split: VGPRs (waves)   exact: VGPRs (waves)
-//   <4, 1, 32, 1>     144 (3)                117 (4)
-//   <4, 1, 64, 1>     210 (2)                192 (2)
-//   <4, 2, 32, 1>     156 (3)                126 (4)
-//   <4, 2, 64, 1>     224 (2)                208 (2)
-//   <4, 3, 64, 1>     236 (2)                218 (2)
-//   <4, 4, 64, 1>     250 (2)                228 (2)
-//   <8, 1, 64, 1>     216 (2)                198 (2)
-//   <8, 2, 64, 1>     234 (2)                212 (2)
-//   <8, 3, 64, 1>     250 (2)                216 (2)
+//   <4, 1, 32, 1>     140 (3)                117 (4)
+//   <4, 1, 64, 1>     206 (2)                192 (2)
+//   <4, 2, 32, 1>     152 (3)                126 (4)
+//   <4, 2, 64, 1>     216 (2)                208 (2)
+//   <4, 3, 64, 1>     230 (2)                218 (2)
+//   <4, 4, 64, 1>     242 (2)                228 (2)
+//   <8, 1, 64, 1>     208 (2)                198 (2)
+//   <8, 2, 64, 1>     226 (2)                212 (2)
+//   <8, 3, 64, 1>     244 (2)                216 (2)
 //   <8, 4, 64, 1>     256 (2)                227 (2)
-//   <8, 3, 32, 1>     196 (2)                162 (3)
+//   <8, 3, 32, 1>     192 (2)                162 (3)
 #include <string.h>
 
 #include "checks.hpp"
@@ -39,33 +39,11 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) void hash_sdf_fwd_kernel(HashGri
                                                                         const float* __restrict__ x, int64_t n,
                                                                         float* __restrict__ sdf,
                                                                         uint32_t* __restrict__ mask) {
-  constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2;
-  constexpr int MW = (NH + 1) * RT;  // mask words per lane
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const PackLayout pl(F, H, NH);
-  // LDS as sdf_fwd_kernel stages it: the exact form the fp32 forward pack [0, fwd_end); the split form the bf16x3
-  // forward block [s_w0, s_fwd_end) followed by the biases and output weights [o_b0, fwd_end)
-  const int n_split = pl.s_fwd_end - pl.s_w0;
-  if (SPLIT) {
-    for (int i = threadIdx.x * 4; i < n_split; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
-    for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + n_split + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
-  } else {
-    for (int i = threadIdx.x * 4; i < pl.fwd_end; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + i);
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
+  using Dec = FwdDecoder<C * L, H, NH, SPLIT, false>;      // sdf_fwd_kernel's
+  constexpr int KS0 = Dec::KS0, MW = Dec::MW;               // MW: mask words per lane
+  const Dec dec(packed);
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t nchunks = (n + 63) / 64;
-  const float* w0p = smem + pl.o_w0;
-  const float* whp = smem + pl.o_wh;
-  const float* b0 = smem + pl.o_b0;
-  const float* bh = smem + pl.o_bh;
-  const float* wo = smem + pl.o_wo;
-  const uint32_t* s_fwd = reinterpret_cast<const uint32_t*>(smem);      // SPLIT
-  const float* s_bias = smem + n_split;                                 // SPLIT
-  const float bo = SPLIT ? s_bias[pl.o_bo - pl.o_b0] : smem[pl.o_bo];
 
   ChunkSched sched(nchunks, wave, 4, false);
   for (int64_t chunk = sched.cur; chunk < sched.end; chunk += sched.step) {
@@ -82,16 +60,7 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) void hash_sdf_fwd_kernel(HashGri
     }
     memory_phase(false);
     uint32_t mw[MW];
-    float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
-    if constexpr (SPLIT) {
-      u32x4 no_mask[H / 16][2];
-      decoder_fwd_split<F, H, NH, false, true, false>(s_fwd, s_bias, lane, f, mw, no_mask, p0, p1, poison);
-    } else {
-      decoder_fwd_exact<F, H, NH>(w0p, whp, b0, bh, wo, lane, f, mw, p0, p1);
-    }      // exact fp32 chains
-    p0 += __shfl_xor(p0, 32);
-    p1 += __shfl_xor(p1, 32);
-    const float sdf_v = SPLIT ? ((hi ? p1 : p0) + bo) + poison : (hi ? p1 : p0) + bo;
+    const float sdf_v = dec.template decode<true>(f, mw);
     if (valid) sdf[p] = sdf_v;
     if (mask) {
       uint32_t* mo = mask + (chunk * 64 + lane) * MW;
@@ -104,16 +73,12 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) void hash_sdf_fwd_kernel(HashGri
 template <int C, int L, int H, int NH>
 static hipError_t launch_hash_fwd_t(FusedShape<C, L, H, NH>, const HashGridK& g, const float* packed, bool exact,
                                     const float* x, int64_t n, float* sdf, uint32_t* mask, hipStream_t s) {
-  PackLayout pl(C * L, H, NH);
   const bool split = use_split(exact);
-  size_t lds = (size_t)(split ? pl.s_fwd_end - pl.s_w0 + (pl.n_bias() + 3) / 4 * 4 : (pl.fwd_end + 3) / 4 * 4) * sizeof(float);
-  int64_t nchunks = (n + 63) / 64;
-  unsigned blocks = (unsigned)((nchunks + 3) / 4);
-  if (blocks > 512u) blocks = 512u;      // persistent: two workgroups per CU
+  const FwdLaunch dims(C * L, H, NH, split, n, 512u);      // persistent: two workgroups per CU
   auto k = split ? hash_sdf_fwd_kernel<C, L, H, NH, true> : hash_sdf_fwd_kernel<C, L, H, NH, false>;
-  hipError_t e = allow_lds((const void*)k, lds);
+  hipError_t e = allow_lds((const void*)k, dims.lds);
   if (e != hipSuccess) return e;
-  k<<<blocks, 256, lds, s>>>(g, packed, x, n, sdf, mask);
+  k<<<dims.blocks, 256, dims.lds, s>>>(g, packed, x, n, sdf, mask);
   return hipGetLastError();
 }
 

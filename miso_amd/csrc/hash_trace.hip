@@ -14,7 +14,7 @@
 //
 // Registers of hash_trace_kernel<C, L, H, NH, SPLIT> (gfx950, hipcc -O3, -Rpass-analysis=kernel-resource-usage): VGPRs
 // and the wavefronts per SIMD they allow; no AGPRs, scratch 0 and no static LDS in every instantiation (the LDS is
-// dynamic: AtlasLaunch sizes it).  The field is evaluated at ONE place of the kernel (see the stages in its body): with
+// dynamic: FwdLaunch sizes it; the counts below are this build's, the same as before FwdDecoder).  The field is evaluated at ONE place of the kernel (see the stages in its body): with
 // a call per stage every H = 64 shape spilled 180 - 800 bytes per lane.  The two exact L = 4 shapes sit at the cap.
 //   shape            split: VGPRs (waves)   exact: VGPRs (waves)
 //   <4, 1, 32, 1>     140 (3)                121 (4)
@@ -33,7 +33,7 @@
 
 #include "checks.hpp"
 #include "hash_grid.hpp"
-#include "atlas_eval.hpp"      // AtlasDecoder, AtlasLaunch
+#include "atlas_eval.hpp"      // AtlasDecoder
 #include "trace_math.hpp"      // add_product, norm3
 #include "../../include/miso_hash_trace.h"
 
@@ -55,8 +55,7 @@ __device__ __forceinline__ float hash_eval(const HashGridK& g, const AtlasDecode
 template <int C, int L, int H, int NH, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void hash_trace_kernel(HashGridK g, TraceK t, const float* __restrict__ packed) {
   using Dec = AtlasDecoder<C, L, H, NH, SPLIT>;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const Dec dec(smem, packed, true);
+  const Dec dec(packed, true);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   const int64_t nchunks = (t.n + 63) / 64;
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void hash_trace_kernel(HashGridK g, TraceK 
 template <int C, int L, int H, int NH>
 static hipError_t launch_hash_trace_t(FusedShape<C, L, H, NH>, const HashGridK& g, const TraceK& t, const float* packed,
                                       bool split, hipStream_t s) {
-  const AtlasLaunch dims(C * L, H, NH, split, true, t.n);
+  const FwdLaunch dims(C * L, H, NH, split, t.n, 2048u);
   auto k = split ? hash_trace_kernel<C, L, H, NH, true> : hash_trace_kernel<C, L, H, NH, false>;
   hipError_t e = allow_dynamic_lds((const void*)k, dims.lds);
   if (e != hipSuccess) return e;

@@ -54,35 +54,13 @@ __global__ __launch_bounds__(64 * PAIR_SDF_WAVES) void pair_sdf_stage_kernel(
   const float* pose_d = pose_all + 12 * d.dst;
 
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const PackLayout pl(F, H, NH);
-  // the pack as atlas_sdf_bwd_kernel stages it: forward part and transposed weights (exact), or the bf16x3 section
-  // followed by the biases and output weights (split)
-  const int n_split = pl.total_all - pl.s_w0;
-  const int n_pack = SPLIT ? n_split + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
-  if (SPLIT) {
-    for (int i = threadIdx.x * 4; i < n_split; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
-    for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + n_split + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
-  } else {
-    for (int i = threadIdx.x * 4; i < pl.total; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + i);
-  }
+  const PackImage<SPLIT, true> img(F, H, NH);      // the whole pack (decoder.hpp)
+  img.stage(packed);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
   const int nw = blockDim.x >> 6;
-  const float* w0p = smem + pl.o_w0;
-  const float* whp = smem + pl.o_wh;
-  const float* b0 = smem + pl.o_b0;
-  const float* bh = smem + pl.o_bh;
-  const float* wo = smem + pl.o_wo;
-  const float* whT = smem + pl.o_whT;
-  const float* w0T = smem + pl.o_w0T;
-  const uint32_t* s_fwd = reinterpret_cast<const uint32_t*>(smem);                                   // SPLIT
-  const uint32_t* s_bwd = reinterpret_cast<const uint32_t*>(smem) + (pl.s_bfirst - pl.s_w0);        // SPLIT
-  const float* s_bias = smem + n_split;                                                              // SPLIT
-  const float bo = SPLIT ? s_bias[pl.o_bo - pl.o_b0] : smem[pl.o_bo];
-  float* dF = smem + n_pack + wave * (64 * FP);      // this wavefront's d-feat tile [64][FP]
+  const float bo = img.bo();
+  float* dF = img.behind() + wave * (64 * FP);      // this wavefront's d-feat tile [64][FP]
 
   float Rs[9], ts[3], Rd[9], td[3];
 #pragma unroll
@@ -156,16 +134,14 @@ __global__ __launch_bounds__(64 * PAIR_SDF_WAVES) void pair_sdf_stage_kernel(
     uint32_t mw[MW];
     u32x4 maskB[H / 16][2];      // SPLIT: the last ReLU's mask as the first backward product's B operand
     float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
-    if constexpr (SPLIT) decoder_fwd_split<F, H, NH, false, false, true, true>(s_fwd, s_bias, lane, f, mw, maskB, p0, p1, poison);
-    else decoder_fwd_exact<F, H, NH, true>(w0p, whp, b0, bh, wo, lane, f, mw, p0, p1);
-    p0 += __shfl_xor(p0, 32);
-    p1 += __shfl_xor(p1, 32);
-    const float sdf = SPLIT ? ((hi ? p1 : p0) + bo) + poison : (hi ? p1 : p0) + bo;
+    if constexpr (SPLIT) decoder_fwd_split<F, H, NH, false, false, true, true>(img.s_fwd(), img.s_bias(), lane, f, mw, maskB, p0, p1, poison);
+    else decoder_fwd_exact<F, H, NH, true>(img.w0p(), img.whp(), img.b0(), img.bh(), img.wo(), lane, f, mw, p0, p1);
+    const float sdf = close_fwd<SPLIT>(p0, p1, hi, bo, poison);
     // ================================ decoder backward of d s = 1 ====================================================
     const float ds[2] = {1.0f, 1.0f};
     f32x16 df[2];
-    if constexpr (SPLIT) decoder_bwd_split<F, H, NH, false>(s_bwd, lane, maskB, mw, ds, df);
-    else decoder_bwd_exact<F, H, NH>(whT, w0T, wo, lane, mw, ds, df);
+    if constexpr (SPLIT) decoder_bwd_split<F, H, NH, false>(img.s_bwd(), lane, maskB, mw, ds, df);
+    else decoder_bwd_exact<F, H, NH>(img.whT(), img.w0T(), img.wo(), lane, mw, ds, df);
     dfeat_to_tile<F, 2>(df, dF, lane & 31, hi);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -292,7 +268,7 @@ __global__ __launch_bounds__(64 * PAIR_SDF_WAVES) void pair_sdf_stage_kernel(
 // dynamic LDS of a launch: the decoder image beside one d-feat tile per wavefront; 0 = more than a workgroup can have
 static size_t pair_sdf_lds_bytes(int C, int L, int H, int NH, bool split) {
   const PackLayout pl(C * L, H, NH);
-  const int pack = split ? pl.total_all - pl.s_w0 + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
+  const int pack = image_floats(pl, split, true);
   const size_t bytes = (size_t)(pack + PAIR_SDF_WAVES * 64 * dfeat_pitch(C * L)) * sizeof(float);
   return bytes <= MISO_LDS_LIMIT ? bytes : 0;
 }

@@ -118,33 +118,12 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) void sdf_fwd_kernel(GridK g, con
   // lin.p.loss_type != 0 (binned batches only): the mapping loss of loss.hip is evaluated on the
   // spot -- d loss / d sdf goes to lin.gsdf_sorted[p] (binned order: the backward reads it
   // coalesced), the two loss sums are accumulated into lin.loss_out; sdf may then be NULL.
-  constexpr int F = C * L, RT = H / 32, KS0 = (F + 1) / 2, KS1 = H / 2;
-  constexpr int MW = (NH + 1) * RT;  // mask words per lane
+  using Dec = FwdDecoder<C * L, H, NH, SPLIT, false>;
+  constexpr int KS0 = Dec::KS0, MW = Dec::MW;      // MW: mask words per lane
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const PackLayout pl(F, H, NH);
-  // LDS: the exact form stages the fp32 forward pack [0, fwd_end); the split form the bf16x3 forward block
-  // [s_w0, s_fwd_end) followed by the biases and output weights [o_b0, fwd_end)
-  const int n_split = pl.s_fwd_end - pl.s_w0;
-  if (SPLIT) {
-    for (int i = threadIdx.x * 4; i < n_split; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
-    for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + n_split + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
-  } else {
-    for (int i = threadIdx.x * 4; i < pl.fwd_end; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + i);
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
+  const Dec dec(packed);      // the forward image to LDS (decoder.hpp)
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t nchunks = (n + 63) / 64;
-  const float* w0p = smem + pl.o_w0;
-  const float* whp = smem + pl.o_wh;
-  const float* b0 = smem + pl.o_b0;
-  const float* bh = smem + pl.o_bh;
-  const float* wo = smem + pl.o_wo;
-  const uint32_t* s_fwd = reinterpret_cast<const uint32_t*>(smem);      // SPLIT
-  const float* s_bias = smem + n_split;                                 // SPLIT
-  const float bo = SPLIT ? s_bias[pl.o_bo - pl.o_b0] : smem[pl.o_bo];
 
   float loss_sdf = 0.0f, loss_fs = 0.0f;
   float inv_n = lin.inv_n;   // mean over the batch rows -- or over the live rows of a padded batch
@@ -185,16 +164,7 @@ __global__ __launch_bounds__(256, MISO_FWD_OCC) void sdf_fwd_kernel(GridK g, con
     }
     memory_phase(false);
     uint32_t mw[MW];
-    float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
-    if constexpr (SPLIT) {
-      u32x4 no_mask[H / 16][2];
-      decoder_fwd_split<F, H, NH, false, true, false>(s_fwd, s_bias, lane, f, mw, no_mask, p0, p1, poison);
-    } else {
-      decoder_fwd_exact<F, H, NH>(w0p, whp, b0, bh, wo, lane, f, mw, p0, p1);
-    }      // exact fp32 chains
-    p0 += __shfl_xor(p0, 32);
-    p1 += __shfl_xor(p1, 32);
-    const float sdf_v = SPLIT ? ((hi ? p1 : p0) + bo) + poison : (hi ? p1 : p0) + bo;
+    const float sdf_v = dec.template decode<true>(f, mw);
     if (valid && sdf) sdf[po] = sdf_v;
     if (lin.p.loss_type && valid) {
       float gsd, gfs;
@@ -390,17 +360,13 @@ __global__ __launch_bounds__(256, 2) void sdf_bwd_kernel(GridK g, const float* _
 template <int C, int L, int H, int NH>
 static hipError_t launch_fwd_t(FusedShape<C, L, H, NH>, const GridK& g, const float* packed, const float* x, int64_t n,
                                float* sdf, uint32_t* mask, const int* perm, const LossInK& lin, hipStream_t s) {
-  PackLayout pl(C * L, H, NH);
   const bool split = use_split(g.flags & MISO_F_EXACT_F32);
-  size_t lds = (size_t)(split ? pl.s_fwd_end - pl.s_w0 + (pl.n_bias() + 3) / 4 * 4 : (pl.fwd_end + 3) / 4 * 4) * sizeof(float);
-  int64_t nchunks = (n + 63) / 64;
-  unsigned blocks = (unsigned)((nchunks + 3) / 4);
-  if (blocks > 512u) blocks = 512u;      // persistent: two workgroups per CU
-  if (lin.p.loss_type && blocks > MISO_LOSS_SLOTS) blocks = MISO_LOSS_SLOTS;   // one loss slot per block
+  FwdLaunch dims(C * L, H, NH, split, n, 512u);      // persistent: two workgroups per CU
+  if (lin.p.loss_type && dims.blocks > MISO_LOSS_SLOTS) dims.blocks = MISO_LOSS_SLOTS;   // one loss slot per block
   auto k = split ? sdf_fwd_kernel<C, L, H, NH, true> : sdf_fwd_kernel<C, L, H, NH, false>;
-  hipError_t e = allow_lds((const void*)k, lds);
+  hipError_t e = allow_lds((const void*)k, dims.lds);
   if (e != hipSuccess) return e;
-  k<<<blocks, 256, lds, s>>>(g, packed, x, n, sdf, mask, perm, lin);
+  k<<<dims.blocks, 256, dims.lds, s>>>(g, packed, x, n, sdf, mask, perm, lin);
   return hipGetLastError();
 }
 

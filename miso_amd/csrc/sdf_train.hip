@@ -84,36 +84,16 @@ __global__ __launch_bounds__(64 * NW, 2) void sdf_train_kernel(GridK g, const fl
   const bool rotate = SCAT && C * L <= MISO_ROTATE_MAX_F && rotate_records;
   const int WAVE_LDS = 64 * FP + (SCAT ? (rotate ? 2 : 1) * 64 * L * REC : 0);
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const PackLayout pl(F, H, NH);
-  // the whole pack: forward part [0, fwd_end), transposed weights [o_whT, total) right behind it; the split form: the
-  // bf16x3 section [s_w0, total_all), then the biases and output weights [o_b0, fwd_end)
-  const int n_split = pl.total_all - pl.s_w0;
-  const int n_pack = SPLIT ? n_split + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
-  if (SPLIT) {
-    for (int i = threadIdx.x * 4; i < n_split; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + pl.s_w0 + i);
-    for (int i = threadIdx.x * 4; i < pl.n_bias(); i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + n_split + i) = *reinterpret_cast<const float4*>(packed + pl.o_b0 + i);
-  } else {
-    for (int i = threadIdx.x * 4; i < pl.total; i += blockDim.x * 4)
-      *reinterpret_cast<float4*>(smem + i) = *reinterpret_cast<const float4*>(packed + i);
-  }
+  const PackImage<SPLIT, true> img(F, H, NH);      // the whole pack (decoder.hpp)
+  img.stage(packed);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), hi = lane >> 5;
   constexpr int PTS = HALF ? 32 : 64;      // points per wavefront and trip
   const int64_t nchunks = (n + PTS - 1) / PTS;
-  const float* w0p = smem + pl.o_w0;
-  const float* whp = smem + pl.o_wh;
-  const float* b0 = smem + pl.o_b0;
-  const float* bh = smem + pl.o_bh;
-  const float* wo = smem + pl.o_wo;
-  const uint32_t* s_fwd = reinterpret_cast<const uint32_t*>(smem);                                   // SPLIT
-  const uint32_t* s_bwd = reinterpret_cast<const uint32_t*>(smem) + (pl.s_bfirst - pl.s_w0);        // SPLIT
-  const float* s_bias = smem + n_split;                                                              // SPLIT
-  const float bo = SPLIT ? s_bias[pl.o_bo - pl.o_b0] : smem[pl.o_bo];
-  const float* whT = smem + pl.o_whT;
-  const float* w0T = smem + pl.o_w0T;
-  float* dF = smem + n_pack + wave * WAVE_LDS;       // this wavefront's d-feat tile [64][FP]
+  const float *w0p = img.w0p(), *whp = img.whp(), *b0 = img.b0(), *bh = img.bh(), *wo = img.wo();      // the exact chains'
+  const float *whT = img.whT(), *w0T = img.w0T();
+  const float bo = img.bo();
+  float* dF = img.behind() + wave * WAVE_LDS;       // this wavefront's d-feat tile [64][FP]
   int* rec = reinterpret_cast<int*>(dF + 64 * FP);                      // SCAT: its cell records [64][L][REC]
   uint32_t scatter_mask = 0;
   if (SCAT)
@@ -149,7 +129,7 @@ __global__ __launch_bounds__(64 * NW, 2) void sdf_train_kernel(GridK g, const fl
     float p0 = 0.0f, p1 = 0.0f, poison = 0.0f;
     u32x4 maskB[H / 16][HALF ? 1 : 2];      // SPLIT: the last ReLU's mask as the first backward product's B operand
     if constexpr (SPLIT) {
-      decoder_fwd_split<F, H, NH, HALF, false, true>(s_fwd, s_bias, lane, f, mw, maskB, p0, p1, poison);
+      decoder_fwd_split<F, H, NH, HALF, false, true>(img.s_fwd(), img.s_bias(), lane, f, mw, maskB, p0, p1, poison);
     } else {
       f32x16 buf[2][RT][2];
       {
@@ -259,6 +239,8 @@ __global__ __launch_bounds__(64 * NW, 2) void sdf_train_kernel(GridK g, const fl
         }
       }
     }
+    // decoder.hpp's close_fwd, written out: through the function (a HALF form of it, by value or by reference) between
+    // 22 and 46 of this kernel's 78 instantiations changed registers past their first matrix instruction
     p0 += __shfl_xor(p0, 32);
     if (!HALF) p1 += __shfl_xor(p1, 32);
     const float sdf_v = SPLIT ? (((!HALF && hi) ? p1 : p0) + bo) + poison : ((!HALF && hi) ? p1 : p0) + bo;
@@ -279,7 +261,7 @@ __global__ __launch_bounds__(64 * NW, 2) void sdf_train_kernel(GridK g, const fl
     // ================================ backward ======================================================================
     f32x16 df[2];
     if constexpr (SPLIT) {
-      decoder_bwd_split<F, H, NH, HALF>(s_bwd, lane, maskB, mw, ds, df);
+      decoder_bwd_split<F, H, NH, HALF>(img.s_bwd(), lane, maskB, mw, ds, df);
     } else {
       f32x16 dbuf[2][RT][2];
 #pragma unroll
@@ -385,7 +367,7 @@ struct TrainPlan {
 static TrainPlan plan_train(int C, int L, int H, int NH, const TrainCase& c) {
   const PackLayout pl(C * L, H, NH);
   const int F = C * L, FP = dfeat_pitch(F), tile = 64 * FP, records = 64 * L * CELL_REC;
-  const int pack = c.split ? pl.total_all - pl.s_w0 + ((pl.n_bias() + 3) / 4) * 4 : ((pl.total + 3) / 4) * 4;
+  const int pack = image_floats(pl, c.split, true);
   const auto bytes = [&](int wavefronts, int record_blocks) {
     return (size_t)(pack + wavefronts * (tile + record_blocks * records)) * sizeof(float);
   };

@@ -23,8 +23,7 @@ namespace miso {
 template <int C, int L, int H, int NH, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void atlas_trace_kernel(AtlasK a, TraceK t, const float* __restrict__ packed) {
   using Dec = AtlasDecoder<C, L, H, NH, SPLIT>;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const Dec dec(smem, packed, true);
+  const Dec dec(packed, true);
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
   const int64_t nchunks = (t.n + 63) / 64;
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(256, 2) void atlas_trace_kernel(AtlasK a, TraceK t,
 template <int C, int L, int H, int NH>
 static hipError_t launch_trace_t(FusedShape<C, L, H, NH>, const AtlasK& a, const TraceK& t, const float* packed, bool split,
                                  hipStream_t s) {
-  const AtlasLaunch dims(C * L, H, NH, split, true, t.n);
+  const FwdLaunch dims(C * L, H, NH, split, t.n, 2048u);
   auto k = split ? atlas_trace_kernel<C, L, H, NH, true> : atlas_trace_kernel<C, L, H, NH, false>;
   hipError_t e = allow_dynamic_lds((const void*)k, dims.lds);
   if (e != hipSuccess) return e;

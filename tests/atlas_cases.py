@@ -50,7 +50,7 @@ K = {name: i for i, name in enumerate(KINDS)}
 SIZES = (1, 63, 64, 65, 257, 513, 1025)
 LATTICES = ((1, 1, 1), (2, 1, 33), (1, 65, 1))
 # The persistent loops take a second trip beyond blocks x wavefronts x 64 points: atlas_sdf_kernel caps its grid at 2048
-# blocks of 4 wavefronts (AtlasLaunch: 2048 x 4 x 64 = 524288), atlas_sdf_bwd_kernel at 256 blocks of 8 wavefronts or 512
+# blocks of 4 wavefronts (FwdLaunch, cap 2048: 2048 x 4 x 64 = 524288), atlas_sdf_bwd_kernel at 256 blocks of 8 wavefronts or 512
 # of 4 (launch_atlas_bwd_t: 131072 either way).  + 65: one full chunk and a one-row chunk on the second trip.
 N_STRIDE_FWD = 2048 * 4 * 64 + 65
 N_STRIDE_BWD = 256 * 8 * 64 + 65
